@@ -11,8 +11,11 @@ encoder (stock PyTorch-ROCm) → HIP prefill → 867 hipGraph-replayed decode st
 weights (no checkpoints offline). N>1: one process per GPU, utterances sharded statically, weights broadcast once
 from rank 0 over RCCL; no collective on the data path ("scaling": "weak").
 
-One JSON line on rank 0. value = whole-job audio-seconds generated per wall-second (max over ranks). Extras:
-roofline (decode-step graph vs HBM), cpu_baseline (oracle port on the host cores, bounded sample), ttft_p50_ms.
+One JSON line on rank 0. value = whole-job audio-seconds generated per wall-second (max over ranks). A plain run sets up,
+warms up, times the --steps generate() calls and prints the line. --full adds the side measurements: roofline (decode-step
+graph vs HBM), cpu_baseline (oracle port on the host cores, bounded sample), ttft_p50_ms, bs=32 / bs=128, codec, streaming,
+sampling, fp32 parity mode, Large-v1. --dump-outputs DIR writes the waveform the last timed step returned (rank 0's) as
+DIR/audio_values.npy (float32), for output-by-output comparison of two builds.
 """
 from __future__ import annotations
 
@@ -658,6 +661,28 @@ def arm_watchdog(out: dict, seconds: float):
     return done.set
 
 
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Writes each [rows, ...] output as out_dir/<name>.npy in float32. What does not fit DUMP_BYTES (split evenly between the arrays) is
+    written as a fixed sample of whole rows - the first rows of a permutation drawn with seed 0, in ascending order - and the rows kept
+    go to out_dir/<name>_rows.npy (float64), so that two builds dump the same rows of the same inputs."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // max(1, len(arrays)) - 4096  # room for the .npy headers and a row index
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        row_bytes = max(1, a[0].nbytes if a.ndim > 1 else a.itemsize)
+        if a.nbytes > budget:
+            keep = max(1, budget // row_bytes)
+            rows = np.sort(torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].numpy())
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU over RCCL), relay
     rank 0's JSON line. Equivalent to `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`."""
@@ -685,14 +710,19 @@ def main():
     ap.add_argument("--model", default="mini", choices=["mini", "large"], help="parler-tts-mini-v1 (BASELINE metric) or parler-tts-large-v1 shapes")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8w"], help="fp8w: bf16 engine streaming OCP e4m3 weights in the decode step (BASELINE configs[4])")
     ap.add_argument("--sample", action="store_true", help="do_sample=True (temperature 1.0, top_k 50: the reference's default generation mode) instead of greedy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bs=32 / TTFT side measurements")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements (roofline, TTFT, CPU baseline, bs=32 / bs=128, codec, "
+                                                        "streaming, sampling, fp32 parity mode, Large-v1); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the bs=32 / TTFT side measurements")
     ap.add_argument("--live-pmc", action="store_true", help="(default since round 3) measure roofline.traffic in this run: two rocprofv3 --pmc child "
                                                             "passes at the timed context, ~20 s per batch size")
     ap.add_argument("--no-live-pmc", action="store_true", help="read roofline.traffic from the committed pass under profiles/ (context 57) instead")
     args = ap.parse_args()
     global LIVE_PMC
     LIVE_PMC = not args.no_live_pmc
+    extras = args.full and not args.no_extras
+    with_cpu_baseline = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -764,11 +794,13 @@ def main():
         per_rank = [float(x.item()) for x in every]
         elapsed = max(per_rank)  # the slowest rank bounds the job
     value = n_ranks * args.bs * args.steps * AUDIO_S / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"audio_values": wav})
 
     out = None
     mname = "parler-tts-mini-v1" if args.model == "mini" else "parler-tts-large-v1"
     ttft_ranks = None
-    if world > 1 and not args.no_extras:  # both halves of the metric on a multi-GPU run: every rank times ITS p50 time-to-first-token, the line carries the max
+    if world > 1 and extras:  # both halves of the metric on a multi-GPU run: every rank times ITS p50 time-to-first-token, the line carries the max
         import torch.distributed as dist
 
         mine = torch.tensor([measure_ttft(model, args.bs, device, reps=9)], device=device if dist.get_backend() == "nccl" else torch.device("cpu"), dtype=torch.float64)
@@ -792,7 +824,7 @@ def main():
             out["per_rank_value"] = [round(args.bs * args.steps * AUDIO_S / t, 3) for t in per_rank]
         if world > 1 and ndev < world:
             out["config"]["note"] = f"functional run: {world} ranks share {ndev} GPU(s), backend {os.environ.get('PTTS_DIST_BACKEND', 'nccl')}; not a scaling measurement"
-        if not args.no_extras:
+        if extras:
             # (N > 1: the other ranks wait in the final barrier while rank 0 measures; no profiler child passes there - the committed PMC pass is quoted)
             out["roofline"] = measure_decode_roofline(model, args.bs, device, live_pmc=(world == 1))
             out["ttft_p50_ms"] = max(ttft_ranks) if ttft_ranks else round(measure_ttft(model, args.bs, device), 2)
@@ -805,11 +837,11 @@ def main():
                     out["ttft"] = {"error": repr(e)[:200]}
         else:
             out["roofline"] = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # a required object of the line: measured before the optional side measurements
+    if rank == 0 and world == 1 and with_cpu_baseline:  # a required object of the line: measured before the optional side measurements
         out["cpu_baseline"] = cpu_baseline()
         out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
     disarm = arm_watchdog(out, float(os.environ.get("PTTS_BENCH_WATCHDOG_S", "600"))) if (rank == 0 and world == 1) else (lambda: None)
-    if rank == 0 and world == 1 and not args.no_extras and args.bs != 32 and args.model == "mini":
+    if rank == 0 and world == 1 and extras and args.bs != 32 and args.model == "mini":
         # side measurement of BASELINE configs[2] (bs=32, same model): one warm-up + one timed generate()
         try:
             d32, p32 = synthetic_batch(32, 0, device)
@@ -829,17 +861,17 @@ def main():
                 out["bs32"]["ttft"] = {"error": repr(e)[:200]}
         except Exception as e:  # side measurement must never break the contract line
             out["bs32"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         try:  # the codec half of the path against ITS bound (MFMA): bf16-operand mode at 1 / 32 utterances, exact-f32 mode at 1
             out["dac"] = measure_dac(device)
         except Exception as e:
             out["dac"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_extras and args.model == "mini":
+    if rank == 0 and world == 1 and extras and args.model == "mini":
         try:  # EOS-terminated batches: the per-sample tail of generate() as one filter kernel + one ragged codec pass
             out["ragged_bs32"] = measure_ragged(model, device, 32)
         except Exception as e:
             out["ragged_bs32"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_extras and args.model == "mini" and args.dtype == "bf16":
+    if rank == 0 and world == 1 and extras and args.model == "mini" and args.dtype == "bf16":
         try:  # the whole-node lever: 128 utterances per GPU (the step is latency-bound at 32, utterances per step are nearly free until the KV stream dominates)
             dt = _timed_generate(model, 128, device)
             out["bs128"] = {"value": round(128 * AUDIO_S / dt, 2), "unit": "audio-seconds/sec", "ms_per_step": round(dt * 1e3, 1),
@@ -875,17 +907,17 @@ def main():
                 model.enable_fp8_kv_cache(False)
             except Exception:  # noqa: BLE001
                 pass
-    if rank == 0 and world == 1 and not args.no_extras and args.bs == 1:
+    if rank == 0 and world == 1 and extras and args.bs == 1:
         try:
             out["streaming"] = measure_ttfa(model, device)
         except Exception as e:
             out["streaming"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_extras and not args.sample and args.model == "mini":
+    if rank == 0 and world == 1 and extras and not args.sample and args.model == "mini":
         try:  # the reference's default generation mode (do_sample=True, init_model_600M.py:57-63): step time beside greedy
             out["sampling"] = measure_sampling_step(model, args.bs, device)
         except Exception as e:
             out["sampling"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_extras and args.model == "mini" and args.dtype == "bf16":
+    if rank == 0 and world == 1 and extras and args.model == "mini" and args.dtype == "bf16":
         try:  # the bit-exact (fp32) engine on the same configuration (its own model object: 288 GB of HBM hold all of them)
             out["fp32_parity_mode"] = measure_fp32_parity_mode(device)
             out["fp32_parity_mode"]["gpu_over_cpu"] = round(out["fp32_parity_mode"]["value"] / out["cpu_baseline"]["value"], 1) if "cpu_baseline" in out else None

@@ -130,7 +130,7 @@ def test_main_prints_one_contract_line_with_everything_stubbed(monkeypatch, caps
             return torch.zeros(kw["input_ids"].shape[0], bench.FRAMES * 512)
 
     fake = FakeModel()
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1", "--full"])
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
@@ -164,6 +164,66 @@ def test_main_prints_one_contract_line_with_everything_stubbed(monkeypatch, caps
     assert j["fp32_parity_mode"]["value"] == 12.0 and j["fp32_parity_mode"]["gpu_over_cpu"] == 80.0 and j["large"] == {"bf16_bs1": {"value": 9.0}}
     # 1 warm-up + 2 timed steps at bs = 1, then the bs = 32 and bs = 128 side measurements (warm-up + timed each)
     assert fake.calls == [1, 1, 1, 32, 32, 128, 128]
+
+
+@pytest.mark.parametrize("bs", [2, 40])
+def test_plain_run_times_the_steps_only_and_dumps_the_last_step(bs, monkeypatch, capsys, tmp_path):
+    """Without --full, bench.main() sets up, warms up, runs exactly --steps timed generate() calls and prints the line: no side measurement
+    is started. --dump-outputs writes the waveform of the LAST timed step as float32; above the size budget a fixed, seeded set of whole
+    utterances (and their row indices) is written instead, the same on every run."""
+    import time
+
+    import numpy as np
+
+    import __graft_entry__ as ge
+
+    class FakeModel:
+        def __init__(self):
+            self.calls = 0
+
+        def generate(self, **kw):
+            self.calls += 1
+            time.sleep(0.02)  # a step long enough for the line's rounding of ms_per_step
+            b = kw["input_ids"].shape[0]
+            return torch.full((b, bench.FRAMES * 512), float(self.calls)) + torch.arange(b, dtype=torch.float32)[:, None]
+
+    def forbidden(*a, **k):
+        raise AssertionError("side measurement in a plain run")
+
+    fake = FakeModel()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2", "--bs", str(bs), "--dump-outputs", str(tmp_path / "out")])
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda i: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(ge, "build", lambda: None)
+    monkeypatch.setattr(bench, "build_model", lambda rank, world, device, dtype, which="mini": fake)
+    monkeypatch.setattr(bench, "synthetic_batch", lambda bs, rank, device: (torch.zeros(bs, bench.N_DESC, dtype=torch.long), torch.zeros(bs, bench.N_PROMPT, dtype=torch.long)))
+    for name in ("measure_decode_roofline", "measure_fp32_parity_mode", "measure_large", "measure_ttft", "measure_ttfa", "measure_ttft_breakdown",
+                 "measure_sampling_step", "cpu_baseline", "measure_dac", "measure_ragged", "_timed_generate"):
+        monkeypatch.setattr(bench, name, forbidden)
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert fake.calls == 5 and j["steps"] == 3 and j["warmup"] == 2 and j["ms_per_step"] > 0
+    assert j["unit"] == "audio-seconds/sec" and j["higher_is_better"] is True and j["dtype"] == "bf16" and j["roofline"] is None
+    assert abs(j["value"] - bs * bench.AUDIO_S / (j["ms_per_step"] / 1e3)) / j["value"] < 1e-2
+    for k in ("cpu_baseline", "ttft_p50_ms", "ttft", "bs32", "bs128", "dac", "ragged_bs32", "streaming", "sampling", "fp32_parity_mode", "large"):
+        assert k not in j, k
+    a = np.load(tmp_path / "out" / "audio_values.npy")
+    assert a.dtype == np.float32 and a.shape[1] == bench.FRAMES * 512 and a[:, 0].min() >= 5.0  # the 5th generate() = the last timed step
+    total = sum(f.stat().st_size for f in (tmp_path / "out").iterdir())
+    assert total <= bench.DUMP_BYTES
+    if bs * bench.FRAMES * 512 * 4 <= bench.DUMP_BYTES - 4096:
+        assert a.shape[0] == bs and np.array_equal(a[:, 0], 5.0 + np.arange(bs)) and not (tmp_path / "out" / "audio_values_rows.npy").exists()
+    else:
+        rows = np.load(tmp_path / "out" / "audio_values_rows.npy")
+        assert rows.dtype == np.float64 and len(rows) == a.shape[0] < bs and np.all(np.diff(rows) > 0)
+        assert np.array_equal(a[:, 0], 5.0 + rows)
+        bench.dump_outputs(str(tmp_path / "again"), {"audio_values": torch.full((bs, bench.FRAMES * 512), 5.0) + torch.arange(bs, dtype=torch.float32)[:, None]})
+        assert np.array_equal(np.load(tmp_path / "again" / "audio_values_rows.npy"), rows)
 
 
 def test_parity_tests_model_copy_equals_bench_build_model():
@@ -240,7 +300,7 @@ bench.build_model = lambda rank, world, device, dtype, which="mini": FakeModel()
 bench.synthetic_batch = lambda bs, rank, device: (torch.zeros(bs, bench.N_DESC, dtype=torch.long), torch.zeros(bs, bench.N_PROMPT, dtype=torch.long))
 bench.measure_ttft = lambda model, bs, device, reps=20: 2.0 + int(os.environ["RANK"])
 bench.measure_decode_roofline = lambda model, bs, device, live_pmc=True: {{"bound": "hbm", "frac": 0.1, "live": live_pmc}}
-sys.argv = ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--bs", "3"]
+sys.argv = ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--bs", "3", "--full"]
 bench.main()
 '''
 

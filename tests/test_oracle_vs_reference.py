@@ -1,20 +1,80 @@
-"""CPU, only where the reference tree is mounted (this build container; skipped on the GPU box, which has no
-/root/reference): the oracle is re-checked LIVE against the reference's own classes - the same comparisons
-oracle/make_golden.py runs before it freezes tests/golden/*.npz. Nothing is written (bytecode writing is disabled by the
-import shim, golden files are not touched)."""
+"""CPU: the oracle and this package checked against the reference's own classes - the same comparisons oracle/make_golden.py
+runs before it freezes tests/golden/*.npz. Where the reference tree is importable every reference result is computed LIVE;
+everywhere else the tests compare against the same results as stored in tests/golden/reference_live.npz (written by running
+this module with PTTS_RECORD_REFERENCE=1 where the tree is importable). Nothing else is written."""
+import os
+
+import numpy as np
 import pytest
 import torch
 
 from oracle.reference_shims import reference_available
 
-pytestmark = pytest.mark.skipif(not reference_available(), reason="/root/reference is not mounted here")
+GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+RECORDED = os.path.join(GOLD, "reference_live.npz")
+_STORE = {}
 
 
 @pytest.fixture(scope="module")
 def ref():
+    """The reference package where its tree is importable, else None (the tests then read the reference's recorded results)."""
+    if not reference_available():
+        yield None
+        return
     from oracle.reference_shims import import_reference
 
-    return import_reference()
+    yield import_reference()
+    if os.environ.get("PTTS_RECORD_REFERENCE"):
+        np.savez_compressed(RECORDED, **_STORE)
+
+
+def _np(v):
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
+def _torch(a):
+    return torch.from_numpy(np.array(a))
+
+
+def rec(ref, key, live):
+    """`live()` (a tensor, a list of arrays or a dict of tensors / None) computed on the reference when `ref` is not None, else the value
+    recorded under `key` in tests/golden/reference_live.npz."""
+    if ref is not None:
+        v = live()
+        if isinstance(v, dict):
+            for k, x in v.items():
+                _STORE[f"{key}__{k}" + ("__none" if x is None else "")] = np.array(0) if x is None else _np(x)
+        elif isinstance(v, (list, tuple)):
+            _STORE[f"{key}__n"] = np.array(len(v))
+            for i, x in enumerate(v):
+                _STORE[f"{key}__{i}"] = _np(x)
+        else:
+            _STORE[key] = _np(v)
+        return v
+    g = _recorded()
+    if key in g.files:
+        return _torch(g[key])
+    if f"{key}__n" in g.files:
+        return [_torch(g[f"{key}__{i}"]) for i in range(int(g[f"{key}__n"]))]
+    out = {}
+    for name in g.files:
+        if name.startswith(key + "__"):
+            k = name[len(key) + 2:]
+            if k.endswith("__none"):
+                out[k[:-6]] = None
+            else:
+                out[k] = _torch(g[name])
+    assert out, f"no recorded reference result {key!r} in {RECORDED}"
+    return out
+
+
+_G = []
+
+
+def _recorded():
+    if not _G:
+        _G.append(np.load(RECORDED))
+    return _G[0]
 
 
 @pytest.mark.parametrize("variant", ["sin", "rope", "gqa"])
@@ -22,7 +82,26 @@ def test_decoder_forward_matches_reference_live(ref, variant):
     import oracle.make_golden as mg
 
     torch.manual_seed(0)
-    worst = mg.gen_decoder(ref, variant, save=False)  # ParlerTTSForCausalLM: prefill with padded masks + 6 cached steps, SDPA and eager
+    if ref is not None:
+        worst = mg.gen_decoder(ref, variant, save=False)  # ParlerTTSForCausalLM: prefill with padded masks + 6 cached steps, SDPA and eager
+    else:  # the same reference logits, frozen by gen_decoder in tests/golden/decoder_<variant>.npz, against the oracle in both attention modes
+        from oracle import decoder_oracle as DO
+
+        g = np.load(os.path.join(GOLD, f"decoder_{variant}.npz"))
+        H, L, nh, F, maxpos, rope, kvh, xkvh = (int(x) for x in g["spec"])
+        spec = DO.DecoderSpec(**{**DO.TINY.__dict__, "hidden_size": H, "num_hidden_layers": L, "num_attention_heads": nh, "ffn_dim": F,
+                                 "max_position_embeddings": maxpos, "rope_embeddings": bool(rope), "num_key_value_heads": kvh,
+                                 "num_cross_attention_key_value_heads": xkvh})
+        sd = DO.make_decoder_weights(spec, seed=int(g["weight_seed"]))
+        enc, enc_mask, prompt, prompt_mask = (_torch(g[k]) for k in ("enc", "enc_mask", "prompt", "prompt_mask"))
+        step_ids = _torch(g["step_ids"])
+        ids0 = torch.full((enc.shape[0] * spec.num_codebooks, 1), spec.bos_token_id, dtype=torch.long)
+        want = [_torch(g["prefill_logits"])] + [_torch(x) for x in g["step_logits"]]
+        worst = 0.0
+        for attn in ("sdpa", "eager"):
+            orc = DO.DecoderOracle(spec, sd, precision="fp32", attn_impl=attn)
+            o = [orc.forward(ids0, enc, enc_mask, prompt, prompt_mask)] + [orc.forward(step_ids[s]) for s in range(step_ids.shape[0])]
+            worst = max(worst, max(float((a - b[:, -1]).abs().max()) for a, b in zip(want, o)))
     assert worst < 2e-6
 
 
@@ -30,17 +109,17 @@ def test_delay_pattern_and_eos_gate_match_reference_live(ref):
     from oracle import decoder_oracle as DO
     import parler_tts_amd as P
 
-    M = ref.modeling_parler_tts
+    M = ref.modeling_parler_tts if ref is not None else None
     for ci, (K, seq_len, max_len, bsz) in enumerate([(9, 1, 30, 2), (4, 3, 8, 1), (9, 13, 40, 1), (9, 1, 12, 1), (2, 1, 3, 2)]):
         g = torch.Generator().manual_seed(ci)
         ids = torch.randint(0, 1024, (bsz * K, seq_len), generator=g)
         ids[:, 0] = 1025
-        a = M.build_delay_pattern_mask(ids, 1025, 1024, max_len, K)
+        a = rec(ref, f"delay_case{ci}", lambda: M.build_delay_pattern_mask(ids, 1025, 1024, max_len, K))
         for impl in (DO.build_delay_pattern_mask, P.build_delay_pattern_mask):  # oracle restatement and the product's closed form
             b = impl(ids, 1025, 1024, max_len, K)
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (ci, impl.__module__)
     K, bsz, V = 9, 2, 1088
-    proc = M.ParlerTTSLogitsProcessor(1024, K, bsz, "cpu")
+    proc = M.ParlerTTSLogitsProcessor(1024, K, bsz, "cpu") if M is not None else None
     gate, mine = DO.EosGate(1024, K, bsz), P.ParlerTTSLogitsProcessor(1024, K, bsz, "cpu")
     g = torch.Generator().manual_seed(3)
     seq = torch.full((bsz * K, 1), 1025, dtype=torch.long)
@@ -48,7 +127,7 @@ def test_delay_pattern_and_eos_gate_match_reference_live(ref):
         nxt = torch.randint(0, 1024, (bsz * K,), generator=g)
         nxt[torch.rand(bsz * K, generator=g) < 0.15] = 1024  # sprinkle EOS
         seq = torch.cat([seq, nxt[:, None]], dim=1)
-        r = proc(seq, torch.zeros(bsz * K, V))
+        r = rec(ref, f"eos_gate_step{step}", lambda: proc(seq, torch.zeros(bsz * K, V)))
         assert torch.equal(r, gate(seq, torch.zeros(bsz * K, V))) and torch.equal(r, mine(seq, torch.zeros(bsz * K, V))), step
 
 
@@ -66,7 +145,7 @@ def test_generate_conditioning_matches_reference_helpers_live(ref, pca, desc_mas
 
     import parler_tts_amd as P
 
-    M = ref.modeling_parler_tts
+    M = ref.modeling_parler_tts if ref is not None else None
     torch.manual_seed(3)
     t5 = T5Config(vocab_size=128, d_model=96, d_kv=32, d_ff=256, num_layers=2, num_heads=4, feed_forward_proj="gated-gelu")
     dec = P.ParlerTTSDecoderConfig(vocab_size=1088, max_position_embeddings=256, num_hidden_layers=2, ffn_dim=256, num_attention_heads=2,
@@ -107,15 +186,20 @@ def test_generate_conditioning_matches_reference_helpers_live(ref, pca, desc_mas
     with pytest.raises(Stop):
         m.generate(input_ids=desc, attention_mask=dm, prompt_input_ids=prompt_ids, prompt_attention_mask=pm, do_sample=False, max_new_tokens=4)
 
-    stub = types.SimpleNamespace(text_encoder=m.text_encoder, get_text_encoder=lambda: m.text_encoder, decoder=types.SimpleNamespace(config=types.SimpleNamespace(hidden_size=dec.hidden_size, cross_attention_hidden_size=None)),
-                                 enc_to_dec_proj=m.enc_to_dec_proj, embed_prompts=m.embed_prompts, prompt_cross_attention=pca, device=torch.device("cpu"),
-                                 embed_positions=M.ParlerTTSSinusoidalPositionalEmbedding(dec.max_position_embeddings, dec.hidden_size))
-    cls = M.ParlerTTSForConditionalGeneration
-    with torch.no_grad():
-        kw = {"attention_mask": dm, "prompt_attention_mask": pm}
-        kw = cls._prepare_text_encoder_kwargs_for_generation(stub, desc, kw, "input_ids", GenerationConfig())
-        kw = cls._prepare_prompt_kwargs_for_generation(stub, prompt_ids, kw)
-    want_enc = kw["encoder_outputs"].last_hidden_state
+    def live():
+        stub = types.SimpleNamespace(text_encoder=m.text_encoder, get_text_encoder=lambda: m.text_encoder, decoder=types.SimpleNamespace(config=types.SimpleNamespace(hidden_size=dec.hidden_size, cross_attention_hidden_size=None)),
+                                     enc_to_dec_proj=m.enc_to_dec_proj, embed_prompts=m.embed_prompts, prompt_cross_attention=pca, device=torch.device("cpu"),
+                                     embed_positions=M.ParlerTTSSinusoidalPositionalEmbedding(dec.max_position_embeddings, dec.hidden_size))
+        cls = M.ParlerTTSForConditionalGeneration
+        with torch.no_grad():
+            kw = {"attention_mask": dm, "prompt_attention_mask": pm}
+            kw = cls._prepare_text_encoder_kwargs_for_generation(stub, desc, kw, "input_ids", GenerationConfig())
+            kw = cls._prepare_prompt_kwargs_for_generation(stub, prompt_ids, kw)
+        return {"encoder_outputs": kw["encoder_outputs"].last_hidden_state, "attention_mask": kw["attention_mask"],
+                "prompt_hidden_states": kw.get("prompt_hidden_states"), "prompt_attention_mask": kw.get("prompt_attention_mask")}
+
+    kw = rec(ref, f"conditioning_pca{int(pca)}_dm{int(desc_mask)}_pm{int(prompt_mask)}", live)
+    want_enc = kw["encoder_outputs"]
 
     def same(a, b):
         return (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and torch.allclose(a.float(), b.float(), atol=1e-6))
@@ -139,7 +223,7 @@ def test_decoder_start_columns_match_reference_helper_live(ref, given):
 
     import parler_tts_amd as P
 
-    M = ref.modeling_parler_tts
+    M = ref.modeling_parler_tts if ref is not None else None
     torch.manual_seed(5)
     t5 = T5Config(vocab_size=128, d_model=128, d_kv=32, d_ff=256, num_layers=2, num_heads=4, feed_forward_proj="gated-gelu")
     dec = P.ParlerTTSDecoderConfig(vocab_size=1088, max_position_embeddings=256, num_hidden_layers=2, ffn_dim=256, num_attention_heads=2,
@@ -184,15 +268,20 @@ def test_decoder_start_columns_match_reference_helper_live(ref, given):
     with pytest.raises(Stop):
         m.generate(input_ids=desc[:1], prompt_input_ids=prompt_ids[:1], decoder_input_ids=None if user is None else user[:K],
                    do_sample=False, max_new_tokens=max_new, streamer=st)
-    stub = types.SimpleNamespace(decoder=types.SimpleNamespace(num_codebooks=K), prompt_cross_attention=True, device=torch.device("cpu"),
-                                 _get_decoder_start_token_id=lambda a, b: a if a is not None else b)
-    kw = {} if user is None else {"decoder_input_ids": user[:K].clone()}
-    ids, _ = M.ParlerTTSForConditionalGeneration._prepare_decoder_input_ids_for_generation(stub, 1, "input_ids", kw, decoder_start_token_id=1025,
-                                                                                         bos_token_id=1025, device=torch.device("cpu"))
+    def live():
+        stub = types.SimpleNamespace(decoder=types.SimpleNamespace(num_codebooks=K), prompt_cross_attention=True, device=torch.device("cpu"),
+                                     _get_decoder_start_token_id=lambda a, b: a if a is not None else b)
+        kw = {} if user is None else {"decoder_input_ids": user[:K].clone()}
+        ids, _ = M.ParlerTTSForConditionalGeneration._prepare_decoder_input_ids_for_generation(stub, 1, "input_ids", kw, decoder_start_token_id=1025,
+                                                                                             bos_token_id=1025, device=torch.device("cpu"))
+        want, _ = ref.build_delay_pattern_mask(ids, 1025, 1024, max_new + ids.shape[1], K)
+        return {"ids": ids, "want": want}
+
+    r = rec(ref, f"start_columns_{given}", live)
+    ids, want = r["ids"], r["want"]
     n_given = ids.shape[1]
     assert n_given == (1 if user is None else 1 + T)
     max_length = max_new + n_given  # :3458-3469: max_new_tokens counts from the given decoder columns
-    want, _ = ref.build_delay_pattern_mask(ids, 1025, 1024, max_length, K)
     assert eng.max_length == max_length
     assert st.first is not None and torch.equal(st.first, want)
     if user is None:
@@ -251,8 +340,8 @@ def test_generate_ids_equal_a_loop_of_the_reference_generate_time_functions_live
 
     import oracle.make_golden as mg
 
-    M = ref.modeling_parler_tts
-    C = M.ParlerTTSForConditionalGeneration
+    M = ref.modeling_parler_tts if ref is not None else None
+    C = M.ParlerTTSForConditionalGeneration if M is not None else None
     m, spec, sd, eng = _product_model_with_oracle_engine(pca)
     K, bos, pad, eos = spec.num_codebooks, spec.bos_token_id, spec.pad_token_id, spec.eos_token_id
     g = torch.Generator().manual_seed(21 + 2 * int(pca) + int(prefix))
@@ -269,47 +358,53 @@ def test_generate_ids_equal_a_loop_of_the_reference_generate_time_functions_live
                max_length=L, min_new_tokens=min_new)
     mine = eng.full  # [B*K, columns]: the delayed ids of the whole run
     # --- the reference's functions -------------------------------------------------------------------------------------------------
-    lm = mg.build_reference_lm(ref, spec, sd)
-    lm.config.cross_attention_hidden_size = None
-    stub = types.SimpleNamespace(
-        text_encoder=m.text_encoder, get_text_encoder=lambda: m.text_encoder, decoder=lm, embed_prompts=m.embed_prompts, prompt_cross_attention=pca,
-        embed_positions=M.ParlerTTSSinusoidalPositionalEmbedding(256, spec.hidden_size),
-        device=torch.device("cpu"), config=types.SimpleNamespace(use_return_dict=True, decoder=types.SimpleNamespace(audio_channels=1)),
-        generation_config=types.SimpleNamespace(bos_token_id=bos, pad_token_id=pad, max_length=L),
-        _get_decoder_start_token_id=lambda a, b: a if a is not None else b)
-    with torch.no_grad():
-        kw = {"attention_mask": dm, "prompt_attention_mask": pm}
-        if prefix:
-            kw["decoder_input_ids"] = codes.clone()
-        kw = C._prepare_text_encoder_kwargs_for_generation(stub, desc, kw, "input_ids", GenerationConfig())
-        kw = C._prepare_prompt_kwargs_for_generation(stub, prompt_ids, kw)
-        ids, kw = C._prepare_decoder_input_ids_for_generation(stub, B, "input_ids", kw, decoder_start_token_id=bos, bos_token_id=bos,
-                                                              device=torch.device("cpu"))
-        given = ids.shape[1]
-        assert given == 1 + T0
-        seq, pattern = lm.build_delay_pattern_mask(ids, bos_token_id=bos, pad_token_id=pad, max_length=L)
-        kw["decoder_delay_pattern_mask"] = pattern
-        kw["past_key_values"] = EncoderDecoderCache(DynamicCache(), DynamicCache())
-        kw["use_cache"] = True
-        kw = C._get_initial_cache_position(stub, seq, kw)
-        assert kw["cache_position"].tolist() == list(range((0 if pca else Pn) + given))  # prompt positions (unless cross-attended) + given columns
-        proc = M.ParlerTTSLogitsProcessor(eos, K, B, "cpu")
-        unfinished = torch.ones(B * K, dtype=torch.long)
-        while True:
-            inputs = C.prepare_inputs_for_generation(stub, seq, **kw)
-            out = C.forward(stub, **inputs, return_dict=True)
-            scores = out.logits[:, -1, :].clone().float()
-            if seq.shape[-1] - given < min_new:
-                scores[:, eos] = -math.inf
-            scores = proc(seq, scores)
-            nxt = torch.argmax(scores, dim=-1)
-            nxt = nxt * unfinished + pad * (1 - unfinished)
-            seq = torch.cat([seq, nxt[:, None]], dim=-1)
-            kw["past_key_values"] = out.past_key_values
-            kw["cache_position"] = kw["cache_position"][-1:] + 1  # GenerationMixin._update_model_kwargs_for_generation
-            unfinished = unfinished & ~((nxt == eos) | (seq.shape[-1] >= L)).long()
-            if unfinished.max() == 0:
-                break
+    def live():
+        lm = mg.build_reference_lm(ref, spec, sd)
+        lm.config.cross_attention_hidden_size = None
+        stub = types.SimpleNamespace(
+            text_encoder=m.text_encoder, get_text_encoder=lambda: m.text_encoder, decoder=lm, embed_prompts=m.embed_prompts, prompt_cross_attention=pca,
+            embed_positions=M.ParlerTTSSinusoidalPositionalEmbedding(256, spec.hidden_size),
+            device=torch.device("cpu"), config=types.SimpleNamespace(use_return_dict=True, decoder=types.SimpleNamespace(audio_channels=1)),
+            generation_config=types.SimpleNamespace(bos_token_id=bos, pad_token_id=pad, max_length=L),
+            _get_decoder_start_token_id=lambda a, b: a if a is not None else b)
+        with torch.no_grad():
+            kw = {"attention_mask": dm, "prompt_attention_mask": pm}
+            if prefix:
+                kw["decoder_input_ids"] = codes.clone()
+            kw = C._prepare_text_encoder_kwargs_for_generation(stub, desc, kw, "input_ids", GenerationConfig())
+            kw = C._prepare_prompt_kwargs_for_generation(stub, prompt_ids, kw)
+            ids, kw = C._prepare_decoder_input_ids_for_generation(stub, B, "input_ids", kw, decoder_start_token_id=bos, bos_token_id=bos,
+                                                                  device=torch.device("cpu"))
+            given = ids.shape[1]
+            seq, pattern = lm.build_delay_pattern_mask(ids, bos_token_id=bos, pad_token_id=pad, max_length=L)
+            kw["decoder_delay_pattern_mask"] = pattern
+            kw["past_key_values"] = EncoderDecoderCache(DynamicCache(), DynamicCache())
+            kw["use_cache"] = True
+            kw = C._get_initial_cache_position(stub, seq, kw)
+            first_positions = kw["cache_position"].clone()
+            proc = M.ParlerTTSLogitsProcessor(eos, K, B, "cpu")
+            unfinished = torch.ones(B * K, dtype=torch.long)
+            while True:
+                inputs = C.prepare_inputs_for_generation(stub, seq, **kw)
+                out = C.forward(stub, **inputs, return_dict=True)
+                scores = out.logits[:, -1, :].clone().float()
+                if seq.shape[-1] - given < min_new:
+                    scores[:, eos] = -math.inf
+                scores = proc(seq, scores)
+                nxt = torch.argmax(scores, dim=-1)
+                nxt = nxt * unfinished + pad * (1 - unfinished)
+                seq = torch.cat([seq, nxt[:, None]], dim=-1)
+                kw["past_key_values"] = out.past_key_values
+                kw["cache_position"] = kw["cache_position"][-1:] + 1  # GenerationMixin._update_model_kwargs_for_generation
+                unfinished = unfinished & ~((nxt == eos) | (seq.shape[-1] >= L)).long()
+                if unfinished.max() == 0:
+                    break
+        return {"seq": seq, "given": torch.tensor(given), "first_positions": first_positions}
+
+    r = rec(ref, f"generate_ids_masks{int(masks)}_pca{int(pca)}_prefix{int(prefix)}", live)
+    seq, given = r["seq"], int(r["given"])
+    assert given == 1 + T0
+    assert r["first_positions"].tolist() == list(range((0 if pca else Pn) + given))  # prompt positions (unless cross-attended) + given columns
     assert seq.shape == mine.shape and seq.shape[1] > given + 8, (seq.shape, mine.shape)
     assert torch.equal(seq, mine)
     assert int((seq[:, given:] == eos).any(dim=1).sum()) >= 2  # EOS really happened on some rows: the gate and the padding were exercised
@@ -317,11 +412,26 @@ def test_generate_ids_equal_a_loop_of_the_reference_generate_time_functions_live
 
 def test_delay_pattern_closed_form_equals_reference_function_property_live(ref):
     """hypothesis: this package's closed-form build_delay_pattern_mask against the reference's loop-built one (modeling:214-276) over
-    random codebook counts, batch sizes, given columns and max lengths (the domain the reference's loop accepts, :241-243)."""
+    random codebook counts, batch sizes, given columns and max lengths (the domain the reference's loop accepts, :241-243). Without the
+    reference tree: 120 cases drawn from the same domain with a fixed seed, against the reference's recorded answers."""
+    import parler_tts_amd as P
+
+    g = torch.Generator().manual_seed(318)
+    cases = []
+    while len(cases) < 120:
+        K, bsz, seq_len, extra, seed = (int(torch.randint(lo, hi + 1, (1,), generator=g)) for lo, hi in ((1, 9), (1, 3), (1, 12), (0, 30), (0, 10_000)))
+        if seq_len + extra < 2 * K - 1 or seq_len + extra >= seq_len + K - 1:
+            cases.append((K, bsz, seq_len, extra, seed))
+    for i, (K, bsz, seq_len, extra, seed) in enumerate(cases):
+        ids = torch.randint(0, 1024, (bsz * K, seq_len), generator=torch.Generator().manual_seed(seed))
+        ids[:, 0] = 1025
+        a = rec(ref, f"delay_property_case{i}", lambda: ref.build_delay_pattern_mask(ids, 1025, 1024, seq_len + extra, K))
+        b = P.build_delay_pattern_mask(ids, 1025, 1024, seq_len + extra, K)
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (K, bsz, seq_len, extra, seed)
+    if ref is None:
+        return
     hypothesis = pytest.importorskip("hypothesis")
     from hypothesis import given, settings, strategies as st
-
-    import parler_tts_amd as P
 
     @settings(max_examples=120, deadline=None)
     @given(K=st.integers(1, 9), bsz=st.integers(1, 3), seq_len=st.integers(1, 12), extra=st.integers(0, 30), seed=st.integers(0, 10_000))
@@ -345,8 +455,6 @@ def test_streamer_equals_reference_streamer_on_random_streams_live(ref, seed):
     import types
 
     import numpy as np
-    from parler_tts.streamer import ParlerTTSStreamer as RefStreamer
-
     import oracle.make_golden as mg
     from oracle import dac_oracle as DA
     from oracle import decoder_oracle as DO
@@ -358,7 +466,6 @@ def test_streamer_equals_reference_streamer_on_random_streams_live(ref, seed):
     L = int(torch.randint(30, 70, (1,), generator=g))
     play_steps = int(torch.randint(10, 24, (1,), generator=g))
     stride = None if seed % 2 == 0 else int(torch.randint(0, 40, (1,), generator=g))
-    dec = mg.build_reference_lm(ref, spec, DO.make_decoder_weights(spec, seed=1234))
     dac = DA.DacOracle(DA.DAC_TINY, DA.make_dac_weights(DA.DAC_TINY, seed=4321))
     hop = DA.DAC_TINY.hop_length
 
@@ -381,10 +488,7 @@ def test_streamer_equals_reference_streamer_on_random_streams_live(ref, seed):
     raw = torch.randint(0, 1024, (K, L), generator=g)
     for _ in range(seed % 3):  # special ids mid-stream: the frame that holds one is dropped (streamer.py:95-104)
         raw[int(torch.randint(0, K, (1,), generator=g)), int(torch.randint(12, L - 1, (1,), generator=g))] = spec.eos_token_id
-    first, _ = dec.build_delay_pattern_mask(torch.full((K, 1), spec.bos_token_id), bos_token_id=spec.bos_token_id, pad_token_id=spec.pad_token_id,
-                                            max_length=L)
-    outs = []
-    for cls, decoder in ((RefStreamer, dec), (ParlerTTSStreamer, types.SimpleNamespace(num_codebooks=K))):
+    def run(cls, decoder, first):
         model = types.SimpleNamespace(decoder=decoder, audio_encoder=Codec(), generation_config=gc, device=torch.device("cpu"),
                                       use_audio_scales=True, use_4dim_audio_codes=True)
         st = cls(model, play_steps=play_steps, stride=stride)
@@ -392,8 +496,20 @@ def test_streamer_equals_reference_streamer_on_random_streams_live(ref, seed):
         for j in range(1, L):
             st.put(raw[:, j])
         st.end()
-        outs.append([np.asarray(c) for c in st])
-    want, got = outs
+        return [np.asarray(c) for c in st]
+
+    def live():
+        from parler_tts.streamer import ParlerTTSStreamer as RefStreamer
+
+        dec = mg.build_reference_lm(ref, spec, DO.make_decoder_weights(spec, seed=1234))
+        first, _ = dec.build_delay_pattern_mask(torch.full((K, 1), spec.bos_token_id), bos_token_id=spec.bos_token_id, pad_token_id=spec.pad_token_id,
+                                                max_length=L)
+        return {"first": first, "chunks": run(RefStreamer, dec, first)}
+
+    lv = live() if ref is not None else None
+    first = rec(ref, f"streamer_seed{seed}_first", lambda: lv["first"])
+    want = [np.asarray(c) for c in rec(ref, f"streamer_seed{seed}_chunks", lambda: lv["chunks"])]
+    got = run(ParlerTTSStreamer, types.SimpleNamespace(num_codebooks=K), first)
     assert len(want) >= 2 and [len(c) for c in got] == [len(c) for c in want], ([len(c) for c in got], [len(c) for c in want])
     for a, b in zip(got, want):  # window decode vs whole-cache decode on the CPU conv kernels: fp32 summation order differs at the 1e-6 level
         assert np.allclose(a, b, atol=2e-5), float(np.abs(a - b).max())
@@ -439,8 +555,8 @@ def test_bf16_oracle_sits_between_reference_fp32_and_reference_bf16_live(ref):
         del m
         return torch.stack(out)
 
-    ref32 = run_reference(torch.float32)
-    ref16 = run_reference(torch.bfloat16)
+    ref32 = rec(ref, "bf16_pin_ref32", lambda: run_reference(torch.float32))
+    ref16 = rec(ref, "bf16_pin_ref16", lambda: run_reference(torch.bfloat16))
     orc = DO.DecoderOracle(spec, sd, precision="bf16")
     o = [orc.forward(ids0, enc, enc_mask, prompt, prompt_mask)[:, -1]]
     for s in range(steps):
