@@ -61,17 +61,8 @@ struct PttsPerDeviceOnce {
 
 // ---- environment switches ------------------------------------------------------------------------------------------------------
 // The product library reads FIFTEEN PTTS_* variables with getenv: each selects the un-fused / alternative side of a node that a parity test
-// compares with the default path (table in DESIGN.md section 6; tests/test_host_logic.py counts them). Every other switch that rounds 1-6 used
-// for an A/B measurement is a development knob: ptts_dev_env() answers nullptr in the product build, so the library takes the measured default
-// and the compiler folds the other side away; `tools/build_variant.sh <name> -DPTTS_DEV_KNOBS` builds a probe library that reads them.
-inline const char* ptts_dev_env(const char* name) {
-#ifdef PTTS_DEV_KNOBS
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
+// compares with the default path (table in DESIGN.md section 6; tests/test_host_logic.py counts them). The other switches that rounds 1-6 used
+// for A/B measurements were removed with the paths they selected; their measurements live in profiles/.
 
 // ---- kernel-argument preload (gfx950) ---------------------------------------------------------------------------------------------
 // A wave's first instructions are s_load of its kernel arguments: one scalar round trip before the first global load can be addressed.
@@ -153,9 +144,6 @@ __device__ __forceinline__ uint4 pack16(const float (&o)[8], bf16_t) {
 
 // 16-byte non-temporal (streamed-once) global load: weights are read exactly once per decode step
 __device__ __forceinline__ uint4 ld_nt16(const uint4* p) {
-#ifdef PTTS_WEIGHT_CACHED  // A/B experiment only (tools/l2_probe.py): let weight lines allocate in L2
-  return *p;
-#endif
   typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
   const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
   return make_uint4(v.x, v.y, v.z, v.w);

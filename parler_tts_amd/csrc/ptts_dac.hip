@@ -44,7 +44,7 @@ struct ConvArgs {
   int stride, Tn;      // input stride of a down-sampling conv (else 1); output frames per phase (Tin unless strided)
   const int* lens;     // ragged decode (ptts_dac_decode_ragged): latent frames per utterance [B] on the device, or null. Utterance b then has
   int len_mul;         // lens[b] * len_mul valid input rows (= output rows per phase): rows beyond read as the zero padding, tiles beyond exit
-  int epi_direct;      // conv_lds_kernel A/B (PTTS_DAC_EPI_DIRECT=1): the round-3 epilogue (a lane stores 4 channels of one frame)
+  int epi_direct;      // conv_lds_kernel: the round-3 epilogue (a lane stores 4 channels of one frame); 0 on every launch (measured A/B path)
 };
 
 // valid input rows of utterance b (buffers keep the full stride a.Tin)
@@ -58,12 +58,8 @@ __device__ __forceinline__ int valid_rows(const ConvArgs& a, int b) { return a.l
 template <bool FAST>
 __device__ __forceinline__ float snake_f(float x, float al, float inv) {
   float s;
-#ifdef PTTS_DAC_FAST_SIN
-  s = __sinf(al * x);
-#else
   if constexpr (FAST) s = __sinf(al * x);
   else s = sinf(al * x);
-#endif
   return x + inv * (s * s);
 }
 __device__ __forceinline__ float4 ld_inv4(const float* alpha, int C, int c) { return *reinterpret_cast<const float4*>(alpha + C + c); }
@@ -458,7 +454,7 @@ struct ResArgs {
   float* out_raw;       // fp32 residual stream after the unit (may alias skip), or null
   void* out_act;        // activated output, bf16 (fp32 if act_f32): NOT the buffer x lives in (neighbouring tiles read x's halo rows)
   int act_f32;
-  int epi_direct;       // A/B (PTTS_DAC_EPI_DIRECT=1): the round-3 epilogue (a lane owns 4 channels of one frame: 64-byte pieces of the stream)
+  int epi_direct;       // the round-3 epilogue (a lane owns 4 channels of one frame: 64-byte pieces of the stream); 0 on every launch (measured A/B path)
   const float* alpha_in;  // XIN instances: [alpha | 1 / (alpha + 1e-9)] of the Snake that turns the fp32 stream `a.x` into this unit's input activation
 };
 
@@ -1397,34 +1393,23 @@ static int run_conv(ptts_dac* d, const ConvLayer& L, const void* x, const float*
   // LDS-tiled kernel where it wins (rocprof per layer, profiles/r02_dac_layers.txt): every k7 conv (2x the direct kernel) and the
   // transposed convs into >= 192 channels. The last transposed conv is bound by its epilogue traffic (two writes per element) and runs as fast
   // on the direct kernel's 4-5 waves per SIMD as on this one's 2 (round 2 said the same of the k1 convs; see lds_k1 below).
-  static const bool no_lds = ptts_dev_env("PTTS_DAC_NO_LDS") != nullptr;
-  static const int lds_min_c = ptts_dev_env("PTTS_DAC_LDS_MIN_C") ? atoi(ptts_dev_env("PTTS_DAC_LDS_MIN_C")) : 96;
-  static const bool lds_small_taps = ptts_dev_env("PTTS_DAC_LDS_K1") != nullptr;
   // k1 convs (the un-fused units of the C = 768 block): on the LDS-tiled kernel from 32 K rows per launch (round 5) - with the whole-row epilogue
   // through LDS it beats the direct kernel at batch 32 (63.1 -> 61.3 ms per decode) and loses 1 % on a single utterance's 6880 rows (2.69 vs 2.71 ms;
-  // profiles/r05_experiments.txt calls 13 / 15). PTTS_DAC_NO_LDS_K1=1: always direct; PTTS_DAC_LDS_K1=1: every k1 / transposed conv on the LDS kernel.
-  static const bool lds_k1_on = !(ptts_dev_env("PTTS_DAC_NO_LDS_K1") && atoi(ptts_dev_env("PTTS_DAC_NO_LDS_K1")));
-  const bool lds_k1 = lds_k1_on && (long long)B * Tin >= 32768;
+  // profiles/r05_experiments.txt calls 13 / 15).
+  const bool lds_k1 = (long long)B * Tin >= 32768;
   // the last transposed conv (-> 96 channels): on the LDS-tiled kernel since round 5. Round 4 measured it equal to the direct kernel (5.19 ms per
   // batch-32 launch) - with the 96-channel staging instance, which needs 324 VGPRs and ran one wave per SIMD; with 32-channel staging chunks
   // (conv_lds_kernel<3, 2, 1, 2>, 228 VGPRs, two waves per SIMD) the batch-32 decode drops 61.3 -> 59.3 ms, 860 frames 2.71 -> 2.67 ms
-  // (profiles/r05_experiments.txt call 15). PTTS_DAC_LAST_UP_LDS=0: the direct kernel.
-  static const bool last_up_lds = !(ptts_dev_env("PTTS_DAC_LAST_UP_LDS") && !atoi(ptts_dev_env("PTTS_DAC_LAST_UP_LDS")));
-  const bool lds_ok = a.ntaps > 2 ? L.Cout >= lds_min_c
-                                  : (lds_small_taps || (a.transposed && L.Cout >= (last_up_lds ? 96 : 192)) || (lds_k1 && !a.transposed && a.ntaps == 1));
-  {
-    const char* ced = ptts_dev_env("PTTS_DAC_EPI_DIRECT");  // read per call (A/B inside one process): the same switch as the fused residual unit's epilogue
-    a.epi_direct = (ced && atoi(ced)) ? 1 : 0;
-  }
-  if (L.bf16 && !no_lds && lds_ok && a.stride == 1 && nstrips % 6 == 0) {
+  // (profiles/r05_experiments.txt call 15).
+  const bool lds_ok = a.ntaps > 2 ? L.Cout >= 96 : ((a.transposed && L.Cout >= 96) || (lds_k1 && !a.transposed && a.ntaps == 1));
+  if (L.bf16 && lds_ok && a.stride == 1 && nstrips % 6 == 0) {
     const int nw = nstrips % 12 == 0 ? 4 : 2;
     const int halo = a.transposed ? a.ntaps - 1 : (a.ntaps - 1) * a.dil;
     // 64-frame tiles (FT = 4) where 128-frame tiles would leave the launch with about one workgroup per CU or fewer (round 5: the first block of a
     // single utterance ran 56-224 workgroups on 256 CUs; the streamer's short windows even fewer): 860 frames 2.34 -> 2.27 ms, a 56-frame window
     // 0.91 -> 0.82 ms; at 432-448 workgroups (two utterances) the smaller tiles LOSE 3.5 % (profiles/r05_experiments.txt call 18), hence the bound.
-    // Four-wave instances only; PTTS_DAC_NO_FT4=1: always 128 frames.
-    static const bool ft4_on = !(ptts_dev_env("PTTS_DAC_NO_FT4") && atoi(ptts_dev_env("PTTS_DAC_NO_FT4")));
-    const bool ft4 = ft4_on && nw == 4 && (long long)((a.Tn + 127) / 128) * a.nphase * B * (nstrips / (3 * nw)) < 320;
+    // Four-wave instances only.
+    const bool ft4 = nw == 4 && (long long)((a.Tn + 127) / 128) * a.nphase * B * (nstrips / (3 * nw)) < 320;
     const int tfr = ft4 ? 64 : 128;
     const dim3 grid((unsigned)(((a.Tn + tfr - 1) / tfr) * a.nphase * B), (unsigned)(nstrips / (3 * nw)));
     bool done = true;
@@ -1450,13 +1435,11 @@ static int run_conv(ptts_dac* d, const ConvLayer& L, const void* x, const float*
   }
   // waves per workgroup: fewer (finer tiles) when the launch would otherwise put < ~6 workgroups on each CU, so the
   // 256 CUs finish together (324 four-wave workgroups on 256 CUs = 63 % balance; 1296 one-wave ones = 84 %+)
-  static int forced_nw = ptts_dev_env("PTTS_DAC_WAVES") ? atoi(ptts_dev_env("PTTS_DAC_WAVES")) : 0;
   int nwb = 4;
   {
     const int CS0 = nstrips % 8 == 0 ? 8 : (nstrips % 6 == 0 ? 6 : (nstrips % 4 == 0 ? 4 : (nstrips % 2 == 0 ? 2 : 1)));
     auto blocks = [&](int nw) { return (long long)((a.Tn + 32 * nw - 1) / (32 * nw)) * a.nphase * B * (nstrips / CS0); };
     while (nwb > 1 && blocks(nwb) < 256LL * 6) nwb >>= 1;
-    if (forced_nw == 1 || forced_nw == 2 || forced_nw == 4) nwb = forced_nw;
   }
   const int ntile = (a.Tn + 32 * nwb - 1) / (32 * nwb);
   // strips per wave: the largest of {8, 6, 4, 2, 1} that divides the layer (real DAC widths: 96/48/24/12/6 strips)
@@ -1497,10 +1480,8 @@ static bool resunit_fusable(const ConvLayer& c7, const ConvLayer& c1) {
 // Measured on MI355X (profiles/r06_dac_xin_ab.txt, r06_dac_up_order_ab.txt; ms per decode of 860 frames, mask 0 | 1 | 3 | 7): 32 utterances 56.16 | 54.86 |
 // 54.35 | 53.99, 8: - | 14.30 | - | 14.13, 4: - | 7.69 | - | 7.55, one utterance 2.409 | 2.316 | 2.335 | 2.349 - the wider units gain only where the launch
 // is bandwidth-bound, hence by the latent frames of the call. PTTS_DAC_XIN=<mask> is read per call (a test switches it inside one process: every mask
-// gives the same bits); the round-3 epilogue (PTTS_DAC_EPI_DIRECT=1, an A/B path) exists for the units on the bf16 activation only.
+// gives the same bits).
 static bool resunit_xin_width(int C, long long frames) {
-  const char* ed = ptts_dev_env("PTTS_DAC_EPI_DIRECT");
-  if (ed && atoi(ed)) return false;
   const char* ev = getenv("PTTS_DAC_XIN");
   const int m = ev ? atoi(ev) : (frames >= 2 * 860 ? 7 : 1);
   return (C == 96 && (m & 1)) || (C == 192 && (m & 2)) || (C == 384 && (m & 4));
@@ -1515,17 +1496,13 @@ static int run_resunit(const ConvLayer& c7, const ConvLayer& c1, const void* x, 
   r.a.B = B; r.a.Tin = T; r.a.Tn = T; r.a.Cin = c7.Cin; r.a.Cout = c7.Cout; r.a.ntaps = 7; r.a.nphase = 1; r.a.stride = 1;
   r.Wp1 = c1.Wp; r.bias1 = c1.bias; r.alpha1 = c1.alpha; r.skip = skip; r.out_raw = out_raw; r.out_act = out_act; r.act_f32 = act_f32 ? 1 : 0;
   r.alpha_in = alpha_in;
-  {
-    const char* ed = ptts_dev_env("PTTS_DAC_EPI_DIRECT");  // read per call (A/B inside one process, like PTTS_DAC_NO_FUSE_RES)
-    r.epi_direct = (ed && atoi(ed)) ? 1 : 0;
-  }
   const dim3 grid((unsigned)(((T + 127) / 128) * B));
   // instances by (width, stream written?, fp32 activation?, input from the stream?, activation written?): compile-time in the kernel (its epilogue is
   // straight-line code). The two-register-set weight prefetch (WD = 1, round 3) serves the XIN instances at C = 96 (registers: see the kernel).
   const bool raw = out_raw != nullptr, xin = alpha_in != nullptr, act = out_act != nullptr;
   if (!act && !(xin && raw)) return ptts_fail(PTTS_E_INVALID, "residual unit: no activation output");
-  if (xin && ((const void*)skip != x || (const void*)out_raw == x || r.epi_direct))
-    return ptts_fail(PTTS_E_INVALID, "residual unit on the stream: x must be the skip buffer, out_raw another one, whole-row epilogue");
+  if (xin && ((const void*)skip != x || (const void*)out_raw == x))
+    return ptts_fail(PTTS_E_INVALID, "residual unit on the stream: x must be the skip buffer, out_raw another one");
   if (act_f32 && c7.Cout != 96) return ptts_fail(PTTS_E_UNSUPPORTED, "residual unit: fp32 activations only at the last block's width");
 #define PTTS_RU_LAUNCH(NWV, RAWV, F32V) \
   hipLaunchKernelGGL((resunit_lds_kernel<NWV, 1, 3, RAWV, F32V>), grid, dim3(NWV * 64), (ResunitLds<NWV, 1>::bytes), st, r)
@@ -1649,8 +1626,7 @@ static int dac_decode_window(ptts_dac* d, const int64_t* codes_dev, long long ld
     }
   }
   const int t_end = emit < 0 ? Tcur : std::min(Tcur, skip + emit);
-  static const bool out_direct = ptts_dev_env("PTTS_DAC_OUT_DIRECT") && atoi(ptts_dev_env("PTTS_DAC_OUT_DIRECT"));  // A/B: the per-thread kernel
-  if (d->out_C == OUT_C && !out_direct && B <= 65535) {
+  if (d->out_C == OUT_C && B <= 65535) {  // otherwise the per-thread kernel
     hipLaunchKernelGGL(conv_out_tanh_lds_kernel, dim3((unsigned)((Tcur + OUT_TILE - 1) / OUT_TILE), (unsigned)B), dim3(OUT_TILE), 0, st, (const float*)cur,
                        d->out_w, d->out_b, wave_dev, Tcur, skip, out_ld, t_end, lens, mul);
   } else {

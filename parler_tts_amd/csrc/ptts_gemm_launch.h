@@ -2,7 +2,6 @@
 // (ptts_lm.hip) and the T5 description encoder (ptts_t5.hip). Every function is internal to its translation unit (anonymous namespace).
 #pragma once
 #include <algorithm>
-#include <stdlib.h>
 
 #include "ptts_common.h"
 #include "ptts_lm_kernels.h"
@@ -15,27 +14,16 @@ namespace {
 // weight fragment). Fewer rows = more, lighter workgroups (the N = 1024 projections run on N / 16 = 64 workgroups per pass) at the price of one L2 re-read
 // of every strip per pass. Measured, us per Mini-v1 step at mid context, rows 64 / 32 / 16 (profiles/r04_experiments.txt call 25):
 //   24: 1235 / 1236 / 1191   32: 1291 / 1292 / 1241   48: 1766 / 1594 / 1554   64: 1958 / 1762 / 1828   96: 2293 / 2183 / 2272   128: 2580 / 2546 / 2713
-// -> 2..3 passes of the smallest tile: 16 rows up to 48 utterances, 32 above (56 utterances: 1764 us on 16-row passes, 60 on 32-row passes 1725; PTTS_MSPLIT_ROWS forces one). Round 3 ran one 32-row pass up to 32
+// -> 2..3 passes of the smallest tile: 16 rows up to 48 utterances, 32 above (56 utterances: 1764 us on 16-row passes, 60 on 32-row passes 1725). Round 3 ran one 32-row pass up to 32
 // utterances and 64-row passes above.
 // `decode` (GemmArgs::decode, set by the caller): the measured policy applies to decode steps; prefill-sized rows keep the 64-row passes
 inline int msplit_rows(int M, int N, bool decode) {
-  static const int forced = [] {
-    const char* ev = ptts_dev_env("PTTS_MSPLIT_ROWS");
-    const int x = ev ? atoi(ev) : 0;
-    return (x == 16 || x == 32 || x == 64) ? x : 0;
-  }();
-  if (forced) return forced;
   // prefill rows (time-to-first-token path): the decode policy only where 64-row passes leave the projection with fewer workgroups than CUs
   // (strips x passes < 256: the N = 1024 .. 3072 projections of a short prompt); wide projections keep the 64-row passes. Measured, prefill + first
   // token in ms (profiles/r04_experiments.txt calls 27-28), 64-row passes | lighter everywhere | lighter where strips x passes < 128:
   //   Mini-v1 33 rows 1.89 | 1.57 | 1.63   66 rows 2.16 | 1.95 | 2.16   101 rows 2.34 | 2.13 | 2.31   132 rows 2.75 | 2.69 | 2.73   fp32 33 rows 3.47 | 2.32 | 2.32
   //   Large-v1 33 rows 3.17 | 3.36 | 3.17 (its 288- / 384-strip projections lose on light passes)
-  // PTTS_MSPLIT_PREFILL = 0: never, 1: everywhere, 2 (default): by workgroup count
-  static const int prefill_mode = ptts_dev_env("PTTS_MSPLIT_PREFILL") ? atoi(ptts_dev_env("PTTS_MSPLIT_PREFILL")) : 2;
-  if (!decode) {
-    const bool lighter = prefill_mode == 1 || (prefill_mode == 2 && N > 0 && (N / 16) * ((M + 63) / 64) < 256);
-    if (!lighter) return M > 32 ? 64 : 32;
-  }
+  if (!decode && !(N > 0 && (N / 16) * ((M + 63) / 64) < 256)) return M > 32 ? 64 : 32;
   if (N >= 8192) return M > 32 ? 64 : 32;  // the LM heads (612 strips): plenty of workgroups already - light passes cost 7.4 -> 10.6 us at 32 utterances (call 29)
   // (the wide projections - QKV, fc1, N >= 3072 - on their own pass size measured no better: 64-row passes for them cost +4 % at 48 / 64 utterances and
   //  are within 0.5 % at 96 / 128, profiles/r04_experiments.txt call 31: one policy for every projection below 8192 rows)
@@ -57,9 +45,15 @@ int launch_gemm_inst(GemmArgs& a, dim3 grid, dim3 block, size_t sh, hipStream_t 
   return PTTS_OK;
 }
 
-// prefill-sized rows on the LDS-tiled kernel (gemm_tile_kernel): the largest tile that still gives every CU a workgroup
-template <typename WT, int EPI, int BNS, int BMT>
-int launch_gemm_tile_inst(const GemmArgs& a, hipStream_t st) {
+// prefill-sized rows on the LDS-tiled kernel (gemm_tile_kernel), 4 x 4 tiles of 16 x 16. Measured (profiles/r05_experiments.txt call 6, time to the
+// first token at 32 utterances = T5 on 2048 rows + prefill on 1056 rows, ms): register-blocked kernel 13.41 | tiles 8x8 14.38, 4x8 12.94, 8x4 11.57,
+// 4x4 11.43 -> the SMALLEST tile: three workgroups per CU hide the staging latency that two stages of register prefetch do not (the loop is still
+// latency-bound: ~250 TFLOP/s); larger tiles need an asynchronous global->LDS ring (ptts_gemm_glds.h). -1 = shape not served (the caller keeps the
+// register-blocked kernel)
+template <typename WT, int EPI>
+int launch_gemm_tile(const GemmArgs& a, hipStream_t st) {
+  constexpr int BNS = 4, BMT = 4;
+  if ((a.N / 16) % BNS || (a.K / Elem<WT>::KT) % 2 || a.K % Elem<WT>::KT) return -1;
   constexpr size_t sh = (size_t)2 * (BNS + BMT) * 2 * 64 * 16;
   static PttsPerDeviceOnce attr_once;
   const int attr_dev = PttsPerDeviceOnce::device();
@@ -73,30 +67,6 @@ int launch_gemm_tile_inst(const GemmArgs& a, hipStream_t st) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "gemm launch failed: %s", hipGetErrorString(e));
   return PTTS_OK;
-}
-// -1 = shape not served (the caller keeps the register-blocked kernel)
-template <typename WT, int EPI>
-int launch_gemm_tile(const GemmArgs& a, hipStream_t st) {
-  static const int mode = ptts_dev_env("PTTS_GEMM_TILE") ? atoi(ptts_dev_env("PTTS_GEMM_TILE")) : 1;  // 0: off (gemm_block_kernel), 1: by workgroup count, 88 / 48 / 84 / 44: force a tile
-  const int nstrips = a.N / 16, nfrag = a.K / Elem<WT>::KT;
-  if (!mode || nstrips % 4 || nfrag % 2 || a.K % Elem<WT>::KT) return -1;
-  auto wgs = [&](int bns, int bmt) { return (nstrips / bns) * ((a.M + bmt * 16 - 1) / (bmt * 16)); };
-  // measured (profiles/r05_experiments.txt call 6, time to the first token at 32 utterances = T5 on 2048 rows + prefill on 1056 rows, ms):
-  //   register-blocked kernel 13.41 | tiles 8x8 14.38, 4x8 12.94, 8x4 11.57, 4x4 11.43 -> the SMALLEST tile: three workgroups per CU hide the
-  //   staging latency that two stages of register prefetch do not (the loop is still latency-bound: ~250 TFLOP/s); larger tiles need an
-  //   asynchronous global->LDS ring (next step)
-  int pick = 44;
-  (void)wgs;
-  if (mode != 1) {
-    pick = mode;
-    if ((pick == 88 || pick == 84) && nstrips % 8) pick = pick == 88 ? 48 : 44;
-  }
-  switch (pick) {
-    case 88: return launch_gemm_tile_inst<WT, EPI, 8, 8>(a, st);
-    case 48: return launch_gemm_tile_inst<WT, EPI, 4, 8>(a, st);
-    case 84: return launch_gemm_tile_inst<WT, EPI, 8, 4>(a, st);
-    default: return launch_gemm_tile_inst<WT, EPI, 4, 4>(a, st);
-  }
 }
 
 template <typename WT, int PRO, int EPI>
@@ -147,13 +117,11 @@ int launch_gemm(GemmArgs a, hipStream_t st) {
     }
   }
   if constexpr (PRO == PRO_COPY) {
-    static const int block_min_m = ptts_dev_env("PTTS_BLOCK_MIN_M") ? atoi(ptts_dev_env("PTTS_BLOCK_MIN_M")) : 256;
+    constexpr int block_min_m = 256;
     // measured (tools/ttft_bs32_probe.py, Mini-v1 prefill ms, strip / block): M=132 5.7 / 8.2, 264 8.3 / 8.1, 528 13.5 / 8.7, 1056 25.7 / 11.2
-    static const int xcd_swz = !(ptts_dev_env("PTTS_GEMM_XCD") && !atoi(ptts_dev_env("PTTS_GEMM_XCD")));
-    a.xcd_swz = xcd_swz;
-    if constexpr (sizeof(WT) == 2) {  // bf16 engine: the LDS-DMA ring (round 6, ptts_gemm_glds.h); PTTS_GEMM_GLDS=0: round 5's register-staged tiles
-      static const bool glds_on = !(ptts_dev_env("PTTS_GEMM_GLDS") && !atoi(ptts_dev_env("PTTS_GEMM_GLDS")));
-      if (glds_on && a.M > block_min_m && EPI != EPI_GELU && !a.x_fo && (!a.kv_layers || EPI == EPI_KV) && !a.stats_out && !a.W8 && !a.rs_part && !a.nx_out) {
+    a.xcd_swz = 1;
+    if constexpr (sizeof(WT) == 2) {  // bf16 engine: the LDS-DMA ring (round 6, ptts_gemm_glds.h)
+      if (a.M > block_min_m && EPI != EPI_GELU && !a.x_fo && (!a.kv_layers || EPI == EPI_KV) && !a.stats_out && !a.W8 && !a.rs_part && !a.nx_out) {
         const int rg = launch_gemm_glds<EPI>(a, st);
         if (rg != -1) return rg;
       }
@@ -192,12 +160,13 @@ int launch_gemm(GemmArgs a, hipStream_t st) {
   return PTTS_OK;
 }
 
+// waves per workgroup: 4 (self-attention, prefill rows), or 1 / 2 / 4 (decode cross-attention: as few as cover the description)
 template <typename WT>
 int launch_attn(const AttnArgs& a, int B, hipStream_t st, int waves = 4) {
   const dim3 grid(a.S, a.nheads, B * a.Q);
   if (a.kscale) {  // e4m3 self-attention cache (ptts_config::kv_fp8): bf16 engine, 4 waves per workgroup
     if constexpr (sizeof(WT) == 2) {
-      if (waves != 4) return ptts_fail(PTTS_E_UNSUPPORTED, "kv_fp8: the attention kernel is built for 4 waves per workgroup (PTTS_ATTN_WAVES=%d)", waves);
+      if (waves != 4) return ptts_fail(PTTS_E_UNSUPPORTED, "kv_fp8: the attention kernel is built for 4 waves per workgroup (%d)", waves);
       hipLaunchKernelGGL((attn_kernel<WT, 4, true>), grid, dim3(256), 0, st, a);
       hipError_t e8 = hipGetLastError();
       if (e8 != hipSuccess) return ptts_fail(PTTS_E_HIP, "attn launch failed: %s", hipGetErrorString(e8));
@@ -208,9 +177,8 @@ int launch_attn(const AttnArgs& a, int B, hipStream_t st, int waves = 4) {
   }
   if (waves == 1) hipLaunchKernelGGL((attn_kernel<WT, 1>), grid, dim3(64), 0, st, a);
   else if (waves == 2) hipLaunchKernelGGL((attn_kernel<WT, 2>), grid, dim3(128), 0, st, a);
-  else if (waves == 8) hipLaunchKernelGGL((attn_kernel<WT, 8>), grid, dim3(512), 0, st, a);
-  else if (waves == 16) hipLaunchKernelGGL((attn_kernel<WT, 16>), grid, dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL((attn_kernel<WT, 4>), grid, dim3(256), 0, st, a);
+  else if (waves == 4) hipLaunchKernelGGL((attn_kernel<WT, 4>), grid, dim3(256), 0, st, a);
+  else return ptts_fail(PTTS_E_UNSUPPORTED, "attn: no instance for %d waves per workgroup", waves);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "attn launch failed: %s", hipGetErrorString(e));
   return PTTS_OK;

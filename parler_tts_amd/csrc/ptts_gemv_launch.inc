@@ -1,7 +1,6 @@
 // Instantiation + dispatch of gemv_kernel for ONE (engine dtype, weight format) pair: included by ptts_gemv_bf16.hip,
 // ptts_gemv_f32.hip and ptts_gemv_w8.hip with GV_WT / GV_W8 / GV_FN defined (three translation units compiled in parallel).
 #include <algorithm>
-#include <cstdlib>
 
 #include "ptts_gemv_kernels.h"
 
@@ -27,17 +26,14 @@ int launch_inst(const GemvArgs& a, hipStream_t st) {
     const int npw = PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * Elem<GV_WT>::EPL / 4 : MB);
     const dim3 grid((waves + 3) / 4), block((npw + 4) * 64);
     const size_t sh = PRO == GV_COPY ? 0 : (size_t)MB * a.K * sizeof(GV_WT);
-    if constexpr (PRO == GV_COPY && MB == 8 && MB * NCH * 1024 <= 64 * 1024) {
+    if constexpr (PRO == GV_COPY && MB == 8 && MB * NCH > 40 && MB * NCH * 1024 <= 64 * 1024) {
       // 5..8 utterances, activations streamed from memory: staged in LDS once per workgroup where the rows do not fit the registers in one
-      // group (Mini fc2: batch 8 step 1054 -> 967 us, batch 5 935 -> 891; profiles/r03_experiments.txt). PTTS_GEMV_STAGE=0: never, 2: every
-      // GV_COPY node (measured equal). Up to the 64 KiB of dynamic LDS a launch gets without opting in: the 96 KiB tile of the Large-v1 fc2
-      // (one workgroup per CU) measured no gain over the register groups and stays on them.
-      static const int stage = ptts_dev_env("PTTS_GEMV_STAGE") ? atoi(ptts_dev_env("PTTS_GEMV_STAGE")) : 1;
+      // group (Mini fc2: batch 8 step 1054 -> 967 us, batch 5 935 -> 891; profiles/r03_experiments.txt; staging every GV_COPY node measured
+      // equal). Up to the 64 KiB of dynamic LDS a launch gets without opting in: the 96 KiB tile of the Large-v1 fc2 (one workgroup per CU)
+      // measured no gain over the register groups and stays on them.
       constexpr size_t tile = (size_t)MB * NCH * 1024;  // MB rows of K * sizeof(WT) = NCH KiB
-      if (stage >= 2 || (stage == 1 && MB * NCH > 40)) {
-        ptts_klaunch(gemv_kernel<GV_WT, NCH, R, PRO, EPI, S, MB, GV_W8, true>, grid, block, tile, st, a);
-        return 0;
-      }
+      ptts_klaunch(gemv_kernel<GV_WT, NCH, R, PRO, EPI, S, MB, GV_W8, true>, grid, block, tile, st, a);
+      return 0;
     }
     ptts_klaunch(gemv_kernel<GV_WT, NCH, R, PRO, EPI, S, MB, GV_W8>, grid, block, sh, st, a);
     return 0;

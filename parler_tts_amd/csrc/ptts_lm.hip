@@ -50,8 +50,6 @@ struct ptts_engine {
   int max_prompt = 0;  // P + 1 rows capacity per utterance
   size_t esize = 4;
   hipStream_t own_stream = nullptr;
-  hipStream_t fold_stream = nullptr;   // cross-attention folding runs here, beside the rest of the prefill
-  hipEvent_t ev_kv = nullptr, ev_fold = nullptr;  // cross K/V cache written / folded matrices ready
   hipEvent_t ev_first = nullptr;                  // first token of the last prefill materialised (recorded right after the sampler tail)
   hipEvent_t ev_tail0 = nullptr;                  // recorded right before that sampler tail (ptts_first_token_times)
   hipEvent_t ev_pre0 = nullptr;                   // recorded when the stream reaches the last ptts_prefill's first piece of work
@@ -86,9 +84,7 @@ struct ptts_engine {
   int prefill_T = 0;                   // voice-prompt columns folded into the current prefill pass (batched multi-column prefill)
   float* lnstat = nullptr;             // strip statistics of the residual rows (EPI_RESID -> PRO_LNS), [max_batch][H/16][2]
   bool use_lns = true;                 // 8 < batch <= 32 decode: LayerNorm fused into the consumer GEMM (no rows_prep node)
-  bool use_fo = true;                  // batch > 8 decode: engine-dtype activations in MFMA B-fragment order (PTTS_NO_FO=1: row-major, for A/B)
   int S_self = 4, S_cross = 1;
-  int attn_waves = 4;  // waves per self-attention workgroup at decode
   int cross_waves = 4; // waves per cross-attention workgroup on the GEMV step: one 8-deep batch of row groups per wave covers max_enc
   // state
   long long* ids = nullptr;
@@ -102,7 +98,6 @@ struct ptts_engine {
   int B = 0, N = 0, P = 0;
   bool prefilled = false;
   bool h_ready = false;  // residual-stream input of the next decode step already embedded by the last tail
-  int xattn_groups_max = 256; // largest batch that runs the fused cross block in groups of 8 (PTTS_XATTN_GROUPS_MAX; above: rows_prep + q GEMM + attention)
   int lnproj = -1;            // -1 = on (3) at every batch size above 8: 8 utterances per workgroup up to 40 (round 4: -5.3 % at 32, -3.2 % at 12; neutral at 64, +12 % at 128
                               // with 8 per workgroup), 16 per workgroup above (round 5, profiles/r05_experiments.txt call 2: 48 / 64 / 96 / 128 utterances -9.7 / -6.6 / -2.3 / -5.1 % per step). Decode at batch > 8: LayerNorm + projection as ONE node tiled over 64 weight rows x lnproj_g utterances instead of rows_prep + strip GEMM
                               // (PTTS_LNPROJ: 0 off, 1 = LN1 + QKV, 2 = + LN3 + fc1 above 32 utterances, 3 = + LN3 + fc1 at 9..32 too instead of the producer-statistics prologue)
@@ -117,7 +112,6 @@ struct ptts_engine {
   float* xpart = nullptr;     // [nheads][H] per-head partial rows of the fused cross block
   float* h2 = nullptr;        // [H] residual row after the cross block (x + partial rows), written by the LN3 + fc1 node
   bool fuse_xq = true;        // GEMV step, un-folded cross block: LN2 + cross-q rows + cross-attention as one node (xq_attn_kernel), PTTS_NO_FUSE_XQ=1 = two nodes
-  int fuse_qa_s = 0;          // KV splits of that node: 0 = by context bucket (1 / 2 / 4 / 8 for <= 256 / 512 / 1024 / more positions), PTTS_FUSE_QA_S forces one
   int lnproj_g = 0;           // utterances per workgroup of that node: 0 = by batch size (8 up to 40 utterances, 16 above), PTTS_LNPROJ_G = 4 / 8 / 16 forces one
   int xattn_g = 0;            // utterances per workgroup of the fused cross block above 8 utterances: 0 = by batch size (2 up to 32, 4 up to 64, 8 above), PTTS_XATTN_G = 8 / 4 / 2 forces one
   bool xattn_g_ok = false;    // the g < 8 instances exist for this width (Mini-v1, Large-v1)
@@ -125,8 +119,6 @@ struct ptts_engine {
   int kv_ub = 0;         // host-side upper bound of the self-KV positions written so far (prefill + one per decode forward)
   int kv_bound = 0;      // attention fetch bound of the next decode forward: kv_ub + 1 rounded up to 64, <= max_ctx
   std::map<long long, hipGraphExec_t> graphs;  // key: 2 * batch size + folded-cross-block flag + context bucket + steps per launch (get_graph)
-  std::map<long long, hipGraphExec_t> prefill_graphs;  // PTTS_PREFILL_GRAPH: the prefill forward of one (batch, description, prompt, voice-prompt) shape
-  bool in_capture = false;
   int* host_pinned = nullptr;
 #ifdef PTTS_TIMING
   long long* dbg_stamps = nullptr;  // measurement build: [layers + 1][5 or 7 nodes][3 workgroups][16] wall-clock stamps of the decode step (ptts_debug_stamps)
@@ -226,10 +218,9 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     const size_t n = (size_t)B * e->N * H;
     hipLaunchKernelGGL((convert_kernel<WT, float>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, e->qc,
                        reinterpret_cast<WT*>(e->xw2), n);
-    static const bool kv_batched = !(ptts_dev_env("PTTS_NO_KV_BATCHED") && atoi(ptts_dev_env("PTTS_NO_KV_BATCHED")));
     // every layer's K/V projection in ONE launch (blockIdx.z = layer): the strip kernel up to 256 rows, the bf16 engine's LDS-DMA GEMM above (round 6:
     // 24 launches of ~17 us at 32 descriptions x 64 tokens were one tenth of that prefill; a shape the GEMM declines falls back to the strips)
-    const bool one_launch = kv_batched && (B * e->N <= 256 || (sizeof(WT) == 2 && H % 64 == 0 && (2 * nkc * 64) % 64 == 0));
+    const bool one_launch = (B * e->N <= 256 || (sizeof(WT) == 2 && H % 64 == 0 && (2 * nkc * 64) % 64 == 0));
     for (int l = 0; l < (one_launch ? 1 : c.num_layers); ++l) {
       GemmArgs g = {};
       g.W = e->L[l].ckv; g.M = B * e->N; g.N = 2 * nkc * 64; g.K = H;
@@ -238,7 +229,6 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
       if (one_launch) { g.kv_layers = e->kv_layers; g.kv_nlayers = c.num_layers; }
       PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_KV>(g, st)));
     }
-    if (e->xfold_ne && B == 1 && !e->in_capture) hipEventRecord(e->ev_kv, st);  // the fold (ptts_prefill) may start now, beside the layer stack
   }
   if (with_embed) {
     EmbedArgs ea = {};
@@ -266,7 +256,6 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     int S_f = 1;
     const int S_cap = M == 1 ? 8 : (M <= 4 ? 4 : 2);  // the combine prologue of the out_proj node holds S + 1 slots per lane: 12-wave workgroups (5..8 utterances) fit 2 splits
     while (S_f < S_cap && S_f * ptts_qkvattn_rows_per_split(mode) < e->kv_bound) S_f *= 2;
-    if (e->fuse_qa_s > 0) S_f = std::min(e->fuse_qa_s, S_cap);
     auto gv = [&](int pro, int epi, int S, GemvArgs g, const char* what) -> int {
       g.M = M;
       const int rc_ = ptts_gemv_launch(mode, pro, epi, S, g, st);
@@ -308,7 +297,7 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
         a.part = e->part; a.stats = e->stats; a.S = e->S_self; a.Q = 1; a.nheads = nh; a.H = H; a.cross = 0;
         a.fused_append = 1; a.scale = scale;
         a.direct_out = e->S_self == 1 ? e->xw : nullptr;
-        PTTS_TRY((launch_attn<WT>(a, B, st, e->attn_waves)));
+        PTTS_TRY((launch_attn<WT>(a, B, st)));
       }
       {  // [combine splits] + out_proj + residual (:1034)
         GemvArgs g = {};
@@ -396,9 +385,8 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
   const bool lns = e->use_lns && !prefill && M > 8 && M <= 32;  // LayerNorm statistics carried by the producer GEMM (PRO_LNS)
   // decode at batch > 8: engine-dtype activations travel between kernels in MFMA B-fragment order (ptts_lm_kernels.h: fo_vec_index)
   // (and the prefill while its rows stay on the strip kernels, M <= 256: a single utterance's 33-position prefill is 240 latency-bound
-  // launches on the time-to-first-token path; PTTS_NO_FO_PREFILL=1 keeps the row-major layout there for A/B)
-  static const bool fo_prefill = !(ptts_dev_env("PTTS_NO_FO_PREFILL") && atoi(ptts_dev_env("PTTS_NO_FO_PREFILL")));
-  const int fo = (e->use_fo && M > 8 && (!prefill || (fo_prefill && M <= 256))) ? 1 : 0;
+  // launches on the time-to-first-token path)
+  const int fo = (M > 8 && (!prefill || M <= 256)) ? 1 : 0;
   // LayerNorm + projection as one node (lnproj_fused_kernel): decode, batch > 8, Mini / Large widths, weights in the engine dtype (e4m3 strips keep
   // streaming bytes through the strip GEMMs)
   const int KTf = Elem<WT>::KT;
@@ -406,20 +394,18 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
   // utterances per workgroup of that node: 8 (one row per wave) up to 40, 16 (two rows per wave, the whole MFMA tile, half the weight re-reads) above
   const int lnproj_g = e->lnproj_g > 0 ? e->lnproj_g : (M <= 40 ? 8 : 16);
   // (round 5: the prefill rows of a short prompt, 8 < M <= 40, run the same fused nodes - three rows_prep nodes less per layer on the
-  //  time-to-first-token path: prefill 1.41 -> 1.29 ms, first token 2.41 -> 2.28 ms at 33 rows, profiles/r05_experiments.txt call 2; PTTS_LNPROJ_PREFILL=0: off)
-  static const bool lnproj_prefill = !(ptts_dev_env("PTTS_LNPROJ_PREFILL") && !atoi(ptts_dev_env("PTTS_LNPROJ_PREFILL")));
-  const bool lnproj_ok = lnproj > 0 && (!prefill || (lnproj_prefill && M <= 40)) && M > 8 && !e->w8_strips && (H == 1024 || H == 1536) && ((H / KTf) / 2) % 8 == 0 && QKV % 64 == 0 && F % 64 == 0;
+  //  time-to-first-token path: prefill 1.41 -> 1.29 ms, first token 2.41 -> 2.28 ms at 33 rows, profiles/r05_experiments.txt call 2)
+  const bool lnproj_ok = lnproj > 0 && (!prefill || M <= 40) && M > 8 && !e->w8_strips && (H == 1024 || H == 1536) && ((H / KTf) / 2) % 8 == 0 && QKV % 64 == 0 && F % 64 == 0;
   // prefill attention on the tiled kernel (8 query rows per workgroup share the K / V tile; PTTS_PREFILL_ATTN=0: one workgroup per query row, attn_kernel)
   const int prefill_attn_mode = getenv("PTTS_PREFILL_ATTN") ? atoi(getenv("PTTS_PREFILL_ATTN")) : 3;  // 0: one workgroup per query row, 1: tiled VALU kernel, 2: f32-MFMA kernel, 3: by batch
   const bool prefill_attn = prefill_attn_mode != 0;
   // prefill rows on the fused LN1 + QKV node, sinusoidal positions, engine-dtype cache: the node's epilogue writes the cache rows itself (no
-  // kv_append node: 24 launches of ~4 us + their boundaries off the time-to-first-token path; PTTS_KV_IN_QKV=0: the separate node)
-  static const bool kv_in_qkv_on = !(ptts_dev_env("PTTS_KV_IN_QKV") && !atoi(ptts_dev_env("PTTS_KV_IN_QKV")));
-  const bool kv_in_qkv = kv_in_qkv_on && prefill && lnproj_ok && !c.rope && !e->L[0].ks_self;
+  // kv_append node: 24 launches of ~4 us + their boundaries off the time-to-first-token path)
+  const bool kv_in_qkv = prefill && lnproj_ok && !c.rope && !e->L[0].ks_self;
   // ... and above 256 rows (a batch's prompts on the > 256-row GEMMs; round 6): the QKV projection's tile epilogue writes them (GemmArgs::kv_col0) -
   // 24 kv_append launches of ~6 us + their boundaries off the time-to-first-token path of a batch. Between 41 and 256 rows the kv_append node stays
   // (fragment-order rows_prep + strips: measured path of round 5).
-  const bool kv_in_gemm = kv_in_qkv_on && prefill && !kv_in_qkv && !lnproj_ok && M > 256 && !c.rope && !e->L[0].ks_self;
+  const bool kv_in_gemm = prefill && !kv_in_qkv && !lnproj_ok && M > 256 && !c.rope && !e->L[0].ks_self;
 #ifdef PTTS_TIMING
 #define PTTS_DBG_BIG(args, l_, k_) (args).dbg = (e->dbg_stamps && !prefill && M > 8) ? e->dbg_stamps + ((size_t)(l_) * 7 + (k_)) * 48 : nullptr
 #else
@@ -466,7 +452,7 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
       a.direct_out = S_used == 1 ? e->xw : nullptr; a.out_fo = fo;
       PTTS_DBG_BIG(a, l, 1);
       if (prefill && prefill_attn) PTTS_TRY((launch_prefill_attn<WT>(a, B, st, prefill_attn_mode)));
-      else PTTS_TRY((launch_attn<WT>(a, B, st, prefill ? 4 : e->attn_waves)));
+      else PTTS_TRY((launch_attn<WT>(a, B, st)));
     }
     {  // [combine splits] + out_proj + residual
       GemmArgs g = {}; g.decode = dec;
@@ -482,7 +468,7 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
       }
     }
     const int KTw = Elem<WT>::KT;
-    if (!prefill && (M <= 8 || (e->xattn_groups && M <= e->xattn_groups_max)) && (H / KTw) % 16 == 0 && (H == 512 || H == 1024 || H == 1536)) {
+    if (!prefill && (M <= 8 || (e->xattn_groups && M <= 256)) && (H / KTw) % 16 == 0 && (H == 512 || H == 1024 || H == 1536)) {
       // decode, small batch: LN2 + cross q projection + cross-attention fused, one workgroup per head
       XAttnArgs x = {};
       x.W = w.cq; x.x = e->h; x.x_ld = H; x.x_row_mul = 1; x.x_row_off = 0; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.K = H;
@@ -579,7 +565,7 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     GemmArgs g = {}; g.decode = dec;
     g.W = e->heads; g.W8 = e->heads_p8; g.wscale = e->heads_sc; g.x = e->h; g.x_ld = H; g.x_row_mul = Q; g.x_row_off = Q - 1; g.gamma = e->lnf_g; g.beta = e->lnf_b;
     g.out = e->logits; g.out_ld = c.num_codebooks * c.vocab_size; g.M = B; g.N = c.num_codebooks * c.vocab_size; g.K = H;
-    g.x_fo = (e->use_fo && B > 8 && (!prefill || (fo_prefill && B <= 256))) ? 1 : 0;
+    g.x_fo = (B > 8 && (!prefill || B <= 256)) ? 1 : 0;
     PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_STORE>(e, g, st)));
   }
   hipError_t err = hipGetLastError();
@@ -612,9 +598,8 @@ int fold_cross(ptts_engine* e, hipStream_t st) {
   const ptts_config& c = e->cfg;
   const int H = c.hidden_size, nh = c.num_heads, NE = e->xfold_ne, n_rep = nh / e->nkc, L = c.num_layers;
   const float qscale = 1.44269504088896340736f / sqrtf((float)(H / nh));
-  // tiled kernels (round 5; bit-identical to the row kernels, PTTS_FOLD_TILED=0 selects those for A/B)
-  static const bool tiled = !(ptts_dev_env("PTTS_FOLD_TILED") && !atoi(ptts_dev_env("PTTS_FOLD_TILED")));
-  if (tiled && H % 64 == 0 && NE <= 64) {
+  // tiled kernels (round 5; bit-identical to the row kernels, which serve the widths the tiles do not)
+  if (H % 64 == 0 && NE <= 64) {
     hipLaunchKernelGGL((xfold_tile_kernel<WT, W8, false>), dim3(H / 64, nh, L), dim3(256), 0, st, e->fold_layers, nh, H, NE, c.max_enc, n_rep, e->dims, qscale);
     hipLaunchKernelGGL((xfold_tile_kernel<WT, W8, true>), dim3(H / 64, nh, L), dim3(256), 0, st, e->fold_layers, nh, H, NE, c.max_enc, n_rep, e->dims, qscale);
   } else {
@@ -632,11 +617,10 @@ int forward_dispatch(ptts_engine* e, bool prefill, hipStream_t st, bool with_emb
 }
 
 // every decode forward appends one self-KV position: advance the host's bound before launching it (eagerly or as a graph)
-static const bool g_no_kv_bound = ptts_dev_env("PTTS_NO_KV_BOUND") && atoi(ptts_dev_env("PTTS_NO_KV_BOUND"));
 static int advance_kv(ptts_engine* e) {
   e->kv_ub += 1;
   const int cap = e->cfg.max_ctx;
-  e->kv_bound = g_no_kv_bound ? cap : std::min(cap, (e->kv_ub + 1 + 63) / 64 * 64);
+  e->kv_bound = std::min(cap, (e->kv_ub + 1 + 63) / 64 * 64);
   return e->kv_bound;
 }
 
@@ -706,9 +690,8 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   int rc = PTTS_OK;
   auto fail = [&](int r) { ptts_engine_destroy(e); return r; };
   if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(ptts_fail(PTTS_E_HIP, "hipStreamCreate failed"));
-  if (hipStreamCreateWithFlags(&e->fold_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e->ev_kv, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_fold, hipEventDisableTiming) != hipSuccess || hipEventCreate(&e->ev_first) != hipSuccess || hipEventCreate(&e->ev_tail0) != hipSuccess || hipEventCreate(&e->ev_pre0) != hipSuccess)
-    return fail(ptts_fail(PTTS_E_HIP, "hipStreamCreate / hipEventCreate failed"));
+  if (hipEventCreate(&e->ev_first) != hipSuccess || hipEventCreate(&e->ev_tail0) != hipSuccess || hipEventCreate(&e->ev_pre0) != hipSuccess)
+    return fail(ptts_fail(PTTS_E_HIP, "hipEventCreate failed"));
   const int H = c.hidden_size, F = c.ffn_dim, K = c.num_codebooks, V = c.vocab_size, nh = c.num_heads;
   const size_t es = e->esize;
   e->L.resize(c.num_layers);
@@ -716,16 +699,14 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   const int gmode = c.dtype == PTTS_F32 ? GV_F32 : GV_BF16;
   // (an engine created for more than GV_MAX_ROWS utterances never takes the GEMV step: it does not hold the row-major copies either -
   // the model-level cache keeps one engine per batch-size class, each with the weight copies its own decode step streams)
-  e->use_gemv = ptts_gemv_k_ok(H, gmode) && ptts_gemv_k_ok(F, gmode) && H <= 2048 && c.max_batch <= GV_MAX_ROWS &&
-                !(ptts_dev_env("PTTS_NO_GEMV") && atoi(ptts_dev_env("PTTS_NO_GEMV")));
+  e->use_gemv = ptts_gemv_k_ok(H, gmode) && ptts_gemv_k_ok(F, gmode) && H <= 2048 && c.max_batch <= GV_MAX_ROWS;
   e->gemv_rows = c.dtype == PTTS_F32 ? 1 : GV_MAX_ROWS;
-  if (const char* ev = ptts_dev_env("PTTS_GEMV_ROWS")) e->gemv_rows = std::max(1, std::min(e->gemv_rows, atoi(ev)));  // A/B knob (tools/)
   e->w8 = c.weights_fp8 != 0;
   // static cross-attention folding: single utterance, sinusoidal positions (RoPE rotates the cross query by position), <= 64
   // description tokens, full cross K/V heads not required (n_rep handled), folded widths must be GEMV shapes
-  if (e->use_gemv && !c.rope && c.max_enc <= 64 && ptts_gemv_k_ok(nh * 64, gmode) && !(ptts_dev_env("PTTS_NO_XFOLD") && atoi(ptts_dev_env("PTTS_NO_XFOLD"))))
+  if (e->use_gemv && !c.rope && c.max_enc <= 64 && ptts_gemv_k_ok(nh * 64, gmode))
     e->xfold_ne = 64;
-  e->w8_strips = e->w8 && !e->use_gemv && !(ptts_dev_env("PTTS_NO_W8_STRIPS") && atoi(ptts_dev_env("PTTS_NO_W8_STRIPS")));
+  e->w8_strips = e->w8 && !e->use_gemv;
   if (c.kv_fp8 && (c.dtype != PTTS_BF16 || c.max_batch <= GV_MAX_ROWS)) {  // by capacity, not by path (a width without GEMV instances runs strips at 1..8 too)
     ptts_engine_destroy(e);
     return ptts_fail(PTTS_E_UNSUPPORTED, "kv_fp8 (e4m3 self-attention cache) needs the bf16 engine created for more than %d utterances (the MFMA strip step)", GV_MAX_ROWS);
@@ -832,13 +813,10 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
     while (s > 1 && (s - 1) * 4 * 8 * 8 >= c.max_ctx) --s;  // do not split below one 8-deep batch of row groups per wave
     e->S_self = s;
     e->S_cross = 1;
-    if (const char* ev = ptts_dev_env("PTTS_ATTN_SPLITS")) e->S_self = std::max(1, std::min(8, atoi(ev)));  // tuning knobs (tools/)
-    if (const char* ev = ptts_dev_env("PTTS_ATTN_WAVES")) e->attn_waves = atoi(ev) == 16 ? 16 : (atoi(ev) == 8 ? 8 : 4);
     {
       const int rows_per_wave = (c.dtype == PTTS_BF16 ? 8 : 4) * 8;  // RPI row groups x 8 loads in flight
       const int need = (c.max_enc + rows_per_wave - 1) / rows_per_wave;
       e->cross_waves = need <= 1 ? 1 : (need <= 2 ? 2 : 4);
-      if (const char* ev = ptts_dev_env("PTTS_CROSS_WAVES")) e->cross_waves = atoi(ev) == 1 ? 1 : (atoi(ev) == 2 ? 2 : 4);
     }
     if (e->use_gemv) while (e->S_self & (e->S_self - 1)) --e->S_self;  // the GEMV combine prologue is instantiated for 2 / 4 / 8 splits
   }
@@ -858,16 +836,13 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   e->fuse_qa = !(getenv("PTTS_NO_FUSE_QA") && atoi(getenv("PTTS_NO_FUSE_QA")));
   if (const char* ev = getenv("PTTS_FUSE_QA_MAX")) e->fuse_qa_max = std::max(1, std::min(GV_MAX_ROWS, atoi(ev)));
   e->fuse_xq = !(getenv("PTTS_NO_FUSE_XQ") && atoi(getenv("PTTS_NO_FUSE_XQ")));
-  if (const char* ev = ptts_dev_env("PTTS_FUSE_QA_S")) { const int v = atoi(ev); if (v == 1 || v == 2 || v == 4 || v == 8) e->fuse_qa_s = v; }
   A(e->alloc(&e->ffn, std::max(rows * F, rows * (size_t)H)));
   A(e->alloc(&e->logits, (size_t)c.max_batch * K * V));
   A(e->alloc(&e->sort_buf, 16));
   A(e->alloc_bytes(&e->xw, (rows + 16) * H * es));  // + 16 rows: fragment order addresses whole 16-row tiles
   A(e->alloc_bytes(&e->xw2, std::max((rows + 16) * F, enc_rows * (size_t)H) * es));
-  e->use_fo = !(ptts_dev_env("PTTS_NO_FO") && atoi(ptts_dev_env("PTTS_NO_FO")));
   A(e->alloc(&e->lnstat, (size_t)c.max_batch * (H / 16) * 2 + 16));
-  e->use_lns = (H == 1024 || H == 1536) && !(ptts_dev_env("PTTS_NO_LNS") && atoi(ptts_dev_env("PTTS_NO_LNS")));
-  if (const char* ev = ptts_dev_env("PTTS_XATTN_GROUPS_MAX")) e->xattn_groups_max = std::max(8, atoi(ev));
+  e->use_lns = H == 1024 || H == 1536;
   if (const char* ev = getenv("PTTS_LNPROJ")) e->lnproj = std::max(0, std::min(3, atoi(ev)));
   if (const char* ev = getenv("PTTS_LNPROJ_G")) e->lnproj_g = atoi(ev) == 4 ? 4 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 8 ? 8 : 0));
   e->xattn_g_ok = (H == 1024 && ((H / (c.dtype == PTTS_BF16 ? 32 : 16)) / 2) % 16 == 0) || H == 1536;
@@ -903,13 +878,9 @@ extern "C" void ptts_engine_destroy(ptts_engine* e) {
   PttsDeviceGuard _dg(e->cfg.device);
   hipDeviceSynchronize();
   for (auto& kv : e->graphs) hipGraphExecDestroy(kv.second);
-  for (auto& kv : e->prefill_graphs) hipGraphExecDestroy(kv.second);
   for (void* p : e->allocs) hipFree(p);
   if (e->host_pinned) hipHostFree(e->host_pinned);
   if (e->own_stream) hipStreamDestroy(e->own_stream);
-  if (e->fold_stream) hipStreamDestroy(e->fold_stream);
-  if (e->ev_kv) hipEventDestroy(e->ev_kv);
-  if (e->ev_fold) hipEventDestroy(e->ev_fold);
   if (e->ev_first) hipEventDestroy(e->ev_first);
   if (e->ev_tail0) hipEventDestroy(e->ev_tail0);
   if (e->ev_pre0) hipEventDestroy(e->ev_pre0);
@@ -1138,49 +1109,13 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
   // causal attention over the same cache).
   const int T = e->pending_T;
   e->pending_T = 0;
-  const bool batched = T > 0 && P + 1 + T <= e->max_prompt && !(ptts_dev_env("PTTS_NO_BATCHED_PREFIX") && atoi(ptts_dev_env("PTTS_NO_BATCHED_PREFIX")));
+  const bool batched = T > 0 && P + 1 + T <= e->max_prompt;
   if (batched) {
     hipLaunchKernelGGL(push_prefix_all_kernel, dim3((B * K * T + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->dims, T, B, K, c.bos_token_id);
     e->prefill_T = T;
   }
   e->xfold_valid = false;  // the prefill itself (and anything before the fold below) runs the un-folded cross-attention
-  // The prefill forward (~290 launches of 4-8 us kernels for one utterance) replayed from ONE captured graph per (batch, description, prompt,
-  // voice-prompt) shape: every operand is an engine-owned buffer and every per-call value (lengths, masks) is device-resident, so the
-  // launch list is a pure function of the shape. Measured (profiles/r05_experiments.txt call 1): time to the first token 2.420 ms with the
-  // graph, 2.401 ms with eager launches - behind the description encoder's 1 ms of GPU time the host is ahead of the GPU either way, and a
-  // graph costs a capture + instantiate per new (batch, description, prompt) shape. OFF by default; PTTS_PREFILL_GRAPH=1 enables it (A/B).
-  static const bool prefill_graph = ptts_dev_env("PTTS_PREFILL_GRAPH") && atoi(ptts_dev_env("PTTS_PREFILL_GRAPH"));
-  int rc_fwd = PTTS_OK;
-  if (prefill_graph) {
-    const long long key = (long long)B | ((long long)N << 12) | ((long long)P << 28) | ((long long)e->prefill_T << 44);
-    auto it = e->prefill_graphs.find(key);
-    hipGraphExec_t ex = nullptr;
-    if (it != e->prefill_graphs.end()) {
-      ex = it->second;
-    } else {
-      hipGraph_t g = nullptr;
-      PTTS_HIP(hipStreamBeginCapture(e->own_stream, hipStreamCaptureModeThreadLocal));
-      e->in_capture = true;
-      rc_fwd = forward_dispatch(e, true, e->own_stream);
-      e->in_capture = false;
-      hipError_t ce = hipStreamEndCapture(e->own_stream, &g);
-      if (rc_fwd != PTTS_OK) { if (g) hipGraphDestroy(g); e->prefill_T = 0; return rc_fwd; }
-      if (ce != hipSuccess) { e->prefill_T = 0; return ptts_fail(PTTS_E_HIP, "hipStreamEndCapture(prefill) failed: %s", hipGetErrorString(ce)); }
-      hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-      hipGraphDestroy(g);
-      if (ie != hipSuccess) { e->prefill_T = 0; return ptts_fail(PTTS_E_HIP, "hipGraphInstantiate(prefill) failed: %s", hipGetErrorString(ie)); }
-      if (e->prefill_graphs.size() >= 32) {  // bounded: a server cycling through many prompt lengths re-captures instead of growing
-        for (auto& kv : e->prefill_graphs) hipGraphExecDestroy(kv.second);
-        e->prefill_graphs.clear();
-      }
-      e->prefill_graphs[key] = ex;
-    }
-    hipError_t le = hipGraphLaunch(ex, st);
-    if (le != hipSuccess) { e->prefill_T = 0; return ptts_fail(PTTS_E_HIP, "hipGraphLaunch(prefill) failed: %s", hipGetErrorString(le)); }
-    if (e->xfold_ne && B == 1) hipEventRecord(e->ev_kv, st);
-  } else {
-    rc_fwd = forward_dispatch(e, true, st);
-  }
+  const int rc_fwd = forward_dispatch(e, true, st);
   e->prefill_T = 0;
   PTTS_TRY(rc_fwd);
   e->kv_ub = P + 1 + (batched ? T : 0);  // self-KV positions written by this pass
@@ -1199,14 +1134,10 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
     // fold's two launches run (time-to-first-token does not pay for it); every decode step that follows on `st` sees the folded
     // matrices by stream order. (Round 2 ran 48 per-layer launches BEFORE the tail: +0.8 ms of time-to-first-token. Running it on a
     // second stream beside the prefill was measured and lost: 8.98 vs 8.44 ms to the first token, and the first streamed chunk 23 ms
-    // later, the decode steps waiting on the second hardware queue; PTTS_FOLD_ASYNC=1 keeps that variant for A/B.)
-    static const bool sync_fold = !(ptts_dev_env("PTTS_FOLD_ASYNC") && atoi(ptts_dev_env("PTTS_FOLD_ASYNC")));
-    hipStream_t fs = sync_fold ? st : e->fold_stream;
-    if (!sync_fold) PTTS_HIP(hipStreamWaitEvent(fs, e->ev_kv, 0));
-    if (c.dtype == PTTS_F32) PTTS_TRY((fold_cross<float, false>(e, fs)));
-    else if (e->w8) PTTS_TRY((fold_cross<bf16_t, true>(e, fs)));
-    else PTTS_TRY((fold_cross<bf16_t, false>(e, fs)));
-    if (!sync_fold) { PTTS_HIP(hipEventRecord(e->ev_fold, fs)); PTTS_HIP(hipStreamWaitEvent(st, e->ev_fold, 0)); }
+    // later, the decode steps waiting on the second hardware queue.)
+    if (c.dtype == PTTS_F32) PTTS_TRY((fold_cross<float, false>(e, st)));
+    else if (e->w8) PTTS_TRY((fold_cross<bf16_t, true>(e, st)));
+    else PTTS_TRY((fold_cross<bf16_t, false>(e, st)));
     e->xfold_valid = true;
   }
   e->h_ready = sample != 0;
@@ -1252,18 +1183,15 @@ static int get_graph(ptts_engine* e, hipGraphExec_t* out) {
 // instantiate of ~170-270 nodes every 64 frames, on the latency-critical streaming path. Bounded: the stock generation
 // config (max_length 2580) is ~41 buckets, three times what a call that stops on EOS needs, and all of them sat between the prefill and
 // the first decode_steps of the first call of every batch size. Graphs are cached for the engine's life, so only the first call of a
-// (batch, fold, bucket) pays. PTTS_NO_PRECAPTURE=1: capture lazily, at the launch that needs the graph (A/B).
+// (batch, fold, bucket) pays.
 static int precapture_graphs(ptts_engine* e, int max_buckets) {
-  static const bool off = ptts_dev_env("PTTS_NO_PRECAPTURE") && atoi(ptts_dev_env("PTTS_NO_PRECAPTURE"));
-  if (off) return PTTS_OK;
   const int cap = e->cfg.max_ctx, saved_ub = e->kv_ub, saved_bound = e->kv_bound;
   const int last_ub = std::min(cap - 1, e->P + e->gp.max_length);  // positions the longest run of this call writes
   int rc = PTTS_OK, done = 0;
   for (int ub = saved_ub + 1; ub <= last_ub && rc == PTTS_OK && done < max_buckets; ++done) {
-    e->kv_bound = g_no_kv_bound ? cap : std::min(cap, (ub + 1 + 63) / 64 * 64);
+    e->kv_bound = std::min(cap, (ub + 1 + 63) / 64 * 64);
     rc = get_graph(e, nullptr);
     ub = e->kv_bound;  // first upper bound of the next bucket: (ub + 1 + 63) / 64 * 64 > kv_bound
-    if (g_no_kv_bound) break;
   }
   e->kv_ub = saved_ub; e->kv_bound = saved_bound;
   return rc;

@@ -318,7 +318,7 @@ struct ptts_t5 {
   void *xw = nullptr, *ctx = nullptr, *ff = nullptr;
   long long* ids = nullptr;
   int* mask = nullptr;
-  bool use_fo = true, use_graph = true;
+  bool use_graph = true;
   std::set<std::string> loaded, required;
   std::map<long long, hipGraphExec_t> graphs;  // key: batch, length, masked?
   int last_graph_nodes = 0;                    // kernel nodes of the graph captured last (ptts_t5_debug_graph_nodes)
@@ -415,7 +415,6 @@ extern "C" int ptts_t5_create(const ptts_t5_config* cfg, ptts_t5** out) {
   A(e->alloc(&e->ids, rows));
   A(e->alloc(&e->mask, rows));
 #undef A
-  e->use_fo = !(ptts_dev_env("PTTS_T5_NO_FO") && atoi(ptts_dev_env("PTTS_T5_NO_FO")));
   e->use_graph = !(getenv("PTTS_T5_NO_GRAPH") && atoi(getenv("PTTS_T5_NO_GRAPH")));
   e->use_fold = D % 64 == 0 && !(getenv("PTTS_T5_NO_FOLD") && atoi(getenv("PTTS_T5_NO_FOLD")));  // (a row's d_model / 16 partials are summed by 4 lanes)
   *out = e;
@@ -463,7 +462,7 @@ template <typename WT>
 int t5_forward(ptts_t5* e, int B, int N, bool has_mask, hipStream_t st) {
   const ptts_t5_config& c = e->cfg;
   const int D = c.d_model, F = c.d_ff, I = e->inner, M = B * N;
-  const int fo = (e->use_fo && M <= 256) ? 1 : 0;  // the rows stay on the strip kernels: engine-dtype activations in MFMA B-fragment order
+  const int fo = M <= 256 ? 1 : 0;  // the rows stay on the strip kernels: engine-dtype activations in MFMA B-fragment order
   hipLaunchKernelGGL((t5_embed_kernel<WT>), dim3(M), dim3(256), 0, st, reinterpret_cast<const WT*>(e->embed), e->ids, e->h, D, c.vocab_size);
   auto prep = [&](const float* gamma) -> int {
     GemmArgs p = {};

@@ -387,20 +387,22 @@ def test_dac_engine_capacities_grow_within_a_memory_bound(monkeypatch):
 
 def test_library_reads_fifteen_switches():
     """the product library reads at most 15 PTTS_* environment variables (56 in round 5), every one of them is a row of the table in
-    DESIGN.md section 6 (with the test that covers both sides) and is set by a test under tests/; everything else goes through ptts_dev_env(), which is
-    compiled out of the product build (-DPTTS_DEV_KNOBS builds only), and the built library carries no development-knob name at all."""
+    DESIGN.md section 6 (with the test that covers both sides) and is set by a test under tests/. The development knobs of rounds 1-6 are gone from
+    the sources, not hidden: no ptts_dev_env() / PTTS_DEV_KNOBS indirection and no A/B macro remains in csrc/, and no other PTTS_* name is quoted there."""
     import glob
     import re
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     srcs = [f for pat in ("*.hip", "*.h", "*.inc") for f in glob.glob(os.path.join(root, "parler_tts_amd", "csrc", pat))]
-    read, dev = set(), set()
+    read, quoted, dev = set(), set(), []
     for f in srcs:
         text = open(f).read()
         read |= set(re.findall(r'(?<![a-z_])getenv\("(PTTS_[A-Z0-9_]+)"\)', text))
-        dev |= set(re.findall(r'ptts_dev_env\("(PTTS_[A-Z0-9_]+)"\)', text))
+        quoted |= set(re.findall(r'"(PTTS_[A-Z0-9_]+)"', text))
+        dev += [(os.path.basename(f), w) for w in ("ptts_dev_env", "PTTS_DEV_KNOBS", "PTTS_WEIGHT_CACHED", "PTTS_DAC_FAST_SIN") if w in text]
     assert 0 < len(read) <= 15, sorted(read)
-    assert not (read & dev), sorted(read & dev)
+    assert not dev, f"development knobs left in csrc/: {dev}"
+    assert quoted == read, f"PTTS_* names quoted in csrc/ but not read with getenv: {sorted(quoted - read)}"
     design = open(os.path.join(root, "DESIGN.md")).read()
     rows = set(re.findall(r"^\| `(PTTS_[A-Z0-9_]+)` \|", design, flags=re.M))
     assert rows == read, sorted(rows ^ read)
@@ -412,5 +414,6 @@ def test_library_reads_fifteen_switches():
     blob = open(N.LIB_PATH, "rb").read()
     for name in read:
         assert name.encode() in blob, f"{name} missing from the built library (stale build?)"
-    leaked = sorted(n for n in dev if n.encode() + b"\0" in blob)
-    assert not leaked, f"development knobs compiled into the product library: {leaked}"
+    api = set(re.findall(r"\b(PTTS_[A-Z0-9_]+)\b", open(os.path.join(root, "include", "ptts.h")).read()))  # C ABI constants (messages may name them)
+    leaked = sorted(n.decode() for n in set(re.findall(rb"(?<![A-Za-z0-9_])(PTTS_[A-Z0-9_]+)\0", blob)) if n.decode() not in read | api)
+    assert not leaked, f"PTTS_* names in the product library that are neither switches nor C ABI constants: {leaked}"

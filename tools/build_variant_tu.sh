@@ -1,8 +1,8 @@
 #!/bin/bash
 # A/B build of chosen translation units: tools/build_variant_tu.sh <name> <tu[,tu...]> [-D flags] compiles parler_tts_amd/csrc/<tu>.hip with the extra
-# flags (e.g. -DPTTS_DEV_KNOBS) and links them with the product's other objects into tools/variants/<name>/libptts_hip_<name>.so + cabi_probe_<name>.
+# flags and links them with the product's other objects into tools/variants/<name>/libptts_hip_<name>.so + cabi_probe_<name>.
 # The product library is not touched (run __graft_entry__.build() first: its objects are used).
-#   tools/build_variant_tu.sh dacdev ptts_dac -DPTTS_DEV_KNOBS        tools/build_variant_tu.sh t5dev ptts_t5,ptts_lm -DPTTS_DEV_KNOBS
+#   tools/build_variant_tu.sh dacx ptts_dac -D<FLAG>        tools/build_variant_tu.sh t5x ptts_t5,ptts_lm -D<FLAG>
 set -e
 name=$1; tus=$2; shift 2
 cd "$(dirname "$0")/.."

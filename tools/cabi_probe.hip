@@ -12,7 +12,7 @@
 //   tools/cabi_probe dac <batch> [frames=<n>] [f32] [reps=<n>] [tag=<text>] [dump=<file>]
 //   tools/cabi_probe t5  <batch> [tokens=<n>] [layers=<n>] [fp32] [reps=<n>] [tag=<text>]   (round 5: the T5 description encoder, ptts_t5_*)
 //   tools/cabi_probe cmp <file a> <file b>
-//   (environment knobs as for tools/step_probe2.py: PTTS_NO_GEMV, PTTS_GEMV_ROWS, PTTS_GEMV_STAGE, PTTS_NO_FO, PTTS_DAC_NO_FUSE_RES ...)
+//   (environment switches: the product's, DESIGN.md section 6, e.g. PTTS_DAC_NO_FUSE_RES; the development knobs were removed, their measurements live in profiles/)
 //
 // `dump=` writes what the run computed (lm: the fp32 logits of the prefill and of <n> teacher-forced eager steps on fixed pseudo-random
 // tokens, then the ids of the free-running graph-replayed steps; dac: the waveform), `cmp` compares two dumps (max |difference|, arg-max

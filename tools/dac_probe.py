@@ -1,5 +1,5 @@
 """GPU probe: 44.1 kHz DAC decode time (bf16-operand mode) for 860 frames at batch 1 / 8 / 32 and for a streaming chunk,
-plus the RMS difference to the direct (L1/L2-operand) kernel selected with PTTS_DAC_NO_LDS=1 in a second process."""
+plus the RMS difference to the direct (L1/L2-operand) kernel (its switch was removed; the measurements live in profiles/)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -7,7 +7,7 @@ import torch
 from parler_tts_amd.engine import DacEngine
 from parler_tts_amd.synthetic import random_dac_state_dict
 
-tag = "direct" if os.environ.get("PTTS_DAC_NO_LDS") else "lds"
+tag = "lds"
 dsd = {k: v.cuda() for k, v in random_dac_state_dict(seed=4321).items()}
 T = 860
 for B in [int(x) for x in os.environ.get("PROBE_B", "1,8,32").split(",")]:

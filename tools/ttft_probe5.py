@@ -1,6 +1,5 @@
 """Round 5: time-to-first-token and its breakdown (bench.measure_ttft / measure_ttft_breakdown) at batch 1 and 32 on bench.py's Mini-v1
-configuration, weights filled on the device. Environment A/B: PTTS_NO_NATIVE_T5=1 (stock transformers T5), PTTS_PREFILL_GRAPH=0 (eager prefill),
-PTTS_T5_NO_GRAPH=1 (eager T5 launches)."""
+configuration, weights filled on the device. Environment A/B: PTTS_NO_NATIVE_T5=1 (stock transformers T5), PTTS_T5_NO_GRAPH=1 (eager T5 launches)."""
 import json
 import os
 import sys

@@ -1,5 +1,5 @@
 """Measurement only (never imported by the product): the time-to-first-token GEMM shapes on the vendor library (torch.matmul -> hipBLASLt / rocBLAS)
-beside tools/gemm_probe's numbers for gemm_glds_kernel - what a tuned library reaches on shapes this small is the practical ceiling the
+beside gemm_probe's numbers for gemm_glds_kernel (profiles/r06_gemm_probe_call*.txt) - what a tuned library reaches on shapes this small is the practical ceiling the
 "35 % of the bf16 peak" target has to be read against. Same protocol as gemm_probe: bf16 operands, fp32-accumulated, 24 weight
 copies rotated so the weights come from HBM, HIP events around 200 launches, best of 5."""
 import torch
