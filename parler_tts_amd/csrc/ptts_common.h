@@ -69,11 +69,17 @@ struct PttsPerDeviceOnce {
 // gfx950's command processor can instead write the first 14 argument dwords of a dispatch into user SGPRs before the first wave starts
 // (LLVM: -mllvm -amdgpu-kernarg-preload-count=14, set in __graft_entry__.build), but only for arguments the kernel takes as SCALARS - a
 // by-value struct stays behind s_load. Measured on a chain of dependent GEMV nodes: -0.075 us per node (profiles/r05_experiments.txt call 9).
-// The nodes of the decode step therefore take the fields in the first 56 bytes of their argument struct A as scalar parameters of their own
+// The nodes of the decode step therefore take the first 56 bytes of their argument struct A - its HEAD - as scalar parameters of their own
 // types (pointers stay pointers: re-assembled from integers they would lose their address space and every load would become a flat_load)
-// and the rest of A as KTail<A>; A's fields are ordered so that everything a wave needs to address its FIRST loads sits in those 56 bytes.
-// Per struct (ptts_gemv.h): <A>_KPARAMS = the parameter list, <A>_KJOIN(a) re-assembles `A a` in registers (SROA: preloaded SGPRs + the
-// tail's s_loads, no memory), ptts_klaunch(kernel, ..., a) splits it on the host.
+// and the rest of A as KTail<A>; A's fields are ordered so that everything a wave needs to address its FIRST loads sits in the head.
+//
+// Each head is declared once, as a list <H>_KHEAD(X) of entries KIND(X, ...) in parameter order. A kind hands the selector X its entry's five forms,
+// X(member, parameter, join, argument, join0): the struct member (PTTS_KMEMBERS), ", type k_name" (PTTS_KPARAMS), the device join of the parameter into
+// h_ (the head re-assembled in registers: SROA, no memory), ", value" for the host launch (ptts_klaunch), and what fills the struct a_ behind the head
+// first. KF(X, type, name): a parameter that is the member of that name and type; KTAIL(X, A): the last parameter, KTail<A> (a head-only struct has
+// none); other kinds are hooks of one declaration, defined next to it. A head is A's own first 56 bytes (PTTS_KMEMBERS opens A; PTTS_KJOIN,
+// PTTS_KLAUNCH), or a struct H of its own in front of A's tail (PTTS_KJOIN_VIA: h_ and `A a`, H::unpack(a) writes what the kernel reads of A's head;
+// PTTS_KLAUNCH_VIA: ptts_klaunch(kernel, ..., h, a) with h from H::pack). PTTS_KMEMBERS checks that the head is exactly 56 bytes.
 typedef unsigned long long ptts_u64;
 template <typename A> struct KTail {
   static_assert(sizeof(A) > 56 && sizeof(A) % 8 == 0, "argument struct: more than the 56 preloaded bytes, a multiple of 8");
@@ -82,12 +88,37 @@ template <typename A> struct KTail {
 // A tail field first used by the EPILOGUE (the output pointer) would be fetched by an s_load right in front of the store - a scalar round trip at
 // the end of the node's critical path. PTTS_KTOUCH(v), placed behind the wave's load burst, makes the compiler fetch it there, in the burst's shadow.
 #define PTTS_KTOUCH(v) asm volatile("" ::"s"(v))
-#define PTTS_KTAIL_JOIN(A, a) __builtin_memcpy(reinterpret_cast<char*>(&a) + 56, &kt_, sizeof(kt_))
 template <typename A> inline KTail<A> ptts_ktail(const A& a) {
   KTail<A> t;
   memcpy(&t, reinterpret_cast<const char*>(&a) + 56, sizeof(t));
   return t;
 }
+
+#define PTTS_KCOMMA ,  // a form's leading comma, produced only after the selector has split its arguments
+#define PTTS_KSEL_MEMBER(m, p, j, g, j0) m
+#define PTTS_KSEL_PARAM(m, p, j, g, j0) p
+#define PTTS_KSEL_JOIN(m, p, j, g, j0) j
+#define PTTS_KSEL_ARG(m, p, j, g, j0) g
+#define PTTS_KSEL_JOIN0(m, p, j, g, j0) j0
+#define KF(X, T, n) X(T n;, PTTS_KCOMMA T k_##n, h_.n = k_##n;, PTTS_KCOMMA h_.n, )
+#define KTAIL(X, A) X(, PTTS_KCOMMA KTail<A> k_tail, , PTTS_KCOMMA ptts_ktail(a_), __builtin_memcpy(reinterpret_cast<char*>(&a_) + 56, &k_tail, sizeof(k_tail));)
+
+#define PTTS_KMEMBERS(H)                                                                                              \
+  struct KHeadEnd_ { H##_KHEAD(PTTS_KSEL_MEMBER) char end_; };                                                        \
+  static_assert(offsetof(KHeadEnd_, end_) == 56, #H ": the head is exactly the 56 preloaded bytes (14 dwords)");       \
+  H##_KHEAD(PTTS_KSEL_MEMBER)
+#define PTTS_KDROP1_(x, ...) __VA_ARGS__
+#define PTTS_KDROP1(...) PTTS_KDROP1_(__VA_ARGS__)
+#define PTTS_KPARAMS(H) PTTS_KDROP1(H##_KHEAD(PTTS_KSEL_PARAM))
+#define PTTS_KJOIN(A, a) A a; { A& a_ = a; A& h_ = a; A##_KHEAD(PTTS_KSEL_JOIN0) A##_KHEAD(PTTS_KSEL_JOIN) }
+#define PTTS_KJOIN_VIA(H, A, a) A a; H h_; { A& a_ = a; H##_KHEAD(PTTS_KSEL_JOIN0) H##_KHEAD(PTTS_KSEL_JOIN) } h_.unpack(a);
+#define PTTS_KLAUNCH(A) template <typename Kn> inline void ptts_klaunch(Kn kern, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const A& a_) {   \
+    const A& h_ = a_;                                                                                                            \
+    hipLaunchKernelGGL(kern, grid, block, shmem, st A##_KHEAD(PTTS_KSEL_ARG));                                                   \
+  }
+#define PTTS_KLAUNCH_VIA(H, A) template <typename Kn> inline void ptts_klaunch(Kn kern, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const H& h_, const A& a_) { \
+    hipLaunchKernelGGL(kern, grid, block, shmem, st H##_KHEAD(PTTS_KSEL_ARG));                                                               \
+  }
 
 // ---- bf16 <-> f32 (round-to-nearest-even, identical to torch's .to(bfloat16)) -------------------------
 __host__ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {

@@ -21,14 +21,43 @@ namespace {
 
 template <int N> __device__ __forceinline__ void ptts_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// Kernel-argument preload (ptts_common.h; call 52): everything that addresses the wave's first LDS-DMA pieces arrives in SGPRs written by the command
+// processor - W, x, K, M, the activation row stride, the tile order and the grid extents (gridDim is a hidden argument behind an s_load); the tail
+// (epilogue operands) comes by s_load in the shadow of the first stage. The two pad slots keep the strip kernel's parameter layout.
+#define GemmGldsHead_KHEAD(X)                                                                                                            \
+  KDBG0(X)                                                                                                                               \
+  KF(X, const void*, W)       /* weights in A-fragment order */                                                                          \
+  KF(X, const void*, pad0_)                                                                                                              \
+  KF(X, const float*, x)      /* activations, bf16 rows with row stride x_ld (consecutive rows: x_row_mul 1, x_row_off 0) */              \
+  KF(X, float*, out) KF(X, int, K) KF(X, int, M) KF(X, int, x_ld)                                                                                           \
+  KF(X, unsigned, tiles)      /* xcd_swz | tiles along N << 1 (11 bits) | tiles along M << 12 (20 bits): the grid; widths and rows checked \
+                                 at engine creation */                                                                                    \
+  KF(X, int, out_ld) KF(X, int, pad1_) KTAIL(X, GemmArgs)
+struct GemmGldsHead {
+  PTTS_KMEMBERS(GemmGldsHead)
+  // the smallest tile is 64 x 64: the extents of any GEMM over N columns and `rows` rows fit the fields if these do
+  static bool fits(long long N, long long rows) { return N / 64 <= 0x7ff && (rows + 63) / 64 <= 0xfffff; }
+  static int pack(const GemmArgs& a, dim3 grid, GemmGldsHead& h) {
+    if (a.x_row_mul != 1 || a.x_row_off != 0) return ptts_fail(PTTS_E_UNSUPPORTED, "gemm_glds: activation rows must be consecutive (x_row_mul %d, x_row_off %d)", a.x_row_mul, a.x_row_off);
+    if (grid.x > 0x7ffu || grid.y > 0xfffffu) return ptts_fail(PTTS_E_UNSUPPORTED, "gemm_glds: %u x %u tiles above the 11- / 20-bit grid extents", grid.x, grid.y);
+    h.W = a.W; h.pad0_ = nullptr; h.x = a.x; h.out = a.out; h.K = a.K; h.M = a.M; h.x_ld = a.x_ld;
+    h.tiles = (a.xcd_swz ? 1u : 0u) | (grid.x << 1) | (grid.y << 12); h.out_ld = a.out_ld; h.pad1_ = 0;
+    return PTTS_OK;
+  }
+  __device__ __forceinline__ void unpack(GemmArgs& a) const {
+    a.W = W; a.x = x; a.out = out; a.K = K; a.M = M; a.out_ld = out_ld;
+  }
+  __device__ __forceinline__ int xcd_swz() const { return tiles & 1; }
+  __device__ __forceinline__ int grid_n() const { return (tiles >> 1) & 0x7ff; }
+  __device__ __forceinline__ int grid_m() const { return (int)(tiles >> 12); }
+};
+PTTS_KLAUNCH_VIA(GemmGldsHead, GemmArgs)
+
 // RP = 1: every fragment read of a stage is issued before its first MFMA; RP = 0: reads and MFMAs one fragment at a time
 template <int EPI, int BNS, int BMT, int WN, int WM, int NST, int RP = 0>
-__global__ void __launch_bounds__(WN * WM * 64) gemm_glds_kernel(PTTS_DBG0_PARAM GemmArgs_KPARAMS) {
-  // Kernel-argument preload (ptts_common.h; call 52): everything that addresses the wave's first LDS-DMA pieces - W, x, K, M and, in the two preloaded slots
-  // the strip kernel's pass geometry occupies, the activation row stride and the tile-order flag + grid extents (launch_gemm_glds_inst; gridDim is a hidden argument behind an s_load) - arrives in SGPRs written by the
-  // command processor; the tail (epilogue operands) comes by s_load in the shadow of the first stage.
-  GemmArgs_KJOIN(a)
-  const int x_ld = a.rows_per_pass, xcd_swz = a.frags_per_wave & 1, grid_n = (a.frags_per_wave >> 1) & 0x7ff, grid_m = (int)((unsigned)a.frags_per_wave >> 12);
+__global__ void __launch_bounds__(WN * WM * 64) gemm_glds_kernel(PTTS_KPARAMS(GemmGldsHead)) {
+  PTTS_KJOIN_VIA(GemmGldsHead, GemmArgs, a)
+  const int x_ld = h_.x_ld, xcd_swz = h_.xcd_swz(), grid_n = h_.grid_n(), grid_m = h_.grid_m();
   typedef bf16_t WT;
   constexpr int FPS = 2;  // fragments per stage: BK = 64
   constexpr int RB = FPS * 64, SPR = RB / 16, RPP = 1024 / RB;  // activation image: bytes per row, 16-byte slots per row, rows per 1 KiB piece
@@ -184,11 +213,9 @@ int launch_gemm_glds_inst(const GemmArgs& a, hipStream_t st) {
     attr_once.done(attr_dev);
   }
   const dim3 grid(a.N / (16 * BNS), (a.M + BMT * 16 - 1) / (BMT * 16), (EPI == EPI_KV && a.kv_layers) ? a.kv_nlayers : 1);
-  if (a.x_row_mul != 1 || a.x_row_off != 0) return ptts_fail(PTTS_E_UNSUPPORTED, "gemm_glds: activation rows must be consecutive (x_row_mul %d, x_row_off %d)", a.x_row_mul, a.x_row_off);
-  GemmArgs b = a;  // the two preloaded slots of the strip kernel's pass geometry carry what this kernel needs to address its first loads
-  if (grid.x > 0x7ffu || grid.y > 0xfffffu) return ptts_fail(PTTS_E_UNSUPPORTED, "gemm_glds: %u x %u tiles do not fit the packed grid extents", grid.x, grid.y);
-  b.rows_per_pass = a.x_ld; b.frags_per_wave = (int)((a.xcd_swz ? 1u : 0u) | (grid.x << 1) | (grid.y << 12));  // tile-order flag | tiles along N | tiles along M
-  ptts_klaunch(gemm_glds_kernel<EPI, BNS, BMT, WN, WM, NST, RP>, grid, dim3(WN * WM * 64), sh, st, b);
+  GemmGldsHead h;
+  PTTS_TRY(GemmGldsHead::pack(a, grid, h));
+  ptts_klaunch(gemm_glds_kernel<EPI, BNS, BMT, WN, WM, NST, RP>, grid, dim3(WN * WM * 64), sh, st, h, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "gemm launch failed: %s", hipGetErrorString(e));
   return PTTS_OK;

@@ -268,8 +268,8 @@ __device__ __forceinline__ void gv_softmax_wave(const GemvArgs& a, char* s_x, in
 // MB = 8 (batch 5..8): the activation chunks of MG utterances sit in registers at a time (MG * NCH <= 40 vectors), the wave's weight
 // registers are reused for every group; groups past the live batch are skipped (workgroup-uniform).
 template <typename WT, int NCH, int R, int PRO, int EPI, int S, int MB, bool W8, bool STG = false>
-__global__ void __launch_bounds__(((PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * Elem<WT>::EPL / 4 : MB)) + 4) * 64) gemv_kernel(GemvArgs_KPARAMS) {
-  GemvArgs_KJOIN(a)
+__global__ void __launch_bounds__(((PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * Elem<WT>::EPL / 4 : MB)) + 4) * 64) gemv_kernel(PTTS_KPARAMS(GemvArgs)) {
+  PTTS_KJOIN(GemvArgs, a)
   static_assert(!STG || (PRO == GV_COPY && MB == 8), "staged activation rows: GV_COPY nodes of the 5..8-utterance instances only");
   constexpr bool HASPRO = PRO != GV_COPY;
   constexpr int EPL = Elem<WT>::EPL;
@@ -434,8 +434,8 @@ __global__ void __launch_bounds__(((PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * 
 // softmax sums differs (the new position is a slot of its own instead of a row inside a split).
 // ------------------------------------------------------------------------------------------------------
 template <typename WT, int NCH, bool W8, int U>
-__global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs_KPARAMS) {
-  QkvAttnArgs_KJOIN(a)
+__global__ void __launch_bounds__(512) qkv_attn_kernel(PTTS_KPARAMS(QkvAttnArgs)) {
+  PTTS_KJOIN(QkvAttnArgs, a)
   constexpr int EPL = Elem<WT>::EPL, LPR = 64 / EPL, RPI = 64 / LPR, NW = 8, RW = 8;
   constexpr int NF4 = NCH * EPL / 4;
   constexpr int ROW_BYTES = NCH * 64 * 16;                          // H * sizeof(WT)
@@ -670,8 +670,8 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(QkvAttnArgs_KPARAMS) {
 // (GV_LNP) adds the rows in a fixed order - no atomics, bit-reproducible.
 // ------------------------------------------------------------------------------------------------------
 template <typename WT, int NCH, int NUR>
-__global__ void __launch_bounds__(512) xfold_attn_kernel(XfoldAttnArgs_KPARAMS) {
-  XfoldAttnArgs_KJOIN(a)
+__global__ void __launch_bounds__(512) xfold_attn_kernel(PTTS_KPARAMS(XfoldAttnArgs)) {
+  PTTS_KJOIN(XfoldAttnArgs, a)
   constexpr int EPL = Elem<WT>::EPL, LPR = 64 / EPL, RPI = 64 / LPR, NW = 8, RW = 8;
   constexpr int NF4 = NCH * EPL / 4;
   constexpr int ROW_BYTES = NCH * 64 * 16;  // H * sizeof(WT)

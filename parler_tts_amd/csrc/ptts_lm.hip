@@ -681,6 +681,15 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   PTTS_CHECK(c.max_batch >= 1 && c.max_ctx >= 2 && c.max_enc >= 1 && c.max_prompt >= 1 && c.max_prompt <= c.max_ctx, PTTS_E_INVALID, "bad capacities");
   const int nkv_ = c.num_kv_heads > 0 ? c.num_kv_heads : c.num_heads, nkc_ = c.num_cross_kv_heads > 0 ? c.num_cross_kv_heads : nkv_;
   PTTS_CHECK(c.num_heads % nkv_ == 0 && c.num_heads % nkc_ == 0, PTTS_E_INVALID, "num_heads %d not divisible by the K/V head counts %d / %d", c.num_heads, nkv_, nkc_);
+  // the bit-packed fields of the preloaded kernel heads: P and the prompt / description mask strides (PrefillAttnHead), the LM heads' row selection
+  // Q, Q - 1 (RowsPrepHead) in 16 bits; the prefill GEMMs' tile grid over B x max_prompt rows and B x max_enc description rows (GemmGldsHead)
+  PTTS_CHECK(c.max_prompt <= 0xffff && c.max_enc <= 0xffff, PTTS_E_UNSUPPORTED, "max_prompt %d / max_enc %d above 65535 (16-bit fields of the prefill kernels)",
+             c.max_prompt, c.max_enc);
+  const long long widest = std::max({(long long)c.hidden_size + 2LL * nkv_ * 64, (long long)c.ffn_dim, 2LL * nkc_ * 64,
+                                    (long long)c.num_codebooks * c.vocab_size});
+  PTTS_CHECK(GemmGldsHead::fits(widest, (long long)c.max_batch * std::max(c.max_prompt, c.max_enc)), PTTS_E_UNSUPPORTED,
+             "max_batch %d x max_prompt %d / max_enc %d rows over widths up to %lld: the prefill GEMM's tile grid exceeds its 20- / 11-bit extents",
+             c.max_batch, c.max_prompt, c.max_enc, widest);
   PTTS_DEVICE(c.device);
   ptts_engine* e = new ptts_engine();
   e->cfg = c;

@@ -86,22 +86,32 @@ enum { EPI_STORE = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_KV = 3, EPI_GELU_WT = 4, 
 
 struct KvLayer { const void* W; void* k; void* v; };  // one layer's operands of the batched cross K/V projection (EPI_KV over blockIdx.z)
 
-// Field order: the first 56 bytes are what a strip-kernel wave needs to ADDRESS its first loads (weight fragments, B fragments of fragment-order
-// rows, the pass's rows): gemm_strip_kernel takes them as scalar parameters that the command processor preloads into SGPRs (ptts_common.h: kernel-
-// argument preload) and everything else as KTail<GemmArgs>. Round 6 measured what fetching this struct by s_load costs a strip node: 0.43 us from the
-// wave's first instruction until the struct is usable, three nodes per layer (profiles/r06_node_stamps_bs32_bs128.txt, slot 14); the other kernels
+// Field order: the head (the first 56 bytes) is what a strip-kernel wave needs to ADDRESS its first loads (weight fragments, B fragments of
+// fragment-order rows, the pass's rows): gemm_strip_kernel takes it as scalar parameters that the command processor preloads into SGPRs (ptts_common.h:
+// kernel-argument preload) and everything else as KTail<GemmArgs>. Round 6 measured what fetching this struct by s_load costs a strip node: 0.43 us from
+// the wave's first instruction until the struct is usable, three nodes per layer (profiles/r06_node_stamps_bs32_bs128.txt, slot 14); the other kernels
 // that take GemmArgs keep the by-value form.
+// KDBG0: the timing build's leading stamp parameter (PTTS_DBG0_PARAM below), the stamp buffer of the struct's tail; nothing in the product library
+#ifdef PTTS_TIMING
+#define KDBG0(X) X(, PTTS_KCOMMA long long* dbg0_, , PTTS_KCOMMA a_.dbg, )
+#else
+#define KDBG0(X) X(, , , , )
+#endif
+// GEMM_KFLAGS: set by ptts_klaunch, m_split | x_fo << 1 | waves per workgroup << 8 (blockDim would be a hidden argument behind an s_load); the join
+// also takes m_split and x_fo from it (their tail copies are never loaded)
+#define GEMM_KFLAGS(X) X(int kflags;, PTTS_KCOMMA int k_kflags, h_.kflags = k_kflags; h_.m_split = k_kflags & 1; h_.x_fo = (k_kflags >> 1) & 1;, \
+                         PTTS_KCOMMA (h_.m_split ? 1 : 0) | (h_.x_fo ? 2 : 0) | ((int)(block.x >> 6) << 8), )
+#define GemmArgs_KHEAD(X)                                                                                                               \
+  KDBG0(X)                                                                                                                              \
+  KF(X, const void*, W)       /* packed strips */                                                                                       \
+  KF(X, const void*, W8)      /* e4m3 strips [N/16][K/64 fragment pairs][64 lanes][16 B] (weights_fp8 engines), or null: bf16 / fp32 strips in W */ \
+  KF(X, const float*, x)      /* PLAIN/LN input; x row index = m * x_row_mul + x_row_off */                                              \
+  KF(X, float*, out) KF(X, int, K) KF(X, int, M)                                                                                                           \
+  KF(X, int, rows_per_pass)   /* activation rows staged in LDS per pass (<= 16 * MTP) */                                                \
+  KF(X, int, frags_per_wave)  /* FULL variant: K/KT/W, a multiple of 8 */                                                               \
+  KF(X, int, out_ld) GEMM_KFLAGS(X) KTAIL(X, GemmArgs)
 struct GemmArgs {
-  // ---- bytes 0..55: preloaded ----
-  const void* W;       // packed strips
-  const void* W8;      // e4m3 strips [N/16][K/64 fragment pairs][64 lanes][16 B] (weights_fp8 engines), or null: bf16 / fp32 strips in W
-  const float* x;      // PLAIN/LN input; x row index = m * x_row_mul + x_row_off
-  float* out;
-  int K, M;
-  int rows_per_pass;   // activation rows staged in LDS per pass (<= 16 * MTP)
-  int frags_per_wave;  // FULL variant: K/KT/W, a multiple of 8
-  int out_ld;
-  int kflags;          // set by ptts_klaunch: m_split | x_fo << 1 | waves per workgroup << 8 (blockDim would be a hidden argument behind an s_load)
+  PTTS_KMEMBERS(GemmArgs)
   // ---- tail: what the decode step's strip instances read first (one or two scalar cache lines behind the preloaded bytes: the s_load latency of
   // this struct grew with the number of lines touched - 0.14 us for lnproj's 100 bytes, 0.43 us for five scattered lines of this one) ----
   int m_split;         // PRO_COPY: blockIdx.z selects ONE pass of rows_per_pass rows (grid.z = passes) instead of looping over them
@@ -147,14 +157,7 @@ struct GemmArgs {
   int decode;          // host-side launch policy only: 1 = a decode-step GEMM (light M passes, msplit_rows), 0 = prefill-sized rows
   const int* row_keep; // PRO_RMS: [M] int32 or null; rows with 0 are written as zeros (masked description positions, modeling_parler_tts.py:3093-3097)
 };
-static_assert(sizeof(GemmArgs) % 8 == 0 && offsetof(GemmArgs, m_split) == 56, "GemmArgs: 56 preloaded bytes + tail");
-#define GemmArgs_KPARAMS                                                                                                                          \
-  const void *kW_, const void *kW8_, const float *kx_, float *kout_, int kK_, int kM_, int krpp_, int kfpw_, int kold_, int kfl_, KTail<GemmArgs> kt_
-#define GemmArgs_KJOIN(a)                                                                                          \
-  GemmArgs a;                                                                                                      \
-  PTTS_KTAIL_JOIN(GemmArgs, a);                                                                                    \
-  a.W = kW_; a.W8 = kW8_; a.x = kx_; a.out = kout_; a.K = kK_; a.M = kM_; a.rows_per_pass = krpp_; a.frags_per_wave = kfpw_; a.out_ld = kold_;  \
-  a.kflags = kfl_; a.m_split = kfl_ & 1; a.x_fo = (kfl_ >> 1) & 1;
+PTTS_KLAUNCH(GemmArgs)
 
 // ---- activations in MFMA B-fragment order ("FO") -----------------------------------------------------------------------------
 // Decode at batch > 8: the engine-dtype activation rows that a PRO_COPY GEMM consumes are written by their producers (rows_prep,
@@ -572,13 +575,6 @@ __device__ __forceinline__ void gemm_store_kv_cols(const GemmArgs& a, int m, int
 #pragma unroll
   for (int e = 0; e < 4; ++e) store_from_f32<WT>(dst + e, r[e]);
 }
-// host side of the split argument list of gemm_strip_kernel (GemmArgs_KPARAMS)
-template <typename Kn> inline void ptts_klaunch(Kn kern, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const GemmArgs& a) {
-  const int kflags = (a.m_split ? 1 : 0) | (a.x_fo ? 2 : 0) | ((int)(block.x >> 6) << 8);
-  hipLaunchKernelGGL(kern, grid, block, shmem, st, PTTS_DBG0_ARG(a) a.W, a.W8, a.x, a.out, a.K, a.M, a.rows_per_pass, a.frags_per_wave, a.out_ld, kflags,
-                     ptts_ktail(a));
-}
-
 // LN / ATTN prologues always reduce over K = hidden_size (<= 8 waves of >= 8 fragments); only the plain prologue
 // (fc2, K = ffn_dim) at batch <= 16 wants 16 waves, so only it pays the 128-VGPR cap of a 1024-thread workgroup.
 template <int PRO, int MTP> struct GemmMaxThreads { static constexpr int value = (PRO == PRO_PLAIN && MTP == 1) ? 1024 : 512; };
@@ -812,9 +808,9 @@ __device__ __forceinline__ void gemm_strip_body(GemmArgs& a) {
 #define PTTS_STRIP_PRELOAD(PRO, EPI, FULL) ((FULL) || (PRO) == PRO_COPY)
 #endif
 template <typename WT, int PRO, int EPI, int MTP, bool FULL, bool W8 = false>
-__global__ void __launch_bounds__((GemmMaxThreads<PRO, MTP>::value)) gemm_strip_kernel(PTTS_DBG0_PARAM GemmArgs_KPARAMS) {
+__global__ void __launch_bounds__((GemmMaxThreads<PRO, MTP>::value)) gemm_strip_kernel(PTTS_KPARAMS(GemmArgs)) {
   PTTS_STAMP0();
-  GemmArgs_KJOIN(a)
+  PTTS_KJOIN(GemmArgs, a)
   gemm_strip_body<WT, PRO, EPI, MTP, FULL, W8>(a);
 }
 template <typename WT, int PRO, int EPI, int MTP, bool FULL, bool W8 = false>
@@ -1183,15 +1179,36 @@ __device__ __forceinline__ void prep_rms_row(const GemmArgs& a, int m, WT* dst, 
   }
 }
 
-// Kernel-argument preload (ptts_common.h; call 54): the node takes the first 56 bytes of GemmArgs as scalars like the GEMMs it feeds. It has no weights, so
-// launch_prep puts what addresses a wave's first loads into the preloaded slots it does not use - gamma / beta in W / W8, the destination in `out`, the row
-// stride in rows_per_pass, x_row_mul | x_row_off << 16 in frags_per_wave, out_fo in out_ld - and the kernel writes them back into the re-assembled struct (in
-// registers: the tail's own copies of those fields are never loaded).
+// Kernel-argument preload (ptts_common.h; call 54): the node takes 56 bytes of scalars in front of KTail<GemmArgs> like the GEMMs it feeds. It has no
+// weights, so its head is its own and holds what addresses a wave's first loads: gamma / beta, the rows, the destination, the row stride and selection.
+#define RowsPrepHead_KHEAD(X)                                                                                                           \
+  KDBG0(X)                                                                                                                              \
+  KF(X, const float*, gamma)  /* PRO_LN / PRO_RMS weight [K] */                                                                         \
+  KF(X, const float*, beta)   /* PRO_LN bias [K] */                                                                                     \
+  KF(X, const float*, x)      /* input rows fp32, row stride x_ld */                                                                    \
+  KF(X, void*, dst)           /* the prepared rows, engine dtype [M][K] (row-major or B-fragment order by out_fo) */                    \
+  KF(X, int, K) KF(X, int, M) KF(X, int, x_ld)                                                                                          \
+  KF(X, unsigned, row_sel)    /* x_row_mul | x_row_off << 16: output row m reads input row m * x_row_mul + x_row_off (the LM heads: the last   \
+                                 position of each utterance, x_row_mul = Q <= max_prompt, checked at engine creation) */                 \
+  KF(X, int, out_fo) KF(X, int, pad_) KTAIL(X, GemmArgs)
+struct RowsPrepHead {
+  PTTS_KMEMBERS(RowsPrepHead)
+  static int pack(const GemmArgs& a, void* dst, RowsPrepHead& h) {
+    if ((unsigned)a.x_row_mul > 0xffffu || (unsigned)a.x_row_off > 0xffffu)
+      return ptts_fail(PTTS_E_UNSUPPORTED, "rows_prep: row selection %d * m + %d above the 16-bit fields", a.x_row_mul, a.x_row_off);
+    h.gamma = a.gamma; h.beta = a.beta; h.x = a.x; h.dst = dst; h.K = a.K; h.M = a.M; h.x_ld = a.x_ld;
+    h.row_sel = (unsigned)a.x_row_mul | ((unsigned)a.x_row_off << 16); h.out_fo = a.out_fo; h.pad_ = 0;
+    return PTTS_OK;
+  }
+  __device__ __forceinline__ void unpack(GemmArgs& a) const {
+    a.gamma = gamma; a.beta = beta; a.x = x; a.out = reinterpret_cast<float*>(dst); a.K = K; a.M = M; a.x_ld = x_ld;
+    a.x_row_mul = row_sel & 0xffff; a.x_row_off = (int)(row_sel >> 16); a.out_fo = out_fo;
+  }
+};
+PTTS_KLAUNCH_VIA(RowsPrepHead, GemmArgs)
 template <typename WT, int PRO>
-__global__ void __launch_bounds__(256) rows_prep_kernel(PTTS_DBG0_PARAM GemmArgs_KPARAMS) {
-  GemmArgs_KJOIN(a)
-  a.gamma = reinterpret_cast<const float*>(a.W); a.beta = reinterpret_cast<const float*>(a.W8);
-  a.x_ld = a.rows_per_pass; a.x_row_mul = a.frags_per_wave & 0xffff; a.x_row_off = (int)((unsigned)a.frags_per_wave >> 16); a.out_fo = a.out_ld;
+__global__ void __launch_bounds__(256) rows_prep_kernel(PTTS_KPARAMS(RowsPrepHead)) {
+  PTTS_KJOIN_VIA(RowsPrepHead, GemmArgs, a)
   WT* __restrict__ dst = reinterpret_cast<WT*>(a.out);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = blockIdx.x * 4 + wave;
@@ -1244,14 +1261,13 @@ __global__ void __launch_bounds__(256) rows_prep_kernel(PTTS_DBG0_PARAM GemmArgs
 //   cross        : static K/V (:872-875), additive padding mask (:1553-1562) as -inf, q rotated if RoPE (quirk)
 // ------------------------------------------------------------------------------------------------------
 struct AttnArgs {
-  // ---- bytes 0..55: what the PREFILL attention kernels take as scalar kernel parameters (preloaded into SGPRs by the command processor; call 54) ----
   const float* q;      // [rows][q_ld], head h at column h*64
   int q_ld;
-  int pre0;            // prefill kernels: P | mask_ld << 16 (launch_prefill_attn)
-  const float* knew;   // fused append sources (same row indexing), or null            | prefill kernels: the mask pointer
-  const float* vnew;   //                                                              | prefill kernels: Q | kv_heads << 32 | n_rep << 48
-  int kv_ld;           //                                                              | prefill kernels: cap
-  int pre1;            // prefill kernels: the description length N (cross block) or -1 (self block)
+  int q_pad_;
+  const float* knew;   // fused append sources (same row indexing), or null
+  const float* vnew;
+  int kv_ld;
+  int kv_pad_;
   void* kcache;
   void* vcache;
   // ---- tail ----
@@ -1277,36 +1293,36 @@ struct AttnArgs {
   int hostP, hostN;    // prefill: the prompt / description lengths of this call as the HOST knows them (dims holds the same numbers on the device)
   PTTS_DBG_FIELD
 };
-static_assert(sizeof(AttnArgs) % 8 == 0 && offsetof(AttnArgs, cap) == 56, "AttnArgs: 56 preloaded bytes + tail");
-// The prefill attention kernels (prefill_attn_kernel, prefill_attn_mfma_kernel) take the first 56 bytes as scalars; they never use knew / vnew / kv_ld, so
-// launch_prefill_attn carries in those slots what addresses a wave's first loads - and what the kernels used to fetch through `dims` on the device (a
-// second, dependent scalar round trip): P, N, Q, the cache capacity, the mask pointer / row stride and the K/V head geometry. PREFILL_ATTN_JOIN writes them
-// back into the re-assembled struct (in registers: the tail's own copies are never loaded) and defines P and NK (N of the cross block, -1 for self).
-#define AttnArgs_KPARAMS \
-  const float *kq_, int kqld_, int kpre0_, const float *kknew_, const float *kvnew_, int kkvld_, int kpre1_, void *kkc_, void *kvc_, KTail<AttnArgs> kt_
-#define PREFILL_ATTN_JOIN(a)                                                                                                          \
-  AttnArgs a;                                                                                                                         \
-  PTTS_KTAIL_JOIN(AttnArgs, a);                                                                                                       \
-  a.q = kq_; a.q_ld = kqld_; a.kcache = kkc_; a.vcache = kvc_; a.cap = kkvld_;                                                        \
-  a.mask = reinterpret_cast<const int*>(kknew_); a.mask_ld = (int)((unsigned)kpre0_ >> 16);                                          \
-  const int P = kpre0_ & 0xffff, NK = kpre1_;                                                                                         \
-  a.cross = NK >= 0;                                                                                                                  \
-  {                                                                                                                                   \
-    const unsigned long long u_ = reinterpret_cast<unsigned long long>(kvnew_);                                                       \
-    a.Q = (int)(u_ & 0xffffffffull); a.kv_heads = (int)((u_ >> 32) & 0xffff); a.n_rep = (int)(u_ >> 48);                              \
+static_assert(sizeof(AttnArgs) % 8 == 0 && offsetof(AttnArgs, cap) == 56, "AttnArgs: the prefill kernels' tail starts at byte 56");
+// The prefill attention kernels (prefill_attn_kernel, prefill_attn_mfma_kernel; call 54) take 56 bytes of scalars in front of KTail<AttnArgs>: what
+// addresses a wave's first loads and what they used to fetch through `dims` on the device (a second, dependent scalar round trip) - the cache
+// capacity, the mask pointer and row stride, P, N, Q and the K/V head geometry. PREFILL_ATTN_JOIN re-assembles AttnArgs (the tail's own copies
+// of those fields are never loaded) and defines P and NK (N of the cross block, -1 for self).
+#define PrefillAttnHead_KHEAD(X)                                                                                                        \
+  KF(X, const float*, q) KF(X, int, q_ld)                                                                                               \
+  KF(X, unsigned, P_mask_ld)  /* P | mask_ld << 16; both <= max_prompt (self) or max_enc (cross), checked at engine creation */          \
+  KF(X, const int*, mask)                                                                                                               \
+  KF(X, ptts_u64, Q_kv_geo)   /* Q | kv_heads << 32 | n_rep << 48 */                                                                    \
+  KF(X, int, cap)                                                                                                                       \
+  KF(X, int, nk)              /* the description length N (cross block) or -1 (self block) */                                           \
+  KF(X, void*, kcache) KF(X, void*, vcache) KTAIL(X, AttnArgs)
+struct PrefillAttnHead {
+  PTTS_KMEMBERS(PrefillAttnHead)
+  static int pack(const AttnArgs& a, PrefillAttnHead& h) {
+    if ((unsigned)a.hostP > 0xffffu || (unsigned)a.mask_ld > 0xffffu || (unsigned)a.kv_heads > 0xffffu || (unsigned)a.n_rep > 0xffffu || a.Q < 0)
+      return ptts_fail(PTTS_E_UNSUPPORTED, "prefill attention: P %d / mask_ld %d / heads %d x %d above the 16-bit fields", a.hostP, a.mask_ld, a.kv_heads, a.n_rep);
+    h.q = a.q; h.q_ld = a.q_ld; h.P_mask_ld = (unsigned)a.hostP | ((unsigned)a.mask_ld << 16); h.mask = a.mask;
+    h.Q_kv_geo = (ptts_u64)(unsigned)a.Q | ((ptts_u64)a.kv_heads << 32) | ((ptts_u64)a.n_rep << 48); h.cap = a.cap; h.nk = a.cross ? a.hostN : -1; h.kcache = a.kcache; h.vcache = a.vcache;
+    return PTTS_OK;
   }
-template <typename Kn> inline int ptts_launch_prefill_attn_kernel(Kn kern, dim3 grid, dim3 block, hipStream_t st, const AttnArgs& a) {
-  if ((unsigned)a.hostP > 0xffffu || (unsigned)a.mask_ld > 0xffffu || (unsigned)a.kv_heads > 0xffffu || (unsigned)a.n_rep > 0xffffu || a.Q < 0)
-    return ptts_fail(PTTS_E_UNSUPPORTED, "prefill attention: P %d / mask_ld %d / heads %d x %d do not fit the packed slots", a.hostP, a.mask_ld, a.kv_heads, a.n_rep);
-  AttnArgs b = a;
-  b.pre0 = (int)((unsigned)a.hostP | ((unsigned)a.mask_ld << 16));
-  b.pre1 = a.cross ? a.hostN : -1;
-  b.knew = reinterpret_cast<const float*>(a.mask);
-  b.vnew = reinterpret_cast<const float*>((unsigned long long)(unsigned)a.Q | ((unsigned long long)a.kv_heads << 32) | ((unsigned long long)a.n_rep << 48));
-  b.kv_ld = a.cap;
-  hipLaunchKernelGGL(kern, grid, block, 0, st, b.q, b.q_ld, b.pre0, b.knew, b.vnew, b.kv_ld, b.pre1, b.kcache, b.vcache, ptts_ktail(b));
-  return PTTS_OK;
-}
+  __device__ __forceinline__ void unpack(AttnArgs& a) const {
+    a.q = q; a.q_ld = q_ld; a.kcache = kcache; a.vcache = vcache; a.cap = cap; a.mask = mask; a.mask_ld = (int)(P_mask_ld >> 16);
+    a.cross = nk >= 0; a.Q = (int)(Q_kv_geo & 0xffffffffull); a.kv_heads = (int)((Q_kv_geo >> 32) & 0xffff); a.n_rep = (int)(Q_kv_geo >> 48);
+  }
+  __device__ __forceinline__ int P() const { return (int)(P_mask_ld & 0xffffu); }
+};
+PTTS_KLAUNCH_VIA(PrefillAttnHead, AttnArgs)
+#define PREFILL_ATTN_JOIN(a) PTTS_KJOIN_VIA(PrefillAttnHead, AttnArgs, a) const int P = h_.P(), NK = h_.nk;
 
 // load EPL consecutive floats of a row chunk, optionally RoPE-rotated (x*cos + rotate_half(x)*sin, modeling:409-436)
 template <int EPL>
@@ -1595,7 +1611,7 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(AttnArgs a) {
 // Reference: modeling_parler_tts.py:906-914 (SDPA), :1474-1501 / :1553-1562 (masks).
 // ------------------------------------------------------------------------------------------------------
 template <typename WT, bool KV8 = false>
-__global__ void __launch_bounds__(256) prefill_attn_kernel(AttnArgs_KPARAMS) {
+__global__ void __launch_bounds__(256) prefill_attn_kernel(PTTS_KPARAMS(PrefillAttnHead)) {
   PREFILL_ATTN_JOIN(a)
   static_assert(!KV8 || sizeof(WT) == 2, "e4m3 cache: bf16 engine");
   constexpr int QW = 2, QB = 4 * QW, EPL = Elem<WT>::EPL;
@@ -1727,7 +1743,7 @@ template <> struct Row8<float> {
 // load -> wait -> LDS store in a row in front of every key block (profiles/r06_prefill_kernels_bs32_v4.txt: 15.4 us per launch for 33 x 33 / 33 x 64 scores
 // per head). Unrolled, all of a thread's K / V pieces are requested before the first is stored. Same arithmetic: bit-identical.
 template <typename WT, int NW>
-__global__ void __launch_bounds__(NW * 64) prefill_attn_mfma_kernel(AttnArgs_KPARAMS) {
+__global__ void __launch_bounds__(NW * 64) prefill_attn_mfma_kernel(PTTS_KPARAMS(PrefillAttnHead)) {
   PREFILL_ATTN_JOIN(a)
   __shared__ __attribute__((aligned(16))) float sK[64 * 64];
   __shared__ __attribute__((aligned(16))) float sV[64 * 64];
@@ -1879,17 +1895,17 @@ __global__ void __launch_bounds__(NW * 64) prefill_attn_mfma_kernel(AttnArgs_KPA
 // cross-XCD round trip by one; output is the normalised context in the engine dtype, read by the out_proj GEMM
 // (PRO_COPY). RoPE quirk kept: q rotated, keys not (:858-859 vs :880).
 // ------------------------------------------------------------------------------------------------------
+// Head: scalar kernel parameters, preloaded into SGPRs by the command processor (ptts_common.h; round 6)
+#define XAttnArgs_KHEAD(X)                                                                                                              \
+  KF(X, const void*, W)       /* packed cross q_proj [H/16][K/KT][64][16 B] */                                                          \
+  KF(X, const float*, x)      /* residual stream h [B][x_ld] */                                                                         \
+  KF(X, const float*, gamma)                                                                                                            \
+  KF(X, void*, kcache) KF(X, void*, vcache)  /* cross K/V [B][heads][cap][64] */                                                      \
+  KF(X, int, x_ld)                                                                                                                      \
+  KF(X, int, K)               /* hidden size */                                                                                         \
+  KF(X, int, B) KF(X, int, cap) KTAIL(X, XAttnArgs)
 struct XAttnArgs {
-  // ---- bytes 0..55: scalar kernel parameters, preloaded into SGPRs by the command processor (ptts_common.h; round 6) ----
-  const void* W;       // packed cross q_proj [H/16][K/KT][64][16 B]
-  const float* x;      // residual stream h [B][x_ld]
-  const float* gamma;
-  void* kcache;        // cross K/V [B][heads][cap][64]
-  void* vcache;
-  int x_ld;
-  int K;               // hidden size
-  int B;
-  int cap;
+  PTTS_KMEMBERS(XAttnArgs)
   // ---- tail (KTail<XAttnArgs>) ----
   int x_row_mul, x_row_off;
   const float* beta;
@@ -1908,22 +1924,13 @@ struct XAttnArgs {
   int xa_pad_;
   PTTS_DBG_FIELD
 };
-static_assert(sizeof(XAttnArgs) % 8 == 0 && offsetof(XAttnArgs, x_row_mul) == 56, "XAttnArgs: 56 preloaded bytes + tail");
-#define XAttnArgs_KPARAMS \
-  const void *kW_, const float *kx_, const float *kg_, void *kkc_, void *kvc_, int kxld_, int kK_, int kB_, int kcap_, KTail<XAttnArgs> kt_
-#define XAttnArgs_KJOIN(a)                                                                                   \
-  XAttnArgs a;                                                                                               \
-  PTTS_KTAIL_JOIN(XAttnArgs, a);                                                                             \
-  a.W = kW_; a.x = kx_; a.gamma = kg_; a.kcache = kkc_; a.vcache = kvc_; a.x_ld = kxld_; a.K = kK_; a.B = kB_; a.cap = kcap_;
-template <typename Kn> inline void ptts_klaunch(Kn kern, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const XAttnArgs& a) {
-  hipLaunchKernelGGL(kern, grid, block, shmem, st, a.W, a.x, a.gamma, a.kcache, a.vcache, a.x_ld, a.K, a.B, a.cap, ptts_ktail(a));
-}
+PTTS_KLAUNCH(XAttnArgs)
 
 // G = utterances per workgroup (8: one per wave; 4 / 2: at batch > 8 the launch covers heads x ceil(B / G) workgroups - 128 / 256 at 32
 // utterances instead of 64 - and the 8 / G waves of an utterance split the description's row groups and merge through LDS).
 template <typename WT, int UW, int NF4, int G = 8>
-__global__ void __launch_bounds__(512) xattn_fused_kernel(XAttnArgs_KPARAMS) {
-  XAttnArgs_KJOIN(a)
+__global__ void __launch_bounds__(512) xattn_fused_kernel(PTTS_KPARAMS(XAttnArgs)) {
+  PTTS_KJOIN(XAttnArgs, a)
   constexpr int KT = Elem<WT>::KT, EPL = Elem<WT>::EPL, LPR = 64 / EPL, RPI = 64 / LPR, U = 8, NWV = 8;
   constexpr int WPU = NWV / G, UA = U / WPU;  // waves per utterance in the attention phase; row groups per wave and batch
   static_assert(G == 8 || G == 4 || G == 2, "utterances per workgroup");
@@ -2131,17 +2138,18 @@ __global__ void __launch_bounds__(512) xattn_fused_kernel(XAttnArgs_KPARAMS) {
 // 8 waves = 4 weight strips x 2 K halves; wave w < nb normalises row b0 + w first.
 // EPI_STORE: fp32 [M][out_ld] (QKV); EPI_GELU_WT: gelu_erf in the engine dtype, row-major or MFMA B-fragment order (fc1 -> fc2).
 // ------------------------------------------------------------------------------------------------------
+// Head: scalar kernel parameters, preloaded into SGPRs by the command processor (ptts_common.h; round 6: the node is on the path of every decode step
+// above 8 utterances twice per layer and of a short prompt's prefill three times per layer)
+#define LnProjArgs_KHEAD(X)                                                                                                             \
+  KDBG0(X)                                                                                                                              \
+  KF(X, const void*, W)       /* packed strips [N/16][K/KT][64][16 B] */                                                                \
+  KF(X, const float*, x)      /* residual stream h [M][x_ld] */                                                                         \
+  KF(X, const float*, gamma) KF(X, const float*, beta) KF(X, void*, out)                                                              \
+  KF(X, int, x_ld)                                                                                                                      \
+  KF(X, int, K)               /* hidden size (= NF4 * 256) */                                                                           \
+  KF(X, int, M) KF(X, int, N) KTAIL(X, LnProjArgs)
 struct LnProjArgs {
-  // ---- bytes 0..55: scalar kernel parameters, preloaded into SGPRs by the command processor (ptts_common.h; round 6: the node is on the path of every
-  // decode step above 8 utterances twice per layer and of a short prompt's prefill three times per layer) ----
-  const void* W;        // packed strips [N/16][K/KT][64][16 B]
-  const float* x;       // residual stream h [M][x_ld]
-  const float* gamma;
-  const float* beta;
-  void* out;
-  int x_ld;
-  int K;                // hidden size (= NF4 * 256)
-  int M, N;
+  PTTS_KMEMBERS(LnProjArgs)
   // ---- tail (KTail<LnProjArgs>) ----
   float invK;
   int out_ld;
@@ -2155,23 +2163,14 @@ struct LnProjArgs {
   int kv_cap, kv_heads, kv_H, kv_pad_;  // columns [kv_H, kv_H + 64 kv_heads) = K, then V
   PTTS_DBG_FIELD
 };
-static_assert(sizeof(LnProjArgs) % 8 == 0 && offsetof(LnProjArgs, invK) == 56, "LnProjArgs: 56 preloaded bytes + tail");
-#define LnProjArgs_KPARAMS \
-  const void *kW_, const float *kx_, const float *kg_, const float *kb_, void *kout_, int kxld_, int kK_, int kM_, int kN_, KTail<LnProjArgs> kt_
-#define LnProjArgs_KJOIN(a)                                                                                  \
-  LnProjArgs a;                                                                                              \
-  PTTS_KTAIL_JOIN(LnProjArgs, a);                                                                            \
-  a.W = kW_; a.x = kx_; a.gamma = kg_; a.beta = kb_; a.out = kout_; a.x_ld = kxld_; a.K = kK_; a.M = kM_; a.N = kN_;
-template <typename Kn> inline void ptts_klaunch(Kn kern, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const LnProjArgs& a) {
-  hipLaunchKernelGGL(kern, grid, block, shmem, st, PTTS_DBG0_ARG(a) a.W, a.x, a.gamma, a.beta, a.out, a.x_ld, a.K, a.M, a.N, ptts_ktail(a));
-}
+PTTS_KLAUNCH(LnProjArgs)
 
 // G = 16 (round 5): two rows per wave (rows w and w + 8, both in flight), all 16 columns of the MFMA tile in use - half the weight re-reads of
 // G = 8 per utterance (the L2 traffic of the strip GEMM it replaces at 64..128 utterances).
 template <typename WT, int UW, int NF4, int G, int EPI>
-__global__ void __launch_bounds__(512) lnproj_fused_kernel(PTTS_DBG0_PARAM LnProjArgs_KPARAMS) {
+__global__ void __launch_bounds__(512) lnproj_fused_kernel(PTTS_KPARAMS(LnProjArgs)) {
   PTTS_STAMP0();
-  LnProjArgs_KJOIN(a)
+  PTTS_KJOIN(LnProjArgs, a)
   constexpr int KT = Elem<WT>::KT, NWV = 8;
   static_assert(G <= 2 * NWV, "at most two rows per wave");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];

@@ -67,34 +67,29 @@ __global__ void pack_weight_ilv_kernel(const ST* __restrict__ src, WT* __restric
   for (int e = 0; e < EPL; ++e) store_from_f32<WT>(d + e, load_as_f32<ST>(src + (size_t)row * K + k + e));
 }
 
+// The attention kernels take the whole struct as SCALAR parameters (14 dwords = exactly what the command processor preloads into SGPRs before the first
+// wave starts, -mllvm -amdgpu-kernarg-preload-count=14, ptts_common.h): no s_load in front of the wave's first loads (call 54). Head only: no tail.
+#define T5AttnArgs_KHEAD(X)                                                                                                             \
+  KF(X, const float*, qkv)    /* [B*N][ld] fp32: q at column h*64, k at inner + h*64, v at 2*inner + h*64 */                            \
+  KF(X, int, ld) KF(X, int, inner)                                                                                                      \
+  KF(X, const float*, bias)   /* [heads][bias_ld], entry (key - query) + bias_zero */                                                   \
+  KF(X, int, bias_ld) KF(X, int, bias_zero)                                                                                             \
+  KF(X, const int*, mask)     /* [B][N] int32 (1 = keep) or null */                                                                     \
+  KF(X, void*, out)           /* [B*N][inner] engine dtype, row-major or MFMA B-fragment order */                                       \
+  KF(X, int, N)                                                                                                                         \
+  KF(X, int, out_fo)
 struct T5AttnArgs {
-  const float* qkv;   // [B*N][ld] fp32: q at column h*64, k at inner + h*64, v at 2*inner + h*64
-  int ld, inner;
-  const float* bias;  // [heads][bias_ld], entry (key - query) + bias_zero
-  int bias_ld, bias_zero;
-  const int* mask;    // [B][N] int32 (1 = keep) or null
-  void* out;          // [B*N][inner] engine dtype, row-major or MFMA B-fragment order
-  int N;
-  int out_fo;
+  PTTS_KMEMBERS(T5AttnArgs)
 };
-// The attention kernels take the struct's fields as SCALAR parameters (14 dwords = exactly what the command processor preloads into SGPRs before the first wave
-// starts, -mllvm -amdgpu-kernarg-preload-count=14, ptts_common.h): no s_load in front of the wave's first loads (call 54).
-static_assert(sizeof(T5AttnArgs) == 56, "T5AttnArgs: the 14 preloaded dwords");
-#define T5AttnArgs_KPARAMS const float *kqkv_, int kld_, int kinner_, const float *kbias_, int kbld_, int kbz_, const int *kmask_, void *kout_, int kN_, int kfo_
-#define T5AttnArgs_KJOIN(a) \
-  T5AttnArgs a;             \
-  a.qkv = kqkv_; a.ld = kld_; a.inner = kinner_; a.bias = kbias_; a.bias_ld = kbld_; a.bias_zero = kbz_; a.mask = kmask_; a.out = kout_; a.N = kN_; a.out_fo = kfo_;
-template <typename Kn> inline void t5_attn_launch(Kn kern, dim3 grid, dim3 block, hipStream_t st, const T5AttnArgs& a) {
-  hipLaunchKernelGGL(kern, grid, block, 0, st, a.qkv, a.ld, a.inner, a.bias, a.bias_ld, a.bias_zero, a.mask, a.out, a.N, a.out_fo);
-}
+PTTS_KLAUNCH(T5AttnArgs)
 
 // T5Attention.forward, encoder self-attention: scores = q k^T (NO 1/sqrt(d) scale) + position_bias (+ (1 - mask) * finfo.min), softmax in fp32,
 // context = p v. One workgroup = 8 queries of one (utterance, head): 4 waves x 2 queries; keys in tiles of 64 (lane = key), K / V tiles staged in
 // LDS once per workgroup, online softmax across tiles. A masked key keeps the score -FLT_MAX exactly as the additive mask leaves it (a fully
 // masked row is therefore uniform over all N keys, like the reference); keys beyond N do not exist.
 template <typename WT>
-__global__ void __launch_bounds__(256) t5_attn_kernel(T5AttnArgs_KPARAMS) {
-  T5AttnArgs_KJOIN(a)
+__global__ void __launch_bounds__(256) t5_attn_kernel(PTTS_KPARAMS(T5AttnArgs)) {
+  PTTS_KJOIN(T5AttnArgs, a)
   constexpr int QW = 2, QB = 4 * QW, EPL = Elem<WT>::EPL;
   __shared__ float sK[64 * 65];
   __shared__ __attribute__((aligned(16))) float sV[64 * 64];
@@ -179,8 +174,8 @@ __global__ void __launch_bounds__(256) t5_attn_kernel(T5AttnArgs_KPARAMS) {
 //                 for the probabilities), B = V[16 kt + 4 g + r][4 j + dt] (one b128 read per key: ptts_common.h, attn_block_*)
 // k order of the q.k sums: d = 16 c + e + 4 g over (c, e) then g (fixed, deterministic); of the p.v sums: keys 16 kt + r + 4 g over (kt, r) then g.
 template <typename WT>
-__global__ void __launch_bounds__(256) t5_attn_mfma_kernel(T5AttnArgs_KPARAMS) {
-  T5AttnArgs_KJOIN(a)
+__global__ void __launch_bounds__(256) t5_attn_mfma_kernel(PTTS_KPARAMS(T5AttnArgs)) {
+  PTTS_KJOIN(T5AttnArgs, a)
   __shared__ __attribute__((aligned(16))) float sK[64 * 64];
   __shared__ __attribute__((aligned(16))) float sV[64 * 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 15, g = lane >> 4;
@@ -364,6 +359,8 @@ extern "C" int ptts_t5_create(const ptts_t5_config* cfg, ptts_t5** out) {
   PTTS_CHECK(c.d_model % 32 == 0 && c.d_ff % 32 == 0 && c.d_model >= 32 && c.d_ff >= 32, PTTS_E_UNSUPPORTED, "d_model / d_ff must be multiples of 32");
   PTTS_CHECK(c.rel_buckets >= 4 && c.rel_buckets % 4 == 0 && c.rel_max_distance > c.rel_buckets / 4, PTTS_E_INVALID, "bad relative-attention buckets %d / max distance %d", c.rel_buckets, c.rel_max_distance);
   PTTS_CHECK(c.max_batch >= 1 && c.max_len >= 1, PTTS_E_INVALID, "bad capacities");
+  PTTS_CHECK(GemmGldsHead::fits(std::max({3LL * c.num_heads * c.d_kv, 2LL * c.d_ff, (long long)c.d_model}), (long long)c.max_batch * c.max_len), PTTS_E_UNSUPPORTED,
+             "max_batch %d x max_len %d rows: the encoder GEMM's tile grid exceeds its 20- / 11-bit extents (GemmGldsHead)", c.max_batch, c.max_len);
   PTTS_DEVICE(c.device);
   ptts_t5* e = new ptts_t5();
   e->cfg = c;
@@ -495,9 +492,9 @@ int t5_forward(ptts_t5* e, int B, int N, bool has_mask, hipStream_t st) {
       a.mask = has_mask ? e->mask : nullptr; a.out = e->ctx; a.out_fo = fo; a.N = N;
       // batches that fill the chip with 64-query workgroups: the f32-MFMA kernel (PTTS_T5_ATTN_MFMA=0: the VALU kernel everywhere; =1: the MFMA kernel everywhere)
       if (mfma_mode == 1 || (mfma_mode == 2 && B * c.num_heads * ((N + 63) / 64) >= 128))
-        t5_attn_launch(t5_attn_mfma_kernel<WT>, dim3((N + 63) / 64, c.num_heads, B), dim3(256), st, a);
+        ptts_klaunch(t5_attn_mfma_kernel<WT>, dim3((N + 63) / 64, c.num_heads, B), dim3(256), 0, st, a);
       else
-        t5_attn_launch(t5_attn_kernel<WT>, dim3((N + 7) / 8, c.num_heads, B), dim3(256), st, a);
+        ptts_klaunch(t5_attn_kernel<WT>, dim3((N + 7) / 8, c.num_heads, B), dim3(256), 0, st, a);
     }
     {  // hidden = hidden + o(context)
       GemmArgs g = {};

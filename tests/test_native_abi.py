@@ -43,6 +43,16 @@ def test_invalid_config_is_value_error_not_crash():
     with pytest.raises(NotImplementedError, match="head_dim"):
         N.check(rc)
     assert lib.ptts_engine_create(None, C.byref(h)) == N.PTTS_E_INVALID
+    # capacities above the 16-bit / tile-grid fields of the preloaded kernel arguments: refused at creation, before any device work
+    for max_ctx, max_enc, max_prompt in ((65536, 16, 65536), (64, 65536, 8)):
+        cfg = N.PttsConfig(1024, 2, 16, 256, 9, 1088, 256, 0, 10000.0, 1024, 1024, 1025, N.PTTS_BF16, 1, max_ctx, max_enc, max_prompt, 0, 0, 0)
+        rc = lib.ptts_engine_create(C.byref(cfg), C.byref(h))
+        with pytest.raises(NotImplementedError, match="above 65535"):
+            N.check(rc)
+    t5 = N.PttsT5Config(100, 128, 64, 256, 1, 2, 32, 128, 1e-6, N.PTTS_BF16, 2048, 65536, 0)
+    rc = lib.ptts_t5_create(C.byref(t5), C.byref(h))
+    with pytest.raises(NotImplementedError, match="tile grid"):
+        N.check(rc)
 
 
 def test_missing_library_fails_loudly(tmp_path):
