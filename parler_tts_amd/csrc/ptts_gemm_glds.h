@@ -13,7 +13,8 @@
 //       group hit 16 different 16-byte slots of the 256-byte bank row (conflict-free; linear rows would be 4-way)
 // Tile: BNS strips (16 weight rows each) x BMT row tiles (16 activation rows each) per workgroup, WN x WM waves of (BNS / WN) x (BMT / WM) MFMA tiles,
 // BK = 64 per stage (2 fragments). Accumulation order over k is ascending whole fragments, no K split: bit-identical to gemm_tile_kernel /
-// gemm_block_kernel (tests compare them bitwise). Epilogues: gemm_store_tile (store / residual / GELU / gated GELU / cross K/V scatter).
+// gemm_block_kernel (tests/test_gemm_kernels_gpu.py compares the three bitwise on random data). Epilogues: gemm_store_tile (store / residual / GELU /
+// gated GELU / cross K/V scatter).
 #pragma once
 #include "ptts_lm_kernels.h"
 

@@ -126,11 +126,15 @@ int launch_gemm(GemmArgs a, hipStream_t st) {
         if (rg != -1) return rg;
       }
     }
-    if (a.M > block_min_m && EPI != EPI_GELU && !a.x_fo && !a.kv_layers && !a.stats_out && !a.W8) {  // LDS-tiled kernel (round 5)
+    // the folded T5 RMSNorm (GemmArgs::rs_part / nx_out) is in the strip epilogue only: the > 256-row kernels below ignore both fields, and the
+    // strip's rstd buffer holds the rows of a pass of at most 64 (ptts_t5.hip folds at <= 256 rows, in fragment order: msplit passes)
+    if ((a.M > block_min_m && (a.rs_part || a.nx_out)) || (a.rs_part && rpp > 64))
+      return ptts_fail(PTTS_E_UNSUPPORTED, "gemm: the folded RMSNorm (rs_part / nx_out) on %d rows in passes of %d: served up to %d rows, 64 per pass", a.M, rpp, block_min_m);
+    if (a.M > block_min_m && EPI != EPI_GELU && !a.x_fo && !a.kv_layers && !a.stats_out && !a.W8 && !a.rs_part && !a.nx_out) {  // LDS-tiled kernel (round 5)
       const int rt = launch_gemm_tile<WT, EPI>(a, st);
       if (rt != -1) return rt;
     }
-    if (a.M > block_min_m && EPI != EPI_GELU && !a.x_fo && !a.kv_layers) {  // prefill-sized: register-blocked kernel, no K split
+    if (a.M > block_min_m && EPI != EPI_GELU && !a.x_fo && !a.kv_layers && !a.rs_part && !a.nx_out) {  // prefill-sized: register-blocked kernel, no K split
       const int nstrips = a.N / 16;
       const int ns = (nstrips % 4 == 0 && nstrips >= 128) ? 4 : (nstrips % 2 == 0 ? 2 : 0);  // N = 1024: 2 strips per wave keeps > 500 waves in flight
       if (ns) {
