@@ -159,6 +159,34 @@ int ptts_state(ptts_engine* e, int32_t* cur_len, int32_t* all_finished, void* st
  * engine, column 0 = BOS. Valid columns: [0, cur_len). */
 int ptts_ids(ptts_engine* e, int64_t** ids_dev, int32_t* row_stride);
 
+/* ---- continuous batching (additive to ABI v8) --------------------------------------------------------------
+ * The reference generates a static batch: `_sample` runs until the LAST row has finished (:3564 `unfinished_sequences.max() == 0`) and a
+ * finished row is padded meanwhile. A session keeps `B` utterance slots instead, each with its own clock (cur_len), its own end and its own
+ * request; a request is admitted into an idle slot while the other slots keep their state bit for bit. A slot is idle -> live
+ * (ptts_admit_row) -> finished (EOS on every codebook or its max_length; the device stops touching it) -> idle (ptts_retire_row).
+ *
+ * ptts_session_begin: opens a session of B <= max_batch slots, all idle; every request is padded to N encoder and P prompt positions
+ *   (masked). Generation parameters are those of the last ptts_set_gen_params, fixed for the session. The static cross-attention fold of
+ *   single-utterance engines is off. Engines with the e4m3 KV cache (kv_fp8) are REFUSED (PTTS_E_UNSUPPORTED), and so is a pending voice
+ *   prompt (ptts_set_audio_prefix). ptts_prefill ends the session.
+ * ptts_admit_row: `row` must be idle. Computes the slot's cross K/V, runs the request's P + 1 positions through the stack into the slot's
+ *   arena rows, resets the slot's sampler state and leaves its step-0 logits in place; with `sample` != 0 it also runs the sampler tail for
+ *   that slot (first token materialised, next column embedded), with 0 the caller continues with ptts_push_tokens / ptts_step_forward.
+ *     enc_dev [N, H] float32, enc_mask_dev [N] int32 or NULL, prompt_dev [P, H] float32 (NULL iff P == 0), prompt_mask_dev [P] int32 or NULL
+ *     max_length: the request's own 1 + max_new_tokens (0 = the session's; otherwise 2 <= max_length <= the session's). The delay pattern
+ *     (its pad triangle, and no pattern at all below 2K - 1 columns: build_delay_pattern_mask :205-276) and the stop test use this value.
+ * ptts_row_state (SYNCHRONISES): per slot, columns written so far (incl. BOS; 1 when idle) and whether it is still generating.
+ * ptts_retire_row: makes a slot idle, whatever its state (cancel, or after its ids were read).
+ * Inside a session ptts_decode_steps / ptts_step_forward advance every live slot by one column (idle and finished slots are left alone:
+ * no ids write, no clock), ptts_push_tokens appends to live slots only, ptts_ids / ptts_logits are indexed by slot, and ptts_state reports slot 0's
+ * columns and whether NO slot is live. The attention fetch
+ * bound of a step is the maximum over occupied slots of P + 1 + steps since admission, so it falls when a long request retires. */
+int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream);
+int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                   const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream);
+int ptts_row_state(ptts_engine* e, int32_t* cur_len_host, int32_t* live_host, void* stream);
+int ptts_retire_row(ptts_engine* e, int32_t row, void* stream);
+
 /* ---- hooks for user LogitsProcessorList / StoppingCriteria (the `logits_processor=` argument, :3418) ----
  * ptts_step_forward: forward only (no tail) for the next position; logits fp32 [B*K, V] at *logits_dev.
  * ptts_push_tokens : append caller-chosen raw tokens [B*K] int64 (already pad-substituted) and per-row

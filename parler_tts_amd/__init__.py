@@ -14,6 +14,7 @@ from .modeling_parler_tts import (
     build_delay_pattern_mask,
 )
 from .streamer import ParlerTTSStreamer
+from .continuous import ContinuousBatcher
 from .distributed import broadcast_model_weights, generate_sharded, shard_batch, shard_range
 
 
@@ -50,6 +51,6 @@ def register_with_transformers() -> bool:
 
 REGISTERED_WITH_TRANSFORMERS = register_with_transformers()
 
-__all__ = ["DACConfig", "DACModel", "ParlerTTSConfig", "ParlerTTSDecoderConfig", "ParlerTTSForCausalLM",
+__all__ = ["ContinuousBatcher", "DACConfig", "DACModel", "ParlerTTSConfig", "ParlerTTSDecoderConfig", "ParlerTTSForCausalLM",
            "ParlerTTSForConditionalGeneration", "ParlerTTSLogitsProcessor", "ParlerTTSStreamer",
            "apply_delay_pattern_mask", "build_delay_pattern_mask", "broadcast_model_weights", "generate_sharded", "shard_batch", "shard_range"]

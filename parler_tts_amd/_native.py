@@ -74,6 +74,10 @@ SYMBOLS = {
     "ptts_step_forward": (C.c_int, [_VP, _VP]),
     "ptts_logits": (C.c_int, [_VP, C.POINTER(_VP)]),
     "ptts_push_tokens": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "ptts_session_begin": (C.c_int, [_VP, _I32, _I32, _I32, _VP]),
+    "ptts_admit_row": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _VP]),
+    "ptts_row_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
+    "ptts_retire_row": (C.c_int, [_VP, _I32, _VP]),
     "ptts_debug_hidden": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_I32)]),
     "ptts_debug_graph_nodes": (C.c_int, [_VP, C.POINTER(_I32)]),
     "ptts_set_audio_prefix": (C.c_int, [_VP, _VP, _I32, _I32, _VP]),

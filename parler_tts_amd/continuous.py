@@ -1,0 +1,213 @@
+"""Continuous batching on top of the engine's session interface (``ptts_session_begin`` / ``ptts_admit_row`` / ``ptts_row_state`` /
+``ptts_retire_row``): a fixed number of utterance slots decode together, a request is admitted into a slot as soon as the previous one
+there has finished, and finished requests are handed out while the others keep going. ``generate()`` is a static batch: it runs until
+its LAST row has finished (reference ``_sample``, modeling_parler_tts.py:3564), which on requests of mixed lengths spends a large share
+of every step on rows that are already done.
+
+A request is computed exactly as a row of a static batch padded to the session's widths: the description is padded (masked) to
+``max_description_tokens``, the prompt to ``max_prompt_tokens`` (padding to the right, so the prompt tokens keep their positions), and
+its ``max_new_tokens`` sets its own delay pattern and end."""
+from __future__ import annotations
+
+import collections
+import copy
+from typing import Deque, Dict, Iterable, Iterator, List, Optional, Tuple
+
+import torch
+
+from .generation_extras import active_extras, check_generation_mode
+from .modeling_parler_tts import apply_delay_pattern_mask, build_delay_pattern_mask
+
+_HOST_LOOP_ARGUMENTS = ("logits_processor", "stopping_criteria", "output_scores", "output_logits")
+_VOICE_ARGUMENTS = ("input_values", "decoder_input_ids")
+
+
+class _Request:
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length")
+
+    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length):
+        self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
+
+
+class ContinuousBatcher:
+    """``slots`` utterances decode together on ``model``'s HIP engine; ``submit`` queues a request (FIFO), iterating yields
+    ``(ticket, waveform 1-D, length)`` as requests finish, ``run(requests)`` returns ``[(waveform, length), ...]`` in submission order.
+
+    ``generation_kwargs`` are ``generate()``'s: ``max_new_tokens`` / ``max_length`` (the session's limit; a request may ask for less),
+    ``min_new_tokens``, ``do_sample``, ``temperature``, ``top_k``, ``top_p``. Everything that needs the host loop, a streamer or a voice
+    prompt raises ``NotImplementedError``. ``poll_steps``: decode steps between two looks at the slots (each look is one host sync);
+    a request that ends by its own ``max_new_tokens`` is known in advance and is met exactly."""
+
+    def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16, **generation_kwargs):
+        if slots < 1 or max_description_tokens < 1 or max_prompt_tokens < 0 or poll_steps < 1:
+            raise ValueError("slots, max_description_tokens and poll_steps must be >= 1 and max_prompt_tokens >= 0")
+        for name in ("streamer",) + _HOST_LOOP_ARGUMENTS:
+            if generation_kwargs.get(name):
+                raise NotImplementedError(f"`{name}` needs generate()'s host loop / streamer, one utterance at a time: not available in a continuous batch")
+            generation_kwargs.pop(name, None)
+        for name in _VOICE_ARGUMENTS:
+            if generation_kwargs.get(name) is not None:
+                raise NotImplementedError(f"`{name}` (voice prompt): a continuous session takes no audio prefix")
+            generation_kwargs.pop(name, None)
+        if getattr(model, "prompt_cross_attention", False):
+            raise NotImplementedError("prompt_cross_attention models: the prompt joins the cross-attention context, which a session keeps at a fixed width")
+        gc = copy.deepcopy(model.generation_config)
+        unused = gc.update(**generation_kwargs)
+        if unused:
+            raise ValueError(f"The following arguments are not generation options: {sorted(unused)}")
+        check_generation_mode(gc)
+        extras = active_extras(gc)
+        if extras:
+            raise NotImplementedError(f"generation options {extras} run on generate()'s host loop (generation_extras): not available in a continuous batch")
+        if int(getattr(gc, "num_return_sequences", 1) or 1) != 1:
+            raise NotImplementedError("num_return_sequences > 1: submit the request several times")
+        self.model, self.slots, self.N, self.P, self.poll_steps = model, int(slots), int(max_description_tokens), int(max_prompt_tokens), int(poll_steps)
+        self.max_length = int(gc.max_new_tokens) + 1 if gc.max_new_tokens is not None else int(gc.max_length)
+        if self.max_length < 2:
+            raise ValueError("`max_length` / `max_new_tokens` leave no room for a generated token")
+        min_new = int(gc.min_new_tokens or 0)
+        if getattr(gc, "min_length", 0):
+            min_new = max(min_new, int(gc.min_length) - 1)
+        do_sample = bool(gc.do_sample)
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if do_sample else 0  # follows torch.manual_seed(), as generate() does
+        d = model.config.decoder
+        self.K, self.bos = d.num_codebooks, d.bos_token_id
+        self.pad = gc.pad_token_id if gc.pad_token_id is not None else d.pad_token_id
+        self.eng = model._get_engine(self.slots, self.N, self.P, self.max_length)
+        self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
+                                top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
+        self.eng.begin_session(self.slots, self.N, self.P)
+        self._queue: Deque[_Request] = collections.deque()
+        self._slot: List[Optional[_Request]] = [None] * self.slots
+        self._cols = [0] * self.slots  # columns a busy slot holds if it has not stopped on EOS: BOS + first token + one per step
+        self._done: Deque[Tuple[int, torch.Tensor, int]] = collections.deque()
+        self._next_ticket = 0
+
+    # -- requests ---------------------------------------------------------------------------------------------------------------
+    def _pad_ids(self, ids, mask, width: int, what: str):
+        ids = torch.as_tensor(ids).long()
+        if ids.dim() == 2 and ids.shape[0] == 1:
+            ids = ids[0]
+        if ids.dim() != 1:
+            raise ValueError(f"{what}: one request at a time ([tokens] or [1, tokens]), got {tuple(ids.shape)}")
+        n = int(ids.shape[0])
+        if n > width:
+            raise ValueError(f"{what} has {n} tokens, the session was opened for {width}")
+        if mask is None:
+            mask = torch.ones(n, dtype=torch.long)
+        mask = torch.as_tensor(mask).long().reshape(-1)
+        if mask.shape[0] != n:
+            raise ValueError(f"{what}: attention mask of {mask.shape[0]} positions for {n} tokens")
+        out_ids, out_mask = torch.zeros(width, dtype=torch.long), torch.zeros(width, dtype=torch.long)
+        out_ids[:n], out_mask[:n] = ids.cpu(), mask.cpu()
+        return out_ids, out_mask
+
+    @torch.no_grad()
+    def submit(self, input_ids, attention_mask=None, prompt_input_ids=None, prompt_attention_mask=None, max_new_tokens: Optional[int] = None) -> int:
+        """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path)."""
+        max_length = self.max_length if max_new_tokens is None else int(max_new_tokens) + 1
+        if max_length < 2:
+            raise ValueError("`max_new_tokens` leaves no room for a generated token")
+        if max_length > self.max_length:
+            raise ValueError(f"max_new_tokens {max_length - 1} exceeds the session's {self.max_length - 1}")
+        dev = self.model.device
+        ids, mask = self._pad_ids(input_ids, attention_mask, self.N, "description")
+        enc = self.model._encode_description(ids[None].to(dev), mask[None].to(dev))[0].float()
+        prompt = pmask = None
+        if self.P > 0:
+            if prompt_input_ids is None:
+                raise ValueError(f"the session was opened for prompts of up to {self.P} tokens: `prompt_input_ids` is required")
+            pids, pmask = self._pad_ids(prompt_input_ids, prompt_attention_mask, self.P, "prompt")
+            prompt = self.model.embed_prompts(pids[None].to(dev))[0].float()
+        elif prompt_input_ids is not None:
+            raise ValueError("the session was opened without prompt positions (max_prompt_tokens = 0)")
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length))
+        return ticket
+
+    # -- scheduler ----------------------------------------------------------------------------------------------------------------
+    def pending(self) -> int:
+        """Requests queued or in a slot (finished ones waiting to be iterated are not counted)."""
+        return len(self._queue) + sum(r is not None for r in self._slot)
+
+    def _poll(self):
+        """Admit FIFO into idle slots, run the live slots up to the next boundary, collect what finished."""
+        for s in range(self.slots):
+            if self._slot[s] is None and self._queue:
+                r = self._queue.popleft()
+                self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True)
+                self._slot[s], self._cols[s] = r, 2
+        busy = [s for s in range(self.slots) if self._slot[s] is not None]
+        if not busy:
+            return
+        # the nearest end by max_length is known to the host: meet it exactly, so that its slot is refilled at once; EOS ends show at a poll
+        n = max(0, min(min(self._slot[s].max_length - self._cols[s] for s in busy), self.poll_steps))
+        if n > 0:
+            self.eng.decode_steps(n)
+            for s in busy:
+                self._cols[s] = min(self._cols[s] + n, self._slot[s].max_length)
+        cur, live = self.eng.row_state()
+        finished = [s for s in busy if not live[s]]
+        if not finished:
+            return
+        group = [(self._slot[s], self.eng.row_ids(s, cur[s])) for s in finished]
+        for s in finished:
+            self.eng.retire_row(s)
+            self._slot[s] = None
+        self._decode_group(group)
+
+    def _codes(self, ids: torch.Tensor, max_length: int) -> torch.Tensor:
+        """Raw ids [K, columns] of one request -> its un-delayed audio codes [K, frames] (generate()'s tail, modeling_parler_tts.py:3585-3600)."""
+        bos_col = ids[:, :1]
+        _, pattern = build_delay_pattern_mask(bos_col, self.bos, self.pad, max_length, self.K)
+        out = apply_delay_pattern_mask(ids, pattern)
+        _, m2 = build_delay_pattern_mask(bos_col, self.bos, self.pad, out.shape[1], self.K)
+        keep = (m2 != self.bos) & (m2 != self.pad)
+        return out[keep].reshape(self.K, -1)
+
+    def _decode_group(self, group):
+        """The requests that finished at the same poll go through the codec as ONE ragged batch (special-id filter + ragged decode); the shorter
+        ones are padded with an id outside the codebook, which the filter drops like any special id."""
+        codes = [self._codes(ids, r.max_length) for r, ids in group]
+        T = max(int(c.shape[1]) for c in codes)
+        if T == 0:
+            for r, _ in group:
+                self._done.append((r.ticket, torch.zeros(1, device=codes[0].device), 1))  # the reference's torch.zeros(1) for no valid frame (:3641)
+            return
+        cb = int(self.model.audio_encoder.config.codebook_size)
+        batch = torch.full((len(group), self.K, T), cb, dtype=torch.long, device=codes[0].device)
+        for i, c in enumerate(codes):
+            batch[i, :, : c.shape[1]] = c
+        wav, frames = self.model.audio_encoder.decode_filtered(batch[None])
+        hop = wav.shape[-1] // T
+        kept = [int(x) for x in frames.tolist()]  # the one host read of the group: its kept-frame counts
+        for i, (r, _) in enumerate(group):
+            n = kept[i]
+            if n > 0:
+                self._done.append((r.ticket, wav[i, 0, : n * hop].clone(), n * hop))
+            else:
+                self._done.append((r.ticket, torch.zeros(1, device=wav.device), 1))
+
+    def __iter__(self) -> Iterator[Tuple[int, torch.Tensor, int]]:
+        """Yields (ticket, waveform, length) in the order requests finish, until nothing is queued or running."""
+        with torch.no_grad():
+            while self._done or self.pending():
+                if not self._done:
+                    self._poll()
+                while self._done:
+                    yield self._done.popleft()
+
+    def run(self, requests: Iterable[Dict]) -> List[Tuple[torch.Tensor, int]]:
+        """``requests``: the keyword arguments of ``submit``, one dict per request. Returns (waveform, length) per request, in submission order."""
+        tickets = [self.submit(**r) for r in requests]
+        got = {t: (w, n) for t, w, n in self}
+        return [got[t] for t in tickets]
+
+    def close(self):
+        """Retires every slot and drops the queue (the engine stays with the model; a later ``generate()`` ends the session by itself)."""
+        self._queue.clear()
+        for s in range(self.slots):
+            if self._slot[s] is not None:
+                self.eng.retire_row(s)
+                self._slot[s] = None

@@ -120,6 +120,14 @@ struct ptts_engine {
   int kv_bound = 0;      // attention fetch bound of the next decode forward: kv_ub + 1 rounded up to 64, <= max_ctx
   std::map<long long, hipGraphExec_t> graphs;  // key: 2 * batch size + folded-cross-block flag + context bucket + steps per launch (get_graph)
   int* host_pinned = nullptr;
+  // continuous session (ptts_session_begin): every slot of the batch has its own clock, end and fetch bound
+  bool session = false;
+  int session_max_length = 0;            // max_length of the generation parameters the session was opened with
+  int* row_maxlen = nullptr;             // [max_batch] device: max_length of the request in each slot
+  float* h_adm = nullptr;                // [max_prompt][H] residual rows of a row prefill: the step input h[B][H] of the other slots is live between steps
+  KvLayer* kv_layers_rows = nullptr;     // [max_batch][layers] operands of the batched cross K/V projection with each slot's arena rows as base
+  std::vector<char> slot_busy;           // host: admitted and not yet retired
+  std::vector<int> slot_ub, slot_maxlen; // host: upper bound of the slot's self-KV positions (P + 1 + steps since admission), its max_length
 #ifdef PTTS_TIMING
   long long* dbg_stamps = nullptr;  // measurement build: [layers + 1][5 or 7 nodes][3 workgroups][16] wall-clock stamps of the decode step (ptts_debug_stamps)
 #endif
@@ -236,6 +244,10 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     ea.ids = e->ids; ea.ids_ld = e->ids_ld; ea.cur_len = e->cur_len; ea.dims = e->dims; ea.h = e->h;
     ea.H = H; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.bos = c.bos_token_id; ea.pad = c.pad_token_id;
     ea.prefill = prefill ? 1 : 0;
+    if (e->session && !prefill) {  // every slot under its own request's delay pattern
+      EmbedSessionArgs es = {ea, e->row_maxlen};
+      hipLaunchKernelGGL((embed_session_kernel<WT>), dim3(1, B), dim3(256), 0, st, es);
+    } else
     hipLaunchKernelGGL((embed_kernel<WT>), dim3(Q, B), dim3(256), 0, st, ea);
   }
   if (e->use_gemv && !prefill && M <= e->gemv_rows) {
@@ -573,7 +585,8 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
   return PTTS_OK;
 }
 
-int launch_tail(ptts_engine* e, hipStream_t st, bool embed_next) {
+// row >= 0 (sessions only): the tail of that one slot (ptts_admit_row)
+int launch_tail(ptts_engine* e, hipStream_t st, bool embed_next, int row = -1) {
   TailArgs t = {};
   if (embed_next) {
     t.tables = e->embed; t.pos_table = e->cfg.rope ? nullptr : e->pos_table; t.dims = e->dims; t.h = e->h;
@@ -584,6 +597,13 @@ int launch_tail(ptts_engine* e, hipStream_t st, bool embed_next) {
   t.B = e->B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
   // one wave per codebook row (greedy arg-max or the sort-free sampler), at least 4 waves for the embedding of the next column
   const int nw = std::min(std::max(e->cfg.num_codebooks, 4), 16);
+  if (e->session) {  // per-slot clocks (tail_session_kernel)
+    TailSessionArgs s = {t, e->row_maxlen, row < 0 ? 0 : row};
+    const dim3 grid(row < 0 ? e->B : 1);
+    if (t.V <= 512) hipLaunchKernelGGL(tail_session_kernel<8>, grid, dim3(nw * 64), 0, st, s);
+    else if (t.V <= 1152) hipLaunchKernelGGL(tail_session_kernel<18>, grid, dim3(nw * 64), 0, st, s);
+    else hipLaunchKernelGGL(tail_session_kernel<32>, grid, dim3(nw * 64), 0, st, s);
+  } else
   if (t.V <= 512) hipLaunchKernelGGL(tail_kernel<8>, dim3(e->B), dim3(nw * 64), 0, st, t);
   else if (t.V <= 1152) hipLaunchKernelGGL(tail_kernel<18>, dim3(e->B), dim3(nw * 64), 0, st, t);
   else hipLaunchKernelGGL(tail_kernel<32>, dim3(e->B), dim3(nw * 64), 0, st, t);
@@ -617,8 +637,19 @@ int forward_dispatch(ptts_engine* e, bool prefill, hipStream_t st, bool with_emb
 }
 
 // every decode forward appends one self-KV position: advance the host's bound before launching it (eagerly or as a graph)
+// (session: one bound per busy slot, capped by the end of its request; the step's bound is their maximum, so it falls when a long request retires)
 static int advance_kv(ptts_engine* e) {
-  e->kv_ub += 1;
+  if (e->session) {
+    int ub = e->P + 1;
+    for (int b = 0; b < e->B; ++b)
+      if (e->slot_busy[b]) {
+        e->slot_ub[b] = std::min(e->slot_ub[b] + 1, e->P + e->slot_maxlen[b]);
+        ub = std::max(ub, e->slot_ub[b]);
+      }
+    e->kv_ub = ub;
+  } else {
+    e->kv_ub += 1;
+  }
   const int cap = e->cfg.max_ctx;
   e->kv_bound = std::min(cap, (e->kv_ub + 1 + 63) / 64 * 64);
   return e->kv_bound;
@@ -866,7 +897,7 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   A(e->alloc(&e->prompt_mask, rows));
   A(e->alloc(&e->dims, 1)); A(e->alloc(&e->gen, 1));
 #undef A
-  if (hipHostMalloc((void**)&e->host_pinned, ((size_t)c.max_batch * K + 16) * 4) != hipSuccess) return fail(ptts_fail(PTTS_E_HIP, "hipHostMalloc failed"));
+  if (hipHostMalloc((void**)&e->host_pinned, ((size_t)c.max_batch * (K + 1) + 16) * 4) != hipSuccess) return fail(ptts_fail(PTTS_E_HIP, "hipHostMalloc failed"));
 #ifdef PTTS_TIMING
   {
     const size_t n = (size_t)(c.num_layers + 1) * 7 * 48;  // 5 nodes per layer of the GEMV step, 7 of the batch > 8 step
@@ -1092,6 +1123,7 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
   hipStream_t st = pick_stream(e, stream);
   const int H = c.hidden_size, K = c.num_codebooks;
   e->B = B; e->N = N; e->P = P;
+  e->session = false;  // a static batch ends a continuous session
   if (sample) PTTS_HIP(hipEventRecord(e->ev_pre0, st));
   // per-call device params travel as kernel arguments (no host staging buffer to keep alive)
   {
@@ -1161,7 +1193,7 @@ static int get_graph(ptts_engine* e, hipGraphExec_t* out) {
   // the node set of the step depends on the batch size and on the folded cross block; the attention fetch bound (a kernel argument)
   // on the 64-position bucket of the context (forward<> reads it from e->kv_bound while capturing). (Several steps of one bucket per
   // graph launch - round 4's PTTS_GRAPH_STEPS - measured 0.3-0.7 %, profiles/r04_experiments.txt call 19: removed in round 6.)
-  const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (e->kv_bound / 64);
+  const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (e->kv_bound / 64) + (e->session ? 1LL << 40 : 0);  // session steps end in their own tail
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) { if (out) *out = it->second; return PTTS_OK; }
   hipGraph_t g = nullptr;
@@ -1195,7 +1227,7 @@ static int get_graph(ptts_engine* e, hipGraphExec_t* out) {
 // (batch, fold, bucket) pays.
 static int precapture_graphs(ptts_engine* e, int max_buckets) {
   const int cap = e->cfg.max_ctx, saved_ub = e->kv_ub, saved_bound = e->kv_bound;
-  const int last_ub = std::min(cap - 1, e->P + e->gp.max_length);  // positions the longest run of this call writes
+  const int last_ub = std::min(cap - 1, e->P + (e->session ? e->session_max_length : e->gp.max_length));  // positions the longest run of this call writes
   int rc = PTTS_OK, done = 0;
   for (int ub = saved_ub + 1; ub <= last_ub && rc == PTTS_OK && done < max_buckets; ++done) {
     e->kv_bound = std::min(cap, (ub + 1 + 63) / 64 * 64);
@@ -1228,6 +1260,150 @@ extern "C" int ptts_decode_steps(ptts_engine* e, int32_t n_steps, void* stream) 
     ++i;
   }
   if (n_steps > 0) PTTS_TRY(precapture_graphs(e, 2));  // the current bucket and the next one, while the GPU works through what was just enqueued
+  return PTTS_OK;
+}
+
+// ---- continuous session ---------------------------------------------------------------------------------------------------------------
+extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_TRY(ptts_weights_ready(e));
+  const ptts_config& c = e->cfg;
+  PTTS_CHECK(!c.kv_fp8, PTTS_E_UNSUPPORTED, "continuous sessions do not run on the e4m3 KV cache (kv_fp8)");
+  PTTS_CHECK(e->pending_T == 0, PTTS_E_UNSUPPORTED, "a voice prompt is pending (ptts_set_audio_prefix): sessions take none");
+  PTTS_CHECK(B >= 1 && B <= c.max_batch, PTTS_E_CAPACITY, "%d slots exceed engine max_batch %d", B, c.max_batch);
+  PTTS_CHECK(N >= 1 && N <= c.max_enc, PTTS_E_CAPACITY, "encoder width %d exceeds engine max_enc %d", N, c.max_enc);
+  PTTS_CHECK(P >= 0 && P + 1 <= e->max_prompt, PTTS_E_CAPACITY, "prompt width %d exceeds engine capacity %d", P, e->max_prompt - 1);
+  PTTS_CHECK(P + e->gp.max_length <= c.max_ctx, PTTS_E_CAPACITY, "P + max_length = %d exceeds engine max_ctx %d", P + e->gp.max_length, c.max_ctx);
+  PTTS_CHECK(P + e->gp.max_length <= c.max_positions || c.rope, PTTS_E_CAPACITY, "P + max_length = %d exceeds max_position_embeddings %d", P + e->gp.max_length, c.max_positions);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = pick_stream(e, stream);
+  const int H = c.hidden_size, K = c.num_codebooks;
+  if (!e->row_maxlen) {  // first session of this engine: the row prefill's own residual rows and per-slot operand tables
+    PTTS_TRY(e->alloc(&e->row_maxlen, (size_t)c.max_batch));
+    PTTS_TRY(e->alloc(&e->h_adm, (size_t)e->max_prompt * H));
+    PTTS_TRY(e->alloc(&e->kv_layers_rows, (size_t)c.max_batch * c.num_layers));
+    std::vector<KvLayer> kl((size_t)c.max_batch * c.num_layers);
+    const size_t kvc = (size_t)e->nkc * c.max_enc * 64 * e->esize;  // one slot's cross K (or V) rows of a layer
+    for (int b = 0; b < c.max_batch; ++b)
+      for (int l = 0; l < c.num_layers; ++l)
+        kl[(size_t)b * c.num_layers + l] = KvLayer{e->L[l].ckv, (char*)e->L[l].k_cross + b * kvc, (char*)e->L[l].v_cross + b * kvc};
+    PTTS_HIP(hipMemcpy(e->kv_layers_rows, kl.data(), kl.size() * sizeof(KvLayer), hipMemcpyHostToDevice));
+  }
+  e->B = B; e->N = N; e->P = P;
+  e->session = true;
+  e->xfold_valid = false;  // the static cross-attention fold belongs to one utterance: off in a session
+  e->session_max_length = e->gp.max_length;
+  e->slot_busy.assign(B, 0); e->slot_ub.assign(B, P + 1); e->slot_maxlen.assign(B, e->gp.max_length);
+  {
+    DevDims hd; hd.P = P; hd.N = N; hd.max_length = e->gp.max_length; hd.T_prefix = 0; hd.prefix = e->prefix; hd.prefix_ld = c.max_ctx;
+    DevGen hg; hg.max_length = e->gp.max_length; hg.min_new_tokens = e->gp.min_new_tokens; hg.do_sample = e->gp.do_sample;
+    hg.top_k = e->gp.top_k; hg.use_eos_gate = e->gp.use_eos_gate; hg.temperature = e->gp.temperature; hg.top_p = e->gp.top_p;
+    hg.seed = e->gp.seed;
+    hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, st, e->dims, e->gen, hd, hg);
+  }
+  // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
+  hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
+                     e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);
+  hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, e->enc_mask, 1, (size_t)B * c.max_enc);
+  hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, e->prompt_mask, 1, (size_t)B * e->max_prompt);
+  PTTS_HIP(hipMemsetAsync(e->h, 0, (size_t)B * H * 4, st));
+  PTTS_HIP(hipMemsetAsync(e->logits, 0, (size_t)B * K * c.vocab_size * 4, st));
+  e->kv_ub = P + 1;
+  e->kv_bound = std::min(c.max_ctx, (e->kv_ub + 1 + 63) / 64 * 64);
+  e->first_recorded = false;
+  e->h_ready = true;  // nothing to embed: no slot is live
+  e->prefilled = true;
+  return PTTS_OK;
+}
+
+// The engine seen as a one-utterance engine whose arenas, masks, ids and logits are those of `row` (enter = true), and back. The prefill
+// kernels address utterance 0 of what they are given; the residual rows go to h_adm, because h[B][H] holds the other slots' next step input.
+static void session_row_view(ptts_engine* e, int row, bool enter) {
+  const ptts_config& c = e->cfg;
+  const long long d = enter ? row : -row;
+  const int K = c.num_codebooks;
+  const long long kvs = (long long)e->nkv * c.max_ctx * 64 * e->esize, kvc = (long long)e->nkc * c.max_enc * 64 * e->esize;
+  for (LayerW& w : e->L) {
+    w.k_self = (char*)w.k_self + d * kvs; w.v_self = (char*)w.v_self + d * kvs;
+    w.k_cross = (char*)w.k_cross + d * kvc; w.v_cross = (char*)w.v_cross + d * kvc;
+  }
+  e->logits += d * K * c.vocab_size;
+  e->ids += d * K * e->ids_ld;
+  e->cur_len += d; e->first_unf += d; e->unfinished += d * K; e->has_eos += d * K;
+  e->enc_mask += d * c.max_enc; e->prompt_mask += d * e->max_prompt;
+  if (enter) e->kv_layers_rows += d * c.num_layers;
+  std::swap(e->kv_layers, e->kv_layers_rows);
+  if (!enter) e->kv_layers_rows += d * c.num_layers;
+  std::swap(e->h, e->h_adm);
+}
+
+extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                              const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream) {
+  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_row: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
+  PTTS_CHECK(!e->slot_busy[row], PTTS_E_INVALID, "slot %d still holds a request (ptts_retire_row first)", row);
+  PTTS_CHECK(e->pending_T == 0, PTTS_E_UNSUPPORTED, "a voice prompt is pending (ptts_set_audio_prefix): sessions take none");
+  const ptts_config& c = e->cfg;
+  const int P = e->P, N = e->N, H = c.hidden_size, K = c.num_codebooks;
+  PTTS_CHECK(P == 0 || prompt_dev, PTTS_E_INVALID, "prompt_dev is null but the session's P > 0");
+  const int L = max_length == 0 ? e->session_max_length : max_length;
+  PTTS_CHECK(L >= 2, PTTS_E_INVALID, "max_length must be 0 (the session's) or >= 2");
+  PTTS_CHECK(L <= e->session_max_length, PTTS_E_CAPACITY, "max_length %d exceeds the session's %d", L, e->session_max_length);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = pick_stream(e, stream);
+  hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
+                     e->row_maxlen, row, 1, K, c.bos_token_id, 1, L);
+  int* em = e->enc_mask + (size_t)row * c.max_enc;
+  int* pm = e->prompt_mask + (size_t)row * e->max_prompt;
+  if (enc_mask_dev) PTTS_HIP(hipMemcpyAsync(em, enc_mask_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, em, 1, (size_t)c.max_enc);
+  if (prompt_mask_dev && P > 0) PTTS_HIP(hipMemcpyAsync(pm, prompt_mask_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, st));
+  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, pm, 1, (size_t)e->max_prompt);
+  // staging as in ptts_prefill: qc and ffn are scratch of a forward, dead between steps
+  PTTS_HIP(hipMemcpyAsync(e->qc, enc_dev, (size_t)N * H * 4, hipMemcpyDeviceToDevice, st));
+  if (P > 0) PTTS_HIP(hipMemcpyAsync(e->ffn, prompt_dev, (size_t)P * H * 4, hipMemcpyDeviceToDevice, st));
+  const int B = e->B;
+  session_row_view(e, row, true);
+  e->B = 1;
+  const int rc_fwd = forward_dispatch(e, true, st);
+  e->B = B;
+  session_row_view(e, row, false);
+  PTTS_TRY(rc_fwd);
+  e->slot_busy[row] = 1; e->slot_ub[row] = P + 1; e->slot_maxlen[row] = L;
+  if (sample) PTTS_TRY(launch_tail(e, st, true, row));  // first token of the request + the embedding of its next column into h[row]
+  else e->h_ready = false;                             // manual path: the next forward embeds every slot's last column
+  return PTTS_OK;
+}
+
+extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_retire_row: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
+  PTTS_DEVICE(e->cfg.device);
+  hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, pick_stream(e, stream), e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
+                     e->first_unf, e->row_maxlen, row, 1, e->cfg.num_codebooks, e->cfg.bos_token_id, 0, e->session_max_length);
+  e->slot_busy[row] = 0; e->slot_ub[row] = e->P + 1;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_row_state(ptts_engine* e, int32_t* cur_len_host, int32_t* live_host, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_row_state: no continuous session (ptts_session_begin)");
+  PTTS_DEVICE(e->cfg.device);
+  hipStream_t st = pick_stream(e, stream);
+  const int B = e->B, K = e->cfg.num_codebooks;
+  int* hp = e->host_pinned;
+  // cur_len[max_batch] and unfinished[max_batch * K] are separate allocations: two enqueued copies, one sync
+  PTTS_HIP(hipMemcpyAsync(hp, e->cur_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  PTTS_HIP(hipMemcpyAsync(hp + B, e->unfinished, (size_t)B * K * 4, hipMemcpyDeviceToHost, st));
+  PTTS_HIP(hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) {
+    int live = 0;
+    for (int k = 0; k < K; ++k) live |= hp[B + b * K + k] > 0;
+    if (cur_len_host) cur_len_host[b] = hp[b];
+    if (live_host) live_host[b] = live;
+  }
   return PTTS_OK;
 }
 
@@ -1293,6 +1469,12 @@ extern "C" int ptts_push_tokens(ptts_engine* e, const int64_t* tokens_dev, const
   PTTS_DEVICE(e->cfg.device);
   hipStream_t st = pick_stream(e, stream);
   const int n = e->B * e->cfg.num_codebooks;
+  if (e->session) {  // only live slots take tokens and move their clock
+    hipLaunchKernelGGL(push_tokens_session_kernel, dim3(e->B), dim3(64), 0, st, (const long long*)tokens_dev, finished_dev, e->ids, e->ids_ld, e->cur_len,
+                       e->unfinished, e->has_eos, e->row_maxlen, e->cfg.num_codebooks, e->cfg.eos_token_id);
+    e->h_ready = false;
+    return PTTS_OK;
+  }
   hipLaunchKernelGGL(push_tokens_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const long long*)tokens_dev, finished_dev, e->ids,
                      e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->B, e->cfg.num_codebooks, e->cfg.eos_token_id);
   hipLaunchKernelGGL(bump_len_kernel, dim3((e->B + 255) / 256), dim3(256), 0, st, e->cur_len, e->B);

@@ -2817,6 +2817,152 @@ __global__ void __launch_bounds__(1024) tail_kernel(TailArgs a) {
   tail_embed_next(a, dd, b, t, s_tok, tid);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Continuous session (ptts_session_begin): every utterance slot has its own clock and its own end. A slot is LIVE iff one of its
+// K flags is positive; an idle or finished slot does nothing at all here (no ids write, no cur_len bump, no embedding), and the
+// stop test and the delay pattern use the slot's own max_length. The sampling hash stays (seed, t, row).
+// ------------------------------------------------------------------------------------------------------
+struct TailSessionArgs {
+  TailArgs t;
+  const int* row_maxlen;  // [B] max_length of the request in each slot
+  int row0;               // first slot of this launch: grid (B) with 0 for a decode step, grid (1) with the slot for an admission
+};
+
+template <int NV>
+__global__ void __launch_bounds__(1024) tail_session_kernel(TailSessionArgs s) {
+  const TailArgs& a = s.t;
+  __shared__ int s_tok[32];
+  const int b = blockIdx.x + s.row0, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const DevGen g = *a.gen;
+  const int t = a.cur_len[b];
+  const int live_local = tid < a.K ? (a.unfinished[b * a.K + tid] > 0) : 0;  // read by all before any wave of this workgroup writes a flag
+  const int fu0 = a.first_unf[b];
+  DevDims dd = *a.dims;
+  const int max_length = s.row_maxlen[b];
+  dd.max_length = max_length;  // the pad triangle (and whether there is a pattern at all) follows the request's own length
+  dd.T_prefix = 0;             // no voice prompt inside a session
+  const int he = lane < a.K ? a.has_eos[b * a.K + lane] : 0;
+  float lg[NV];
+  const int k0 = w;
+  if (k0 < a.K) {
+    const float* sc0 = a.logits + (size_t)(b * a.K + k0) * a.V;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) lg[i] = (lane + 64 * i < a.V) ? sc0[lane + 64 * i] : -INFINITY;
+  }
+  const int unf0 = k0 < a.K ? (a.unfinished[b * a.K + k0] > 0) : 0;
+  if (!__syncthreads_or(live_local)) return;  // idle or finished slot
+
+  int fu = fu0;
+  if (__shfl(he, fu0) > 0 && fu0 < a.K - 1) fu += 1;
+  if (tid == 0) a.first_unf[b] = fu;
+  const bool block_eos_all = (t - 1) < g.min_new_tokens;
+
+  for (int k = w; k < a.K; k += (int)(blockDim.x >> 6)) {
+    const int row = b * a.K + k;
+    if (k != k0) {
+      const float* sc = a.logits + (size_t)row * a.V;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) lg[i] = (lane + 64 * i < a.V) ? sc[lane + 64 * i] : -INFINITY;
+    }
+    const bool eos_blocked = block_eos_all || (g.use_eos_gate && k > fu);
+    int widx;
+    if (!g.do_sample) {
+      float best = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int v = lane + 64 * i;
+        float x = lg[i];
+        if (eos_blocked && v == a.eos) x = -INFINITY;
+        if (v < a.V && (x > best || (x == best && v < bi))) { best = x; bi = v; }
+      }
+      const float wbest = wave_max(best);
+      const float cand = (best == wbest) ? (float)bi : 3.0e9f;
+      widx = (int)(-wave_max(-cand));
+    } else {
+      const unsigned long long hsh = splitmix64(g.seed ^ splitmix64(((unsigned long long)t << 32) ^ (unsigned long long)row));
+      const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);
+      widx = wave_sample_row<NV>(lg, a.V, lane, g, eos_blocked, a.eos, u);
+    }
+    if (lane == 0) {
+      const int unf = k == k0 ? unf0 : (a.unfinished[row] > 0);
+      const int nxt = unf ? widx : a.pad;
+      a.ids[(size_t)row * a.ids_ld + t] = nxt;
+      s_tok[k] = nxt;
+      if (nxt == a.eos) a.has_eos[row] = 1;
+      if (unf && ((nxt == a.eos) || (t + 1 >= max_length))) a.unfinished[row] = -(t + 1);
+    }
+  }
+  __syncthreads();
+  if (tid == 0) a.cur_len[b] = t + 1;
+  tail_embed_next(a, dd, b, t, s_tok, tid);
+}
+
+// manual path inside a session (ptts_step_forward): embedding of every slot's last column under the slot's own delay pattern
+struct EmbedSessionArgs {
+  EmbedArgs e;
+  const int* row_maxlen;
+};
+template <typename WT>
+__global__ void embed_session_kernel(EmbedSessionArgs s) {
+  const EmbedArgs& a = s.e;
+  const int b = blockIdx.y;
+  DevDims dd = *a.dims;
+  dd.max_length = s.row_maxlen[b];
+  dd.T_prefix = 0;
+  const int j = a.cur_len[b] - 1;
+  const int pos = dd.P + j;
+  float* out = a.h + (size_t)b * a.H;
+  const WT* tab = reinterpret_cast<const WT*>(a.tables);
+  __shared__ int s_tok[32];
+  if (threadIdx.x < a.K) s_tok[threadIdx.x] = (int)delayed_token(a.ids, a.ids_ld, b * a.K + threadIdx.x, threadIdx.x, j, a.K, dd, a.bos, a.pad);
+  __syncthreads();
+  for (int d = threadIdx.x; d < a.H; d += blockDim.x) {
+    float acc = 0.f;
+    for (int k = 0; k < a.K; ++k) acc += Elem<WT>::ld(tab + ((size_t)k * a.V1 + s_tok[k]) * a.H + d);
+    if (a.pos_table) acc += a.pos_table[(size_t)pos * a.H + d];
+    out[d] = acc;
+  }
+}
+
+// ptts_push_tokens inside a session: one workgroup per slot; only live slots take their K tokens and move their clock, and a slot
+// that has reached its own max_length finishes instead of writing past it
+static __global__ void push_tokens_session_kernel(const long long* tokens, const int* finished, long long* ids, int ids_ld, int* cur_len,
+                                                  int* unfinished, int* has_eos, const int* row_maxlen, int K, int eos) {
+  const int b = blockIdx.x, k = threadIdx.x, row = b * K + k;
+  const int unf = k < K ? unfinished[row] : 0;
+  const int t = cur_len[b];
+  if (!__syncthreads_or(unf > 0)) return;
+  if (k < K) {
+    if (t < row_maxlen[b]) {
+      const long long tk = tokens[row];
+      ids[(size_t)row * ids_ld + t] = tk;
+      if (tk == eos) has_eos[row] = 1;
+    }
+    if (unf > 0 && ((finished && finished[row]) || t + 1 >= row_maxlen[b])) unfinished[row] = -(t + 1);
+  }
+  if (k == 0 && t < row_maxlen[b]) cur_len[b] = t + 1;
+}
+
+// session begin (row < 0: every slot) / ptts_retire_row: the slot is idle - clock at 1 (the cheapest context the attention kernels can be
+// given), BOS in column 0 so that the step's embedding of an idle slot reads a valid table row, no flag positive
+// ptts_admit_row (live = 1): same reset with the K flags raised and the request's own max_length
+static __global__ void session_reset_rows_kernel(long long* ids, int ids_ld, int* cur_len, int* unfinished, int* has_eos, int* first_unf,
+                                                 int* row_maxlen, int row0, int nrows, int K, int bos, int live, int max_length) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nrows * K) {
+    const size_t r = (size_t)row0 * K + i;
+    ids[r * ids_ld] = bos;
+    unfinished[r] = live;
+    has_eos[r] = 0;
+  }
+  if (i < nrows) {
+    cur_len[row0 + i] = 1;
+    first_unf[row0 + i] = 0;
+    row_maxlen[row0 + i] = max_length;
+  }
+}
+
 // manual path: append caller-chosen tokens (user LogitsProcessorList / StoppingCriteria ran on the host side)
 static __global__ void push_tokens_kernel(const long long* tokens, const int* finished, long long* ids, int ids_ld, int* cur_len,
                                    int* unfinished, int* has_eos, int B, int K, int eos) {

@@ -233,6 +233,59 @@ class DecoderEngine:
                                           _stream_ptr(device=self.device)), "ptts_push_tokens")
         self._keep2 = (tk, fn)
 
+    # -- continuous batching (ptts_session_begin / ptts_admit_row / ptts_row_state / ptts_retire_row) -------------
+    def begin_session(self, slots: int, enc_width: int, prompt_width: int):
+        """Opens a continuous session: ``slots`` utterance slots, all idle; every request is padded to ``enc_width`` description and
+        ``prompt_width`` prompt positions. Generation parameters are those of the last ``set_gen_params``."""
+        N.check(self.lib.ptts_session_begin(self._h, int(slots), int(enc_width), int(prompt_width), _stream_ptr(device=self.device)), "ptts_session_begin")
+        self.B, self.P, self.session_N = int(slots), int(prompt_width), int(enc_width)
+
+    def admit_row(self, row: int, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
+                  prompt_mask: Optional[torch.Tensor], max_length: int = 0, sample: bool = True):
+        """Prefills ONE request (``enc`` [N, H], ``prompt`` [P, H] at the session's widths) into the idle slot ``row``; the other slots
+        keep their state. ``max_length`` = the request's own 1 + max_new_tokens (0: the session's)."""
+        enc = enc.to(self.device, torch.float32).contiguous()
+        if enc.dim() != 2 or tuple(enc.shape) != (self.session_N, self.H):
+            raise ValueError(f"encoder states {tuple(enc.shape)} do not match the session's [{self.session_N}, {self.H}]")
+        keep = [enc]
+        pr = em = pm = None
+        if self.P > 0:
+            if prompt is None or tuple(prompt.shape) != (self.P, self.H):
+                raise ValueError(f"prompt embeddings {None if prompt is None else tuple(prompt.shape)} do not match the session's [{self.P}, {self.H}]")
+            pr = prompt.to(self.device, torch.float32).contiguous()
+            keep.append(pr)
+        if enc_mask is not None:
+            em = enc_mask.to(self.device, torch.int32).reshape(-1).contiguous()
+            if em.numel() != self.session_N:
+                raise ValueError(f"attention_mask of {em.numel()} positions does not match the session's {self.session_N}")
+            keep.append(em)
+        if prompt_mask is not None and self.P > 0:
+            pm = prompt_mask.to(self.device, torch.int32).reshape(-1).contiguous()
+            if pm.numel() != self.P:
+                raise ValueError(f"prompt_attention_mask of {pm.numel()} positions does not match the session's {self.P}")
+            keep.append(pm)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+        N.check(self.lib.ptts_admit_row(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), int(max_length), int(sample),
+                                        _stream_ptr(device=self.device)), "ptts_admit_row")
+        if not hasattr(self, "_keep_rows"):
+            self._keep_rows = {}
+        self._keep_rows[int(row)] = keep  # consumed asynchronously by the enqueued kernels
+
+    def row_state(self) -> Tuple[list, list]:
+        """(cur_len, live) per slot: columns written so far incl. BOS, and whether the slot is still generating. Synchronises."""
+        cur, live = (C.c_int32 * self.B)(), (C.c_int32 * self.B)()
+        N.check(self.lib.ptts_row_state(self._h, cur, live, _stream_ptr(device=self.device)), "ptts_row_state")
+        return list(cur), [bool(v) for v in live]
+
+    def retire_row(self, row: int):
+        N.check(self.lib.ptts_retire_row(self._h, int(row), _stream_ptr(device=self.device)), "ptts_retire_row")
+
+    def row_ids(self, row: int, cols: int) -> torch.Tensor:
+        """Raw ids [K, cols] of one slot (a copy)."""
+        p, ld = C.c_void_p(), C.c_int32()
+        N.check(self.lib.ptts_ids(self._h, C.byref(p), C.byref(ld)), "ptts_ids")
+        return self._copy_out(p.value + int(row) * self.K * ld.value * 8, (self.K, int(cols)), torch.int64, row_stride=ld.value)
+
     def generate_ids(self, enc, enc_mask, prompt, prompt_mask, poll_every: int = 64, audio_prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
         """prefill + graph-replayed decode until every row finished; returns raw ids [B*K, Lout]. ``audio_prefix``:
         un-delayed voice-prompt codes [B, K, T] continued by the decoder."""

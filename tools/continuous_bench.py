@@ -1,0 +1,268 @@
+#!/usr/bin/env python
+"""Continuous batching against static batching on a request stream of mixed lengths (Mini-v1 shapes, bf16, synthetic weights).
+
+  python tools/continuous_bench.py [--repeats 5] [--static-only] [--out FILE]
+
+256 requests whose lengths come from a fixed seeded list (uniform 150..860 frames, set through per-request max_new_tokens; EOS is blocked,
+so lengths are exact), 32 slots. Reports
+  (a) static   : model.generate() on consecutive groups of 32 in arrival order (every group runs to its longest request); audio-s/s counts the
+                 frames that were ASKED for, not the padding a static batch generates beyond them
+  (b) batcher  : parler_tts_amd.ContinuousBatcher on the same list
+  (c) ideal    : sum over groups of (32 x the group's longest) / sum of lengths - the ratio (b)/(a) would reach with free admissions, a session
+                 step as fast as the static one and no codec / encoder time
+  (d) step time: one decode step of a session with 32 live slots, and with 16 live + 16 idle slots, against the static batch-32 step, at the
+                 same context
+  (e) admission: GPU time of one ptts_admit_row while the other slots hold live requests
+A and B alternate inside one process after every graph has been warmed; medians and the observed spread are printed. --static-only runs (a)
+and the static step of (d) alone (it needs nothing of the session interface, so it also runs on a tree without it)."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402  (model shapes, synthetic inputs, HIP event timer)
+
+SLOTS, N_REQ, FRAMES_LO, FRAMES_HI, LIST_SEED = 32, 256, 150, 860, 20240
+K = bench.K_CODEBOOKS
+SEC_PER_FRAME = 512 / 44100.0
+
+
+def request_frames():
+    g = torch.Generator().manual_seed(LIST_SEED)
+    return [int(x) for x in torch.randint(FRAMES_LO, FRAMES_HI + 1, (N_REQ,), generator=g)]
+
+
+def ideal_ratio(frames):
+    groups = [frames[i:i + SLOTS] for i in range(0, len(frames), SLOTS)]
+    return sum(SLOTS * max(g) for g in groups) / sum(frames)
+
+
+def schedule_steps(frames):
+    """(static, continuous) decode steps of the two schedules on this list, from the list alone: a static group runs max + K - 1 columns behind
+    its prefill's first token; the FIFO slot schedule is simulated with every slot refilled the step its request ends (its drain at the end of
+    the list, when nothing is left to admit, included)."""
+    cols = [f + K - 1 for f in frames]  # columns to generate; the first comes with the prefill / admission
+    static = sum(max(cols[i:i + SLOTS]) - 1 for i in range(0, len(cols), SLOTS))
+    queue, left, steps = list(cols), [0] * SLOTS, 0
+    while queue or any(left):
+        for s in range(SLOTS):
+            if left[s] == 0 and queue:
+                left[s] = queue.pop(0) - 1
+        n = min(x for x in left if x > 0) if any(left) else 0
+        steps += n
+        left = [max(0, x - n) for x in left]
+    return static, steps
+
+
+def inputs(device):
+    g = torch.Generator().manual_seed(7)
+    desc = torch.randint(3, 32100, (N_REQ, bench.N_DESC), generator=g)
+    desc[:, -1] = 1
+    prompt = torch.randint(3, 32100, (N_REQ, bench.N_PROMPT), generator=g)
+    prompt[:, -1] = 1
+    return desc.to(device), prompt.to(device)
+
+
+def run_static(model, desc, prompt, frames):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(0, N_REQ, SLOTS):
+        new = max(frames[i:i + SLOTS]) + K - 1
+        model.generate(input_ids=desc[i:i + SLOTS], prompt_input_ids=prompt[i:i + SLOTS], do_sample=False, max_new_tokens=new, min_new_tokens=new)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def run_batcher(model, desc, prompt, frames):
+    import parler_tts_amd as P
+
+    new_max = FRAMES_HI + K - 1
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    cb = P.ContinuousBatcher(model, slots=SLOTS, max_description_tokens=bench.N_DESC, max_prompt_tokens=bench.N_PROMPT, poll_steps=16, do_sample=False,
+                             max_new_tokens=new_max, min_new_tokens=new_max)
+    tickets = [cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1) for i in range(N_REQ)]
+    torch.cuda.synchronize()
+    t_submit = time.perf_counter() - t0
+    got = {t: n for t, w, n in cb}
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert [got[t] for t in tickets] == [f * 512 for f in frames], "the batcher returned other lengths than were asked for"
+    return dt, t_submit
+
+
+def batcher_breakdown(model, desc, prompt, frames):
+    """One extra run with a device synchronisation around each phase (so phases no longer overlap host work: an attribution, not a throughput)."""
+    import parler_tts_amd as P
+
+    new_max = FRAMES_HI + K - 1
+    cb = P.ContinuousBatcher(model, slots=SLOTS, max_description_tokens=bench.N_DESC, max_prompt_tokens=bench.N_PROMPT, poll_steps=16, do_sample=False,
+                             max_new_tokens=new_max, min_new_tokens=new_max)
+    acc = {"admit": 0.0, "steps": 0.0, "poll": 0.0, "ids+retire": 0.0, "codec": 0.0}
+    count = {k: 0 for k in acc}
+
+    def timed(key, fn):
+        def wrapper(*a, **k):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = fn(*a, **k)
+            torch.cuda.synchronize()
+            acc[key] += time.perf_counter() - t
+            count[key] += 1
+            return out
+        return wrapper
+
+    eng = cb.eng
+    saved = (eng.admit_row, eng.decode_steps, eng.row_state, eng.row_ids)
+    eng.admit_row, eng.decode_steps = timed("admit", eng.admit_row), timed("steps", eng.decode_steps)
+    eng.row_state, eng.row_ids = timed("poll", eng.row_state), timed("ids+retire", eng.row_ids)
+    cb._decode_group = timed("codec", cb._decode_group)
+    try:
+        for i in range(N_REQ):
+            cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1)
+        t0 = time.perf_counter()
+        for _ in cb:
+            pass
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+    finally:
+        eng.admit_row, eng.decode_steps, eng.row_state, eng.row_ids = saved
+    return total, acc, count
+
+
+class Events:
+    def __init__(self):
+        self.hip = bench.hip_event_timer()
+        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
+        self.hip.hipEventCreate(C.byref(self.e0)); self.hip.hipEventCreate(C.byref(self.e1))
+
+    def ms(self, fn):
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.hip.hipEventRecord(self.e0, st)
+        fn()
+        self.hip.hipEventRecord(self.e1, st)
+        self.hip.hipEventSynchronize(self.e1)
+        out = C.c_float()
+        self.hip.hipEventElapsedTime(C.byref(out), self.e0, self.e1)
+        return out.value
+
+
+WARM_STEPS, TIMED_STEPS = 200, 200  # context ~ 33 + 2 + 200 .. + 400: the same 64-position buckets on both sides
+
+
+def step_static(model, enc, pr, ev):
+    eng = model._get_engine(SLOTS, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1)
+    eng.set_gen_params(max_length=bench.NEW_TOKENS + 1, min_new_tokens=bench.NEW_TOKENS)
+    eng.prefill(enc[:SLOTS], None, pr[:SLOTS], None, sample=True)
+    eng.decode_steps(WARM_STEPS)
+    return ev.ms(lambda: eng.decode_steps(TIMED_STEPS)) / TIMED_STEPS
+
+
+def step_session(model, enc, pr, ev, live):
+    eng = model._get_engine(SLOTS, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1)
+    eng.set_gen_params(max_length=bench.NEW_TOKENS + 1, min_new_tokens=bench.NEW_TOKENS)
+    eng.begin_session(SLOTS, bench.N_DESC, bench.N_PROMPT)
+    for s in range(live):
+        eng.admit_row(s, enc[s], None, pr[s], None)
+    eng.decode_steps(WARM_STEPS)
+    step = ev.ms(lambda: eng.decode_steps(TIMED_STEPS)) / TIMED_STEPS
+    admit = None
+    if live == SLOTS:  # one admission with the 31 other slots live: retire a slot, then time its re-admission
+        eng.retire_row(5)
+        admit = ev.ms(lambda: eng.admit_row(5, enc[40], None, pr[40], None))
+    return step, admit
+
+
+def med_spread(xs):
+    return statistics.median(xs), min(xs), max(xs)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--static-only", action="store_true")
+    ap.add_argument("--out", default=None, help="also append the report to this file")
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    frames = request_frames()
+    audio_s = sum(frames) * SEC_PER_FRAME
+    model = bench.build_model_on_device(dev, torch.bfloat16, "mini")
+    desc, prompt = inputs(dev)
+    lines = []
+
+    def say(msg):
+        print(msg, flush=True)
+        lines.append(msg)
+
+    say(f"[continuous_bench] Mini-v1 bf16 synthetic, {N_REQ} requests of {FRAMES_LO}..{FRAMES_HI} frames (seed {LIST_SEED}: sum {sum(frames)} frames = "
+        f"{audio_s:.1f} s of audio, mean {sum(frames) / N_REQ:.0f}), {SLOTS} slots; ideal ratio (c) = {ideal_ratio(frames):.3f}")
+    st_steps, cb_steps = schedule_steps(frames)
+    say(f"  decode steps of the schedules themselves: static {st_steps}, FIFO slots {cb_steps} (ratio {st_steps / cb_steps:.3f}: (c) less the drain of the "
+        f"last requests, when nothing is left to admit)")
+    with torch.no_grad():
+        enc = model._encode_description(desc[:64], None).float()
+        pr = model.embed_prompts(prompt[:64]).float()
+        ev = Events()
+        # warm every graph of both paths (T5 graphs at batch 32 and 1, step graphs of every context bucket, codec engines)
+        run_static(model, desc, prompt, frames)
+        if not a.static_only:
+            run_batcher(model, desc, prompt, frames)
+        st, cb, sub = [], [], []
+        for r in range(a.repeats):
+            st.append(run_static(model, desc, prompt, frames))
+            if not a.static_only:
+                dt, ts = run_batcher(model, desc, prompt, frames)
+                cb.append(dt); sub.append(ts)
+            say(f"  repeat {r}: static {st[-1]:.3f} s" + ("" if a.static_only else f", batcher {cb[-1]:.3f} s (of which submit / encode {sub[-1]:.3f} s)"))
+        m, lo, hi = med_spread(st)
+        say(f"(a) static batching : median {m:.3f} s = {audio_s / m:.1f} audio-s/s (spread {audio_s / hi:.1f} .. {audio_s / lo:.1f})")
+        res = {"static_s": m, "static_audio_s_per_s": audio_s / m, "ideal_ratio": ideal_ratio(frames)}
+        if not a.static_only:
+            mb, lob, hib = med_spread(cb)
+            say(f"(b) ContinuousBatcher: median {mb:.3f} s = {audio_s / mb:.1f} audio-s/s (spread {audio_s / hib:.1f} .. {audio_s / lob:.1f}); "
+                f"submit (256 single-description encodes + prompt embeddings) median {statistics.median(sub):.3f} s of it")
+            say(f"    (b)/(a) = {m / mb:.3f} against the ideal (c) = {ideal_ratio(frames):.3f}")
+            res.update(batcher_s=mb, batcher_audio_s_per_s=audio_s / mb, ratio=m / mb, submit_s=statistics.median(sub))
+            total, acc, count = batcher_breakdown(model, desc, prompt, frames)
+            say(f"    where the batcher's time goes (one run with a sync around each phase, {total:.3f} s after the submits): " +
+                ", ".join(f"{k} {acc[k]:.3f} s / {count[k]} calls" for k in acc) + f", rest (Python between the calls) {total - sum(acc.values()):.3f} s")
+            res["breakdown_s"] = {k: round(v, 4) for k, v in acc.items()}
+        s_static, s32, s16, adm = [], [], [], []
+        for r in range(a.repeats + 1):  # first round warms the step graphs of these contexts
+            x = step_static(model, enc, pr, ev)
+            if not a.static_only:
+                y, ad = step_session(model, enc, pr, ev, SLOTS)
+                z, _ = step_session(model, enc, pr, ev, SLOTS // 2)
+            if r == 0:
+                continue
+            s_static.append(x)
+            if not a.static_only:
+                s32.append(y); s16.append(z); adm.append(ad)
+        m, lo, hi = med_spread(s_static)
+        say(f"(d) static batch-32 step, context ~235..435: median {m * 1e3:.1f} us ({lo * 1e3:.1f} .. {hi * 1e3:.1f})")
+        res["static_step_us"] = m * 1e3
+        if not a.static_only:
+            for name, xs, key in (("session step, 32 live slots", s32, "session32_step_us"), ("session step, 16 live + 16 idle slots", s16, "session16_step_us")):
+                mm, lo, hi = med_spread(xs)
+                say(f"    {name}: median {mm * 1e3:.1f} us ({lo * 1e3:.1f} .. {hi * 1e3:.1f})")
+                res[key] = mm * 1e3
+            mm, lo, hi = med_spread(adm)
+            say(f"(e) one admission (33-position row prefill + cross K/V + first token) beside 31 live slots: median {mm:.3f} ms ({lo:.3f} .. {hi:.3f})")
+            res["admit_ms"] = mm
+    say(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,72 @@
+#!/usr/bin/env python
+"""Per-kernel comparison of the gfx950 code objects of two builds of libptts_hip.so (no GPU needed): which kernels exist in both, and whether
+their instruction streams are identical.
+
+  python tools/isa_compare.py OLD/libptts_hip.so [NEW/libptts_hip.so] > profiles/<name>.txt
+
+A change that only ADDS kernels must leave every kernel of the old build in place with the same instructions: a different stream in an
+existing kernel means its code generation moved (a shared device function, a struct layout, an inlining decision) and is listed by name.
+Addresses and the disassembler's comments are ignored; branch offsets are relative, so identical code compares equal wherever it is placed."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_audit import LLVM, ROOT, demangle, short  # noqa: E402
+
+
+def kernels(lib):
+    """{mangled kernel name: [instruction lines]} over every embedded gfx950 code object"""
+    tmp = tempfile.mkdtemp(prefix="isa_compare_")
+    try:
+        path = os.path.join(tmp, "lib.so")
+        shutil.copy(lib, path)
+        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", path], capture_output=True, cwd=tmp)
+        out = {}
+        for f in sorted(f for f in os.listdir(tmp) if "amdgcn" in f):
+            obj = os.path.join(tmp, f)
+            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", obj], capture_output=True, text=True).stdout
+            names = set(re.findall(r"^\s+\.name:\s+(\S+)$", notes, flags=re.M))
+            dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", obj], capture_output=True, text=True).stdout
+            cur = None
+            for line in dis.splitlines():
+                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+                if m:
+                    cur = out.setdefault(m.group(1), []) if m.group(1) in names else None
+                    continue
+                if cur is not None and line.strip():
+                    cur.append(re.sub(r"\s*//.*$", "", line).strip())
+        return out
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def main():
+    if len(sys.argv) < 2:
+        sys.exit(__doc__)
+    old_lib = sys.argv[1]
+    new_lib = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "parler_tts_amd", "libptts_hip.so")
+    old, new = kernels(old_lib), kernels(new_lib)
+    same = [k for k in old if k in new and old[k] == new[k]]
+    differ = [k for k in old if k in new and old[k] != new[k]]
+    gone = [k for k in old if k not in new]
+    added = [k for k in new if k not in old]
+    print(f"# tools/isa_compare.py: {len(old)} kernels in the old build, {len(new)} in the new one")
+    print(f"identical instructions : {len(same)}")
+    print(f"different instructions : {len(differ)}")
+    print(f"missing from the new   : {len(gone)}")
+    print(f"added by the new       : {len(added)}")
+    for title, ks, both in (("different instructions", differ, True), ("missing from the new build", gone, False), ("added by the new build", added, False)):
+        if ks:
+            print(f"\n## {title}")
+            for k, dn in sorted(zip(ks, demangle(ks)), key=lambda x: x[1]):
+                extra = f"  ({len(old[k])} -> {len(new[k])} instructions)" if both else f"  ({len((new if k in new else old)[k])} instructions)"
+                print(f"{short(dn)}{extra}")
+    return 1 if differ or gone else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
