@@ -248,6 +248,41 @@ int ptts_dac_decode_ragged(ptts_dac* d, const int64_t* codes_dev, const int32_t*
  *     which lets generate() decode finished frames chunk by chunk on a second stream while ptts_decode_steps keeps running. */
 int ptts_dac_decode_chunk(ptts_dac* d, const int64_t* codes_dev, int64_t codes_ld, int32_t first_frame, int32_t n_frames,
                           int32_t halo, float* wave_dev, int64_t wave_ld, int32_t n_emit, int32_t B, void* stream);
+/* ---- streaming out of a continuous session (additive to ABI v8) ---------------------------------------------
+ * The reference streams ONE utterance (parler_tts/streamer.py:66-131 re-decodes the whole token cache at every `play_steps`) and filters the
+ * special ids of a finished utterance as a whole (modeling_parler_tts.py:3615-3647). In a session every slot is at its own frame, and the
+ * frames the filter keeps are a subsequence of a request's frames, not a prefix. The codec engine therefore owns a per-slot stream table ON
+ * THE DEVICE: the kept (un-delayed, filtered) codes so far [slots][K][cap_frames], and per slot the raw frames absorbed, the frames kept and
+ * the kept frames already emitted.
+ *
+ * stream_open : (re)allocates and clears the table; slots <= max_batch. The only call of the three that allocates (and so synchronises).
+ * stream_reset: a new request enters the slot: its three counters return to 0 (enqueued).
+ * stream_decode, per listed row (slots that are not listed are untouched), all enqueued on `stream`, no synchronisation, no allocation:
+ *   1. absorb: raw frame f of codebook k is ids_dev[(slot*K + k)*ids_ld + col0 + f + k*delay] - col0 = 1, delay = 1 is the raw id buffer of
+ *      the decoder engine under the delay pattern (read in place), col0 = 0, delay = 0 is plain codes [rows][K][ids_ld]. Of the raw frames
+ *      [absorbed, complete) those whose K ids all lie in [0, codebook_size) are appended, in order, to the slot's kept codes (:3627-3636);
+ *      absorbed = complete.
+ *   2. plan: ready = kept - emitted; emit = ready if `final`, else ready - halo if that is >= min_emit (min_emit < 1 counts as 1), else 0.
+ *   3. decode: if emit > 0 the window of KEPT frames [max(0, emitted - halo), kept) goes through the codec as one ragged row, the samples of
+ *      kept frames [emitted, emitted + emit) are written to wave_dev[r*wave_ld + 0 .. hop*emit), the rest of the row is zero,
+ *      out_dev[r] = {emit, kept} and emitted += emit. A row with emit == 0 has length 0: its tiles exit at once.
+ *   With halo >= the decoder's one-sided receptive field the concatenation of a slot's emitted samples over successive calls equals what
+ *   compact_codes + decode_ragged yield for the whole utterance: non-final chunks keep `halo` kept frames back as right context, the final
+ *   one has the true end.
+ *   The host never reads device state: it bounds every row's window by halo + (an upper bound of ready it keeps per slot: + complete -
+ *   absorbed per call, at most halo + min_emit - 1 after a non-final pass, 0 after a final one). The largest bound sizes the launch (shorter
+ *   rows exit early) and must fit max_frames (PTTS_E_CAPACITY); wave_ld must hold hop * that bound of emit. PTTS_E_INVALID with a message:
+ *   slot out of range or listed twice, `complete` decreasing, beyond cap_frames or beyond ids_ld, R > slots, wave_ld too short. */
+typedef struct {
+  int32_t slot;
+  int32_t complete; /* raw frames [0, complete) of the slot's request are final in ids_dev (non-decreasing per request) */
+  int32_t final;    /* 1: the request has ended, nothing will follow: flush */
+  int32_t min_emit; /* not final: emit only if at least this many kept frames can be emitted with the right halo kept back */
+} ptts_dac_stream_row;
+int ptts_dac_stream_open(ptts_dac* d, int32_t slots, int32_t cap_frames, void* stream);
+int ptts_dac_stream_reset(ptts_dac* d, int32_t slot, void* stream);
+int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64_t ids_ld, int32_t col0, int32_t delay, const ptts_dac_stream_row* rows_host,
+                           int32_t R, int32_t halo, float* wave_dev, int64_t wave_ld, int32_t* out_dev, void* stream);
 /* DACModel.encode for voice prompts (dac_wrapper/modeling_dac.py:33-104, used by modeling_parler_tts.py:3136-3194):
  * wave_dev float32 [B, L], L a multiple of the hop (the caller applies model.preprocess's right zero padding, :64)
  * -> codes_dev int64 [B, n_quantizers, L/hop]  (model.encode :95: encoder stack + residual VQ nearest-neighbour search).

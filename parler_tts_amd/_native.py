@@ -52,6 +52,11 @@ class PttsDacConfig(C.Structure):
     ]
 
 
+class PttsDacStreamRow(C.Structure):
+    """ptts_dac_stream_row: one listed slot of a ``ptts_dac_stream_decode`` pass."""
+    _fields_ = [("slot", C.c_int32), ("complete", C.c_int32), ("final", C.c_int32), ("min_emit", C.c_int32)]
+
+
 ABI_VERSION = 8  # PTTS_ABI_VERSION in include/ptts.h
 
 # every symbol include/ptts.h declares: name -> (restype, argtypes)
@@ -89,6 +94,9 @@ SYMBOLS = {
     "ptts_dac_compact_codes": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP]),
     "ptts_dac_decode_ragged": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP]),
     "ptts_dac_decode_chunk": (C.c_int, [_VP, _VP, C.c_int64, _I32, _I32, _I32, _VP, C.c_int64, _I32, _I32, _VP]),
+    "ptts_dac_stream_open": (C.c_int, [_VP, _I32, _I32, _VP]),
+    "ptts_dac_stream_reset": (C.c_int, [_VP, _I32, _VP]),
+    "ptts_dac_stream_decode": (C.c_int, [_VP, _VP, C.c_int64, _I32, _I32, C.POINTER(PttsDacStreamRow), _I32, _I32, _VP, C.c_int64, _VP, _VP]),
     "ptts_dac_encode": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     "ptts_dac_debug_latents": (C.c_int, [_VP, C.POINTER(_VP)]),
     "ptts_t5_create": (C.c_int, [C.POINTER(PttsT5Config), C.POINTER(_VP)]),

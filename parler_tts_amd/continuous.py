@@ -6,7 +6,13 @@ of every step on rows that are already done.
 
 A request is computed exactly as a row of a static batch padded to the session's widths: the description is padded (masked) to
 ``max_description_tokens``, the prompt to ``max_prompt_tokens`` (padding to the right, so the prompt tokens keep their positions), and
-its ``max_new_tokens`` sets its own delay pattern and end."""
+its ``max_new_tokens`` sets its own delay pattern and end.
+
+Streaming mode (``stream_chunk_frames``): a request's audio leaves in chunks while its slot is still decoding. The codec engine keeps, per
+slot and on the device, the request's kept (un-delayed, special-id filtered) codes and how many of them were emitted
+(``ptts_dac_stream_decode``); every poll lists the slots that have a chunk ready and ONE windowed codec pass serves them all, reading the
+decoder engine's raw id buffer in place on the stream the decode steps run on. The concatenation of a request's chunks is the waveform
+the non-streaming mode yields for it."""
 from __future__ import annotations
 
 import collections
@@ -36,11 +42,23 @@ class ContinuousBatcher:
     ``generation_kwargs`` are ``generate()``'s: ``max_new_tokens`` / ``max_length`` (the session's limit; a request may ask for less),
     ``min_new_tokens``, ``do_sample``, ``temperature``, ``top_k``, ``top_p``. Everything that needs the host loop, a streamer or a voice
     prompt raises ``NotImplementedError``. ``poll_steps``: decode steps between two looks at the slots (each look is one host sync);
-    a request that ends by its own ``max_new_tokens`` is known in advance and is met exactly."""
+    a request that ends by its own ``max_new_tokens`` is known in advance and is met exactly.
 
-    def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16, **generation_kwargs):
+    ``stream_chunk_frames`` (default ``None``: off) switches to streaming: ``chunks()`` yields ``(ticket, chunk 1-D float32, last)`` as soon as
+    a slot holds ``stream_chunk_frames`` kept frames beyond the codec's right halo (``stream_first_chunk_frames`` for a request's first chunk,
+    default the same), ``last`` is True exactly once per ticket, and ``__iter__`` / ``run()`` raise. ``cancel(ticket)`` drops a request in either
+    mode. The stream table lives in ONE codec engine, sized at construction for ``slots`` windows; should another call replace that engine
+    (``DACModel._get_engine`` does when it needs more capacity), the next codec pass raises ``RuntimeError`` - the requests in flight are lost,
+    nothing is restarted silently."""
+
+    def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16,
+                 stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, **generation_kwargs):
         if slots < 1 or max_description_tokens < 1 or max_prompt_tokens < 0 or poll_steps < 1:
             raise ValueError("slots, max_description_tokens and poll_steps must be >= 1 and max_prompt_tokens >= 0")
+        if stream_chunk_frames is None and stream_first_chunk_frames is not None:
+            raise ValueError("`stream_first_chunk_frames` needs `stream_chunk_frames` (streaming mode)")
+        if stream_chunk_frames is not None and (int(stream_chunk_frames) < 1 or (stream_first_chunk_frames is not None and int(stream_first_chunk_frames) < 1)):
+            raise ValueError("`stream_chunk_frames` and `stream_first_chunk_frames` must be >= 1")
         for name in ("streamer",) + _HOST_LOOP_ARGUMENTS:
             if generation_kwargs.get(name):
                 raise NotImplementedError(f"`{name}` needs generate()'s host loop / streamer, one utterance at a time: not available in a continuous batch")
@@ -82,6 +100,22 @@ class ContinuousBatcher:
         self._cols = [0] * self.slots  # columns a busy slot holds if it has not stopped on EOS: BOS + first token + one per step
         self._done: Deque[Tuple[int, torch.Tensor, int]] = collections.deque()
         self._next_ticket = 0
+        self.chunk = None if stream_chunk_frames is None else int(stream_chunk_frames)
+        if self.chunk is not None:
+            from .streamer import receptive_halo_frames
+
+            ae = model.audio_encoder
+            self.first_chunk = self.chunk if stream_first_chunk_frames is None else int(stream_first_chunk_frames)
+            self.halo = receptive_halo_frames(getattr(ae, "decoder_rates", (8, 8, 4, 2)))
+            # a window = left halo + what is ready. Ready stays below chunk + halo + poll_steps on the host's own count; the library bounds it
+            # without reading the device (ptts.h), which after dropped frames is looser by up to another chunk + halo
+            big = max(self.chunk, self.first_chunk)
+            self.window_frames = min(3 * self.halo + 2 * big + self.poll_steps + 8, max(self.max_length, 1))
+            ae.stream_open(self.slots, self.max_length, self.window_frames)
+            self._absorbed, self._kept, self._emitted = [0] * self.slots, [0] * self.slots, [0] * self.slots
+            self._first_out = [False] * self.slots  # the request's first chunk is still outstanding
+            self._out: Deque[Tuple[int, torch.Tensor, bool]] = collections.deque()
+            self.codec_passes, self.codec_rows, self.whole_requests = 0, 0, 0  # passes, listed rows, requests that ended below 2K - 1 columns
 
     # -- requests ---------------------------------------------------------------------------------------------------------------
     def _pad_ids(self, ids, mask, width: int, what: str):
@@ -157,6 +191,125 @@ class ContinuousBatcher:
             self._slot[s] = None
         self._decode_group(group)
 
+    # -- streaming ----------------------------------------------------------------------------------------------------------------
+    def _admit(self):
+        for s in range(self.slots):
+            if self._slot[s] is None and self._queue:
+                r = self._queue.popleft()
+                self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True)
+                self.model.audio_encoder.stream_reset(s)
+                self._slot[s], self._cols[s] = r, 2
+                self._absorbed[s] = self._kept[s] = self._emitted[s] = 0
+                self._first_out[s] = True
+
+    def _streams(self, s: int, cur: int) -> bool:
+        """Whether slot s's frames can be named yet: below 2K - 1 columns build_delay_pattern_mask applies no pattern at all, and `cur` alone
+        cannot tell which un-delay the finished request will get; a request whose max_length is below 2K - 1 never gets the pattern."""
+        return self._slot[s].max_length >= 2 * self.K - 1 and cur >= 2 * self.K - 1
+
+    def _want(self, s: int) -> int:
+        return self.first_chunk if self._first_out[s] else self.chunk
+
+    def _first_chunk_steps(self, s: int) -> Optional[int]:
+        """Steps until slot s, whose first chunk is outstanding, can have it (no frame dropped from here on): kept + new raw frames - emitted
+        - halo >= first_chunk with complete = columns - K, i.e. first_chunk + halo + K columns on a clean request."""
+        if not self._first_out[s] or self._slot[s].max_length < 2 * self.K - 1:
+            return None
+        need = self.first_chunk + self.halo - (self._kept[s] - self._emitted[s])  # raw frames still to absorb
+        cols = max(2 * self.K - 1, self._absorbed[s] + need + self.K)
+        return cols - self._cols[s]
+
+    def _poll_stream(self):
+        """Admit, run to the next boundary (a poll, the nearest max_length end, or the nearest first chunk), then ONE codec pass over every
+        slot that has a chunk ready or has finished."""
+        self._admit()
+        busy = [s for s in range(self.slots) if self._slot[s] is not None]
+        if not busy:
+            return
+        n = min(min(self._slot[s].max_length - self._cols[s] for s in busy), self.poll_steps)
+        for s in busy:
+            f = self._first_chunk_steps(s)
+            if f is not None and f >= 1:
+                n = min(n, f)
+        n = max(0, n)
+        if n > 0:
+            self.eng.decode_steps(n)
+            for s in busy:
+                self._cols[s] = min(self._cols[s] + n, self._slot[s].max_length)
+        cur, live = self.eng.row_state()
+        rows, whole = [], []
+        for s in busy:
+            r, done = self._slot[s], not live[s]
+            if not self._streams(s, cur[s]):
+                if done:
+                    whole.append(s)  # ended below 2K - 1 columns: today's un-delay + filtered decode, as one last chunk
+                continue
+            complete = min(cur[s], r.max_length) - self.K
+            if done:
+                rows.append((s, complete, 1, 0))
+            elif self._kept[s] + (complete - self._absorbed[s]) - self._emitted[s] - self.halo >= self._want(s):
+                rows.append((s, complete, 0, self._want(s)))
+        if rows:
+            ptr, ld = self.eng.ids_buffer()
+            wave, out = self.model.audio_encoder.stream_decode(ptr, ld, rows, self.halo, col0=1, delay=1)
+            self.codec_passes += 1
+            self.codec_rows += len(rows)
+            hop = self.model._codec_hop()
+            pairs = out.tolist()  # the pass's one host read: (emit, kept) per row
+            for i, (s, complete, final, _) in enumerate(rows):
+                emit, kept = int(pairs[i][0]), int(pairs[i][1])
+                self._absorbed[s], self._kept[s] = complete, kept
+                self._emitted[s] += emit
+                t = self._slot[s].ticket
+                if emit > 0:
+                    self._out.append((t, wave[i, : emit * hop].clone(), bool(final)))
+                    self._first_out[s] = False
+                elif final:  # nothing left to flush: the flag alone, or the reference's torch.zeros(1) for a request without any valid frame (:3641)
+                    self._out.append((t, torch.zeros(1 if self._emitted[s] == 0 else 0, device=wave.device), True))
+        group = [(self._slot[s], self.eng.row_ids(s, cur[s])) for s in whole]
+        for s in busy:
+            if not live[s]:
+                self.eng.retire_row(s)
+                self._slot[s] = None
+        if group:
+            self.whole_requests += len(group)
+            done_before = len(self._done)
+            self._decode_group(group)
+            while len(self._done) > done_before:
+                t, w, _ = self._done.pop()
+                self._out.append((t, w, True))
+
+    def chunks(self) -> Iterator[Tuple[int, torch.Tensor, bool]]:
+        """Streaming mode: yields (ticket, chunk, last) in the order chunks become available, until nothing is queued or running. The chunks of
+        a ticket concatenate to the waveform the non-streaming mode yields for the same request; ``last`` is True exactly once per ticket."""
+        if self.chunk is None:
+            raise RuntimeError("chunks() needs streaming mode: construct the batcher with `stream_chunk_frames`")
+        with torch.no_grad():
+            while self._out or self.pending():
+                if not self._out:
+                    self._poll_stream()
+                while self._out:
+                    yield self._out.popleft()
+
+    def cancel(self, ticket: int) -> bool:
+        """Drops a request: a queued one leaves the queue, one in a slot is retired (``ptts_retire_row``: the slot is idle for the next
+        admission), and nothing of it that is waiting to be handed out follows. False if the ticket is unknown or already finished."""
+        found = False
+        for r in list(self._queue):
+            if r.ticket == ticket:
+                self._queue.remove(r)
+                found = True
+        for s in range(self.slots):
+            if self._slot[s] is not None and self._slot[s].ticket == ticket:
+                self.eng.retire_row(s)
+                self._slot[s] = None
+                found = True
+        if found:
+            self._done = collections.deque(d for d in self._done if d[0] != ticket)
+            if self.chunk is not None:
+                self._out = collections.deque(c for c in self._out if c[0] != ticket)
+        return found
+
     def _codes(self, ids: torch.Tensor, max_length: int) -> torch.Tensor:
         """Raw ids [K, columns] of one request -> its un-delayed audio codes [K, frames] (generate()'s tail, modeling_parler_tts.py:3585-3600)."""
         bos_col = ids[:, :1]
@@ -191,6 +344,8 @@ class ContinuousBatcher:
 
     def __iter__(self) -> Iterator[Tuple[int, torch.Tensor, int]]:
         """Yields (ticket, waveform, length) in the order requests finish, until nothing is queued or running."""
+        if self.chunk is not None:
+            raise RuntimeError("this batcher streams (`stream_chunk_frames`): iterate chunks() instead")
         with torch.no_grad():
             while self._done or self.pending():
                 if not self._done:

@@ -1115,6 +1115,12 @@ struct ptts_dac {
   std::set<std::string> loaded, required;
   bool table_ready = false;
   int hop = 1;
+  // stream table (ptts_dac_stream_open): kept codes [slots][K][cap], counters [slots][4] = absorbed, kept, emitted, -; the plan of the pass in
+  // flight [5][slots] = window length (the ragged `lens`), window start, skip and end in samples, slot. Host side: what the host knows without
+  // reading the device - the raw frames absorbed (exact) and an upper bound of kept - emitted per slot.
+  int *st_tab = nullptr, *st_state = nullptr, *st_plan = nullptr;
+  int st_slots = 0, st_cap = 0;
+  std::vector<int> st_absorbed, st_ready_ub;
 
   template <typename T> int alloc(T** p, size_t n) {
     void* v = nullptr;
@@ -1131,6 +1137,7 @@ extern "C" void ptts_dac_destroy(ptts_dac* d) {
   PttsDeviceGuard _dg(d->cfg.device);
   hipDeviceSynchronize();
   for (void* p : d->allocs) hipFree(p);
+  for (void* p : {(void*)d->st_tab, (void*)d->st_state, (void*)d->st_plan}) if (p) hipFree(p);
   if (d->own_stream) hipStreamDestroy(d->own_stream);
   delete d;
 }
@@ -1550,13 +1557,203 @@ static int run_resunit(const ConvLayer& c7, const ConvLayer& c1, const void* x, 
   return PTTS_OK;
 }
 
+// ---- streaming out of a continuous session (ptts_dac_stream_decode) ----------------------------------------------------------------
+// Every slot of a session is at its own frame and the special-id filter keeps a SUBSEQUENCE of a request's frames, so the codec's window of a
+// slot is counted in kept frames and lives in a per-slot table on the device. One pass = absorb + plan (one workgroup per listed row), a
+// gather that reads each row's window out of the table, the unchanged convolution stack on the left-aligned windows (ragged: `lens`), the
+// final convolution with a per-row emit range, and a zero fill of every row's tail.
+namespace {
+
+constexpr int STREAM_ROWS = 32;  // descriptors per absorb launch: they travel as kernel arguments (no staging buffer, nothing to synchronise)
+struct StreamRowsArg {
+  int r0, n;
+  ptts_dac_stream_row row[STREAM_ROWS];
+};
+struct StreamPlan {
+  const int *tab, *lens, *start, *skip, *tend, *slot;
+  int cap;
+};
+
+// compact_codes_kernel's ballot scan with an append offset and the (col0, delay) indexing of the raw id buffer; lane 0 then plans the row.
+__global__ void __launch_bounds__(256) stream_absorb_kernel(StreamRowsArg ra, const long long* __restrict__ ids, long long ids_ld, int col0, int delay,
+                                                            int K, int ncodes, int* __restrict__ tab, int cap, int* __restrict__ state, int halo,
+                                                            int hop, int Tmax, long long wave_ld, int* __restrict__ p_lens, int* __restrict__ p_start,
+                                                            int* __restrict__ p_skip, int* __restrict__ p_tend, int* __restrict__ p_slot,
+                                                            int* __restrict__ out) {
+  __shared__ int s_wsum[4];
+  __shared__ int s_base;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ptts_dac_stream_row row = ra.row[blockIdx.x];
+  const int r = ra.r0 + blockIdx.x;
+  int* st = state + (size_t)row.slot * 4;
+  const int absorbed = st[0], kept0 = st[1], emitted = st[2];
+  const long long* src = ids + (size_t)row.slot * K * ids_ld + col0;
+  int* dst = tab + (size_t)row.slot * K * cap;
+  if (tid == 0) s_base = 0;
+  __syncthreads();
+  for (int c0 = absorbed; c0 < row.complete; c0 += 256) {
+    const int f = c0 + tid;
+    int keep = 0;
+    if (f < row.complete) {
+      keep = 1;
+      for (int k = 0; k < K; ++k) { const long long v = src[(size_t)k * ids_ld + f + k * delay]; if (v < 0 || v >= ncodes) keep = 0; }
+    }
+    const unsigned long long m = __ballot(keep);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_wsum[wave] = __popcll(m);
+    __syncthreads();
+    int off = kept0 + s_base;
+    for (int w2 = 0; w2 < wave; ++w2) off += s_wsum[w2];
+    if (keep && off + before < cap)
+      for (int k = 0; k < K; ++k) dst[(size_t)k * cap + off + before] = (int)src[(size_t)k * ids_ld + f + k * delay];
+    __syncthreads();
+    if (tid == 0) s_base += s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const int kept = min(kept0 + s_base, cap);
+  const int ready = kept - emitted;
+  int emit = row.final ? ready : (ready - halo >= max(row.min_emit, 1) ? ready - halo : 0);
+  const int w0 = max(0, emitted - halo);
+  // the host sized the launch and the output rows from upper bounds of these: never true, and if it were, no store leaves its buffer
+  if (emit < 0 || kept - w0 > Tmax || (long long)emit * hop > wave_ld) emit = 0;
+  p_lens[r] = emit > 0 ? kept - w0 : 0;
+  p_start[r] = w0;
+  p_skip[r] = (emitted - w0) * hop;
+  p_tend[r] = (emitted - w0 + emit) * hop;
+  p_slot[r] = row.slot;
+  out[2 * r] = emit;
+  out[2 * r + 1] = kept;
+  st[0] = row.complete;
+  st[1] = kept;
+  st[2] = emitted + emit;
+}
+
+// rvq_gather_kernel reading row r's window [start[r], start[r] + lens[r]) of its slot's kept codes (same sum order over the codebooks)
+__global__ void rvq_gather_stream_kernel(StreamPlan sp, const float* __restrict__ table, void* __restrict__ z, int K, int T, int ncodes, int latent,
+                                         int z_bf16) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  if (t >= sp.lens[b]) return;
+  __shared__ int s_code[32];
+  if (threadIdx.x < K) {
+    int cde = sp.tab[((size_t)sp.slot[b] * K + threadIdx.x) * sp.cap + sp.start[b] + t];
+    if (cde < 0) cde = 0;
+    if (cde >= ncodes) cde = ncodes - 1;
+    s_code[threadIdx.x] = cde;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < latent; c += blockDim.x) {
+    float acc = 0.f;
+    for (int i = 0; i < K; ++i) acc += table[((size_t)i * ncodes + s_code[i]) * latent + c];
+    if (z_bf16) reinterpret_cast<bf16_t*>(z)[((size_t)b * T + t) * latent + c] = f32_to_bf16(acc);
+    else reinterpret_cast<float*>(z)[((size_t)b * T + t) * latent + c] = acc;
+  }
+}
+
+// conv_out_tanh_kernel with the emit range [skips[b], tends[b]) per row; the same fma order per sample
+__global__ void conv_out_tanh_stream_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                            float* __restrict__ out, int B, int T, int C, int ktaps, const int* __restrict__ skips, long long out_ld,
+                                            const int* __restrict__ tends, const int* __restrict__ lens, int len_mul) {
+  extern __shared__ float sw[];
+  for (int i = threadIdx.x; i < ktaps * C; i += blockDim.x) sw[i] = w[i];
+  __syncthreads();
+  const int TG = (T + OUT_OS - 1) / OUT_OS;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)B * TG) return;
+  const int b = (int)(idx / TG), t0 = (int)(idx % TG) * OUT_OS;
+  const int Tv = min(T, lens[b] * len_mul);
+  const int skip = skips[b], t_end = min(tends[b], Tv);
+  if (t0 + OUT_OS <= skip || t0 >= t_end) return;
+  float acc[OUT_OS];
+#pragma unroll
+  for (int s = 0; s < OUT_OS; ++s) acc[s] = bias[0];
+  const int half = ktaps / 2;
+  for (int r = 0; r < OUT_OS + ktaps - 1; ++r) {
+    const int ti = t0 - half + r;
+    if (ti < 0 || ti >= Tv) continue;
+    const float4* xr = reinterpret_cast<const float4*>(x + ((size_t)b * T + ti) * C);
+    for (int c4 = 0; c4 < C / 4; ++c4) {
+      const float4 xv = xr[c4];
+#pragma unroll
+      for (int s = 0; s < OUT_OS; ++s) {
+        const int tap = r - s;
+        if (tap >= 0 && tap < ktaps) {
+          const float4 wv = reinterpret_cast<const float4*>(sw + tap * C)[c4];
+          acc[s] = fmaf(xv.x, wv.x, acc[s]); acc[s] = fmaf(xv.y, wv.y, acc[s]); acc[s] = fmaf(xv.z, wv.z, acc[s]); acc[s] = fmaf(xv.w, wv.w, acc[s]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < OUT_OS; ++s) {
+    const int t = t0 + s;
+    if (t < Tv && t >= skip && t < t_end) out[(size_t)b * out_ld + (t - skip)] = tanhf(acc[s]);
+  }
+}
+
+// conv_out_tanh_lds_kernel with the emit range per row; staging, fma order and tanh as there
+__global__ void __launch_bounds__(OUT_TILE) conv_out_tanh_lds_stream_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                            const float* __restrict__ bias, float* __restrict__ out, int T,
+                                                                            const int* __restrict__ skips, long long out_ld,
+                                                                            const int* __restrict__ tends, const int* __restrict__ lens, int len_mul) {
+  __shared__ __attribute__((aligned(16))) float sx[(OUT_TILE + 6) * OUT_ROW];
+  __shared__ __attribute__((aligned(16))) float sw[7 * OUT_C];
+  const int b = blockIdx.y, t0 = blockIdx.x * OUT_TILE, tid = threadIdx.x;
+  const int Tv = min(T, lens[b] * len_mul);
+  const int skip = skips[b], t_end = min(tends[b], Tv);
+  if (t0 + OUT_TILE <= skip || t0 >= t_end) return;  // workgroup-uniform: nothing of this tile is emitted
+  for (int i = tid; i < 7 * OUT_C / 4; i += OUT_TILE) reinterpret_cast<float4*>(sw)[i] = reinterpret_cast<const float4*>(w)[i];
+  const float4* xb = reinterpret_cast<const float4*>(x + (size_t)b * T * OUT_C);
+  constexpr int NV = (OUT_TILE + 6) * (OUT_C / 4), UL = 9;
+  for (int i0 = tid; i0 < NV; i0 += UL * OUT_TILE) {
+    float4 v[UL];
+#pragma unroll
+    for (int u = 0; u < UL; ++u) {
+      const int i = min(i0 + u * OUT_TILE, NV - 1), r = i / (OUT_C / 4), ti = t0 - 3 + r;
+      v[u] = (ti >= 0 && ti < Tv) ? xb[(size_t)ti * (OUT_C / 4) + (i - r * (OUT_C / 4))] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < UL; ++u) {
+      const int i = i0 + u * OUT_TILE, r = i / (OUT_C / 4);
+      if (i < NV) *reinterpret_cast<float4*>(sx + r * OUT_ROW + (i - r * (OUT_C / 4)) * 4) = v[u];
+    }
+  }
+  __syncthreads();
+  const int t = t0 + tid;
+  if (t >= Tv || t < skip || t >= t_end) return;
+  float acc = bias[0];
+#pragma unroll 1
+  for (int tap = 0; tap < 7; ++tap) {
+    const int ti = t - 3 + tap;
+    if (ti < 0 || ti >= Tv) continue;
+    const float* xr = sx + (tid + tap) * OUT_ROW;
+    const float* wr = sw + tap * OUT_C;
+#pragma unroll
+    for (int c4 = 0; c4 < OUT_C / 4; ++c4) {
+      const float4 xv = *reinterpret_cast<const float4*>(xr + c4 * 4), wv = *reinterpret_cast<const float4*>(wr + c4 * 4);
+      acc = fmaf(xv.x, wv.x, acc); acc = fmaf(xv.y, wv.y, acc); acc = fmaf(xv.z, wv.z, acc); acc = fmaf(xv.w, wv.w, acc);
+    }
+  }
+  out[(size_t)b * out_ld + (t - skip)] = tanhf(acc);
+}
+
+// samples [hop * emit, wave_ld) of every row are zero (emit = out[2r], written by the absorb kernel of the same pass)
+__global__ void stream_zero_tail_kernel(float* __restrict__ wave, long long wave_ld, const int* __restrict__ out, int hop) {
+  const int r = blockIdx.y;
+  const long long from = (long long)out[2 * r] * hop;
+  for (long long i = (long long)blockIdx.x * 1024 + threadIdx.x; i < min(wave_ld, ((long long)blockIdx.x + 1) * 1024); i += 256)
+    if (i >= from) wave[(size_t)r * wave_ld + i] = 0.f;
+}
+
+}  // namespace
+
 // parity probe (ptts_dac_debug_decode_upto): the buffers holding a stage's outputs when the decode stops there
 struct DacDebugTap { void* act; int act_is_bf16; float* raw; int rows, channels; };
 
 // decode the window [t0, t0 + T) of codes rows with stride `ld`; samples [skip, hop*T) of the window go to wave_dev rows of out_ld
 static int dac_decode_window(ptts_dac* d, const int64_t* codes_dev, long long ld, int t0, float* wave_dev, int skip, long long out_ld,
                              int32_t B, int32_t T, void* stream, int emit = -1, const int* lens = nullptr, int stop_stage = -1,
-                             DacDebugTap* tap = nullptr) {
+                             DacDebugTap* tap = nullptr, const StreamPlan* sp = nullptr) {
   PTTS_TRY(ptts_dac_weights_ready(d));
   const ptts_dac_config& c = d->cfg;
   PTTS_CHECK(B >= 1 && B <= c.max_batch, PTTS_E_CAPACITY, "batch %d exceeds dac max_batch %d", B, c.max_batch);
@@ -1572,8 +1769,12 @@ static int dac_decode_window(ptts_dac* d, const int64_t* codes_dev, long long ld
     d->table_ready = true;
   }
   const bool bf = c.compute_dtype == PTTS_BF16;
-  hipLaunchKernelGGL(rvq_gather_kernel, dim3(T, B), dim3(256), 0, st, (const long long*)codes_dev, d->table, (void*)d->bufZ, c.num_codebooks, T,
-                     c.codebook_size, c.latent_dim, bf ? 1 : 0, ld, t0, lens);
+  if (sp)  // streaming pass: row b's window comes out of its slot's kept codes; lens == sp->lens
+    hipLaunchKernelGGL(rvq_gather_stream_kernel, dim3(T, B), dim3(256), 0, st, *sp, (const float*)d->table, (void*)d->bufZ, c.num_codebooks, T,
+                       c.codebook_size, c.latent_dim, bf ? 1 : 0);
+  else
+    hipLaunchKernelGGL(rvq_gather_kernel, dim3(T, B), dim3(256), 0, st, (const long long*)codes_dev, d->table, (void*)d->bufZ, c.num_codebooks, T,
+                       c.codebook_size, c.latent_dim, bf ? 1 : 0, ld, t0, lens);
   float *cur = d->bufA0, *other = d->bufA1;
   int Tcur = T, mul = 1;  // mul: rows per latent frame at the current layer (ragged decode: utterance b has lens[b] * mul valid rows)
   size_t li = 0;
@@ -1626,7 +1827,16 @@ static int dac_decode_window(ptts_dac* d, const int64_t* codes_dev, long long ld
     }
   }
   const int t_end = emit < 0 ? Tcur : std::min(Tcur, skip + emit);
-  if (d->out_C == OUT_C && B <= 65535) {  // otherwise the per-thread kernel
+  if (sp) {  // per-row emit range
+    if (d->out_C == OUT_C && B <= 65535) {
+      hipLaunchKernelGGL(conv_out_tanh_lds_stream_kernel, dim3((unsigned)((Tcur + OUT_TILE - 1) / OUT_TILE), (unsigned)B), dim3(OUT_TILE), 0, st,
+                         (const float*)cur, (const float*)d->out_w, (const float*)d->out_b, wave_dev, Tcur, sp->skip, out_ld, sp->tend, lens, mul);
+    } else {
+      const size_t n = (size_t)B * ((Tcur + OUT_OS - 1) / OUT_OS);
+      hipLaunchKernelGGL(conv_out_tanh_stream_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)7 * d->out_C * 4, st, (const float*)cur,
+                         (const float*)d->out_w, (const float*)d->out_b, wave_dev, B, Tcur, d->out_C, 7, sp->skip, out_ld, sp->tend, lens, mul);
+    }
+  } else if (d->out_C == OUT_C && B <= 65535) {  // otherwise the per-thread kernel
     hipLaunchKernelGGL(conv_out_tanh_lds_kernel, dim3((unsigned)((Tcur + OUT_TILE - 1) / OUT_TILE), (unsigned)B), dim3(OUT_TILE), 0, st, (const float*)cur,
                        d->out_w, d->out_b, wave_dev, Tcur, skip, out_ld, t_end, lens, mul);
   } else {
@@ -1724,6 +1934,106 @@ extern "C" int ptts_dac_decode_chunk(ptts_dac* d, const int64_t* codes_dev, int6
   const int w0 = first_frame > halo ? first_frame - halo : 0;
   return dac_decode_window(d, codes_dev, codes_ld, w0, wave_dev, (first_frame - w0) * d->hop, wave_ld, B, first_frame + n_frames - w0, stream,
                            n_emit * d->hop);
+}
+
+// ---- streaming out of a continuous session: include/ptts.h "streaming out of a continuous session" ----
+extern "C" int ptts_dac_stream_open(ptts_dac* d, int32_t slots, int32_t cap_frames, void* stream) {
+  PTTS_CHECK(d, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(slots >= 1 && slots <= d->cfg.max_batch, PTTS_E_CAPACITY, "stream slots %d exceed dac max_batch %d", slots, d->cfg.max_batch);
+  PTTS_CHECK(cap_frames >= 1, PTTS_E_INVALID, "bad stream capacity %d", cap_frames);
+  PTTS_DEVICE(d->cfg.device);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (slots != d->st_slots || cap_frames != d->st_cap) {
+    PTTS_HIP(hipStreamSynchronize(st));  // a pass in flight still reads the old table
+    for (int** p : {&d->st_tab, &d->st_state, &d->st_plan}) { if (*p) hipFree(*p); *p = nullptr; }
+    d->st_slots = d->st_cap = 0;
+    PTTS_HIP(hipMalloc((void**)&d->st_tab, (size_t)slots * d->cfg.num_codebooks * cap_frames * sizeof(int)));
+    PTTS_HIP(hipMalloc((void**)&d->st_state, (size_t)slots * 4 * sizeof(int)));
+    PTTS_HIP(hipMalloc((void**)&d->st_plan, (size_t)slots * 5 * sizeof(int)));
+    d->st_slots = slots;
+    d->st_cap = cap_frames;
+  }
+  PTTS_HIP(hipMemsetAsync(d->st_state, 0, (size_t)slots * 4 * sizeof(int), st));
+  PTTS_HIP(hipMemsetAsync(d->st_plan, 0, (size_t)slots * 5 * sizeof(int), st));
+  d->st_absorbed.assign(slots, 0);
+  d->st_ready_ub.assign(slots, 0);
+  return PTTS_OK;
+}
+
+extern "C" int ptts_dac_stream_reset(ptts_dac* d, int32_t slot, void* stream) {
+  PTTS_CHECK(d, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(d->st_slots > 0, PTTS_E_INVALID, "no stream table: call ptts_dac_stream_open first");
+  PTTS_CHECK(slot >= 0 && slot < d->st_slots, PTTS_E_INVALID, "stream slot %d out of range [0, %d)", slot, d->st_slots);
+  PTTS_DEVICE(d->cfg.device);
+  PTTS_HIP(hipMemsetAsync(d->st_state + (size_t)slot * 4, 0, 4 * sizeof(int), reinterpret_cast<hipStream_t>(stream)));
+  d->st_absorbed[slot] = d->st_ready_ub[slot] = 0;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64_t ids_ld, int32_t col0, int32_t delay,
+                                      const ptts_dac_stream_row* rows_host, int32_t R, int32_t halo, float* wave_dev, int64_t wave_ld,
+                                      int32_t* out_dev, void* stream) {
+  PTTS_CHECK(d && ids_dev && rows_host && wave_dev && out_dev, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(d->st_slots > 0, PTTS_E_INVALID, "no stream table: call ptts_dac_stream_open first");
+  PTTS_TRY(ptts_dac_weights_ready(d));
+  const ptts_dac_config& c = d->cfg;
+  const int K = c.num_codebooks;
+  PTTS_CHECK(R >= 1 && R <= d->st_slots, PTTS_E_INVALID, "bad stream pass: %d rows for %d slots", R, d->st_slots);
+  PTTS_CHECK(halo >= 0 && col0 >= 0 && delay >= 0 && ids_ld >= 1 && wave_ld >= 1, PTTS_E_INVALID, "bad stream pass: halo %d, col0 %d, delay %d, ids_ld %lld, wave_ld %lld",
+             halo, col0, delay, (long long)ids_ld, (long long)wave_ld);
+  // validate every row and bound its window before anything is enqueued or counted
+  int T = 0;
+  long long emit_ub_max = 0;
+  std::vector<char> seen(d->st_slots, 0);
+  for (int r = 0; r < R; ++r) {
+    const ptts_dac_stream_row& w = rows_host[r];
+    PTTS_CHECK(w.slot >= 0 && w.slot < d->st_slots, PTTS_E_INVALID, "bad stream row %d: slot %d out of range [0, %d)", r, w.slot, d->st_slots);
+    PTTS_CHECK(!seen[w.slot], PTTS_E_INVALID, "bad stream row %d: slot %d listed twice", r, w.slot);
+    seen[w.slot] = 1;
+    PTTS_CHECK(w.complete >= d->st_absorbed[w.slot], PTTS_E_INVALID, "bad stream row %d: complete %d decreases (slot %d has absorbed %d raw frames)", r,
+               w.complete, w.slot, d->st_absorbed[w.slot]);
+    PTTS_CHECK(w.complete <= d->st_cap, PTTS_E_INVALID, "bad stream row %d: complete %d beyond the table's %d frames", r, w.complete, d->st_cap);
+    PTTS_CHECK((long long)col0 + w.complete + (long long)(K - 1) * delay <= ids_ld || w.complete == d->st_absorbed[w.slot], PTTS_E_INVALID,
+               "bad stream row %d: complete %d reads beyond ids_ld %lld (col0 %d, delay %d)", r, w.complete, (long long)ids_ld, col0, delay);
+    const int ready_ub = d->st_ready_ub[w.slot] + (w.complete - d->st_absorbed[w.slot]);
+    const int emit_ub = w.final ? ready_ub : (ready_ub - halo >= std::max(w.min_emit, 1) ? ready_ub - halo : 0);
+    if (emit_ub > 0) {
+      T = std::max(T, std::min(halo + ready_ub, w.complete));  // the window holds kept frames only: never more than the raw frames
+      emit_ub_max = std::max<long long>(emit_ub_max, emit_ub);
+    }
+  }
+  PTTS_CHECK(T <= c.max_frames, PTTS_E_CAPACITY, "stream window of up to %d frames exceeds dac max_frames %d", T, c.max_frames);
+  PTTS_CHECK(R <= c.max_batch, PTTS_E_CAPACITY, "batch %d exceeds dac max_batch %d", R, c.max_batch);
+  PTTS_CHECK(wave_ld >= emit_ub_max * d->hop, PTTS_E_INVALID, "wave_ld %lld < %lld frames that may be emitted", (long long)wave_ld, emit_ub_max);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int* pl = d->st_plan;
+  const int S = d->st_slots;
+  for (int r0 = 0; r0 < R; r0 += STREAM_ROWS) {
+    StreamRowsArg ra;
+    ra.r0 = r0;
+    ra.n = std::min(STREAM_ROWS, R - r0);
+    memset(ra.row, 0, sizeof ra.row);
+    memcpy(ra.row, rows_host + r0, (size_t)ra.n * sizeof(ptts_dac_stream_row));
+    hipLaunchKernelGGL(stream_absorb_kernel, dim3(ra.n), dim3(256), 0, st, ra, (const long long*)ids_dev, (long long)ids_ld, col0, delay, K, c.codebook_size,
+                       d->st_tab, d->st_cap, d->st_state, halo, d->hop, T, (long long)wave_ld, pl, pl + S, pl + 2 * S, pl + 3 * S, pl + 4 * S, (int*)out_dev);
+  }
+  for (int r = 0; r < R; ++r) {
+    const ptts_dac_stream_row& w = rows_host[r];
+    int ub = d->st_ready_ub[w.slot] + (w.complete - d->st_absorbed[w.slot]);
+    ub = w.final ? 0 : std::min(ub, halo + std::max(w.min_emit, 1) - 1);  // emitted: `halo` frames are left; not emitted: fewer than halo + min_emit were ready
+    d->st_ready_ub[w.slot] = ub;
+    d->st_absorbed[w.slot] = w.complete;
+  }
+  if (T > 0) {
+    const StreamPlan sp{d->st_tab, pl, pl + S, pl + 2 * S, pl + 3 * S, pl + 4 * S, d->st_cap};
+    PTTS_TRY(dac_decode_window(d, nullptr, 0, 0, wave_dev, 0, wave_ld, R, T, stream, -1, pl, -1, nullptr, &sp));
+  }
+  hipLaunchKernelGGL(stream_zero_tail_kernel, dim3((unsigned)((wave_ld + 1023) / 1024), (unsigned)R), dim3(256), 0, st, wave_dev, (long long)wave_ld,
+                     (const int*)out_dev, d->hop);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "stream decode launch failed: %s", hipGetErrorString(e));
+  return PTTS_OK;
 }
 
 // DACModel.encode (dac_wrapper/modeling_dac.py:33-104) for one chunk: wave_dev float32 [B][L] with L a multiple of the hop

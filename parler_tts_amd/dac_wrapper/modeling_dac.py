@@ -59,6 +59,7 @@ class DACModel(torch.nn.Module):
         self._weights: Dict[str, torch.Tensor] = {}  # dac.model.DAC names under the reference's "model." prefix
         self._engine: Optional[DacEngine] = None
         self._engine_dev = None
+        self._stream_engine: Optional[DacEngine] = None  # the engine that holds the stream table (stream_open)
         self._dummy = torch.nn.Parameter(torch.zeros(1), requires_grad=False)  # tracks .to(device)
 
     @property
@@ -219,6 +220,34 @@ class DACModel(torch.nn.Module):
         n_frames = T - first_frame if n_frames is None else n_frames
         eng = self._get_engine(B, min(T, n_frames + halo), whole_batch=True)  # window = n_frames + halo frames, every utterance in one pass
         return DACDecoderOutput(eng.decode_chunk(codes, first_frame, n_frames, halo, out=out, n_emit=n_emit))
+
+    # -- streaming out of a continuous session (not in the reference wrapper) -----------------------------------------
+    def stream_open(self, slots: int, cap_frames: int, window_frames: int):
+        """Opens the per-slot stream table (``ptts_dac_stream_open``) in a codec engine sized ONCE for ``slots`` rows of ``window_frames``
+        frames. The table lives in that engine: if a later ``decode`` / ``encode`` call needs more capacity and ``_get_engine`` replaces the
+        engine, the table and the requests in flight are lost, and ``stream_reset`` / ``stream_decode`` raise ``RuntimeError`` until
+        ``stream_open`` is called again (the streaming ``ContinuousBatcher`` does that and restarts nothing: it lets the error surface)."""
+        eng = self._get_engine(slots, window_frames, whole_batch=True)
+        eng.stream_open(slots, cap_frames)
+        self._stream_engine = eng
+        return eng
+
+    def _stream(self) -> DacEngine:
+        if self._stream_engine is None:
+            raise RuntimeError("no stream table: call stream_open first")
+        if self._engine is not self._stream_engine:
+            self._stream_engine = None
+            raise RuntimeError("the codec engine was replaced (a call needed more capacity): the stream table and the requests in flight are "
+                               "lost; call stream_open again")
+        return self._stream_engine
+
+    def stream_reset(self, slot: int):
+        self._stream().stream_reset(slot)
+
+    @torch.no_grad()
+    def stream_decode(self, ids, ids_ld, rows, halo: int, col0: int = 0, delay: int = 0):
+        """``DacEngine.stream_decode`` on the engine that holds the table: (wave [R, ld], out [R, 2] = (emit, kept)) on the device."""
+        return self._stream().stream_decode(ids, ids_ld, rows, halo, col0=col0, delay=delay)
 
     def forward(self, tensor):
         raise ValueError("`DACModel.forward` not implemented yet")  # modeling_dac.py:144-145

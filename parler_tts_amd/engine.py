@@ -286,6 +286,13 @@ class DecoderEngine:
         N.check(self.lib.ptts_ids(self._h, C.byref(p), C.byref(ld)), "ptts_ids")
         return self._copy_out(p.value + int(row) * self.K * ld.value * 8, (self.K, int(cols)), torch.int64, row_stride=ld.value)
 
+    def ids_buffer(self) -> Tuple[int, int]:
+        """(device pointer, row stride in columns) of the engine's own raw id buffer int64 [B*K, stride] (``ptts_ids``), NOT a copy: what
+        ``DacEngine.stream_decode`` reads in place (``col0=1, delay=1``), ordered behind the decode steps on the same stream."""
+        p, ld = C.c_void_p(), C.c_int32()
+        N.check(self.lib.ptts_ids(self._h, C.byref(p), C.byref(ld)), "ptts_ids")
+        return int(p.value), int(ld.value)
+
     def generate_ids(self, enc, enc_mask, prompt, prompt_mask, poll_every: int = 64, audio_prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
         """prefill + graph-replayed decode until every row finished; returns raw ids [B*K, Lout]. ``audio_prefix``:
         un-delayed voice-prompt codes [B, K, T] continued by the decoder."""
@@ -509,6 +516,51 @@ class DacEngine:
                                                C.c_void_p(ptr), int(ld), int(n_emit), B, _stream_ptr(device=self.device)), "ptts_dac_decode_chunk")
         self._keep = codes
         return dst
+
+    # -- streaming out of a continuous session (ptts_dac_stream_open / _reset / _decode) ---------------------------
+    def stream_open(self, slots: int, cap_frames: int):
+        """(Re)allocates and clears the per-slot stream table: kept codes [slots, K, cap_frames] and the counters, on the device."""
+        N.check(self.lib.ptts_dac_stream_open(self._h, int(slots), int(cap_frames), _stream_ptr(device=self.device)), "ptts_dac_stream_open")
+        self.stream_slots, self.stream_cap = int(slots), int(cap_frames)
+        self._st_absorbed, self._st_ready_ub = [0] * int(slots), [0] * int(slots)  # the library's host-side bounds, mirrored to size `wave`
+
+    def stream_reset(self, slot: int):
+        """A new request enters ``slot``: its counters return to 0 (enqueued)."""
+        N.check(self.lib.ptts_dac_stream_reset(self._h, int(slot), _stream_ptr(device=self.device)), "ptts_dac_stream_reset")
+        self._st_absorbed[int(slot)] = self._st_ready_ub[int(slot)] = 0
+
+    def stream_decode(self, ids, ids_ld: Optional[int], rows, halo: int, col0: int = 0, delay: int = 0):
+        """One windowed codec pass over the listed slots (``ptts_dac_stream_decode``). ``ids``: an int64 device tensor [slots, K, ld] of plain
+        codes (``col0=0, delay=0``), or the pointer of ``DecoderEngine.ids_buffer()`` with its stride ``ids_ld`` (``col0=1, delay=1``), read in
+        place. ``rows``: ``(slot, complete, final, min_emit)`` per listed slot. Returns ``(wave float32 [R, ld], out int32 [R, 2])`` on the
+        device: row r holds ``hop * out[r, 0]`` samples (zero beyond), ``out[r] = (emit, kept)``. Enqueued on the current stream; no sync."""
+        if not getattr(self, "stream_slots", 0):
+            raise ValueError("no stream table: call stream_open first")
+        if isinstance(ids, torch.Tensor):
+            if ids.device != self.device or ids.dtype != torch.int64 or not ids.is_contiguous():
+                ids = ids.to(self.device, torch.int64).contiguous()
+            ptr, ids_ld = ids.data_ptr(), int(ids.shape[-1])
+            self._keep = ids
+        else:
+            ptr, ids_ld = int(ids), int(ids_ld)
+        rows = [tuple(int(v) for v in r) for r in rows]
+        R = len(rows)
+        arr = (N.PttsDacStreamRow * max(R, 1))(*[N.PttsDacStreamRow(*r) for r in rows])
+        emit_ub, bounds = 1, []
+        for slot, complete, final, min_emit in rows:
+            ub = 0
+            if 0 <= slot < self.stream_slots:  # a bad descriptor is refused by the library with its own message
+                ub = self._st_ready_ub[slot] + max(0, complete - self._st_absorbed[slot])
+                emit_ub = max(emit_ub, ub if final else ub - int(halo))
+            bounds.append(ub)
+        wave = torch.empty(max(R, 1), self.hop * emit_ub, dtype=torch.float32, device=self.device)
+        out = torch.empty(max(R, 1), 2, dtype=torch.int32, device=self.device)
+        N.check(self.lib.ptts_dac_stream_decode(self._h, C.c_void_p(ptr), ids_ld, int(col0), int(delay), arr, R, int(halo), C.c_void_p(wave.data_ptr()),
+                                                int(wave.shape[1]), C.c_void_p(out.data_ptr()), _stream_ptr(device=self.device)), "ptts_dac_stream_decode")
+        for (slot, complete, final, min_emit), ub in zip(rows, bounds):
+            self._st_ready_ub[slot] = 0 if final else min(ub, int(halo) + max(min_emit, 1) - 1)
+            self._st_absorbed[slot] = complete
+        return wave, out
 
     def encode(self, wave: torch.Tensor, n_quantizers: Optional[int] = None) -> torch.Tensor:
         """waveform float32 [B, 1, L] (L a multiple of the hop) → codes int64 [B, n_quantizers, L / hop]."""

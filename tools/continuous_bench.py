@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Continuous batching against static batching on a request stream of mixed lengths (Mini-v1 shapes, bf16, synthetic weights).
 
-  python tools/continuous_bench.py [--repeats 5] [--static-only] [--out FILE]
+  python tools/continuous_bench.py [--repeats 5] [--static-only] [--stream [--stream-chunks 43,86]] [--out FILE]
 
 256 requests whose lengths come from a fixed seeded list (uniform 150..860 frames, set through per-request max_new_tokens; EOS is blocked,
 so lengths are exact), 32 slots. Reports
@@ -14,7 +14,11 @@ so lengths are exact), 32 slots. Reports
                  same context
   (e) admission: GPU time of one ptts_admit_row while the other slots hold live requests
 A and B alternate inside one process after every graph has been warmed; medians and the observed spread are printed. --static-only runs (a)
-and the static step of (d) alone (it needs nothing of the session interface, so it also runs on a tree without it)."""
+and the static step of (d) alone (it needs nothing of the session interface, so it also runs on a tree without it).
+
+--stream measures the streaming mode instead of (a), (d), (e): (b) and the streaming batcher (`stream_chunk_frames`) alternate on the same list;
+per chunk size it reports audio-s/s next to (b), the codec passes and the mean rows per pass, and per request the host time from its admission
+and from its submission to its first chunk (p50 / p90 / max), next to admission -> whole waveform of the non-streaming batcher."""
 import argparse
 import ctypes as C
 import json
@@ -96,6 +100,88 @@ def run_batcher(model, desc, prompt, frames):
     dt = time.perf_counter() - t0
     assert [got[t] for t in tickets] == [f * 512 for f in frames], "the batcher returned other lengths than were asked for"
     return dt, t_submit
+
+
+def _quantiles(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2], xs[min(len(xs) - 1, int(0.9 * len(xs)))], xs[-1]
+
+
+def run_latency(model, desc, prompt, frames, chunk):
+    """One run with host timestamps: per request its submission, its admission (FIFO: the i-th ptts_admit_row is ticket i) and the moment its
+    first audio is in the caller's hands - the first chunk (streaming, `chunk` frames) or the whole waveform (chunk None). Both modes read the
+    codec's counts back before they yield, so the samples exist by then."""
+    import parler_tts_amd as P
+
+    new_max = FRAMES_HI + K - 1
+    kw = {} if chunk is None else {"stream_chunk_frames": chunk}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    cb = P.ContinuousBatcher(model, slots=SLOTS, max_description_tokens=bench.N_DESC, max_prompt_tokens=bench.N_PROMPT, poll_steps=16, do_sample=False,
+                             max_new_tokens=new_max, min_new_tokens=new_max, **kw)
+    admitted, eng, real = [], cb.eng, cb.eng.admit_row
+
+    def admit_row(*a, **k):
+        admitted.append(time.perf_counter())
+        return real(*a, **k)
+
+    eng.admit_row = admit_row
+    submitted, first, samples = {}, {}, {}
+    try:
+        for i in range(N_REQ):
+            t = cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1)
+            submitted[t] = time.perf_counter()
+        if chunk is None:
+            for t, w, n in cb:
+                first[t], samples[t] = time.perf_counter(), n
+        else:
+            for t, c, last in cb.chunks():
+                first.setdefault(t, time.perf_counter())
+                samples[t] = samples.get(t, 0) + c.shape[0]
+    finally:
+        eng.admit_row = real
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert [samples[t] for t in range(N_REQ)] == [f * 512 for f in frames], "the batcher returned other lengths than were asked for"
+    since_admit = [first[t] - admitted[t] for t in range(N_REQ)]
+    since_submit = [first[t] - submitted[t] for t in range(N_REQ)]
+    return dt, since_admit, since_submit, (getattr(cb, "codec_passes", 0), getattr(cb, "codec_rows", 0))
+
+
+def stream_report(model, desc, prompt, frames, audio_s, chunks, repeats, say):
+    res = {}
+    run_batcher(model, desc, prompt, frames)
+    for c in chunks:
+        run_latency(model, desc, prompt, frames, c)  # warm: the codec engine of this window size, the stream table
+    base, runs = [], {c: [] for c in chunks}
+    for r in range(repeats):
+        base.append(run_batcher(model, desc, prompt, frames)[0])
+        for c in chunks:
+            runs[c].append(run_latency(model, desc, prompt, frames, c))
+        say(f"  repeat {r}: batcher {base[-1]:.3f} s, " + ", ".join(f"streaming {c} frames {runs[c][-1][0]:.3f} s" for c in chunks))
+    mb, lob, hib = med_spread(base)
+    say(f"(b) ContinuousBatcher: median {mb:.3f} s = {audio_s / mb:.1f} audio-s/s (spread {audio_s / hib:.1f} .. {audio_s / lob:.1f})")
+    res.update(batcher_s=mb, batcher_audio_s_per_s=audio_s / mb)
+    _, adm, sub, _ = run_latency(model, desc, prompt, frames, None)
+    a50, a90, amax = _quantiles(adm)
+    s50, s90, smax = _quantiles(sub)
+    say(f"    not streaming: admission -> whole waveform p50 {a50:.3f} s, p90 {a90:.3f} s, max {amax:.3f} s; submission -> whole waveform p50 {s50:.3f} s, "
+        f"p90 {s90:.3f} s, max {smax:.3f} s")
+    res["whole_since_admission_s"] = [round(a50, 4), round(a90, 4), round(amax, 4)]
+    for c in chunks:
+        m, lo, hi = med_spread([x[0] for x in runs[c]])
+        adm = [v for x in runs[c] for v in x[1]]
+        sub = [v for x in runs[c] for v in x[2]]
+        a50, a90, amax = _quantiles(adm)
+        s50, s90, smax = _quantiles(sub)
+        passes, rows = runs[c][-1][3]
+        say(f"(s) streaming, chunks of {c} frames ({c * SEC_PER_FRAME:.2f} s): median {m:.3f} s = {audio_s / m:.1f} audio-s/s (spread {audio_s / hi:.1f} .. "
+            f"{audio_s / lo:.1f}) = {mb / m:.3f} of (b); {passes} codec passes, {rows / max(passes, 1):.1f} rows per pass")
+        say(f"    admission -> first chunk p50 {a50 * 1e3:.1f} ms, p90 {a90 * 1e3:.1f} ms, max {amax * 1e3:.1f} ms; submission -> first chunk p50 {s50:.3f} s, "
+            f"p90 {s90:.3f} s, max {smax:.3f} s (all {N_REQ} requests are submitted up front: this one is queueing time)")
+        res[f"stream{c}"] = {"s": m, "audio_s_per_s": audio_s / m, "of_b": mb / m, "passes": passes, "rows_per_pass": rows / max(passes, 1),
+                             "first_since_admission_ms": [round(a50 * 1e3, 2), round(a90 * 1e3, 2), round(amax * 1e3, 2)]}
+    return res
 
 
 def batcher_breakdown(model, desc, prompt, frames):
@@ -188,6 +274,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--static-only", action="store_true")
+    ap.add_argument("--stream", action="store_true", help="measure the streaming mode against (b) instead of (a), (d), (e)")
+    ap.add_argument("--stream-chunks", default="43,86", help="stream_chunk_frames values to measure")
     ap.add_argument("--out", default=None, help="also append the report to this file")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -207,6 +295,15 @@ def main():
     st_steps, cb_steps = schedule_steps(frames)
     say(f"  decode steps of the schedules themselves: static {st_steps}, FIFO slots {cb_steps} (ratio {st_steps / cb_steps:.3f}: (c) less the drain of the "
         f"last requests, when nothing is left to admit)")
+    if a.stream:
+        with torch.no_grad():
+            res = stream_report(model, desc, prompt, frames, audio_s, [int(c) for c in a.stream_chunks.split(",")], a.repeats, say)
+        say(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     with torch.no_grad():
         enc = model._encode_description(desc[:64], None).float()
         pr = model.embed_prompts(prompt[:64]).float()

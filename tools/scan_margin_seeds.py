@@ -75,6 +75,13 @@ def main():
     if want("gen_fixed"):
         for rope in (False, True):
             scan(f"gen_fixed rope={rope}", C.GEN_FIXED_SEEDS[rope], lambda s, rope=rope: gen_margin(s[0], s[1], "fixed", rope), [(2, 100 + i) for i in range(40)])
+    if want("stream_e2e"):  # tests/test_continuous_streaming_gpu.py: one request per (input seed, max_new_tokens), each scanned on its own
+        import test_continuous_streaming_gpu as TS
+
+        m, spec, sd, dsd = C.tiny_model(seed=TS.E2E_MODEL_SEED)
+        for seed, n in TS.E2E_SCANNED:
+            f = lambda s, n=n: TS.e2e_oracle(m, spec, sd, dsd, TS.e2e_request(s, n), "cpu")[0].min_margin
+            scan(f"stream_e2e {n} tokens", seed, f, list(range(500, 700)), want=1)
     if want("gen_voice"):
         scan("gen_voice", C.GEN_VOICE_SEEDS, lambda s: gen_margin(s[0], s[1], "voice"), [(0, 100 + i) for i in range(40)])
 
