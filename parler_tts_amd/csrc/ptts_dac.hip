@@ -786,10 +786,17 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2,
 // they touch are read once (60 float4 loads per sample instead of 168; the kernel was 187 us of the 860-frame decode, L1-bound on
 // the 7x re-read). Per sample the fma order is unchanged (bias, then tap 0..6 x channel 0..C-1), so the exact-f32 mode is bit-identical.
 // samples [skip, t_end) of every utterance are written to out[b * out_ld + (t - skip)] (skip > 0: the halo frames of a chunk)
+// ROWS (the streaming pass out of a session): the emit range is [skip[b], t_end[b]) per row instead of one range for the batch
 constexpr int OUT_OS = 4;
+template <bool ROWS> struct EmitArg { using T = int; };
+template <> struct EmitArg<true> { using T = const int* __restrict__; };
+__device__ __forceinline__ int emit_of(int v, int) { return v; }
+__device__ __forceinline__ int emit_of(const int* v, int b) { return v[b]; }
+
+template <bool ROWS>
 __global__ void conv_out_tanh_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                     float* __restrict__ out, int B, int T, int C, int ktaps, int skip, long long out_ld, int t_end,
-                                     const int* __restrict__ lens, int len_mul) {
+                                     float* __restrict__ out, int B, int T, int C, int ktaps, typename EmitArg<ROWS>::T skip_of, long long out_ld,
+                                     typename EmitArg<ROWS>::T t_end_of, const int* __restrict__ lens, int len_mul) {
   extern __shared__ float sw[];
   for (int i = threadIdx.x; i < ktaps * C; i += blockDim.x) sw[i] = w[i];
   __syncthreads();
@@ -798,7 +805,7 @@ __global__ void conv_out_tanh_kernel(const float* __restrict__ x, const float* _
   if (idx >= (size_t)B * TG) return;
   const int b = (int)(idx / TG), t0 = (int)(idx % TG) * OUT_OS;
   const int Tv = lens ? min(T, lens[b] * len_mul) : T;  // ragged decode: samples of this utterance (rows beyond are the zero padding)
-  t_end = min(t_end, Tv);
+  const int skip = emit_of(skip_of, b), t_end = min(emit_of(t_end_of, b), Tv);
   if (t0 + OUT_OS <= skip || t0 >= t_end) return;
   float acc[OUT_OS];
 #pragma unroll
@@ -834,14 +841,15 @@ __global__ void conv_out_tanh_kernel(const float* __restrict__ x, const float* _
 // 4-bank slots), the 7 x 96 weights are read as wave-uniform broadcasts. Thread t then computes sample t with EXACTLY the fma order
 // of the reference restatement (bias, tap 0..6 x channel 0..95): the exact-f32 mode stays bit-identical to the direct kernel.
 constexpr int OUT_TILE = 64, OUT_C = 96, OUT_ROW = 100;  // 64 samples per (one-wave) workgroup: 28 KB of LDS, 5 workgroups per CU
+template <bool ROWS>
 __global__ void __launch_bounds__(OUT_TILE) conv_out_tanh_lds_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                                     float* __restrict__ out, int T, int skip, long long out_ld, int t_end,
-                                                                     const int* __restrict__ lens, int len_mul) {
+                                                                     float* __restrict__ out, int T, typename EmitArg<ROWS>::T skip_of, long long out_ld,
+                                                                     typename EmitArg<ROWS>::T t_end_of, const int* __restrict__ lens, int len_mul) {
   __shared__ __attribute__((aligned(16))) float sx[(OUT_TILE + 6) * OUT_ROW];
   __shared__ __attribute__((aligned(16))) float sw[7 * OUT_C];
   const int b = blockIdx.y, t0 = blockIdx.x * OUT_TILE, tid = threadIdx.x;
   const int Tv = lens ? min(T, lens[b] * len_mul) : T;  // ragged decode: samples of this utterance (rows beyond are the zero padding)
-  t_end = min(t_end, Tv);
+  const int skip = emit_of(skip_of, b), t_end = min(emit_of(t_end_of, b), Tv);
   if (t0 + OUT_TILE <= skip || t0 >= t_end) return;  // workgroup-uniform: nothing of this tile is emitted
   for (int i = tid; i < 7 * OUT_C / 4; i += OUT_TILE) reinterpret_cast<float4*>(sw)[i] = reinterpret_cast<const float4*>(w)[i];
   const float4* xb = reinterpret_cast<const float4*>(x + (size_t)b * T * OUT_C);
@@ -1016,15 +1024,27 @@ __global__ void rvq_table_kernel(const float* __restrict__ cb, const float* __re
   table[idx] = acc + bias[c];
 }
 
+// streaming out of a continuous session (ptts_dac_stream_decode): one pass's plan, [row] arrays written by stream_absorb_kernel
+struct StreamPlan {
+  const int *tab, *lens, *start, *skip, *tend, *slot;
+  int cap;
+};
+template <bool STREAM> struct GatherSrc { using T = const long long* __restrict__; };
+template <> struct GatherSrc<true> { using T = StreamPlan; };
+
 // z[b][t][c] = sum_i table[i][codes[b][i][t]][c]   (sequential over i, like from_codes)
 // codes rows have stride `ld` frames and the window starts at frame `t0` (chunked / streaming decode reads a slice in place)
-__global__ void rvq_gather_kernel(const long long* __restrict__ codes, const float* __restrict__ table, void* __restrict__ z,
+// STREAM: row b's window [start[b], start[b] + lens[b]) of its slot's kept codes instead (ld / t0 unused, lens == src.lens)
+template <bool STREAM>
+__global__ void rvq_gather_kernel(typename GatherSrc<STREAM>::T src, const float* __restrict__ table, void* __restrict__ z,
                                   int K, int T, int ncodes, int latent, int z_bf16, long long ld, int t0, const int* __restrict__ lens) {
   const int t = blockIdx.x, b = blockIdx.y;
   if (lens && t >= lens[b]) return;  // ragged decode: frames beyond the utterance's length are never read
   __shared__ int s_code[32];
   if (threadIdx.x < K) {
-    long long cde = codes[((size_t)b * K + threadIdx.x) * ld + t0 + t];
+    long long cde;
+    if constexpr (STREAM) cde = src.tab[((size_t)src.slot[b] * K + threadIdx.x) * src.cap + src.start[b] + t];
+    else cde = src[((size_t)b * K + threadIdx.x) * ld + t0 + t];
     if (cde < 0) cde = 0;
     if (cde >= ncodes) cde = ncodes - 1;
     s_code[threadIdx.x] = (int)cde;
@@ -1569,11 +1589,6 @@ struct StreamRowsArg {
   int r0, n;
   ptts_dac_stream_row row[STREAM_ROWS];
 };
-struct StreamPlan {
-  const int *tab, *lens, *start, *skip, *tend, *slot;
-  int cap;
-};
-
 // compact_codes_kernel's ballot scan with an append offset and the (col0, delay) indexing of the raw id buffer; lane 0 then plans the row.
 __global__ void __launch_bounds__(256) stream_absorb_kernel(StreamRowsArg ra, const long long* __restrict__ ids, long long ids_ld, int col0, int delay,
                                                             int K, int ncodes, int* __restrict__ tab, int cap, int* __restrict__ state, int halo,
@@ -1629,114 +1644,6 @@ __global__ void __launch_bounds__(256) stream_absorb_kernel(StreamRowsArg ra, co
   st[2] = emitted + emit;
 }
 
-// rvq_gather_kernel reading row r's window [start[r], start[r] + lens[r]) of its slot's kept codes (same sum order over the codebooks)
-__global__ void rvq_gather_stream_kernel(StreamPlan sp, const float* __restrict__ table, void* __restrict__ z, int K, int T, int ncodes, int latent,
-                                         int z_bf16) {
-  const int t = blockIdx.x, b = blockIdx.y;
-  if (t >= sp.lens[b]) return;
-  __shared__ int s_code[32];
-  if (threadIdx.x < K) {
-    int cde = sp.tab[((size_t)sp.slot[b] * K + threadIdx.x) * sp.cap + sp.start[b] + t];
-    if (cde < 0) cde = 0;
-    if (cde >= ncodes) cde = ncodes - 1;
-    s_code[threadIdx.x] = cde;
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < latent; c += blockDim.x) {
-    float acc = 0.f;
-    for (int i = 0; i < K; ++i) acc += table[((size_t)i * ncodes + s_code[i]) * latent + c];
-    if (z_bf16) reinterpret_cast<bf16_t*>(z)[((size_t)b * T + t) * latent + c] = f32_to_bf16(acc);
-    else reinterpret_cast<float*>(z)[((size_t)b * T + t) * latent + c] = acc;
-  }
-}
-
-// conv_out_tanh_kernel with the emit range [skips[b], tends[b]) per row; the same fma order per sample
-__global__ void conv_out_tanh_stream_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                            float* __restrict__ out, int B, int T, int C, int ktaps, const int* __restrict__ skips, long long out_ld,
-                                            const int* __restrict__ tends, const int* __restrict__ lens, int len_mul) {
-  extern __shared__ float sw[];
-  for (int i = threadIdx.x; i < ktaps * C; i += blockDim.x) sw[i] = w[i];
-  __syncthreads();
-  const int TG = (T + OUT_OS - 1) / OUT_OS;
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (size_t)B * TG) return;
-  const int b = (int)(idx / TG), t0 = (int)(idx % TG) * OUT_OS;
-  const int Tv = min(T, lens[b] * len_mul);
-  const int skip = skips[b], t_end = min(tends[b], Tv);
-  if (t0 + OUT_OS <= skip || t0 >= t_end) return;
-  float acc[OUT_OS];
-#pragma unroll
-  for (int s = 0; s < OUT_OS; ++s) acc[s] = bias[0];
-  const int half = ktaps / 2;
-  for (int r = 0; r < OUT_OS + ktaps - 1; ++r) {
-    const int ti = t0 - half + r;
-    if (ti < 0 || ti >= Tv) continue;
-    const float4* xr = reinterpret_cast<const float4*>(x + ((size_t)b * T + ti) * C);
-    for (int c4 = 0; c4 < C / 4; ++c4) {
-      const float4 xv = xr[c4];
-#pragma unroll
-      for (int s = 0; s < OUT_OS; ++s) {
-        const int tap = r - s;
-        if (tap >= 0 && tap < ktaps) {
-          const float4 wv = reinterpret_cast<const float4*>(sw + tap * C)[c4];
-          acc[s] = fmaf(xv.x, wv.x, acc[s]); acc[s] = fmaf(xv.y, wv.y, acc[s]); acc[s] = fmaf(xv.z, wv.z, acc[s]); acc[s] = fmaf(xv.w, wv.w, acc[s]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < OUT_OS; ++s) {
-    const int t = t0 + s;
-    if (t < Tv && t >= skip && t < t_end) out[(size_t)b * out_ld + (t - skip)] = tanhf(acc[s]);
-  }
-}
-
-// conv_out_tanh_lds_kernel with the emit range per row; staging, fma order and tanh as there
-__global__ void __launch_bounds__(OUT_TILE) conv_out_tanh_lds_stream_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                            const float* __restrict__ bias, float* __restrict__ out, int T,
-                                                                            const int* __restrict__ skips, long long out_ld,
-                                                                            const int* __restrict__ tends, const int* __restrict__ lens, int len_mul) {
-  __shared__ __attribute__((aligned(16))) float sx[(OUT_TILE + 6) * OUT_ROW];
-  __shared__ __attribute__((aligned(16))) float sw[7 * OUT_C];
-  const int b = blockIdx.y, t0 = blockIdx.x * OUT_TILE, tid = threadIdx.x;
-  const int Tv = min(T, lens[b] * len_mul);
-  const int skip = skips[b], t_end = min(tends[b], Tv);
-  if (t0 + OUT_TILE <= skip || t0 >= t_end) return;  // workgroup-uniform: nothing of this tile is emitted
-  for (int i = tid; i < 7 * OUT_C / 4; i += OUT_TILE) reinterpret_cast<float4*>(sw)[i] = reinterpret_cast<const float4*>(w)[i];
-  const float4* xb = reinterpret_cast<const float4*>(x + (size_t)b * T * OUT_C);
-  constexpr int NV = (OUT_TILE + 6) * (OUT_C / 4), UL = 9;
-  for (int i0 = tid; i0 < NV; i0 += UL * OUT_TILE) {
-    float4 v[UL];
-#pragma unroll
-    for (int u = 0; u < UL; ++u) {
-      const int i = min(i0 + u * OUT_TILE, NV - 1), r = i / (OUT_C / 4), ti = t0 - 3 + r;
-      v[u] = (ti >= 0 && ti < Tv) ? xb[(size_t)ti * (OUT_C / 4) + (i - r * (OUT_C / 4))] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < UL; ++u) {
-      const int i = i0 + u * OUT_TILE, r = i / (OUT_C / 4);
-      if (i < NV) *reinterpret_cast<float4*>(sx + r * OUT_ROW + (i - r * (OUT_C / 4)) * 4) = v[u];
-    }
-  }
-  __syncthreads();
-  const int t = t0 + tid;
-  if (t >= Tv || t < skip || t >= t_end) return;
-  float acc = bias[0];
-#pragma unroll 1
-  for (int tap = 0; tap < 7; ++tap) {
-    const int ti = t - 3 + tap;
-    if (ti < 0 || ti >= Tv) continue;
-    const float* xr = sx + (tid + tap) * OUT_ROW;
-    const float* wr = sw + tap * OUT_C;
-#pragma unroll
-    for (int c4 = 0; c4 < OUT_C / 4; ++c4) {
-      const float4 xv = *reinterpret_cast<const float4*>(xr + c4 * 4), wv = *reinterpret_cast<const float4*>(wr + c4 * 4);
-      acc = fmaf(xv.x, wv.x, acc); acc = fmaf(xv.y, wv.y, acc); acc = fmaf(xv.z, wv.z, acc); acc = fmaf(xv.w, wv.w, acc);
-    }
-  }
-  out[(size_t)b * out_ld + (t - skip)] = tanhf(acc);
-}
-
 // samples [hop * emit, wave_ld) of every row are zero (emit = out[2r], written by the absorb kernel of the same pass)
 __global__ void stream_zero_tail_kernel(float* __restrict__ wave, long long wave_ld, const int* __restrict__ out, int hop) {
   const int r = blockIdx.y;
@@ -1769,12 +1676,12 @@ static int dac_decode_window(ptts_dac* d, const int64_t* codes_dev, long long ld
     d->table_ready = true;
   }
   const bool bf = c.compute_dtype == PTTS_BF16;
-  if (sp)  // streaming pass: row b's window comes out of its slot's kept codes; lens == sp->lens
-    hipLaunchKernelGGL(rvq_gather_stream_kernel, dim3(T, B), dim3(256), 0, st, *sp, (const float*)d->table, (void*)d->bufZ, c.num_codebooks, T,
-                       c.codebook_size, c.latent_dim, bf ? 1 : 0);
-  else
-    hipLaunchKernelGGL(rvq_gather_kernel, dim3(T, B), dim3(256), 0, st, (const long long*)codes_dev, d->table, (void*)d->bufZ, c.num_codebooks, T,
-                       c.codebook_size, c.latent_dim, bf ? 1 : 0, ld, t0, lens);
+  auto gather = [&](auto stream_pass, auto src) {  // streaming pass: row b's window comes out of its slot's kept codes; lens == sp->lens
+    hipLaunchKernelGGL((rvq_gather_kernel<decltype(stream_pass)::value>), dim3(T, B), dim3(256), 0, st, src, (const float*)d->table, (void*)d->bufZ,
+                       c.num_codebooks, T, c.codebook_size, c.latent_dim, bf ? 1 : 0, ld, t0, lens);
+  };
+  if (sp) gather(std::true_type{}, *sp);
+  else gather(std::false_type{}, (const long long*)codes_dev);
   float *cur = d->bufA0, *other = d->bufA1;
   int Tcur = T, mul = 1;  // mul: rows per latent frame at the current layer (ragged decode: utterance b has lens[b] * mul valid rows)
   size_t li = 0;
@@ -1826,24 +1733,19 @@ static int dac_decode_window(ptts_dac* d, const int64_t* codes_dev, long long ld
       if (stop_here(d->bufY, c1.Cout, last)) return PTTS_OK;
     }
   }
-  const int t_end = emit < 0 ? Tcur : std::min(Tcur, skip + emit);
-  if (sp) {  // per-row emit range
+  auto conv_out = [&](auto rows, auto skip_of, auto t_end_of) {  // LDS-tiled at the 44.1 kHz width, otherwise the per-thread kernel
+    constexpr bool ROWS = decltype(rows)::value;
     if (d->out_C == OUT_C && B <= 65535) {
-      hipLaunchKernelGGL(conv_out_tanh_lds_stream_kernel, dim3((unsigned)((Tcur + OUT_TILE - 1) / OUT_TILE), (unsigned)B), dim3(OUT_TILE), 0, st,
-                         (const float*)cur, (const float*)d->out_w, (const float*)d->out_b, wave_dev, Tcur, sp->skip, out_ld, sp->tend, lens, mul);
+      hipLaunchKernelGGL((conv_out_tanh_lds_kernel<ROWS>), dim3((unsigned)((Tcur + OUT_TILE - 1) / OUT_TILE), (unsigned)B), dim3(OUT_TILE), 0, st,
+                         (const float*)cur, (const float*)d->out_w, (const float*)d->out_b, wave_dev, Tcur, skip_of, out_ld, t_end_of, lens, mul);
     } else {
       const size_t n = (size_t)B * ((Tcur + OUT_OS - 1) / OUT_OS);
-      hipLaunchKernelGGL(conv_out_tanh_stream_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)7 * d->out_C * 4, st, (const float*)cur,
-                         (const float*)d->out_w, (const float*)d->out_b, wave_dev, B, Tcur, d->out_C, 7, sp->skip, out_ld, sp->tend, lens, mul);
+      hipLaunchKernelGGL((conv_out_tanh_kernel<ROWS>), dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)7 * d->out_C * 4, st, (const float*)cur,
+                         (const float*)d->out_w, (const float*)d->out_b, wave_dev, B, Tcur, d->out_C, 7, skip_of, out_ld, t_end_of, lens, mul);
     }
-  } else if (d->out_C == OUT_C && B <= 65535) {  // otherwise the per-thread kernel
-    hipLaunchKernelGGL(conv_out_tanh_lds_kernel, dim3((unsigned)((Tcur + OUT_TILE - 1) / OUT_TILE), (unsigned)B), dim3(OUT_TILE), 0, st, (const float*)cur,
-                       d->out_w, d->out_b, wave_dev, Tcur, skip, out_ld, t_end, lens, mul);
-  } else {
-    const size_t n = (size_t)B * ((Tcur + OUT_OS - 1) / OUT_OS);
-    hipLaunchKernelGGL(conv_out_tanh_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)7 * d->out_C * 4, st, cur, d->out_w, d->out_b,
-                       wave_dev, B, Tcur, d->out_C, 7, skip, out_ld, t_end, lens, mul);
-  }
+  };
+  if (sp) conv_out(std::true_type{}, sp->skip, sp->tend);  // per-row emit range
+  else conv_out(std::false_type{}, skip, emit < 0 ? Tcur : std::min(Tcur, skip + emit));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "dac launch failed: %s", hipGetErrorString(e));
   return PTTS_OK;

@@ -4,6 +4,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <string.h>
 
@@ -244,11 +245,10 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     ea.ids = e->ids; ea.ids_ld = e->ids_ld; ea.cur_len = e->cur_len; ea.dims = e->dims; ea.h = e->h;
     ea.H = H; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.bos = c.bos_token_id; ea.pad = c.pad_token_id;
     ea.prefill = prefill ? 1 : 0;
-    if (e->session && !prefill) {  // every slot under its own request's delay pattern
-      EmbedSessionArgs es = {ea, e->row_maxlen};
-      hipLaunchKernelGGL((embed_session_kernel<WT>), dim3(1, B), dim3(256), 0, st, es);
-    } else
-    hipLaunchKernelGGL((embed_kernel<WT>), dim3(Q, B), dim3(256), 0, st, ea);
+    if (e->session && !prefill)  // every slot under its own request's delay pattern
+      hipLaunchKernelGGL((embed_kernel<WT, true>), dim3(1, B), dim3(256), 0, st, EmbedSessionArgs{ea, e->row_maxlen});
+    else
+      hipLaunchKernelGGL((embed_kernel<WT, false>), dim3(Q, B), dim3(256), 0, st, ea);
   }
   if (e->use_gemv && !prefill && M <= e->gemv_rows) {
     // batch 1..4: 8 row-per-wave GEMV / attention nodes per layer, every weight matrix spread over all CUs and read once
@@ -597,16 +597,16 @@ int launch_tail(ptts_engine* e, hipStream_t st, bool embed_next, int row = -1) {
   t.B = e->B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
   // one wave per codebook row (greedy arg-max or the sort-free sampler), at least 4 waves for the embedding of the next column
   const int nw = std::min(std::max(e->cfg.num_codebooks, 4), 16);
-  if (e->session) {  // per-slot clocks (tail_session_kernel)
-    TailSessionArgs s = {t, e->row_maxlen, row < 0 ? 0 : row};
-    const dim3 grid(row < 0 ? e->B : 1);
-    if (t.V <= 512) hipLaunchKernelGGL(tail_session_kernel<8>, grid, dim3(nw * 64), 0, st, s);
-    else if (t.V <= 1152) hipLaunchKernelGGL(tail_session_kernel<18>, grid, dim3(nw * 64), 0, st, s);
-    else hipLaunchKernelGGL(tail_session_kernel<32>, grid, dim3(nw * 64), 0, st, s);
-  } else
-  if (t.V <= 512) hipLaunchKernelGGL(tail_kernel<8>, dim3(e->B), dim3(nw * 64), 0, st, t);
-  else if (t.V <= 1152) hipLaunchKernelGGL(tail_kernel<18>, dim3(e->B), dim3(nw * 64), 0, st, t);
-  else hipLaunchKernelGGL(tail_kernel<32>, dim3(e->B), dim3(nw * 64), 0, st, t);
+  auto launch = [&](auto session, const auto& args, dim3 grid) {  // one NV dispatch for both instances
+    constexpr bool S = decltype(session)::value;
+    if (t.V <= 512) hipLaunchKernelGGL((tail_kernel<8, S>), grid, dim3(nw * 64), 0, st, args);
+    else if (t.V <= 1152) hipLaunchKernelGGL((tail_kernel<18, S>), grid, dim3(nw * 64), 0, st, args);
+    else hipLaunchKernelGGL((tail_kernel<32, S>), grid, dim3(nw * 64), 0, st, args);
+  };
+  if (e->session)  // per-slot clocks
+    launch(std::true_type{}, TailSessionArgs{t, e->row_maxlen, row < 0 ? 0 : row}, dim3(row < 0 ? e->B : 1));
+  else
+    launch(std::false_type{}, t, dim3(e->B));
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "tail launch failed: %s", hipGetErrorString(err));
   return PTTS_OK;
@@ -1107,40 +1107,49 @@ extern "C" int ptts_set_audio_prefix(ptts_engine* e, const int64_t* codes_dev, i
 
 static int precapture_graphs(ptts_engine* e, int max_buckets);
 
+// shape checks shared by ptts_prefill and ptts_session_begin (a session speaks of slots and of the widths every request is padded to)
+static int check_call_shape(const ptts_engine* e, int B, int N, int P, bool session) {
+  const ptts_config& c = e->cfg;
+  PTTS_CHECK(B >= 1 && B <= c.max_batch, PTTS_E_CAPACITY, session ? "%d slots exceed engine max_batch %d" : "batch %d exceeds engine max_batch %d", B, c.max_batch);
+  PTTS_CHECK(N >= 1 && N <= c.max_enc, PTTS_E_CAPACITY, session ? "encoder width %d exceeds engine max_enc %d" : "encoder length %d exceeds engine max_enc %d", N, c.max_enc);
+  PTTS_CHECK(P >= 0 && P + 1 <= e->max_prompt, PTTS_E_CAPACITY, session ? "prompt width %d exceeds engine capacity %d" : "prompt length %d exceeds engine capacity %d", P, e->max_prompt - 1);
+  PTTS_CHECK(P + e->gp.max_length <= c.max_ctx, PTTS_E_CAPACITY, "P + max_length = %d exceeds engine max_ctx %d", P + e->gp.max_length, c.max_ctx);
+  PTTS_CHECK(P + e->gp.max_length <= c.max_positions || c.rope, PTTS_E_CAPACITY, "P + max_length = %d exceeds max_position_embeddings %d", P + e->gp.max_length, c.max_positions);
+  return PTTS_OK;
+}
+
+// per-call device params travel as kernel arguments (no host staging buffer to keep alive); e->B / N / P are set by the caller
+static void launch_set_params(ptts_engine* e, int T_prefix, hipStream_t st) {
+  DevDims hd; hd.P = e->P; hd.N = e->N; hd.max_length = e->gp.max_length;
+  hd.T_prefix = T_prefix; hd.prefix = e->prefix; hd.prefix_ld = e->cfg.max_ctx;
+  DevGen hg; hg.max_length = e->gp.max_length; hg.min_new_tokens = e->gp.min_new_tokens; hg.do_sample = e->gp.do_sample;
+  hg.top_k = e->gp.top_k; hg.use_eos_gate = e->gp.use_eos_gate; hg.temperature = e->gp.temperature; hg.top_p = e->gp.top_p;
+  hg.seed = e->gp.seed;
+  hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, st, e->dims, e->gen, hd, hg);
+}
+
 extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
                             const int32_t* prompt_mask_dev, int32_t B, int32_t N, int32_t P, int32_t sample, void* stream) {
   PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
   PTTS_TRY(ptts_weights_ready(e));
   const ptts_config& c = e->cfg;
-  PTTS_CHECK(B >= 1 && B <= c.max_batch, PTTS_E_CAPACITY, "batch %d exceeds engine max_batch %d", B, c.max_batch);
-  PTTS_CHECK(N >= 1 && N <= c.max_enc, PTTS_E_CAPACITY, "encoder length %d exceeds engine max_enc %d", N, c.max_enc);
-  PTTS_CHECK(P >= 0 && P + 1 <= e->max_prompt, PTTS_E_CAPACITY, "prompt length %d exceeds engine capacity %d", P, e->max_prompt - 1);
+  PTTS_TRY(check_call_shape(e, B, N, P, false));
   PTTS_CHECK(P == 0 || prompt_dev, PTTS_E_INVALID, "prompt_dev is null but P > 0");
   PTTS_CHECK(e->pending_T + 2 <= e->gp.max_length, PTTS_E_INVALID, "voice prompt of %d frames leaves no room below max_length %d", e->pending_T, e->gp.max_length);
-  PTTS_CHECK(P + e->gp.max_length <= c.max_ctx, PTTS_E_CAPACITY, "P + max_length = %d exceeds engine max_ctx %d", P + e->gp.max_length, c.max_ctx);
-  PTTS_CHECK(P + e->gp.max_length <= c.max_positions || c.rope, PTTS_E_CAPACITY, "P + max_length = %d exceeds max_position_embeddings %d", P + e->gp.max_length, c.max_positions);
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
   const int H = c.hidden_size, K = c.num_codebooks;
   e->B = B; e->N = N; e->P = P;
   e->session = false;  // a static batch ends a continuous session
   if (sample) PTTS_HIP(hipEventRecord(e->ev_pre0, st));
-  // per-call device params travel as kernel arguments (no host staging buffer to keep alive)
-  {
-    DevDims hd; hd.P = P; hd.N = N; hd.max_length = e->gp.max_length;
-    hd.T_prefix = e->pending_T; hd.prefix = e->prefix; hd.prefix_ld = c.max_ctx;
-    DevGen hg; hg.max_length = e->gp.max_length; hg.min_new_tokens = e->gp.min_new_tokens; hg.do_sample = e->gp.do_sample;
-    hg.top_k = e->gp.top_k; hg.use_eos_gate = e->gp.use_eos_gate; hg.temperature = e->gp.temperature; hg.top_p = e->gp.top_p;
-    hg.seed = e->gp.seed;
-    hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, st, e->dims, e->gen, hd, hg);
-  }
+  launch_set_params(e, e->pending_T, st);
   // masks (all-ones when absent so the captured graph never changes shape)
   if (enc_mask_dev) PTTS_HIP(hipMemcpy2DAsync(e->enc_mask, (size_t)c.max_enc * 4, enc_mask_dev, (size_t)N * 4, (size_t)N * 4, B, hipMemcpyDeviceToDevice, st));
   else hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, e->enc_mask, 1, (size_t)B * c.max_enc);
   if (prompt_mask_dev && P > 0) PTTS_HIP(hipMemcpy2DAsync(e->prompt_mask, (size_t)e->max_prompt * 4, prompt_mask_dev, (size_t)P * 4, (size_t)P * 4, B, hipMemcpyDeviceToDevice, st));
   else hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, e->prompt_mask, 1, (size_t)B * e->max_prompt);
-  hipLaunchKernelGGL(reset_state_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished,
-                     e->has_eos, e->first_unf, B, K, c.bos_token_id);
+  hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished,
+                     e->has_eos, e->first_unf, (int*)nullptr, 0, B, K, c.bos_token_id, 1, 0);  // every row live; no per-row end
   // stage inputs: encoder states -> qc (consumed by the cross K/V projection), prompt embeddings -> ffn
   PTTS_HIP(hipMemcpyAsync(e->qc, enc_dev, (size_t)B * N * H * 4, hipMemcpyDeviceToDevice, st));
   if (P > 0) PTTS_HIP(hipMemcpyAsync(e->ffn, prompt_dev, (size_t)B * P * H * 4, hipMemcpyDeviceToDevice, st));
@@ -1270,11 +1279,7 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
   const ptts_config& c = e->cfg;
   PTTS_CHECK(!c.kv_fp8, PTTS_E_UNSUPPORTED, "continuous sessions do not run on the e4m3 KV cache (kv_fp8)");
   PTTS_CHECK(e->pending_T == 0, PTTS_E_UNSUPPORTED, "a voice prompt is pending (ptts_set_audio_prefix): sessions take none");
-  PTTS_CHECK(B >= 1 && B <= c.max_batch, PTTS_E_CAPACITY, "%d slots exceed engine max_batch %d", B, c.max_batch);
-  PTTS_CHECK(N >= 1 && N <= c.max_enc, PTTS_E_CAPACITY, "encoder width %d exceeds engine max_enc %d", N, c.max_enc);
-  PTTS_CHECK(P >= 0 && P + 1 <= e->max_prompt, PTTS_E_CAPACITY, "prompt width %d exceeds engine capacity %d", P, e->max_prompt - 1);
-  PTTS_CHECK(P + e->gp.max_length <= c.max_ctx, PTTS_E_CAPACITY, "P + max_length = %d exceeds engine max_ctx %d", P + e->gp.max_length, c.max_ctx);
-  PTTS_CHECK(P + e->gp.max_length <= c.max_positions || c.rope, PTTS_E_CAPACITY, "P + max_length = %d exceeds max_position_embeddings %d", P + e->gp.max_length, c.max_positions);
+  PTTS_TRY(check_call_shape(e, B, N, P, true));
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
   const int H = c.hidden_size, K = c.num_codebooks;
@@ -1294,13 +1299,7 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
   e->xfold_valid = false;  // the static cross-attention fold belongs to one utterance: off in a session
   e->session_max_length = e->gp.max_length;
   e->slot_busy.assign(B, 0); e->slot_ub.assign(B, P + 1); e->slot_maxlen.assign(B, e->gp.max_length);
-  {
-    DevDims hd; hd.P = P; hd.N = N; hd.max_length = e->gp.max_length; hd.T_prefix = 0; hd.prefix = e->prefix; hd.prefix_ld = c.max_ctx;
-    DevGen hg; hg.max_length = e->gp.max_length; hg.min_new_tokens = e->gp.min_new_tokens; hg.do_sample = e->gp.do_sample;
-    hg.top_k = e->gp.top_k; hg.use_eos_gate = e->gp.use_eos_gate; hg.temperature = e->gp.temperature; hg.top_p = e->gp.top_p;
-    hg.seed = e->gp.seed;
-    hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, st, e->dims, e->gen, hd, hg);
-  }
+  launch_set_params(e, 0, st);
   // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);

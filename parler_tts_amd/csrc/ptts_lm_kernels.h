@@ -2526,24 +2526,42 @@ struct EmbedArgs {
   int prefill;             // 1: grid (P+1, B) rows; 0: grid (1, B), column cur_len-1 at position P + cur_len - 1
 };
 
-template <typename WT>
-__global__ void embed_kernel(EmbedArgs a) {
+// manual path inside a session (ptts_step_forward): embedding of every slot's last column under the slot's own delay pattern
+struct EmbedSessionArgs : EmbedArgs {
+  const int* row_maxlen;
+};
+template <bool SESSION> struct EmbedK { using T = EmbedArgs; };
+template <> struct EmbedK<true> { using T = EmbedSessionArgs; };
+
+// SESSION: decode only (grid (1, B)), max_length from the slot's request and no voice prompt
+template <typename WT, bool SESSION>
+__global__ void embed_kernel(typename EmbedK<SESSION>::T p) {
+  const EmbedArgs& a = p;
   const int b = blockIdx.y;
   const int P = a.dims->P;
-  const int qi = blockIdx.x;
-  const int Q = a.prefill ? (int)gridDim.x : 1;        // prefill: P prompt positions + the given decoder columns (BOS [+ voice-prompt prefix])
-  const int j = a.prefill ? max(qi - P, 0) : a.cur_len[b] - 1;  // token column
-  const int pos = a.prefill ? qi : P + j;              // absolute position (padded prompt ids still count, :1470)
+  const int prefill = SESSION ? 0 : a.prefill;
+  const int qi = SESSION ? 0 : blockIdx.x;
+  const int Q = prefill ? (int)gridDim.x : 1;        // prefill: P prompt positions + the given decoder columns (BOS [+ voice-prompt prefix])
+  const int j = prefill ? max(qi - P, 0) : a.cur_len[b] - 1;  // token column
+  const int pos = prefill ? qi : P + j;              // absolute position (padded prompt ids still count, :1470)
   float* out = a.h + ((size_t)b * Q + qi) * a.H;
   const WT* tab = reinterpret_cast<const WT*>(a.tables);
-  if (a.prefill && qi < P) {
+  if (prefill && qi < P) {
     const float* pr = a.prompt + ((size_t)b * P + qi) * a.H;
     for (int d = threadIdx.x; d < a.H; d += blockDim.x) out[d] = pr[d] + (a.pos_table ? a.pos_table[(size_t)pos * a.H + d] : 0.f);
     return;
   }
   __shared__ int s_tok[32];
-  if (threadIdx.x < a.K)
-    s_tok[threadIdx.x] = (int)delayed_token(a.ids, a.ids_ld, b * a.K + threadIdx.x, threadIdx.x, j, a.K, *a.dims, a.bos, a.pad);
+  if (threadIdx.x < a.K) {
+    if constexpr (SESSION) {
+      DevDims dd = *a.dims;
+      dd.max_length = p.row_maxlen[b];
+      dd.T_prefix = 0;
+      s_tok[threadIdx.x] = (int)delayed_token(a.ids, a.ids_ld, b * a.K + threadIdx.x, threadIdx.x, j, a.K, dd, a.bos, a.pad);
+    } else {
+      s_tok[threadIdx.x] = (int)delayed_token(a.ids, a.ids_ld, b * a.K + threadIdx.x, threadIdx.x, j, a.K, *a.dims, a.bos, a.pad);
+    }
+  }
   __syncthreads();
   for (int d = threadIdx.x; d < a.H; d += blockDim.x) {
     float acc = 0.f;
@@ -2739,24 +2757,48 @@ __device__ __forceinline__ void tail_embed_next(const TailArgs& a, const DevDims
   }
 }
 
+// Continuous session (ptts_session_begin): every utterance slot has its own clock and its own end. A slot is LIVE iff one of its
+// K flags is positive; an idle or finished slot does nothing at all here (no ids write, no cur_len bump, no embedding), and the
+// stop test and the delay pattern use the slot's own max_length. The sampling hash stays (seed, t, row).
+struct TailSessionArgs : TailArgs {
+  const int* row_maxlen;  // [B] max_length of the request in each slot
+  int row0;               // first slot of this launch: grid (B) with 0 for a decode step, grid (1) with the slot for an admission
+};
+template <bool SESSION> struct TailK { using T = TailArgs; };
+template <> struct TailK<true> { using T = TailSessionArgs; };
+
 // NV = logits per lane: 8 (vocab <= 512), 18 (<= 1152: Mini / Large v1, vocab 1088) or 32 (<= 2048)
-template <int NV>
-__global__ void __launch_bounds__(1024) tail_kernel(TailArgs a) {
+// SESSION = the per-slot instance (TailSessionArgs); the body is written once, here, not in a shared device function: the static
+// instances are on the measured path and keep their instructions only this way (profiles/twin_kernels_isa_compare.txt)
+template <int NV, bool SESSION>
+__global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p) {
+  const TailArgs& a = p;
   __shared__ int s_tok[32];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int b = blockIdx.x;
+  if constexpr (SESSION) b += p.row0;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // ---- t = 0: every load that does not depend on another load goes in flight together (the step's critical path ends
   // here: lengths / flags / parameters / this wave's logits row are ONE round trip, the embedding rows a second one)
   const DevGen g = *a.gen;
   const int t = a.cur_len[b];  // column the new token is written to; t-1 new tokens generated so far
-  // "has the reference loop already exited?" = every row finished BEFORE this step. Rows that finish during this very launch
+  // static: "has the reference loop already exited?" = every row finished BEFORE this step. Rows that finish during this very launch
   // (other workgroups, stamp -(t + 1)) still count as active here, so the answer does not depend on workgroup timing.
+  // session: is this slot live (read by all before any wave of this workgroup writes a flag)
   int any_local = 0;
-  for (int i = tid; i < a.B * a.K; i += blockDim.x) {
-    const int v = a.unfinished[i];
-    any_local |= (v > 0) | (v <= -(t + 1));
+  if constexpr (SESSION) {
+    any_local = tid < a.K ? (a.unfinished[b * a.K + tid] > 0) : 0;
+  } else {
+    for (int i = tid; i < a.B * a.K; i += blockDim.x) {
+      const int v = a.unfinished[i];
+      any_local |= (v > 0) | (v <= -(t + 1));
+    }
   }
   const int fu0 = a.first_unf[b];
-  const DevDims dd = *a.dims;  // the embedding of the next column needs P / max_length / the voice-prompt prefix: fetched now, not after the argmax
+  DevDims dd = *a.dims;  // the embedding of the next column needs P / max_length / the voice-prompt prefix: fetched now, not after the argmax
+  if constexpr (SESSION) {
+    dd.max_length = p.row_maxlen[b];  // the pad triangle (and whether there is a pattern at all) follows the request's own length
+    dd.T_prefix = 0;                  // no voice prompt inside a session
+  }
   const int t_prefix = dd.T_prefix;
   const int he = lane < a.K ? a.has_eos[b * a.K + lane] : 0;  // every wave: the K EOS flags of this utterance
   float lg[NV];
@@ -2767,7 +2809,8 @@ __global__ void __launch_bounds__(1024) tail_kernel(TailArgs a) {
     for (int i = 0; i < NV; ++i) lg[i] = (lane + 64 * i < a.V) ? sc0[lane + 64 * i] : -INFINITY;
   }
   const int unf0 = k0 < a.K ? (a.unfinished[b * a.K + k0] > 0) : 0;
-  if (!__syncthreads_or(any_local)) return;  // every row of every utterance finished: the reference loop has exited (no-op step)
+  // static: every row of every utterance finished, the reference loop has exited (no-op step); session: idle or finished slot
+  if (!__syncthreads_or(any_local)) return;
 
   int fu = fu0;
   if (__shfl(he, fu0) > 0 && fu0 < a.K - 1) fu += 1;  // logits_processors.py:48 (advance <= 1 per step)
@@ -2809,120 +2852,13 @@ __global__ void __launch_bounds__(1024) tail_kernel(TailArgs a) {
       a.ids[(size_t)row * a.ids_ld + t] = nxt;
       s_tok[k] = nxt;
       if (nxt == a.eos) a.has_eos[row] = 1;
-      if (unf && ((nxt == a.eos) || (t + 1 >= g.max_length))) a.unfinished[row] = -(t + 1);  // EosTokenCriteria | MaxLengthCriteria
+      // EosTokenCriteria | MaxLengthCriteria (the slot's own length in a session)
+      if (unf && ((nxt == a.eos) || (t + 1 >= (SESSION ? dd.max_length : g.max_length)))) a.unfinished[row] = -(t + 1);
     }
   }
   __syncthreads();
   if (tid == 0) a.cur_len[b] = t + 1;
   tail_embed_next(a, dd, b, t, s_tok, tid);
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Continuous session (ptts_session_begin): every utterance slot has its own clock and its own end. A slot is LIVE iff one of its
-// K flags is positive; an idle or finished slot does nothing at all here (no ids write, no cur_len bump, no embedding), and the
-// stop test and the delay pattern use the slot's own max_length. The sampling hash stays (seed, t, row).
-// ------------------------------------------------------------------------------------------------------
-struct TailSessionArgs {
-  TailArgs t;
-  const int* row_maxlen;  // [B] max_length of the request in each slot
-  int row0;               // first slot of this launch: grid (B) with 0 for a decode step, grid (1) with the slot for an admission
-};
-
-template <int NV>
-__global__ void __launch_bounds__(1024) tail_session_kernel(TailSessionArgs s) {
-  const TailArgs& a = s.t;
-  __shared__ int s_tok[32];
-  const int b = blockIdx.x + s.row0, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const DevGen g = *a.gen;
-  const int t = a.cur_len[b];
-  const int live_local = tid < a.K ? (a.unfinished[b * a.K + tid] > 0) : 0;  // read by all before any wave of this workgroup writes a flag
-  const int fu0 = a.first_unf[b];
-  DevDims dd = *a.dims;
-  const int max_length = s.row_maxlen[b];
-  dd.max_length = max_length;  // the pad triangle (and whether there is a pattern at all) follows the request's own length
-  dd.T_prefix = 0;             // no voice prompt inside a session
-  const int he = lane < a.K ? a.has_eos[b * a.K + lane] : 0;
-  float lg[NV];
-  const int k0 = w;
-  if (k0 < a.K) {
-    const float* sc0 = a.logits + (size_t)(b * a.K + k0) * a.V;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) lg[i] = (lane + 64 * i < a.V) ? sc0[lane + 64 * i] : -INFINITY;
-  }
-  const int unf0 = k0 < a.K ? (a.unfinished[b * a.K + k0] > 0) : 0;
-  if (!__syncthreads_or(live_local)) return;  // idle or finished slot
-
-  int fu = fu0;
-  if (__shfl(he, fu0) > 0 && fu0 < a.K - 1) fu += 1;
-  if (tid == 0) a.first_unf[b] = fu;
-  const bool block_eos_all = (t - 1) < g.min_new_tokens;
-
-  for (int k = w; k < a.K; k += (int)(blockDim.x >> 6)) {
-    const int row = b * a.K + k;
-    if (k != k0) {
-      const float* sc = a.logits + (size_t)row * a.V;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) lg[i] = (lane + 64 * i < a.V) ? sc[lane + 64 * i] : -INFINITY;
-    }
-    const bool eos_blocked = block_eos_all || (g.use_eos_gate && k > fu);
-    int widx;
-    if (!g.do_sample) {
-      float best = -INFINITY;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int v = lane + 64 * i;
-        float x = lg[i];
-        if (eos_blocked && v == a.eos) x = -INFINITY;
-        if (v < a.V && (x > best || (x == best && v < bi))) { best = x; bi = v; }
-      }
-      const float wbest = wave_max(best);
-      const float cand = (best == wbest) ? (float)bi : 3.0e9f;
-      widx = (int)(-wave_max(-cand));
-    } else {
-      const unsigned long long hsh = splitmix64(g.seed ^ splitmix64(((unsigned long long)t << 32) ^ (unsigned long long)row));
-      const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);
-      widx = wave_sample_row<NV>(lg, a.V, lane, g, eos_blocked, a.eos, u);
-    }
-    if (lane == 0) {
-      const int unf = k == k0 ? unf0 : (a.unfinished[row] > 0);
-      const int nxt = unf ? widx : a.pad;
-      a.ids[(size_t)row * a.ids_ld + t] = nxt;
-      s_tok[k] = nxt;
-      if (nxt == a.eos) a.has_eos[row] = 1;
-      if (unf && ((nxt == a.eos) || (t + 1 >= max_length))) a.unfinished[row] = -(t + 1);
-    }
-  }
-  __syncthreads();
-  if (tid == 0) a.cur_len[b] = t + 1;
-  tail_embed_next(a, dd, b, t, s_tok, tid);
-}
-
-// manual path inside a session (ptts_step_forward): embedding of every slot's last column under the slot's own delay pattern
-struct EmbedSessionArgs {
-  EmbedArgs e;
-  const int* row_maxlen;
-};
-template <typename WT>
-__global__ void embed_session_kernel(EmbedSessionArgs s) {
-  const EmbedArgs& a = s.e;
-  const int b = blockIdx.y;
-  DevDims dd = *a.dims;
-  dd.max_length = s.row_maxlen[b];
-  dd.T_prefix = 0;
-  const int j = a.cur_len[b] - 1;
-  const int pos = dd.P + j;
-  float* out = a.h + (size_t)b * a.H;
-  const WT* tab = reinterpret_cast<const WT*>(a.tables);
-  __shared__ int s_tok[32];
-  if (threadIdx.x < a.K) s_tok[threadIdx.x] = (int)delayed_token(a.ids, a.ids_ld, b * a.K + threadIdx.x, threadIdx.x, j, a.K, dd, a.bos, a.pad);
-  __syncthreads();
-  for (int d = threadIdx.x; d < a.H; d += blockDim.x) {
-    float acc = 0.f;
-    for (int k = 0; k < a.K; ++k) acc += Elem<WT>::ld(tab + ((size_t)k * a.V1 + s_tok[k]) * a.H + d);
-    if (a.pos_table) acc += a.pos_table[(size_t)pos * a.H + d];
-    out[d] = acc;
-  }
 }
 
 // ptts_push_tokens inside a session: one workgroup per slot; only live slots take their K tokens and move their clock, and a slot
@@ -2947,6 +2883,7 @@ static __global__ void push_tokens_session_kernel(const long long* tokens, const
 // session begin (row < 0: every slot) / ptts_retire_row: the slot is idle - clock at 1 (the cheapest context the attention kernels can be
 // given), BOS in column 0 so that the step's embedding of an idle slot reads a valid table row, no flag positive
 // ptts_admit_row (live = 1): same reset with the K flags raised and the request's own max_length
+// ptts_prefill: every row live, row_maxlen null (the static path stops on DevGen::max_length)
 static __global__ void session_reset_rows_kernel(long long* ids, int ids_ld, int* cur_len, int* unfinished, int* has_eos, int* first_unf,
                                                  int* row_maxlen, int row0, int nrows, int K, int bos, int live, int max_length) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2959,7 +2896,7 @@ static __global__ void session_reset_rows_kernel(long long* ids, int ids_ld, int
   if (i < nrows) {
     cur_len[row0 + i] = 1;
     first_unf[row0 + i] = 0;
-    row_maxlen[row0 + i] = max_length;
+    if (row_maxlen) row_maxlen[row0 + i] = max_length;
   }
 }
 
@@ -3000,20 +2937,6 @@ static __global__ void set_len_kernel(int* cur_len, int B, int v) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) cur_len[b] = v;
 }
-static __global__ void reset_state_kernel(long long* ids, int ids_ld, int* cur_len, int* unfinished, int* has_eos, int* first_unf,
-                                   int B, int K, int bos) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B * K) {
-    ids[(size_t)i * ids_ld] = bos;
-    unfinished[i] = 1;
-    has_eos[i] = 0;
-  }
-  if (i < B) {
-    cur_len[i] = 1;
-    first_unf[i] = 0;
-  }
-}
-
 static __global__ void set_params_kernel(DevDims* dd, DevGen* dg, DevDims d, DevGen g) {
   *dd = d;
   *dg = g;
