@@ -13,6 +13,7 @@
 #include "ptts_gemv.h"
 #include "ptts_strip_w8.h"
 #include "ptts_gemm_launch.h"
+#include "ptts_tail_launch.h"
 
 thread_local std::string g_ptts_err;
 int ptts_fail(int code, const char* fmt, ...) {
@@ -595,18 +596,9 @@ int launch_tail(ptts_engine* e, hipStream_t st, bool embed_next, int row = -1) {
   t.logits = e->logits; t.ids = e->ids; t.ids_ld = e->ids_ld; t.cur_len = e->cur_len; t.unfinished = e->unfinished;
   t.has_eos = e->has_eos; t.first_unf = e->first_unf; t.gen = e->gen; t.sort_buf = e->sort_buf;
   t.B = e->B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
-  // one wave per codebook row (greedy arg-max or the sort-free sampler), at least 4 waves for the embedding of the next column
-  const int nw = std::min(std::max(e->cfg.num_codebooks, 4), 16);
-  auto launch = [&](auto session, const auto& args, dim3 grid) {  // one NV dispatch for both instances
-    constexpr bool S = decltype(session)::value;
-    if (t.V <= 512) hipLaunchKernelGGL((tail_kernel<8, S>), grid, dim3(nw * 64), 0, st, args);
-    else if (t.V <= 1152) hipLaunchKernelGGL((tail_kernel<18, S>), grid, dim3(nw * 64), 0, st, args);
-    else hipLaunchKernelGGL((tail_kernel<32, S>), grid, dim3(nw * 64), 0, st, args);
-  };
-  if (e->session)  // per-slot clocks
-    launch(std::true_type{}, TailSessionArgs{t, e->row_maxlen, row < 0 ? 0 : row}, dim3(row < 0 ? e->B : 1));
-  else
-    launch(std::false_type{}, t, dim3(e->B));
+  // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
+  if (e->session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? e->B : 1), st);
+  else tail_launch(t, nullptr, 0, dim3(e->B), st);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "tail launch failed: %s", hipGetErrorString(err));
   return PTTS_OK;

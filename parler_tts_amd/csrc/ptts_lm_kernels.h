@@ -2843,7 +2843,7 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
       widx = (int)(-wave_max(-cand));
     } else {
       const unsigned long long hsh = splitmix64(g.seed ^ splitmix64(((unsigned long long)t << 32) ^ (unsigned long long)row));
-      const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);  // (0,1)
+      const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);  // [2^-25, 1], DESIGN.md 4.6
       widx = wave_sample_row<NV>(lg, a.V, lane, g, eos_blocked, a.eos, u);
     }
     if (lane == 0) {

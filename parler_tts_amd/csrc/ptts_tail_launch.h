@@ -1,0 +1,25 @@
+// Host-side launch of the sampler tail (tail_kernel<NV, SESSION>, ptts_lm_kernels.h): the one place that picks the instance.
+// Shared by the engine (launch_tail, ptts_lm.hip) and the test harness (tests/native/tail_harness.hip), so that a test of the
+// kernel runs the instance, the wave count and the argument struct the product would run for the same (V, K).
+#pragma once
+#include <algorithm>
+#include <type_traits>
+
+#include "ptts_lm_kernels.h"
+
+// row_maxlen null: the static instances (every utterance on the shared clock, stop on DevGen::max_length; row0 unused).
+// row_maxlen set: the session instances, slot b = row0 + blockIdx.x under its own max_length - grid (B) with row0 0 for a
+// decode step, grid (1) with row0 = the slot for an admission.
+// NV = logits per lane: 8 up to vocab 512, 18 up to 1152, 32 up to PTTS_SORT_N. One wave per codebook row (greedy arg-max or the
+// sort-free sampler), at least 4 waves for the embedding of the next column, at most 16 (more codebooks loop).
+static inline void tail_launch(const TailArgs& t, const int* row_maxlen, int row0, dim3 grid, hipStream_t st) {
+  const int nw = std::min(std::max(t.K, 4), 16);
+  auto launch = [&](auto session, const auto& args) {  // one NV dispatch for both instances
+    constexpr bool S = decltype(session)::value;
+    if (t.V <= 512) hipLaunchKernelGGL((tail_kernel<8, S>), grid, dim3(nw * 64), 0, st, args);
+    else if (t.V <= 1152) hipLaunchKernelGGL((tail_kernel<18, S>), grid, dim3(nw * 64), 0, st, args);
+    else hipLaunchKernelGGL((tail_kernel<32, S>), grid, dim3(nw * 64), 0, st, args);
+  };
+  if (row_maxlen) launch(std::true_type{}, TailSessionArgs{t, row_maxlen, row0});  // per-slot clocks
+  else launch(std::false_type{}, t);
+}
