@@ -166,7 +166,8 @@ int ptts_ids(ptts_engine* e, int64_t** ids_dev, int32_t* row_stride);
  * (ptts_admit_row) -> finished (EOS on every codebook or its max_length; the device stops touching it) -> idle (ptts_retire_row).
  *
  * ptts_session_begin: opens a session of B <= max_batch slots, all idle; every request is padded to N encoder and P prompt positions
- *   (masked). Generation parameters are those of the last ptts_set_gen_params, fixed for the session. The static cross-attention fold of
+ *   (masked). Generation parameters are those of the last ptts_set_gen_params for every request that brings none of its own
+ *   (ptts_admit_row_gen); the session's own stay fixed while it lasts, and no slot has a record of its own when it opens. The static cross-attention fold of
  *   single-utterance engines is off. Engines with the e4m3 KV cache (kv_fp8) are REFUSED (PTTS_E_UNSUPPORTED), and so is a pending voice
  *   prompt (ptts_set_audio_prefix). ptts_prefill ends the session.
  * ptts_admit_row: `row` must be idle. Computes the slot's cross K/V, runs the request's P + 1 positions through the stack into the slot's
@@ -175,8 +176,19 @@ int ptts_ids(ptts_engine* e, int64_t** ids_dev, int32_t* row_stride);
  *     enc_dev [N, H] float32, enc_mask_dev [N] int32 or NULL, prompt_dev [P, H] float32 (NULL iff P == 0), prompt_mask_dev [P] int32 or NULL
  *     max_length: the request's own 1 + max_new_tokens (0 = the session's; otherwise 2 <= max_length <= the session's). The delay pattern
  *     (its pad triangle, and no pattern at all below 2K - 1 columns: build_delay_pattern_mask :205-276) and the stop test use this value.
+ * ptts_admit_row_gen: ptts_admit_row plus the request's own sampler parameters and seed - what the reference takes as a GenerationConfig per
+ *   generate() call (:3395-3552) and applies in `_sample` (MinNewTokens, temperature / top-k / top-p warpers, greedy or multinomial), here per
+ *   SLOT of one session: a greedy request decodes beside a sampled one in the same step. `gp` == NULL is exactly ptts_admit_row. Otherwise the slot
+ *   reads min_new_tokens, do_sample, temperature, top_k, top_p and use_eos_gate from its own record until it is retired, and its draws come from
+ *   (gp->seed, the slot's own column, the codebook index inside the slot): neither the slot index nor the session's clock or seed enter, so a
+ *   request with a given seed yields the same tokens from the same logits wherever and whenever it runs. Slots admitted without a record keep
+ *   (session seed, column, slot * K + codebook). gp->max_length must be 0 or equal to the `max_length` argument, which rules the slot's end.
+ *   PTTS_E_INVALID (the checks of ptts_set_gen_params): temperature not finite or <= 0, top_p outside (0, 1], top_k < 0, min_new_tokens < 0.
+ *   With `sample` == 0 the record is stored and only a later device tail (ptts_decode_steps) would read it. No step graph is captured again:
+ *   the records live in one device array the graphs already point to.
  * ptts_row_state (SYNCHRONISES): per slot, columns written so far (incl. BOS; 1 when idle) and whether it is still generating.
- * ptts_retire_row: makes a slot idle, whatever its state (cancel, or after its ids were read).
+ * ptts_retire_row: makes a slot idle, whatever its state (cancel, or after its ids were read), and drops its sampler record: a later
+ *   ptts_admit_row into the slot samples on the session's parameters.
  * Inside a session ptts_decode_steps / ptts_step_forward advance every live slot by one column (idle and finished slots are left alone:
  * no ids write, no clock), ptts_push_tokens appends to live slots only, ptts_ids / ptts_logits are indexed by slot, and ptts_state reports slot 0's
  * columns and whether NO slot is live. The attention fetch
@@ -184,6 +196,8 @@ int ptts_ids(ptts_engine* e, int64_t** ids_dev, int32_t* row_stride);
 int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream);
 int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
                    const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream);
+int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                       const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, const ptts_gen_params* gp, void* stream);
 int ptts_row_state(ptts_engine* e, int32_t* cur_len_host, int32_t* live_host, void* stream);
 int ptts_retire_row(ptts_engine* e, int32_t row, void* stream);
 

@@ -81,6 +81,7 @@ SYMBOLS = {
     "ptts_push_tokens": (C.c_int, [_VP, _VP, _VP, _VP]),
     "ptts_session_begin": (C.c_int, [_VP, _I32, _I32, _I32, _VP]),
     "ptts_admit_row": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _VP]),
+    "ptts_admit_row_gen": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _I32, _I32, C.POINTER(PttsGenParams), _VP]),
     "ptts_row_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "ptts_retire_row": (C.c_int, [_VP, _I32, _VP]),
     "ptts_debug_hidden": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_I32)]),

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import collections
 import copy
+import math
 from typing import Deque, Dict, Iterable, Iterator, List, Optional, Tuple
 
 import torch
@@ -29,10 +30,11 @@ _VOICE_ARGUMENTS = ("input_values", "decoder_input_ids")
 
 
 class _Request:
-    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length")
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen")
 
-    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length):
+    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None):
         self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
+        self.gen = gen  # the request's own sampler record (DecoderEngine.admit_row's `gen`), or None: the session's
 
 
 class ContinuousBatcher:
@@ -40,7 +42,8 @@ class ContinuousBatcher:
     ``(ticket, waveform 1-D, length)`` as requests finish, ``run(requests)`` returns ``[(waveform, length), ...]`` in submission order.
 
     ``generation_kwargs`` are ``generate()``'s: ``max_new_tokens`` / ``max_length`` (the session's limit; a request may ask for less),
-    ``min_new_tokens``, ``do_sample``, ``temperature``, ``top_k``, ``top_p``. Everything that needs the host loop, a streamer or a voice
+    ``min_new_tokens``, ``do_sample``, ``temperature``, ``top_k``, ``top_p``: the session's values, which ``submit`` may override per request
+    (with a ``seed`` of its own, see there). Everything that needs the host loop, a streamer or a voice
     prompt raises ``NotImplementedError``. ``poll_steps``: decode steps between two looks at the slots (each look is one host sync);
     a request that ends by its own ``max_new_tokens`` is known in advance and is met exactly.
 
@@ -95,6 +98,9 @@ class ContinuousBatcher:
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
         self.eng.begin_session(self.slots, self.N, self.P)
+        # what a request's own record starts from (submit): the session's values as the caller gave them (top_k is not zeroed for a greedy session)
+        self._gen = dict(min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0), top_k=int(gc.top_k or 0),
+                         top_p=float(gc.top_p if gc.top_p is not None else 1.0))
         self._queue: Deque[_Request] = collections.deque()
         self._slot: List[Optional[_Request]] = [None] * self.slots
         self._cols = [0] * self.slots  # columns a busy slot holds if it has not stopped on EOS: BOS + first token + one per step
@@ -136,14 +142,43 @@ class ContinuousBatcher:
         out_ids[:n], out_mask[:n] = ids.cpu(), mask.cpu()
         return out_ids, out_mask
 
+    def _request_gen(self, do_sample, temperature, top_k, top_p, min_new_tokens, seed) -> Optional[dict]:
+        """The sampler record of a request that sets any of these options (the session's values fill the rest), or None. ``seed`` stays
+        ``None`` here where the caller gave none: submit draws it once nothing can refuse the request any more."""
+        given = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_new_tokens=min_new_tokens)
+        if seed is None and all(v is None for v in given.values()):
+            return None
+        gen = dict(self._gen)
+        gen.update({k: v for k, v in given.items() if v is not None})
+        gen["do_sample"], gen["temperature"], gen["top_p"] = bool(gen["do_sample"]), float(gen["temperature"]), float(gen["top_p"])
+        gen["top_k"], gen["min_new_tokens"] = int(gen["top_k"]), int(gen["min_new_tokens"])
+        if not (math.isfinite(gen["temperature"]) and gen["temperature"] > 0.0):
+            raise ValueError(f"`temperature` must be a finite number > 0, got {gen['temperature']}")
+        if not 0.0 < gen["top_p"] <= 1.0:
+            raise ValueError(f"`top_p` must be in (0, 1], got {gen['top_p']}")
+        if gen["top_k"] < 0:
+            raise ValueError(f"`top_k` must be >= 0, got {gen['top_k']}")
+        if gen["min_new_tokens"] < 0:
+            raise ValueError(f"`min_new_tokens` must be >= 0, got {gen['min_new_tokens']}")
+        gen["use_eos_gate"] = True
+        gen["seed"] = None if seed is None else int(seed) & (2 ** 64 - 1)  # without effect on a greedy request
+        return gen
+
     @torch.no_grad()
-    def submit(self, input_ids, attention_mask=None, prompt_input_ids=None, prompt_attention_mask=None, max_new_tokens: Optional[int] = None) -> int:
-        """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path)."""
+    def submit(self, input_ids, attention_mask=None, prompt_input_ids=None, prompt_attention_mask=None, max_new_tokens: Optional[int] = None,
+               do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
+               min_new_tokens: Optional[int] = None, seed: Optional[int] = None) -> int:
+        """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path).
+        ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_new_tokens``: the request's own sampler settings; an option left ``None``
+        takes the session's value. A request that sets any of them (or ``seed``) draws from its own stream ``(seed, column, codebook)``: with a
+        ``seed`` it gives the same tokens in whichever slot and at whatever time it runs, with ``seed=None`` one is drawn from torch's RNG here
+        (``torch.manual_seed`` governs the run). A request that sets none is admitted on the session's parameters and draw stream."""
         max_length = self.max_length if max_new_tokens is None else int(max_new_tokens) + 1
         if max_length < 2:
             raise ValueError("`max_new_tokens` leaves no room for a generated token")
         if max_length > self.max_length:
             raise ValueError(f"max_new_tokens {max_length - 1} exceeds the session's {self.max_length - 1}")
+        gen = self._request_gen(do_sample, temperature, top_k, top_p, min_new_tokens, seed)
         dev = self.model.device
         ids, mask = self._pad_ids(input_ids, attention_mask, self.N, "description")
         enc = self.model._encode_description(ids[None].to(dev), mask[None].to(dev))[0].float()
@@ -155,9 +190,11 @@ class ContinuousBatcher:
             prompt = self.model.embed_prompts(pids[None].to(dev))[0].float()
         elif prompt_input_ids is not None:
             raise ValueError("the session was opened without prompt positions (max_prompt_tokens = 0)")
+        if gen is not None and gen["seed"] is None:  # follows torch.manual_seed(), as the session's seed does; a refused submit draws nothing
+            gen["seed"] = int(torch.randint(0, 2 ** 62, (1,)).item()) if gen["do_sample"] else 0
         ticket = self._next_ticket
         self._next_ticket += 1
-        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length))
+        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen))
         return ticket
 
     # -- scheduler ----------------------------------------------------------------------------------------------------------------
@@ -165,13 +202,17 @@ class ContinuousBatcher:
         """Requests queued or in a slot (finished ones waiting to be iterated are not counted)."""
         return len(self._queue) + sum(r is not None for r in self._slot)
 
+    def _admit_into(self, s: int, r: _Request):
+        """The one admission of both modes. A request without a record of its own goes through the same call as ever (no `gen` keyword)."""
+        kw = {} if r.gen is None else {"gen": dict(r.gen)}
+        self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True, **kw)
+        self._slot[s], self._cols[s] = r, 2
+
     def _poll(self):
         """Admit FIFO into idle slots, run the live slots up to the next boundary, collect what finished."""
         for s in range(self.slots):
             if self._slot[s] is None and self._queue:
-                r = self._queue.popleft()
-                self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True)
-                self._slot[s], self._cols[s] = r, 2
+                self._admit_into(s, self._queue.popleft())
         busy = [s for s in range(self.slots) if self._slot[s] is not None]
         if not busy:
             return
@@ -195,10 +236,8 @@ class ContinuousBatcher:
     def _admit(self):
         for s in range(self.slots):
             if self._slot[s] is None and self._queue:
-                r = self._queue.popleft()
-                self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True)
+                self._admit_into(s, self._queue.popleft())
                 self.model.audio_encoder.stream_reset(s)
-                self._slot[s], self._cols[s] = r, 2
                 self._absorbed[s] = self._kept[s] = self._emitted[s] = 0
                 self._first_out[s] = True
 

@@ -126,6 +126,7 @@ struct ptts_engine {
   bool session = false;
   int session_max_length = 0;            // max_length of the generation parameters the session was opened with
   int* row_maxlen = nullptr;             // [max_batch] device: max_length of the request in each slot
+  SlotGen* slot_gen = nullptr;           // [max_batch] device: sampler record of the request in each slot (ptts_admit_row_gen); own = 0: the session's
   float* h_adm = nullptr;                // [max_prompt][H] residual rows of a row prefill: the step input h[B][H] of the other slots is live between steps
   KvLayer* kv_layers_rows = nullptr;     // [max_batch][layers] operands of the batched cross K/V projection with each slot's arena rows as base
   std::vector<char> slot_busy;           // host: admitted and not yet retired
@@ -597,7 +598,7 @@ int launch_tail(ptts_engine* e, hipStream_t st, bool embed_next, int row = -1) {
   t.has_eos = e->has_eos; t.first_unf = e->first_unf; t.gen = e->gen; t.sort_buf = e->sort_buf;
   t.B = e->B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
   // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
-  if (e->session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? e->B : 1), st);
+  if (e->session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? e->B : 1), st, e->slot_gen);
   else tail_launch(t, nullptr, 0, dim3(e->B), st);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "tail launch failed: %s", hipGetErrorString(err));
@@ -1072,13 +1073,29 @@ extern "C" int ptts_load_weight_fp8(ptts_engine* e, const char* name_c, const ui
   return PTTS_OK;
 }
 
+// the sampler fields of ptts_set_gen_params (the session's) and of ptts_admit_row_gen (one request's: the record reaches the device as it is,
+// so its temperature is checked whether or not the request samples, and its min_new_tokens too)
+static int check_sampler_params(const ptts_gen_params* gp, bool per_request) {
+  if (per_request) PTTS_CHECK(std::isfinite(gp->temperature) && gp->temperature > 0.f, PTTS_E_INVALID, "temperature must be finite and > 0");
+  else PTTS_CHECK(!gp->do_sample || gp->temperature > 0.f, PTTS_E_INVALID, "temperature must be > 0");
+  PTTS_CHECK(gp->top_p > 0.f && gp->top_p <= 1.f, PTTS_E_INVALID, "top_p must be in (0, 1]");
+  PTTS_CHECK(gp->top_k >= 0, PTTS_E_INVALID, "top_k must be >= 0");
+  if (per_request) PTTS_CHECK(gp->min_new_tokens >= 0, PTTS_E_INVALID, "min_new_tokens must be >= 0");
+  return PTTS_OK;
+}
+
+static DevGen dev_gen_of(const ptts_gen_params& gp, int max_length) {
+  DevGen hg; hg.max_length = max_length; hg.min_new_tokens = gp.min_new_tokens; hg.do_sample = gp.do_sample;
+  hg.top_k = gp.top_k; hg.use_eos_gate = gp.use_eos_gate; hg.temperature = gp.temperature; hg.top_p = gp.top_p;
+  hg.seed = gp.seed;
+  return hg;
+}
+
 extern "C" int ptts_set_gen_params(ptts_engine* e, const ptts_gen_params* gp) {
   PTTS_CHECK(e && gp, PTTS_E_INVALID, "null argument");
   PTTS_CHECK(gp->max_length >= 2, PTTS_E_INVALID, "max_length must be >= 2 (BOS column + 1 token)");
   PTTS_CHECK(gp->max_length <= e->cfg.max_ctx, PTTS_E_CAPACITY, "max_length %d exceeds engine max_ctx %d", gp->max_length, e->cfg.max_ctx);
-  PTTS_CHECK(!gp->do_sample || gp->temperature > 0.f, PTTS_E_INVALID, "temperature must be > 0");
-  PTTS_CHECK(gp->top_p > 0.f && gp->top_p <= 1.f, PTTS_E_INVALID, "top_p must be in (0, 1]");
-  PTTS_CHECK(gp->top_k >= 0, PTTS_E_INVALID, "top_k must be >= 0");
+  PTTS_TRY(check_sampler_params(gp, false));
   e->gp = *gp;
   return PTTS_OK;
 }
@@ -1114,10 +1131,7 @@ static int check_call_shape(const ptts_engine* e, int B, int N, int P, bool sess
 static void launch_set_params(ptts_engine* e, int T_prefix, hipStream_t st) {
   DevDims hd; hd.P = e->P; hd.N = e->N; hd.max_length = e->gp.max_length;
   hd.T_prefix = T_prefix; hd.prefix = e->prefix; hd.prefix_ld = e->cfg.max_ctx;
-  DevGen hg; hg.max_length = e->gp.max_length; hg.min_new_tokens = e->gp.min_new_tokens; hg.do_sample = e->gp.do_sample;
-  hg.top_k = e->gp.top_k; hg.use_eos_gate = e->gp.use_eos_gate; hg.temperature = e->gp.temperature; hg.top_p = e->gp.top_p;
-  hg.seed = e->gp.seed;
-  hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, st, e->dims, e->gen, hd, hg);
+  hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, st, e->dims, e->gen, hd, dev_gen_of(e->gp, e->gp.max_length));
 }
 
 extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
@@ -1277,6 +1291,7 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
   const int H = c.hidden_size, K = c.num_codebooks;
   if (!e->row_maxlen) {  // first session of this engine: the row prefill's own residual rows and per-slot operand tables
     PTTS_TRY(e->alloc(&e->row_maxlen, (size_t)c.max_batch));
+    PTTS_TRY(e->alloc(&e->slot_gen, (size_t)c.max_batch));  // with row_maxlen: the step graphs hold a pointer that never changes
     PTTS_TRY(e->alloc(&e->h_adm, (size_t)e->max_prompt * H));
     PTTS_TRY(e->alloc(&e->kv_layers_rows, (size_t)c.max_batch * c.num_layers));
     std::vector<KvLayer> kl((size_t)c.max_batch * c.num_layers);
@@ -1292,6 +1307,7 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
   e->session_max_length = e->gp.max_length;
   e->slot_busy.assign(B, 0); e->slot_ub.assign(B, P + 1); e->slot_maxlen.assign(B, e->gp.max_length);
   launch_set_params(e, 0, st);
+  hipLaunchKernelGGL(set_slot_gen_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->slot_gen, 0, c.max_batch, SlotGen{});  // no slot has a record of its own
   // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);
@@ -1328,8 +1344,8 @@ static void session_row_view(ptts_engine* e, int row, bool enter) {
   std::swap(e->h, e->h_adm);
 }
 
-extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
-                              const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream) {
+extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                                  const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, const ptts_gen_params* gp, void* stream) {
   PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
   PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_row: no continuous session (ptts_session_begin)");
   PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
@@ -1341,6 +1357,11 @@ extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev,
   const int L = max_length == 0 ? e->session_max_length : max_length;
   PTTS_CHECK(L >= 2, PTTS_E_INVALID, "max_length must be 0 (the session's) or >= 2");
   PTTS_CHECK(L <= e->session_max_length, PTTS_E_CAPACITY, "max_length %d exceeds the session's %d", L, e->session_max_length);
+  if (gp) {
+    PTTS_TRY(check_sampler_params(gp, true));
+    PTTS_CHECK(gp->max_length == 0 || gp->max_length == max_length, PTTS_E_INVALID,
+               "gen params max_length %d differs from the max_length argument %d (which rules the slot's end)", gp->max_length, max_length);
+  }
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
@@ -1362,9 +1383,17 @@ extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev,
   session_row_view(e, row, false);
   PTTS_TRY(rc_fwd);
   e->slot_busy[row] = 1; e->slot_ub[row] = P + 1; e->slot_maxlen[row] = L;
+  // the request's own sampler record, written once nothing can refuse the admission any more (a refused one leaves the slot's record cleared);
+  // a slot admitted without one kept own = 0 from session begin / its last ptts_retire_row
+  if (gp) hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, st, e->slot_gen, row, 1, SlotGen{dev_gen_of(*gp, L), 1, 0});
   if (sample) PTTS_TRY(launch_tail(e, st, true, row));  // first token of the request + the embedding of its next column into h[row]
   else e->h_ready = false;                             // manual path: the next forward embeds every slot's last column
   return PTTS_OK;
+}
+
+extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                              const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream) {
+  return ptts_admit_row_gen(e, row, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_length, sample, nullptr, stream);
 }
 
 extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
@@ -1374,6 +1403,7 @@ extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
   PTTS_DEVICE(e->cfg.device);
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, pick_stream(e, stream), e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, row, 1, e->cfg.num_codebooks, e->cfg.bos_token_id, 0, e->session_max_length);
+  hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_gen, row, 1, SlotGen{});  // the next plain admission samples on the session's
   e->slot_busy[row] = 0; e->slot_ub[row] = e->P + 1;
   return PTTS_OK;
 }

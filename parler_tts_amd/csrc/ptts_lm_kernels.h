@@ -2759,10 +2759,20 @@ __device__ __forceinline__ void tail_embed_next(const TailArgs& a, const DevDims
 
 // Continuous session (ptts_session_begin): every utterance slot has its own clock and its own end. A slot is LIVE iff one of its
 // K flags is positive; an idle or finished slot does nothing at all here (no ids write, no cur_len bump, no embedding), and the
-// stop test and the delay pattern use the slot's own max_length. The sampling hash stays (seed, t, row).
+// stop test and the delay pattern use the slot's own max_length.
+// A slot may hold the sampler record of its request (SlotGen, ptts_admit_row_gen): it then reads its parameters from the record
+// (all of DevGen but max_length: the slot's end stays row_maxlen) and draws from (record seed, t, row_base + k) - its own column and the
+// codebook index inside the slot, so the tokens of a request do not depend on the slot it runs in nor on what runs beside it. Every
+// other slot reads *gen and draws from (session seed, t, b * K + k).
+struct SlotGen {
+  DevGen g;
+  int own;       // 1: this slot samples on g; 0: on the session's DevGen
+  int row_base;  // own: first row index of the slot in the draw hash (0: the hash sees the codebook index alone)
+};
 struct TailSessionArgs : TailArgs {
   const int* row_maxlen;  // [B] max_length of the request in each slot
   int row0;               // first slot of this launch: grid (B) with 0 for a decode step, grid (1) with the slot for an admission
+  const SlotGen* slot_gen = nullptr;  // [B] per-slot records, or null: every slot on *gen
 };
 template <bool SESSION> struct TailK { using T = TailArgs; };
 template <> struct TailK<true> { using T = TailSessionArgs; };
@@ -2779,7 +2789,8 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // ---- t = 0: every load that does not depend on another load goes in flight together (the step's critical path ends
   // here: lengths / flags / parameters / this wave's logits row are ONE round trip, the embedding rows a second one)
-  const DevGen g = *a.gen;
+  DevGen g = *a.gen;
+  int hrow0 = b * a.K;  // first row index of this utterance in the draw hash
   const int t = a.cur_len[b];  // column the new token is written to; t-1 new tokens generated so far
   // static: "has the reference loop already exited?" = every row finished BEFORE this step. Rows that finish during this very launch
   // (other workgroups, stamp -(t + 1)) still count as active here, so the answer does not depend on workgroup timing.
@@ -2798,6 +2809,23 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
   if constexpr (SESSION) {
     dd.max_length = p.row_maxlen[b];  // the pad triangle (and whether there is a pattern at all) follows the request's own length
     dd.T_prefix = 0;                  // no voice prompt inside a session
+  }
+  if constexpr (SESSION) {
+    // the slot's own record rides in the same batch of loads as *gen: both addresses come from kernel arguments alone (without records they
+    // fall back on *gen, read twice), and the choice between the two sets of values is made in registers - no flag is waited for first
+    // (written BEHIND the other loads of this prologue on purpose: in front of them the compiler ran out of SGPRs for the group and issued
+    // row_maxlen[b] behind a wait of its own, profiles/per_request_sampling_isa_compare.txt)
+    const bool recs = p.slot_gen != nullptr;
+    const DevGen* sgp = recs ? &p.slot_gen[b].g : a.gen;
+    const int* sfp = recs ? &p.slot_gen[b].own : &a.gen->max_length;  // {own, row_base}
+    const DevGen sg = *sgp;
+    const int sown = sfp[0], sbase = sfp[1];
+    const bool own = recs && sown != 0;
+    g.min_new_tokens = own ? sg.min_new_tokens : g.min_new_tokens; g.do_sample = own ? sg.do_sample : g.do_sample;
+    g.top_k = own ? sg.top_k : g.top_k; g.use_eos_gate = own ? sg.use_eos_gate : g.use_eos_gate;
+    g.temperature = own ? sg.temperature : g.temperature; g.top_p = own ? sg.top_p : g.top_p;
+    g.seed = own ? sg.seed : g.seed;
+    hrow0 = own ? sbase : hrow0;
   }
   const int t_prefix = dd.T_prefix;
   const int he = lane < a.K ? a.has_eos[b * a.K + lane] : 0;  // every wave: the K EOS flags of this utterance
@@ -2842,7 +2870,8 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
       const float cand = (best == wbest) ? (float)bi : 3.0e9f;  // vocabulary indices are exact in fp32
       widx = (int)(-wave_max(-cand));
     } else {
-      const unsigned long long hsh = splitmix64(g.seed ^ splitmix64(((unsigned long long)t << 32) ^ (unsigned long long)row));
+      const int hrow = SESSION ? hrow0 + k : row;  // a slot with its own record: the codebook index inside the slot
+      const unsigned long long hsh = splitmix64(g.seed ^ splitmix64(((unsigned long long)t << 32) ^ (unsigned long long)hrow));
       const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);  // [2^-25, 1], DESIGN.md 4.6
       widx = wave_sample_row<NV>(lg, a.V, lane, g, eos_blocked, a.eos, u);
     }
@@ -2940,6 +2969,12 @@ static __global__ void set_len_kernel(int* cur_len, int B, int v) {
 static __global__ void set_params_kernel(DevDims* dd, DevGen* dg, DevDims d, DevGen g) {
   *dd = d;
   *dg = g;
+}
+// the sampler record of slots [row0, row0 + nrows): ptts_admit_row_gen writes one slot's (own = 1), session begin and ptts_retire_row clear
+// theirs (own = 0). The record travels by value as a kernel argument (no staging buffer, no copy to wait on)
+static __global__ void set_slot_gen_kernel(SlotGen* recs, int row0, int nrows, SlotGen rec) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nrows) recs[row0 + i] = rec;
 }
 
 static __global__ void fill_int_kernel(int* p, int v, size_t n) {

@@ -236,14 +236,26 @@ class DecoderEngine:
     # -- continuous batching (ptts_session_begin / ptts_admit_row / ptts_row_state / ptts_retire_row) -------------
     def begin_session(self, slots: int, enc_width: int, prompt_width: int):
         """Opens a continuous session: ``slots`` utterance slots, all idle; every request is padded to ``enc_width`` description and
-        ``prompt_width`` prompt positions. Generation parameters are those of the last ``set_gen_params``."""
+        ``prompt_width`` prompt positions. Generation parameters are those of the last ``set_gen_params``, for every request that brings
+        none of its own (``admit_row(..., gen=...)``)."""
         N.check(self.lib.ptts_session_begin(self._h, int(slots), int(enc_width), int(prompt_width), _stream_ptr(device=self.device)), "ptts_session_begin")
         self.B, self.P, self.session_N = int(slots), int(prompt_width), int(enc_width)
 
     def admit_row(self, row: int, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
-                  prompt_mask: Optional[torch.Tensor], max_length: int = 0, sample: bool = True):
+                  prompt_mask: Optional[torch.Tensor], max_length: int = 0, sample: bool = True, gen: Optional[dict] = None):
         """Prefills ONE request (``enc`` [N, H], ``prompt`` [P, H] at the session's widths) into the idle slot ``row``; the other slots
-        keep their state. ``max_length`` = the request's own 1 + max_new_tokens (0: the session's)."""
+        keep their state. ``max_length`` = the request's own 1 + max_new_tokens (0: the session's).
+        ``gen``: the request's own sampler settings and seed (``ptts_admit_row_gen``) - keys ``min_new_tokens, do_sample, temperature, top_k,
+        top_p, use_eos_gate, seed``, a key left out takes ``set_gen_params``'s default; the slot then draws from ``(seed, column, codebook)``,
+        whichever slot it is. ``None``: the session's parameters and draw stream (``ptts_admit_row``)."""
+        gp = None
+        if gen is not None:
+            unknown = set(gen) - {"min_new_tokens", "do_sample", "temperature", "top_k", "top_p", "use_eos_gate", "seed"}
+            if unknown:
+                raise ValueError(f"unknown per-request generation parameters {sorted(unknown)}")
+            gp = N.PttsGenParams(0, int(gen.get("min_new_tokens", 0)), int(bool(gen.get("do_sample", False))), float(gen.get("temperature", 1.0)),
+                                 int(gen.get("top_k", 0) or 0), float(gen.get("top_p", 1.0)), int(bool(gen.get("use_eos_gate", True))),
+                                 int(gen.get("seed", 0)) & (2 ** 64 - 1))  # max_length 0: the `max_length` argument rules the slot's end
         enc = enc.to(self.device, torch.float32).contiguous()
         if enc.dim() != 2 or tuple(enc.shape) != (self.session_N, self.H):
             raise ValueError(f"encoder states {tuple(enc.shape)} do not match the session's [{self.session_N}, {self.H}]")
@@ -265,8 +277,12 @@ class DecoderEngine:
                 raise ValueError(f"prompt_attention_mask of {pm.numel()} positions does not match the session's {self.P}")
             keep.append(pm)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
-        N.check(self.lib.ptts_admit_row(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), int(max_length), int(sample),
-                                        _stream_ptr(device=self.device)), "ptts_admit_row")
+        if gp is None:
+            N.check(self.lib.ptts_admit_row(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), int(max_length), int(sample),
+                                            _stream_ptr(device=self.device)), "ptts_admit_row")
+        else:
+            N.check(self.lib.ptts_admit_row_gen(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), int(max_length), int(sample), C.byref(gp),
+                                                _stream_ptr(device=self.device)), "ptts_admit_row_gen")
         if not hasattr(self, "_keep_rows"):
             self._keep_rows = {}
         self._keep_rows[int(row)] = keep  # consumed asynchronously by the enqueued kernels

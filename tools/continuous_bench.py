@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Continuous batching against static batching on a request stream of mixed lengths (Mini-v1 shapes, bf16, synthetic weights).
 
-  python tools/continuous_bench.py [--repeats 5] [--static-only] [--stream [--stream-chunks 43,86]] [--out FILE]
+  python tools/continuous_bench.py [--repeats 5] [--static-only] [--per-request] [--stream [--stream-chunks 43,86]] [--out FILE]
 
 256 requests whose lengths come from a fixed seeded list (uniform 150..860 frames, set through per-request max_new_tokens; EOS is blocked,
 so lengths are exact), 32 slots. Reports
@@ -15,6 +15,9 @@ so lengths are exact), 32 slots. Reports
   (e) admission: GPU time of one ptts_admit_row while the other slots hold live requests
 A and B alternate inside one process after every graph has been warmed; medians and the observed spread are printed. --static-only runs (a)
 and the static step of (d) alone (it needs nothing of the session interface, so it also runs on a tree without it).
+
+--per-request adds (p): the batcher of (b) with every second request carrying its own sampler record (ptts_admit_row_gen) - alternately a greedy
+one and a sampled one with a seed (temperature 0.7, top-k 50), min_new_tokens as the session's so that lengths stay exact - alternating with (b).
 
 --stream measures the streaming mode instead of (a), (d), (e): (b) and the streaming batcher (`stream_chunk_frames`) alternate on the same list;
 per chunk size it reports audio-s/s next to (b), the codec passes and the mean rows per pass, and per request the host time from its admission
@@ -84,7 +87,14 @@ def run_static(model, desc, prompt, frames):
     return time.perf_counter() - t0
 
 
-def run_batcher(model, desc, prompt, frames):
+def request_options(i):
+    """--per-request: the sampler options of request i - none for every second one, else alternately greedy and sampled with a seed."""
+    if i % 2 == 0:
+        return {}
+    return {"do_sample": False} if i % 4 == 1 else {"do_sample": True, "temperature": 0.7, "top_k": 50, "seed": 1000 + i}
+
+
+def run_batcher(model, desc, prompt, frames, per_request=False):
     import parler_tts_amd as P
 
     new_max = FRAMES_HI + K - 1
@@ -92,7 +102,8 @@ def run_batcher(model, desc, prompt, frames):
     t0 = time.perf_counter()
     cb = P.ContinuousBatcher(model, slots=SLOTS, max_description_tokens=bench.N_DESC, max_prompt_tokens=bench.N_PROMPT, poll_steps=16, do_sample=False,
                              max_new_tokens=new_max, min_new_tokens=new_max)
-    tickets = [cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1) for i in range(N_REQ)]
+    tickets = [cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1, **(request_options(i) if per_request else {}))
+               for i in range(N_REQ)]
     torch.cuda.synchronize()
     t_submit = time.perf_counter() - t0
     got = {t: n for t, w, n in cb}
@@ -274,6 +285,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--static-only", action="store_true")
+    ap.add_argument("--per-request", action="store_true", help="also measure (p): every second request with its own sampler record")
     ap.add_argument("--stream", action="store_true", help="measure the streaming mode against (b) instead of (a), (d), (e)")
     ap.add_argument("--stream-chunks", default="43,86", help="stream_chunk_frames values to measure")
     ap.add_argument("--out", default=None, help="also append the report to this file")
@@ -312,13 +324,19 @@ def main():
         run_static(model, desc, prompt, frames)
         if not a.static_only:
             run_batcher(model, desc, prompt, frames)
-        st, cb, sub = [], [], []
+        per_request = a.per_request and not a.static_only
+        if per_request:
+            run_batcher(model, desc, prompt, frames, per_request=True)
+        st, cb, sub, pr_t = [], [], [], []
         for r in range(a.repeats):
             st.append(run_static(model, desc, prompt, frames))
             if not a.static_only:
                 dt, ts = run_batcher(model, desc, prompt, frames)
                 cb.append(dt); sub.append(ts)
-            say(f"  repeat {r}: static {st[-1]:.3f} s" + ("" if a.static_only else f", batcher {cb[-1]:.3f} s (of which submit / encode {sub[-1]:.3f} s)"))
+            if per_request:
+                pr_t.append(run_batcher(model, desc, prompt, frames, per_request=True)[0])
+            say(f"  repeat {r}: static {st[-1]:.3f} s" + ("" if a.static_only else f", batcher {cb[-1]:.3f} s (of which submit / encode {sub[-1]:.3f} s)") +
+                (f", per-request records {pr_t[-1]:.3f} s" if per_request else ""))
         m, lo, hi = med_spread(st)
         say(f"(a) static batching : median {m:.3f} s = {audio_s / m:.1f} audio-s/s (spread {audio_s / hi:.1f} .. {audio_s / lo:.1f})")
         res = {"static_s": m, "static_audio_s_per_s": audio_s / m, "ideal_ratio": ideal_ratio(frames)}
@@ -328,6 +346,11 @@ def main():
                 f"submit (256 single-description encodes + prompt embeddings) median {statistics.median(sub):.3f} s of it")
             say(f"    (b)/(a) = {m / mb:.3f} against the ideal (c) = {ideal_ratio(frames):.3f}")
             res.update(batcher_s=mb, batcher_audio_s_per_s=audio_s / mb, ratio=m / mb, submit_s=statistics.median(sub))
+            if per_request:
+                mp, lop, hip_ = med_spread(pr_t)
+                say(f"(p) ContinuousBatcher, every second request with its own sampler record (greedy / sampled with a seed): median {mp:.3f} s = "
+                    f"{audio_s / mp:.1f} audio-s/s (spread {audio_s / hip_:.1f} .. {audio_s / lop:.1f}) = {mb / mp:.3f} of (b)")
+                res.update(per_request_s=mp, per_request_audio_s_per_s=audio_s / mp)
             total, acc, count = batcher_breakdown(model, desc, prompt, frames)
             say(f"    where the batcher's time goes (one run with a sync around each phase, {total:.3f} s after the submits): " +
                 ", ".join(f"{k} {acc[k]:.3f} s / {count[k]} calls" for k in acc) + f", rest (Python between the calls) {total - sum(acc.values()):.3f} s")
