@@ -44,7 +44,6 @@ struct ConvArgs {
   int stride, Tn;      // input stride of a down-sampling conv (else 1); output frames per phase (Tin unless strided)
   const int* lens;     // ragged decode (ptts_dac_decode_ragged): latent frames per utterance [B] on the device, or null. Utterance b then has
   int len_mul;         // lens[b] * len_mul valid input rows (= output rows per phase): rows beyond read as the zero padding, tiles beyond exit
-  int epi_direct;      // conv_lds_kernel: the round-3 epilogue (a lane stores 4 channels of one frame); 0 on every launch (measured A/B path)
 };
 
 // valid input rows of utterance b (buffers keep the full stride a.Tin)
@@ -169,386 +168,72 @@ __global__ void __launch_bounds__(256) conv_mfma_kernel(ConvArgs a) {
   if (CS >= 8) { emit(acc[6 % CS][0], 6, 0); emit(acc[6 % CS][1], 6, 1); emit(acc[7 % CS][0], 7, 0); emit(acc[7 % CS][1], 7, 1); }
 }
 
-// LDS-tiled variant of the bf16-operand kernel for the stride-1 layers of the 44.1 kHz stack (k7 dilated convs, k1 convs,
-// the 2-tap phases of the transposed convs): the kernel above fetches every activation fragment from L1/L2 once per TAP and
-// every weight fragment once per WAVE (10 KB per wave per 256 MFMA cycles = 160 B/clk/CU asked of a 64 B/clk L1), and ran at
-// 10 % of the bf16 MFMA peak. Here a workgroup owns 128 consecutive frames x NW*CSW 16-channel strips:
-//   * the activation slab of one KCH-channel chunk ([128 + halo] rows x KCH bf16) is staged ONCE into LDS and read by all
-//     taps (7x fewer global reads) and all waves; rows are RS = KCH*2 + 32 bytes apart: RS/32 is odd, so the 16 lanes of each
-//     ds_read_b128 service group land on 16 distinct 16-byte bank slots for ANY row base (the tap offset tap*dil is arbitrary);
-//   * waves split the output strips (CSW each) and share the frames, so every wave's weight fragments are its own: CSW KB
-//     per wave per k-step from L2/L1 (24 B/clk/CU at CSW = 3), prefetched one k-step ahead in registers, also across chunks;
-//   * two LDS buffers: chunk c+1 is fetched into registers while chunk c computes and committed before the ONE barrier of
-//     the chunk; B fragments are read in two halves of 4 frame tiles, each half in flight under the other half's 12 MFMAs.
-// Per k-step and wave: 24 MFMAs 16x16x32 (384 cycles) against 8 ds_read_b128 + 3 global 16-B loads.
-// FT (round 5): 16-frame tiles per workgroup - 8 (128 frames), or 4 where 128-frame tiles leave the launch with fewer than two workgroups per CU (the
-// first block of a single utterance: 56-224 workgroups on 256 CUs; the short windows of the streamer). Same k order per output: bit-identical.
-template <int CSW, int NW, int KS, int MAXHALO, int FT = 8>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) conv_lds_kernel(ConvArgs a) {
-  constexpr int TF = FT * 16, HF = FT / 2;
+// The staged-slab MFMA accumulation of conv_lds_kernel and of resunit_lds_kernel's k7 phase, written once:
+//   acc[s][f] += sum over (chunk c, tap, kk) of W[strip s][tap][c * KCH + kk * 32 ..] * x[frame tile f + rel(tap)][same channels]
+// for the calling wave's CSW strips and the workgroup's FT 16-frame tiles. `slab`: two buffers of MAXROWS * RS bytes in LDS; `xb`: the utterance's
+// activation rows; `Wp`: the packed fragments of this wave's first strip (+ lane), strips nk * 64 float4 apart. Every thread of the workgroup calls it
+// (barriers inside); the last chunk's barrier has retired every slab read when it returns.
+//   * chunk c + 1 is fetched into the staging registers at step 0 of chunk c and committed to the other buffer before the ONE barrier of the chunk;
+//   * weight fragments are requested WD k-steps ahead, also across chunks, into WD + 1 register sets that ROTATE (never copied: a copy makes the
+//     compiler wait for the loads it has just issued). WD = 3: four sets; WD = 1: two sets, where the registers do not reach (see ResunitXinWD).
+//     A k-step is 24 MFMAs = 384 cycles per wave, ~770 with the SIMD's second wave interleaved: one step ahead is ~0.3 us, less than an L2 round
+//     trip - and the fragments DO come from the L2 every time (a wave re-streams its 3 strips x 7 taps x C channels = 129 KB at C = 192 per tile
+//     through a 32 KB L1 shared by 8 waves), so with WD = 1 every k-step waited for its weights: MFMA pipe 23-28 % busy (profiles/r03_pmc_dac_mfma.txt);
+//   * B fragments are read in two halves of FT / 2 frame tiles, each half in flight under the other half's MFMAs.
+// XIN: `xb` is the fp32 residual stream; a staged slot is 32 bytes of it (two uint4) that become the slot's 16 bytes of bf16 at commit time
+// (Snake with `s_ain` = [alpha | 1 / (alpha + 1e-9)] of all Cin channels in LDS, rounded once). Rows outside the utterance read as zeros either
+// way (Snake(0) = 0: the conv's zero padding).
+// C7 = 0: channels, taps, dilation and the transposed conv's phase addressing (`ph`) come from `a` at run time (conv_lds_kernel). C7 = C: a plain k7
+// conv over C channels (the residual unit): k-steps per chunk, chunks and their product are compile-time constants.
+template <int CSW, int NW, int KS, int FT, int MAXHALO, int WD, bool XIN, int C7>
+__device__ __forceinline__ void slab_mfma_loop(f32x4 (&acc)[CSW][FT], unsigned char* const slab, const float* const s_ain, const ConvArgs& a,
+                                               const char* const xb, const float4* const Wp, const int nk, const int t0, const int Tv, const int ph) {
   static_assert(FT == 8 || FT == 4, "frame tiles per workgroup");
-  constexpr int KCH = 32 * KS;
-  constexpr int RS = KS * 64 + 32;
-  constexpr int SL = KS * 4;  // 16-byte slots per slab row
+  static_assert(WD == 3 || WD == 1, "weight prefetch depth: four or two rotating register sets");
+  constexpr int TF = FT * 16, HF = FT / 2;
+  constexpr int KCH = 32 * KS;          // channels per staged chunk
+  constexpr int RS = KS * 64 + 32;      // slab row stride in bytes: RS / 32 is odd (conflict-free ds_read_b128 for any row base)
+  constexpr int SL = KS * 4;            // 16-byte slots per slab row
   constexpr int NT = NW * 64;
   constexpr int MAXROWS = TF + MAXHALO;
-  constexpr int NST = (MAXROWS * SL + NT - 1) / NT;  // staged 16-byte pieces per thread and chunk
-  __shared__ __attribute__((aligned(16))) unsigned char slab[2][MAXROWS * RS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int q = lane >> 4, j = lane & 15;
-  const int ntile = (a.Tn + TF - 1) / TF;
-  // (round 6, profiles/r06_dac_up_order_ab.txt: the phases of a transposed conv as neighbours in ONE XCD's queue - sharing its L2 copy of the input tile -
-  //  or the phase as the slowest index - one phase's weights L2-resident at a time - measured equal to this order, 54.2-54.7 vs 53.8-54.2 ms per batch-32
-  //  decode, bit-identical: the re-fetched bytes the PMC table shows for these layers do not cost time. Not kept.)
-  const int tile = blockIdx.x % ntile, ph = (blockIdx.x / ntile) % a.nphase, b = blockIdx.x / (ntile * a.nphase);
-  const int nstrips = a.Cout / 16;
-  const int strip0 = (blockIdx.y * NW + wave) * CSW;
-  const int cpt = a.Cin / 32, nk = a.ntaps * cpt;
-  const int nchunk = a.Cin / KCH;
-  const int NS = a.ntaps * KS;  // k-steps per chunk
-  const int t0 = tile * TF;
-  const int Tv = valid_rows(a, b), Tnv = a.lens ? Tv : a.Tn;  // ragged decode: this utterance's rows (workgroup-uniform)
-  if (t0 >= Tnv) return;
-  // slab row r holds input frame t0 + o0 + r; tap `tap` of output frame t0 + f reads row f + rel(tap)
-  const int o0 = a.transposed ? (ph + a.pad) / a.nphase - (a.ntaps - 1) : -a.pad;
-  const int halo = a.transposed ? a.ntaps - 1 : (a.ntaps - 1) * a.dil;
-  const int nslot = (TF + halo) * SL;
-  const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)b * a.Tin * a.Cin * 2;
-  const float4* Wp = reinterpret_cast<const float4*>(a.Wp) + ((size_t)ph * nstrips + strip0) * nk * 64 + lane;
-  const int lrow = j * RS + q * 16;
-
-  f32x4 acc[CSW][FT];
-#pragma unroll
-  for (int s = 0; s < CSW; ++s)
-#pragma unroll
-    for (int f = 0; f < FT; ++f) acc[s][f] = f32x4{0, 0, 0, 0};
-
-  uint4 stg[NST];
-#define PTTS_SLAB_FETCH(C)                                                                                              \
-  _Pragma("unroll") for (int i_ = 0; i_ < NST; ++i_) {                                                                    \
-    const int idx_ = tid + i_ * NT, r_ = idx_ / SL, sl_ = idx_ - r_ * SL, ti_ = t0 + o0 + r_;                              \
-    stg[i_] = make_uint4(0, 0, 0, 0);                                                                                    \
-    if (idx_ < nslot && ti_ >= 0 && ti_ < Tv)                                                                             \
-      stg[i_] = *reinterpret_cast<const uint4*>(xb + ((size_t)ti_ * a.Cin + (size_t)(C) * KCH) * 2 + sl_ * 16);            \
-  }
-#define PTTS_SLAB_COMMIT(BUF)                                                                                           \
-  _Pragma("unroll") for (int i_ = 0; i_ < NST; ++i_) {                                                                    \
-    const int idx_ = tid + i_ * NT, r_ = idx_ / SL, sl_ = idx_ - r_ * SL;                                                  \
-    if (idx_ < nslot) *reinterpret_cast<uint4*>(&slab[BUF][r_ * RS + sl_ * 16]) = stg[i_];                                 \
-  }
-  // weight fragments of k-step (chunk C, step S): ks = tap * cpt + C * KS + kk
-#define PTTS_W_FETCH(WF, C, S)                                                                                          \
-  do {                                                                                                                  \
-    const int tap_ = (S) / KS, kk_ = (S) - tap_ * KS;                                                                     \
-    const float4* wp_ = Wp + (size_t)(tap_ * cpt + (C) * KS + kk_) * 64;                                                  \
-    _Pragma("unroll") for (int s_ = 0; s_ < CSW; ++s_) WF[s_] = wp_[(size_t)s_ * nk * 64];                               \
-  } while (0)
-  // B fragments (4 frame tiles from F0) of step S out of buffer SB
-#define PTTS_B_FETCH(BV, SB, S, F0)                                                                                     \
-  do {                                                                                                                  \
-    const int tap_ = (S) / KS, kk_ = (S) - tap_ * KS;                                                                     \
-    const int rel_ = a.transposed ? (a.ntaps - 1 - tap_) : tap_ * a.dil;                                                  \
-    const unsigned char* sp_ = (SB) + (rel_ + (F0) * 16) * RS + kk_ * 64 + lrow;                                          \
-    _Pragma("unroll") for (int f_ = 0; f_ < HF; ++f_) BV[f_] = *reinterpret_cast<const uint4*>(sp_ + f_ * 16 * RS);       \
-  } while (0)
-
-  // One k-step: MFMAs of (chunk c, step st) with the weight fragments WC while WN receives those of the NEXT k-step (possibly the
-  // first of chunk c + 1). The register sets rotate (never copied: a copy makes the compiler wait for the loads it has just issued). The last step of a chunk commits the staged slab and holds the chunk's barrier.
-#define PTTS_MFMA_HALF(WC, BV, F0)                                                                                      \
-  _Pragma("unroll") for (int f_ = 0; f_ < HF; ++f_) _Pragma("unroll") for (int s_ = 0; s_ < CSW; ++s_)                     \
-    acc[s_][(F0) + f_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, WC[s_]), __builtin_bit_cast(bf16x8, BV[f_]), acc[s_][(F0) + f_], 0, 0, 0);
-#define PTTS_STEP(WC, WN)                                                                                               \
-  {                                                                                                                     \
-    const unsigned char* sb_ = slab[c & 1];                                                                               \
-    const bool more_ = c + 1 < nchunk, lastst_ = st + 1 == NS;                                                            \
-    const int gn_ = min(gi + 3, total - 1); /* weights of k-step + 3 (resunit_lds_kernel: WD). Unconditional (a valid */    \
-    const int gc_ = gn_ / NS;               /* re-fetch at the very end): a branch here would merge into a conservative */ \
-    if (st == 0 && more_) { PTTS_SLAB_FETCH(c + 1); } /* vmcnt on the MFMAs below */                                      \
-    PTTS_W_FETCH(WN, gc_, gn_ - gc_ * NS);                                                                                \
-    PTTS_B_FETCH(bB, sb_, st, HF);                                                                                        \
-    PTTS_MFMA_HALF(WC, bA, 0)                                                                                             \
-    if (!lastst_) PTTS_B_FETCH(bA, sb_, st + 1, 0);                                                                       \
-    PTTS_MFMA_HALF(WC, bB, HF)                                                                                            \
-    if (lastst_) {                                                                                                        \
-      if (more_) { PTTS_SLAB_COMMIT((c + 1) & 1); }                                                                       \
-      __syncthreads();                                                                                                    \
-      if (more_) PTTS_B_FETCH(bA, slab[(c + 1) & 1], 0, 0);                                                               \
-      ++c;                                                                                                                \
-      st = 0;                                                                                                             \
-    } else {                                                                                                              \
-      ++st;                                                                                                               \
-    }                                                                                                                     \
-    ++gi;                                                                                                                 \
-  }
+  constexpr int NST = (MAXROWS * SL + NT - 1) / NT;  // staged slots per thread and chunk
+  constexpr bool K7 = C7 != 0;
+  static_assert(C7 % KCH == 0, "chunk width");
+  const int tid = threadIdx.x, q = (tid & 63) >> 4, j = tid & 15;
+  const int Cin = K7 ? C7 : a.Cin;
+  const int cpt = Cin / 32, nchunk = Cin / KCH;
+  const int NS = (K7 ? 7 : a.ntaps) * KS;  // k-steps per chunk
   const int total = nchunk * NS;
-  float4 w0[CSW], w1[CSW], w2[CSW], w3[CSW];  // four register sets: k-step g computes out of w[g % 4] while the fragments of k-step g + 3 land
-  uint4 bA[HF], bB[HF];
-  PTTS_W_FETCH(w0, 0, 0);
-  { const int g1_ = min(1, total - 1), c1_ = g1_ / NS; PTTS_W_FETCH(w1, c1_, g1_ - c1_ * NS); }
-  { const int g2_ = min(2, total - 1), c2_ = g2_ / NS; PTTS_W_FETCH(w2, c2_, g2_ - c2_ * NS); }
-  PTTS_SLAB_FETCH(0);
-  PTTS_SLAB_COMMIT(0);
-  __syncthreads();
-  PTTS_B_FETCH(bA, slab[0], 0, 0);
-  int c = 0, st = 0, gi = 0;
-  for (int g = 0; g < total; g += 4) {
-    PTTS_STEP(w0, w3)
-    if (g + 1 < total) PTTS_STEP(w1, w0)
-    if (g + 2 < total) PTTS_STEP(w2, w1)
-    if (g + 3 < total) PTTS_STEP(w3, w2)
-  }
-#undef PTTS_STEP
-#undef PTTS_MFMA_HALF
-#undef PTTS_SLAB_FETCH
-#undef PTTS_SLAB_COMMIT
-#undef PTTS_W_FETCH
-#undef PTTS_B_FETCH
-  const int Tout = a.Tn * a.nphase;
-  // epilogue through LDS (default; as resunit_lds_kernel's): the workgroup's output tile [128 frames][NW * 48 channels] goes through the slab
-  // memory in passes of EF frames as fp32 rows, and every lane then moves 16 CONSECUTIVE bytes of a row (a row of the tile = NW * 192 bytes of
-  // an output row; the rows of a transposed conv's phase are `nphase` rows apart). The direct form below stores 64-byte pieces per lane group:
-  // the transposed convs ran 45-55 % parked at 25 % MFMA busy (profiles/r04_pmc_dac_sq.txt). Same fp32 operations in the same order.
-  if (!a.epi_direct) {
-    constexpr int CW = NW * CSW * 16, RSE = CW * 4 + 16, SLB = 2 * MAXROWS * RS, VPR = CW / 4;
-    constexpr int EF0 = SLB / RSE;
-    constexpr int EF1 = EF0 >= 128 ? 128 : (EF0 >= 64 ? 64 : (EF0 >= 32 ? 32 : 16)), EF = EF1 > TF ? TF : EF1, TPP = EF / 16;
-    static_assert(EF0 >= 16, "one 16-frame pass of the output tile fits the slab memory");
-    unsigned char* et = &slab[0][0];  // the last chunk's barrier has retired every slab read
-    const int c0 = blockIdx.y * CW;
-    // Round 5 (as resunit_lds_kernel's epilogue): the Snake parameters of this workgroup's CW channels go through LDS, and a pass over EF whole
-    // rows is ONE straight-line block per (residual?, stream?, activation format) - no load from global memory and no branch between the stores,
-    // so no s_waitcnt vmcnt(0) (= "until my last stores are acknowledged") in front of every row piece.
-    constexpr int NPT = EF * VPR / NT;
-    static_assert(EF * VPR % NT == 0, "row pieces per thread and pass");
-    int tid_e = tid;  // an opaque copy for the epilogue's address arithmetic: computed from `tid` it is hoisted above the MFMA loop and spilled there
-    asm volatile("" : "+v"(tid_e));
-    static_assert(EF * RSE + 2 * CW * 4 <= SLB, "LDS: one pass of the output tile + the Snake parameters");
-    float* s_al = reinterpret_cast<float*>(et + EF * RSE);  // [2][CW]: alpha | 1 / (alpha + 1e-9)
-    if (a.out_act)
-      for (int i = tid; i < 2 * VPR; i += NT) {
-        const int hf = i / VPR, c4 = i - hf * VPR;
-        reinterpret_cast<float4*>(s_al)[i] = *reinterpret_cast<const float4*>(a.alpha + (size_t)hf * a.Cout + c0 + c4 * 4);
-      }
-    typedef std::integral_constant<int, 0> I0_;
-    typedef std::integral_constant<int, 1> I1_;
-    typedef std::integral_constant<int, 2> I2_;
-    auto pass = [&](auto skip_c, auto raw_c, auto act_c, const int r0, const int rows) __attribute__((always_inline)) {
-      constexpr bool SK = decltype(skip_c)::value != 0, RW = decltype(raw_c)::value != 0;
-      constexpr int AC = decltype(act_c)::value;  // 0: no activation output, 1: bf16, 2: fp32
-      auto offs = [&](const int i) { const int rr = i / VPR, cv = i - rr * VPR; return ((size_t)b * Tout + (size_t)(r0 + rr) * a.nphase + ph) * a.Cout + c0 + cv * 4; };
-      auto piece = [&](const int i, const size_t o, const float4 sk) __attribute__((always_inline)) {
-        const int rr = i / VPR, cv = i - rr * VPR;
-        float4 v = *reinterpret_cast<const float4*>(et + rr * RSE + cv * 16);
-        if constexpr (SK) { v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w; }
-        if constexpr (RW) *reinterpret_cast<float4*>(a.out_raw + o) = v;
-        if constexpr (AC != 0) {
-          const float4 al = *reinterpret_cast<const float4*>(s_al + cv * 4), ia = *reinterpret_cast<const float4*>(s_al + CW + cv * 4);
-          const float4 sv = make_float4(snake_f<true>(v.x, al.x, ia.x), snake_f<true>(v.y, al.y, ia.y), snake_f<true>(v.z, al.z, ia.z), snake_f<true>(v.w, al.w, ia.w));
-          if constexpr (AC == 1) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.out_act) + o) = make_uint2(pack_bf16x2(sv.x, sv.y), pack_bf16x2(sv.z, sv.w));
-          else *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out_act) + o) = sv;
-        }
-      };
-      if (rows == EF) {
-        constexpr int GP = NPT > 6 ? 6 : NPT;  // residual values in flight per group (registers: acc is still live for the next pass)
-        static_assert(NPT % GP == 0, "row pieces per group");
-#pragma unroll
-        for (int k0 = 0; k0 < NPT; k0 += GP) {
-          float4 skp[SK ? GP : 1];
-          if constexpr (SK) {
-#pragma unroll
-            for (int k = 0; k < GP; ++k) skp[k] = *reinterpret_cast<const float4*>(a.skip + offs(tid_e + (k0 + k) * NT));
-          }
-#pragma unroll
-          for (int k = 0; k < GP; ++k) piece(tid_e + (k0 + k) * NT, offs(tid_e + (k0 + k) * NT), SK ? skp[SK ? k : 0] : make_float4(0.f, 0.f, 0.f, 0.f));
-        }
-      } else {
-#pragma unroll 2
-        for (int k = 0; k < NPT; ++k) {
-          const int i = tid_e + k * NT;
-          if (i / VPR < rows) {
-            const size_t o = offs(i);
-            float4 sk = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (SK) sk = *reinterpret_cast<const float4*>(a.skip + o);
-            piece(i, o, sk);
-          }
-        }
-      }
-    };
-    auto by_act = [&](auto skip_c, auto raw_c, const int r0, const int rows) __attribute__((always_inline)) {
-      if (!a.out_act) pass(skip_c, raw_c, I0_(), r0, rows);
-      else if (a.act_f32) pass(skip_c, raw_c, I2_(), r0, rows);
-      else pass(skip_c, raw_c, I1_(), r0, rows);
-    };
-    // (explicitly instantiated per pass: inside a `#pragma unroll` loop the dispatch below stopped the unroller and `acc` went to scratch)
-    auto do_pass = [&](auto p0_c) __attribute__((always_inline)) {
-      constexpr int p0 = decltype(p0_c)::value;
-      if constexpr (p0 < FT) {
-#pragma unroll
-      for (int s = 0; s < CSW; ++s) {
-        const float4 bs = *reinterpret_cast<const float4*>(a.bias + (strip0 + s) * 16 + q * 4);
-#pragma unroll
-        for (int f = 0; f < TPP; ++f) {
-          const f32x4 av = acc[s][p0 + f];
-          *reinterpret_cast<float4*>(et + (f * 16 + j) * RSE + ((wave * CSW + s) * 16 + q * 4) * 4) = make_float4(av[0] + bs.x, av[1] + bs.y, av[2] + bs.z, av[3] + bs.w);
-        }
-      }
-      __syncthreads();
-      const int r0 = t0 + p0 * 16, rows = min(EF, Tnv - r0);
-      if (a.skip) { if (a.out_raw) by_act(I1_(), I1_(), r0, rows); else by_act(I1_(), I0_(), r0, rows); }
-      else { if (a.out_raw) by_act(I0_(), I1_(), r0, rows); else by_act(I0_(), I0_(), r0, rows); }
-      if (p0 + TPP < FT) __syncthreads();  // the tile memory is rewritten by the next pass
-      }
-    };
-    do_pass(std::integral_constant<int, 0>()); do_pass(std::integral_constant<int, TPP>()); do_pass(std::integral_constant<int, 2 * TPP>());
-    do_pass(std::integral_constant<int, 3 * TPP>()); do_pass(std::integral_constant<int, 4 * TPP>()); do_pass(std::integral_constant<int, 5 * TPP>());
-    do_pass(std::integral_constant<int, 6 * TPP>()); do_pass(std::integral_constant<int, 7 * TPP>());
-    return;
-  }
-  // direct epilogue: as conv_mfma_kernel (D[row = co_local = q*4 + r][col = frame j]); explicit (s, f) calls keep `acc` statically indexed
-  auto emit = [&](const f32x4 av, const int s, const int f) {
-    const int jj = t0 + f * 16 + j;
-    if (jj >= Tnv) return;
-    const int co = (strip0 + s) * 16 + q * 4;
-    const float4 bs = *reinterpret_cast<const float4*>(a.bias + co);
-    const size_t o = ((size_t)b * Tout + (size_t)jj * a.nphase + ph) * a.Cout + co;
-    float4 v = make_float4(av[0] + bs.x, av[1] + bs.y, av[2] + bs.z, av[3] + bs.w);
-    if (a.skip) {
-      const float4 sk = *reinterpret_cast<const float4*>(a.skip + o);
-      v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w;
-    }
-    if (a.out_raw) *reinterpret_cast<float4*>(a.out_raw + o) = v;
-    if (a.out_act) {
-      const float4 al = *reinterpret_cast<const float4*>(a.alpha + co), ia = ld_inv4(a.alpha, a.Cout, co);
-      const float4 sv = make_float4(snake_f<true>(v.x, al.x, ia.x), snake_f<true>(v.y, al.y, ia.y), snake_f<true>(v.z, al.z, ia.z), snake_f<true>(v.w, al.w, ia.w));
-      if (!a.act_f32) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.out_act) + o) = make_uint2(pack_bf16x2(sv.x, sv.y), pack_bf16x2(sv.z, sv.w));
-      else *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out_act) + o) = sv;
-    }
-  };
-#define PTTS_EMIT_ROW(S)                                                                                                  \
-  if (CSW > (S)) {                                                                                                        \
-    emit(acc[(S) % CSW][0], S, 0); emit(acc[(S) % CSW][1], S, 1); emit(acc[(S) % CSW][2], S, 2); emit(acc[(S) % CSW][3], S, 3); \
-    if (FT > 4) { emit(acc[(S) % CSW][4 % FT], S, 4); emit(acc[(S) % CSW][5 % FT], S, 5); emit(acc[(S) % CSW][6 % FT], S, 6); emit(acc[(S) % CSW][7 % FT], S, 7); } \
-  }
-  PTTS_EMIT_ROW(0)
-  PTTS_EMIT_ROW(1)
-  PTTS_EMIT_ROW(2)
-  PTTS_EMIT_ROW(3)
-#undef PTTS_EMIT_ROW
-}
-
-// Fused residual unit (default; PTTS_DAC_NO_FUSE_RES=1 restores the two-launch path for A/B): one residual unit of the three narrower blocks
-// (C = 384 / 192 / 96) in ONE launch (measured on MI355X, profiles/r03_experiments.txt: 860 frames 3.62 -> 3.25 ms, batch 32 109.4 -> 97.5 ms):
-//   y = Snake_a(conv_k7_dil(x) + b7)  ->  bf16 tile in LDS  ->  out = skip + conv_k1(y) + b1 ; act = Snake_a1(out)
-// The workgroup owns all C channels of 128 frames (NW * 3 strips = C / 16), so the k1 GEMM's operand never leaves the CU: the unit's
-// HBM traffic drops from 16 to 12 bytes per element (no bf16 round trip of y) and one launch per unit goes away (per-layer table,
-// profiles/r02_dac_layers.txt: k7 + k1 = 339 us at C = 192, 260 us at C = 96, the k1 half bound by its epilogue traffic).
-// Phase A is conv_lds_kernel<3, NW, 1, 54>'s loop; the y tile overlays the two slab buffers once the last chunk's barrier has passed.
-// weight prefetch depth of the XIN instances per width (registers: an XIN unit stages twice the bytes per slab slot)
-template <int NW> struct ResunitXinWD { static constexpr int value = NW == 2 ? 1 : 3; };
-struct ResArgs {
-  ConvArgs a;           // the k7 conv (x, Wp, bias, alpha = Snake between the two convs, dil, pad, B, Tin, Cin = Cout = C)
-  const void* Wp1;      // k1 weights, packed [C/16][C/32][64][8 bf16]
-  const float* bias1;
-  const float* alpha1;  // Snake of the unit's output (the next layer's input activation)
-  const float* skip;    // fp32 residual stream [B][T][C]
-  float* out_raw;       // fp32 residual stream after the unit (may alias skip), or null
-  void* out_act;        // activated output, bf16 (fp32 if act_f32): NOT the buffer x lives in (neighbouring tiles read x's halo rows)
-  int act_f32;
-  int epi_direct;       // the round-3 epilogue (a lane owns 4 channels of one frame: 64-byte pieces of the stream); 0 on every launch (measured A/B path)
-  const float* alpha_in;  // XIN instances: [alpha | 1 / (alpha + 1e-9)] of the Snake that turns the fp32 stream `a.x` into this unit's input activation
-};
-
-// dynamic LDS of resunit_lds_kernel<NW>: the two slab buffers of phase A, overlaid by the y tile [128 frames][C bf16 + pad] of phase B
-// (NW = 8, C = 384: 100 KB - above the 64 KB a static __shared__ array may declare, hence dynamic for every instance)
-template <int NW, int KS = 1> struct ResunitLds {
-  static constexpr int C = NW * 3 * 16, slabs = 2 * (128 + 54) * (KS * 64 + 32), ytile = 128 * (C * 2 + 32);
-  static constexpr int etile = 64 * (C * 4 + 16);  // epilogue: half of the output tile as fp32 rows (16 bytes of padding: the 16 frames of one store hit 16 different bank groups)
-  static constexpr int ain = slabs + 2 * C * 4;  // XIN instances: the input Snake's [alpha | 1 / alpha] behind the two slabs
-  static constexpr int bytes0 = ain > ytile ? ain : ytile;
-  static constexpr int bytes = bytes0 > etile ? bytes0 : etile;
-};
-// KS: 32-channel k-steps per staged chunk (1: 64-byte slab rows, the round-3 form; 2 for C >= 192: twice the bytes in flight per staging
-// round and twice the MFMA work to hide them behind - the units ran latency x concurrency-bound at ~2.7 TB/s with ~12-16 KB in flight per workgroup)
-// WD: how many k-steps ahead a wave requests its weight fragments (1: two register sets, the round-3 form; 3: four sets). A k-step is 24 MFMAs
-// = 384 cycles per wave, ~770 with the SIMD's second wave interleaved: one step ahead is ~0.3 us, less than an L2 round trip - and the
-// fragments DO come from the L2 every time (a wave re-streams its 3 strips x 7 taps x C channels = 129 KB at C = 192 per tile through a
-// 32 KB L1 shared by 8 waves), so every k-step waited for its weights: MFMA pipe 23-28 % busy (profiles/r03_pmc_dac_mfma.txt).
-// RAW / F32 (round 5): does the launch write the fp32 stream, and is the activation written as fp32 (the unit feeding the final conv)? Compile-time,
-// so that the epilogue's pass over a whole half tile is ONE straight-line block (see there).
-// XIN / ACT (round 6): the codec is HBM-bound at batch 32 (profiles/r06_pmc_dac_bs32.txt: 195.7 GB per decode, the C = 96 units at 4.5-4.6 TB/s), so bytes
-// are what is left to cut. An XIN unit takes its input straight from the fp32 residual stream (`a.x` = `skip`): the Snake of the PREVIOUS layer's
-// output is evaluated on the way into the LDS slab (same function on the same fp32 values, rounded to bf16 once: bit-identical to reading the bf16
-// activation the producer would have written), and a producer whose consumer is an XIN unit does not write that activation at all (ACT = false):
-// per element and unit 12 C -> ~9.7 C bytes (halo rows of the stream are fp32 now, the bf16 copy is neither written nor read).
-template <int NW, int KS = 1, int WD = 3, bool RAW = true, bool F32 = false, bool XIN = false, bool ACT = true>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) resunit_lds_kernel(ResArgs ra) {
-  constexpr int CSW = 3, FT = 8, TF = FT * 16, MAXHALO = 54;
-  constexpr int C = NW * CSW * 16;
-  constexpr int KCH = 32 * KS, RS = KS * 64 + 32, SL = KS * 4, NT = NW * 64;
-  constexpr int MAXROWS = TF + MAXHALO;
-  constexpr int NST = (MAXROWS * SL + NT - 1) / NT;
-  constexpr int RS2 = C * 2 + 32;  // y tile row stride: an odd multiple of 32 bytes, conflict-free ds_read_b128 like the slab
-  constexpr int NK1 = C / 32;      // k-steps of the k1 GEMM
-  static_assert(ResunitLds<NW, KS>::bytes >= 2 * MAXROWS * RS && ResunitLds<NW, KS>::bytes >= TF * RS2, "LDS size");
-  static_assert(C % KCH == 0, "chunk width");
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const ConvArgs& a = ra.a;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int q = lane >> 4, j = lane & 15;
-  const int ntile = (a.Tn + TF - 1) / TF;
-  const int tile = blockIdx.x % ntile, b = blockIdx.x / ntile;
-  const int strip0 = wave * CSW;
-  const int cpt = C / 32, nk = a.ntaps * cpt;
-  constexpr int nchunk = C / KCH;
-  constexpr int NS = 7 * KS;  // k-steps per chunk (the unit's first conv is k7: run_resunit)
-  const int t0 = tile * TF;
-  const int Tv = valid_rows(a, b);  // ragged decode: this utterance's rows (workgroup-uniform)
-  if (t0 >= Tv) return;
-  const int o0 = -a.pad;
-  const int halo = (a.ntaps - 1) * a.dil;
+  // slab row r holds input frame t0 + o0 + r; tap `tap` of output frame t0 + f reads row f + rel(tap)
+  const bool tr = !K7 && a.transposed;
+  const int o0 = tr ? (ph + a.pad) / a.nphase - (a.ntaps - 1) : -a.pad;
+  const int halo = tr ? a.ntaps - 1 : (a.ntaps - 1) * a.dil;
   const int nslot = (TF + halo) * SL;
-  const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)b * a.Tin * C * (XIN ? 4 : 2);
-  float* s_ain = reinterpret_cast<float*>(lds + 2 * MAXROWS * RS);  // XIN: [2][C]
-  if constexpr (XIN) {
-    for (int i = tid; i < 2 * C / 4; i += NT) reinterpret_cast<float4*>(s_ain)[i] = reinterpret_cast<const float4*>(ra.alpha_in)[i];
-    __syncthreads();
-  }
-  const float4* Wp = reinterpret_cast<const float4*>(a.Wp) + (size_t)strip0 * nk * 64 + lane;
   const int lrow = j * RS + q * 16;
-  unsigned char* slab0 = lds;
-  unsigned char* slab1 = lds + MAXROWS * RS;
 
-  f32x4 acc[CSW][FT];
-#pragma unroll
-  for (int s = 0; s < CSW; ++s)
-#pragma unroll
-    for (int f = 0; f < FT; ++f) acc[s][f] = f32x4{0, 0, 0, 0};
-
-  // a staged 16-byte slot = 8 bf16 channels of one frame: 16 bytes of the bf16 activation, or (XIN) 32 bytes of the fp32 stream that become those 16
-  // bytes at commit time (Snake, rounded once); rows outside the utterance read as zeros either way (Snake(0) = 0: the conv's zero padding)
   uint4 stg[XIN ? 2 * NST : NST];
-#define RU_SLAB_FETCH(CC)                                                                                               \
+#define PTTS_SLAB_FETCH(C)                                                                                              \
   _Pragma("unroll") for (int i_ = 0; i_ < NST; ++i_) {                                                                    \
     const int idx_ = tid + i_ * NT, r_ = idx_ / SL, sl_ = idx_ - r_ * SL, ti_ = t0 + o0 + r_;                              \
     const bool ok_ = idx_ < nslot && ti_ >= 0 && ti_ < Tv;                                                                \
     if constexpr (XIN) {                                                                                                  \
       stg[2 * i_] = make_uint4(0, 0, 0, 0); stg[2 * i_ + 1] = make_uint4(0, 0, 0, 0);                                     \
       if (ok_) {                                                                                                          \
-        const uint4* p_ = reinterpret_cast<const uint4*>(xb + ((size_t)ti_ * C + (size_t)(CC) * KCH) * 4 + sl_ * 32);     \
+        const uint4* p_ = reinterpret_cast<const uint4*>(xb + ((size_t)ti_ * Cin + (size_t)(C) * KCH) * 4 + sl_ * 32);    \
         stg[2 * i_] = p_[0]; stg[2 * i_ + 1] = p_[1];                                                                     \
       }                                                                                                                   \
     } else {                                                                                                              \
       stg[i_] = make_uint4(0, 0, 0, 0);                                                                                   \
-      if (ok_) stg[i_] = *reinterpret_cast<const uint4*>(xb + ((size_t)ti_ * C + (size_t)(CC) * KCH) * 2 + sl_ * 16);     \
+      if (ok_) stg[i_] = *reinterpret_cast<const uint4*>(xb + ((size_t)ti_ * Cin + (size_t)(C) * KCH) * 2 + sl_ * 16);    \
     }                                                                                                                     \
   }
-#define RU_SLAB_COMMIT(BUFP, CC)                                                                                        \
+#define PTTS_SLAB_COMMIT(BUFP, C)                                                                                       \
   {                                                                                                                     \
     float4 al0_, al1_, ia0_, ia1_;                                                                                        \
-    if constexpr (XIN) {  /* the thread's slot column is the same for every i_ (NT % SL == 0): 8 channels of chunk CC */   \
-      const float* ap_ = s_ain + (CC) * KCH + (tid % SL) * 8;                                                             \
+    if constexpr (XIN) {  /* the thread's slot column is the same for every i_ (NT % SL == 0): 8 channels of chunk C */    \
+      const float* ap_ = s_ain + (C) * KCH + (tid % SL) * 8;                                                              \
       al0_ = *reinterpret_cast<const float4*>(ap_); al1_ = *reinterpret_cast<const float4*>(ap_ + 4);                      \
-      ia0_ = *reinterpret_cast<const float4*>(ap_ + C); ia1_ = *reinterpret_cast<const float4*>(ap_ + C + 4);              \
+      ia0_ = *reinterpret_cast<const float4*>(ap_ + Cin); ia1_ = *reinterpret_cast<const float4*>(ap_ + Cin + 4);          \
     }                                                                                                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < NST; ++i_) {                                                                  \
       const int idx_ = tid + i_ * NT, r_ = idx_ / SL, sl_ = idx_ - r_ * SL;                                                \
@@ -565,37 +250,42 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2,
       if (idx_ < nslot) *reinterpret_cast<uint4*>((BUFP) + r_ * RS + sl_ * 16) = v_;                                       \
     }                                                                                                                     \
   }
-#define RU_W_FETCH(WF, CC, S)                                                                                           \
+  // weight fragments of global k-step G = chunk * NS + step: ks = tap * cpt + chunk * KS + kk
+#define PTTS_W_FETCH(WF, G)                                                                                             \
+  do {                                                                                                                  \
+    const int c_ = (G) / NS, s_ = (G) - c_ * NS, tap_ = s_ / KS, kk_ = s_ - tap_ * KS;                                    \
+    const float4* wp_ = Wp + (size_t)(tap_ * cpt + c_ * KS + kk_) * 64;                                                   \
+    _Pragma("unroll") for (int w_ = 0; w_ < CSW; ++w_) WF[w_] = wp_[(size_t)w_ * nk * 64];                               \
+  } while (0)
+  // B fragments (HF frame tiles from F0) of step S out of buffer SB
+#define PTTS_B_FETCH(BV, SB, S, F0)                                                                                     \
   do {                                                                                                                  \
     const int tap_ = (S) / KS, kk_ = (S) - tap_ * KS;                                                                     \
-    const float4* wp_ = Wp + (size_t)(tap_ * cpt + (CC) * KS + kk_) * 64;                                                 \
-    _Pragma("unroll") for (int s_ = 0; s_ < CSW; ++s_) WF[s_] = wp_[(size_t)s_ * nk * 64];                               \
+    const int rel_ = tr ? (a.ntaps - 1 - tap_) : tap_ * a.dil;                                                            \
+    const unsigned char* sp_ = (SB) + (rel_ + (F0) * 16) * RS + kk_ * 64 + lrow;                                          \
+    _Pragma("unroll") for (int f_ = 0; f_ < HF; ++f_) BV[f_] = *reinterpret_cast<const uint4*>(sp_ + f_ * 16 * RS);       \
   } while (0)
-#define RU_B_FETCH(BV, SB, S, F0)                                                                                       \
-  do {                                                                                                                  \
-    const int tap_ = (S) / KS, kk_ = (S) - tap_ * KS;                                                                     \
-    const unsigned char* sp_ = (SB) + (tap_ * a.dil + (F0) * 16) * RS + kk_ * 64 + lrow;                                  \
-    _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_) BV[f_] = *reinterpret_cast<const uint4*>(sp_ + f_ * 16 * RS);       \
-  } while (0)
-#define RU_MFMA_HALF(WC, BV, F0)                                                                                        \
-  _Pragma("unroll") for (int f_ = 0; f_ < 4; ++f_) _Pragma("unroll") for (int s_ = 0; s_ < CSW; ++s_)                      \
+#define PTTS_MFMA_HALF(WC, BV, F0)                                                                                      \
+  _Pragma("unroll") for (int f_ = 0; f_ < HF; ++f_) _Pragma("unroll") for (int s_ = 0; s_ < CSW; ++s_)                     \
     acc[s_][(F0) + f_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, WC[s_]), __builtin_bit_cast(bf16x8, BV[f_]), acc[s_][(F0) + f_], 0, 0, 0);
-#define RU_STEP(WC, WN)                                                                                                 \
+  // One k-step: MFMAs of (chunk c, step st) with the weight fragments WC while WN receives those of k-step gi + WD (possibly of a later chunk).
+  // That fetch is unconditional (a valid re-fetch of the last k-step at the very end): a branch here would merge into a conservative vmcnt on
+  // the MFMAs below. The last step of a chunk commits the staged slab and holds the chunk's barrier.
+#define PTTS_STEP(WC, WN)                                                                                               \
   {                                                                                                                     \
-    const unsigned char* sb_ = (c & 1) ? slab1 : slab0;                                                                   \
-    unsigned char* nb_ = (c & 1) ? slab0 : slab1;                                                                         \
+    const unsigned char* sb_ = slab + (c & 1) * (MAXROWS * RS);                                                           \
+    unsigned char* nb_ = slab + ((c + 1) & 1) * (MAXROWS * RS);                                                           \
     const bool more_ = c + 1 < nchunk, lastst_ = st + 1 == NS;                                                            \
-    const int gn_ = min(gi + WD, total - 1); /* unconditional (a valid re-fetch at the very end): a branch here would */   \
-    if (st == 0 && more_) { RU_SLAB_FETCH(c + 1); } /* merge into a conservative vmcnt on the MFMAs below */             \
-    RU_W_FETCH(WN, gn_ / NS, gn_ % NS);                                                                                   \
-    RU_B_FETCH(bB, sb_, st, 4);                                                                                           \
-    RU_MFMA_HALF(WC, bA, 0)                                                                                               \
-    if (!lastst_) RU_B_FETCH(bA, sb_, st + 1, 0);                                                                         \
-    RU_MFMA_HALF(WC, bB, 4)                                                                                               \
+    if (st == 0 && more_) { PTTS_SLAB_FETCH(c + 1); }                                                                     \
+    PTTS_W_FETCH(WN, min(gi + WD, total - 1));                                                                            \
+    PTTS_B_FETCH(bB, sb_, st, HF);                                                                                        \
+    PTTS_MFMA_HALF(WC, bA, 0)                                                                                             \
+    if (!lastst_) PTTS_B_FETCH(bA, sb_, st + 1, 0);                                                                       \
+    PTTS_MFMA_HALF(WC, bB, HF)                                                                                            \
     if (lastst_) {                                                                                                        \
-      if (more_) { RU_SLAB_COMMIT(nb_, c + 1); }                                                                          \
+      if (more_) { PTTS_SLAB_COMMIT(nb_, c + 1); }                                                                        \
       __syncthreads();                                                                                                    \
-      if (more_) RU_B_FETCH(bA, nb_, 0, 0);                                                                               \
+      if (more_) PTTS_B_FETCH(bA, nb_, 0, 0);                                                                             \
       ++c;                                                                                                                \
       st = 0;                                                                                                             \
     } else {                                                                                                              \
@@ -603,38 +293,250 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2,
     }                                                                                                                     \
     ++gi;                                                                                                                 \
   }
-  constexpr int total = nchunk * NS;
-  float4 w0[CSW], w1[CSW], w2[CSW], w3[CSW];
-  uint4 bA[4], bB[4];
-  RU_W_FETCH(w0, 0, 0);
+  float4 w0[CSW], w1[CSW], w2[CSW], w3[CSW];  // WD = 3: k-step g computes out of w[g % 4] while the fragments of k-step g + 3 land in w[(g + 3) % 4]
+  uint4 bA[HF], bB[HF];
+  PTTS_W_FETCH(w0, 0);
   if constexpr (WD == 3) {
-    RU_W_FETCH(w1, (1 < total ? 1 : 0) / NS, (1 < total ? 1 : 0) % NS);
-    RU_W_FETCH(w2, (2 < total ? 2 : 0) / NS, (2 < total ? 2 : 0) % NS);
+    PTTS_W_FETCH(w1, min(1, total - 1));
+    PTTS_W_FETCH(w2, min(2, total - 1));
   }
-  RU_SLAB_FETCH(0);
-  RU_SLAB_COMMIT(slab0, 0);
+  PTTS_SLAB_FETCH(0);
+  PTTS_SLAB_COMMIT(slab, 0);
   __syncthreads();
-  RU_B_FETCH(bA, slab0, 0, 0);
+  PTTS_B_FETCH(bA, slab, 0, 0);
   int c = 0, st = 0, gi = 0;
-  if constexpr (WD == 3) {  // four register sets: k-step g computes out of w[g % 4] while the fragments of k-step g + 3 land in w[(g + 3) % 4]
+  if constexpr (WD == 3) {
     for (int g = 0; g < total; g += 4) {
-      RU_STEP(w0, w3)
-      if (g + 1 < total) RU_STEP(w1, w0)
-      if (g + 2 < total) RU_STEP(w2, w1)
-      if (g + 3 < total) RU_STEP(w3, w2)
+      PTTS_STEP(w0, w3)
+      if (g + 1 < total) PTTS_STEP(w1, w0)
+      if (g + 2 < total) PTTS_STEP(w2, w1)
+      if (g + 3 < total) PTTS_STEP(w3, w2)
     }
   } else {
     for (int g = 0; g < total; g += 2) {
-      RU_STEP(w0, w1)
-      if (g + 1 < total) RU_STEP(w1, w0)
+      PTTS_STEP(w0, w1)
+      if (g + 1 < total) PTTS_STEP(w1, w0)
     }
   }
-#undef RU_STEP
-#undef RU_MFMA_HALF
-#undef RU_B_FETCH
-#undef RU_W_FETCH
-#undef RU_SLAB_COMMIT
-#undef RU_SLAB_FETCH
+#undef PTTS_STEP
+#undef PTTS_MFMA_HALF
+#undef PTTS_B_FETCH
+#undef PTTS_W_FETCH
+#undef PTTS_SLAB_COMMIT
+#undef PTTS_SLAB_FETCH
+}
+
+// LDS-tiled variant of the bf16-operand kernel for the stride-1 layers of the 44.1 kHz stack (k7 dilated convs, k1 convs,
+// the 2-tap phases of the transposed convs): the kernel above fetches every activation fragment from L1/L2 once per TAP and
+// every weight fragment once per WAVE (10 KB per wave per 256 MFMA cycles = 160 B/clk/CU asked of a 64 B/clk L1), and ran at
+// 10 % of the bf16 MFMA peak. Here a workgroup owns 128 consecutive frames x NW*CSW 16-channel strips:
+//   * the activation slab of one KCH-channel chunk ([128 + halo] rows x KCH bf16, KCH = 32 * KS) is staged ONCE into LDS and read by all
+//     taps (7x fewer global reads) and all waves; rows are RS = KCH*2 + 32 bytes apart: RS/32 is odd, so the 16 lanes of each
+//     ds_read_b128 service group land on 16 distinct 16-byte bank slots for ANY row base (the tap offset tap*dil is arbitrary);
+//   * waves split the output strips (CSW each) and share the frames, so every wave's weight fragments are its own: CSW KB
+//     per wave per k-step from L2/L1 (24 B/clk/CU at CSW = 3), prefetched three k-steps ahead in registers, also across chunks;
+//   * two LDS buffers, one barrier per chunk, B fragments in two halves: slab_mfma_loop above, shared with resunit_lds_kernel.
+// Per k-step and wave: 24 MFMAs 16x16x32 (384 cycles) against 8 ds_read_b128 + 3 global 16-B loads.
+// MAXHALO: the largest (ntaps - 1) * dil the instance serves (sizes the slab).
+// FT (round 5): 16-frame tiles per workgroup - 8 (128 frames), or 4 where 128-frame tiles leave the launch with fewer than two workgroups per CU (the
+// first block of a single utterance: 56-224 workgroups on 256 CUs; the short windows of the streamer). Same k order per output: bit-identical.
+template <int CSW, int NW, int KS, int MAXHALO, int FT = 8>
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) conv_lds_kernel(ConvArgs a) {
+  constexpr int TF = FT * 16, RS = KS * 64 + 32, NT = NW * 64, MAXROWS = TF + MAXHALO;  // as slab_mfma_loop's
+  __shared__ __attribute__((aligned(16))) unsigned char slab[2][MAXROWS * RS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = lane >> 4, j = lane & 15;
+  const int ntile = (a.Tn + TF - 1) / TF;
+  // (round 6, profiles/r06_dac_up_order_ab.txt: the phases of a transposed conv as neighbours in ONE XCD's queue - sharing its L2 copy of the input tile -
+  //  or the phase as the slowest index - one phase's weights L2-resident at a time - measured equal to this order, 54.2-54.7 vs 53.8-54.2 ms per batch-32
+  //  decode, bit-identical: the re-fetched bytes the PMC table shows for these layers do not cost time. Not kept.)
+  const int tile = blockIdx.x % ntile, ph = (blockIdx.x / ntile) % a.nphase, b = blockIdx.x / (ntile * a.nphase);
+  const int nstrips = a.Cout / 16;
+  const int strip0 = (blockIdx.y * NW + wave) * CSW;
+  const int nk = a.ntaps * (a.Cin / 32);
+  const int t0 = tile * TF;
+  const int Tv = valid_rows(a, b), Tnv = a.lens ? Tv : a.Tn;  // ragged decode: this utterance's rows (workgroup-uniform)
+  if (t0 >= Tnv) return;
+  const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)b * a.Tin * a.Cin * 2;
+  const float4* Wp = reinterpret_cast<const float4*>(a.Wp) + ((size_t)ph * nstrips + strip0) * nk * 64 + lane;
+
+  f32x4 acc[CSW][FT];
+#pragma unroll
+  for (int s = 0; s < CSW; ++s)
+#pragma unroll
+    for (int f = 0; f < FT; ++f) acc[s][f] = f32x4{0, 0, 0, 0};
+  slab_mfma_loop<CSW, NW, KS, FT, MAXHALO, 3, false, 0>(acc, &slab[0][0], nullptr, a, xb, Wp, nk, t0, Tv, ph);
+  const int Tout = a.Tn * a.nphase;
+  // epilogue through LDS (as resunit_lds_kernel's): the workgroup's output tile [128 frames][NW * 48 channels] goes through the slab
+  // memory in passes of EF frames as fp32 rows, and every lane then moves 16 CONSECUTIVE bytes of a row (a row of the tile = NW * 192 bytes of
+  // an output row; the rows of a transposed conv's phase are `nphase` rows apart). Why not straight out of the accumulators: DESIGN.md §5.
+  constexpr int CW = NW * CSW * 16, RSE = CW * 4 + 16, SLB = 2 * MAXROWS * RS, VPR = CW / 4;
+  constexpr int EF0 = SLB / RSE;
+  constexpr int EF1 = EF0 >= 128 ? 128 : (EF0 >= 64 ? 64 : (EF0 >= 32 ? 32 : 16)), EF = EF1 > TF ? TF : EF1, TPP = EF / 16;
+  static_assert(EF0 >= 16, "one 16-frame pass of the output tile fits the slab memory");
+  unsigned char* et = &slab[0][0];  // the last chunk's barrier has retired every slab read
+  const int c0 = blockIdx.y * CW;
+  // Round 5 (as resunit_lds_kernel's epilogue): the Snake parameters of this workgroup's CW channels go through LDS, and a pass over EF whole
+  // rows is ONE straight-line block per (residual?, stream?, activation format) - no load from global memory and no branch between the stores,
+  // so no s_waitcnt vmcnt(0) (= "until my last stores are acknowledged") in front of every row piece.
+  constexpr int NPT = EF * VPR / NT;
+  static_assert(EF * VPR % NT == 0, "row pieces per thread and pass");
+  int tid_e = tid;  // an opaque copy for the epilogue's address arithmetic: computed from `tid` it is hoisted above the MFMA loop and spilled there
+  asm volatile("" : "+v"(tid_e));
+  static_assert(EF * RSE + 2 * CW * 4 <= SLB, "LDS: one pass of the output tile + the Snake parameters");
+  float* s_al = reinterpret_cast<float*>(et + EF * RSE);  // [2][CW]: alpha | 1 / (alpha + 1e-9)
+  if (a.out_act)
+    for (int i = tid; i < 2 * VPR; i += NT) {
+      const int hf = i / VPR, c4 = i - hf * VPR;
+      reinterpret_cast<float4*>(s_al)[i] = *reinterpret_cast<const float4*>(a.alpha + (size_t)hf * a.Cout + c0 + c4 * 4);
+    }
+  typedef std::integral_constant<int, 0> I0_;
+  typedef std::integral_constant<int, 1> I1_;
+  typedef std::integral_constant<int, 2> I2_;
+  auto pass = [&](auto skip_c, auto raw_c, auto act_c, const int r0, const int rows) __attribute__((always_inline)) {
+    constexpr bool SK = decltype(skip_c)::value != 0, RW = decltype(raw_c)::value != 0;
+    constexpr int AC = decltype(act_c)::value;  // 0: no activation output, 1: bf16, 2: fp32
+    auto offs = [&](const int i) { const int rr = i / VPR, cv = i - rr * VPR; return ((size_t)b * Tout + (size_t)(r0 + rr) * a.nphase + ph) * a.Cout + c0 + cv * 4; };
+    auto piece = [&](const int i, const size_t o, const float4 sk) __attribute__((always_inline)) {
+      const int rr = i / VPR, cv = i - rr * VPR;
+      float4 v = *reinterpret_cast<const float4*>(et + rr * RSE + cv * 16);
+      if constexpr (SK) { v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w; }
+      if constexpr (RW) *reinterpret_cast<float4*>(a.out_raw + o) = v;
+      if constexpr (AC != 0) {
+        const float4 al = *reinterpret_cast<const float4*>(s_al + cv * 4), ia = *reinterpret_cast<const float4*>(s_al + CW + cv * 4);
+        const float4 sv = make_float4(snake_f<true>(v.x, al.x, ia.x), snake_f<true>(v.y, al.y, ia.y), snake_f<true>(v.z, al.z, ia.z), snake_f<true>(v.w, al.w, ia.w));
+        if constexpr (AC == 1) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.out_act) + o) = make_uint2(pack_bf16x2(sv.x, sv.y), pack_bf16x2(sv.z, sv.w));
+        else *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out_act) + o) = sv;
+      }
+    };
+    if (rows == EF) {
+      constexpr int GP = NPT > 6 ? 6 : NPT;  // residual values in flight per group (registers: acc is still live for the next pass)
+      static_assert(NPT % GP == 0, "row pieces per group");
+#pragma unroll
+      for (int k0 = 0; k0 < NPT; k0 += GP) {
+        float4 skp[SK ? GP : 1];
+        if constexpr (SK) {
+#pragma unroll
+          for (int k = 0; k < GP; ++k) skp[k] = *reinterpret_cast<const float4*>(a.skip + offs(tid_e + (k0 + k) * NT));
+        }
+#pragma unroll
+        for (int k = 0; k < GP; ++k) piece(tid_e + (k0 + k) * NT, offs(tid_e + (k0 + k) * NT), SK ? skp[SK ? k : 0] : make_float4(0.f, 0.f, 0.f, 0.f));
+      }
+    } else {
+#pragma unroll 2
+      for (int k = 0; k < NPT; ++k) {
+        const int i = tid_e + k * NT;
+        if (i / VPR < rows) {
+          const size_t o = offs(i);
+          float4 sk = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (SK) sk = *reinterpret_cast<const float4*>(a.skip + o);
+          piece(i, o, sk);
+        }
+      }
+    }
+  };
+  auto by_act = [&](auto skip_c, auto raw_c, const int r0, const int rows) __attribute__((always_inline)) {
+    if (!a.out_act) pass(skip_c, raw_c, I0_(), r0, rows);
+    else if (a.act_f32) pass(skip_c, raw_c, I2_(), r0, rows);
+    else pass(skip_c, raw_c, I1_(), r0, rows);
+  };
+  // (explicitly instantiated per pass: inside a `#pragma unroll` loop the dispatch below stopped the unroller and `acc` went to scratch)
+  auto do_pass = [&](auto p0_c) __attribute__((always_inline)) {
+    constexpr int p0 = decltype(p0_c)::value;
+    if constexpr (p0 < FT) {
+#pragma unroll
+    for (int s = 0; s < CSW; ++s) {
+      const float4 bs = *reinterpret_cast<const float4*>(a.bias + (strip0 + s) * 16 + q * 4);
+#pragma unroll
+      for (int f = 0; f < TPP; ++f) {
+        const f32x4 av = acc[s][p0 + f];
+        *reinterpret_cast<float4*>(et + (f * 16 + j) * RSE + ((wave * CSW + s) * 16 + q * 4) * 4) = make_float4(av[0] + bs.x, av[1] + bs.y, av[2] + bs.z, av[3] + bs.w);
+      }
+    }
+    __syncthreads();
+    const int r0 = t0 + p0 * 16, rows = min(EF, Tnv - r0);
+    if (a.skip) { if (a.out_raw) by_act(I1_(), I1_(), r0, rows); else by_act(I1_(), I0_(), r0, rows); }
+    else { if (a.out_raw) by_act(I0_(), I1_(), r0, rows); else by_act(I0_(), I0_(), r0, rows); }
+    if (p0 + TPP < FT) __syncthreads();  // the tile memory is rewritten by the next pass
+    }
+  };
+  do_pass(std::integral_constant<int, 0>()); do_pass(std::integral_constant<int, TPP>()); do_pass(std::integral_constant<int, 2 * TPP>());
+  do_pass(std::integral_constant<int, 3 * TPP>()); do_pass(std::integral_constant<int, 4 * TPP>()); do_pass(std::integral_constant<int, 5 * TPP>());
+  do_pass(std::integral_constant<int, 6 * TPP>()); do_pass(std::integral_constant<int, 7 * TPP>());
+}
+
+// Fused residual unit (default; PTTS_DAC_NO_FUSE_RES=1 restores the two-launch path for A/B): one residual unit of the three narrower blocks
+// (C = 384 / 192 / 96) in ONE launch (measured on MI355X, profiles/r03_experiments.txt: 860 frames 3.62 -> 3.25 ms, batch 32 109.4 -> 97.5 ms):
+//   y = Snake_a(conv_k7_dil(x) + b7)  ->  bf16 tile in LDS  ->  out = skip + conv_k1(y) + b1 ; act = Snake_a1(out)
+// The workgroup owns all C channels of 128 frames (NW * 3 strips = C / 16), so the k1 GEMM's operand never leaves the CU: the unit's
+// HBM traffic drops from 16 to 12 bytes per element (no bf16 round trip of y) and one launch per unit goes away (per-layer table,
+// profiles/r02_dac_layers.txt: k7 + k1 = 339 us at C = 192, 260 us at C = 96, the k1 half bound by its epilogue traffic).
+// Phase A is slab_mfma_loop as conv_lds_kernel<3, NW, 1, 54> runs it; the y tile overlays the two slab buffers once the last chunk's barrier has passed.
+// weight prefetch depth (slab_mfma_loop's WD) of the XIN instances per width (registers: an XIN unit stages twice the bytes per slab slot)
+template <int NW> struct ResunitXinWD { static constexpr int value = NW == 2 ? 1 : 3; };
+struct ResArgs {
+  ConvArgs a;           // the k7 conv (x, Wp, bias, alpha = Snake between the two convs, dil, pad, B, Tin, Cin = Cout = C)
+  const void* Wp1;      // k1 weights, packed [C/16][C/32][64][8 bf16]
+  const float* bias1;
+  const float* alpha1;  // Snake of the unit's output (the next layer's input activation)
+  const float* skip;    // fp32 residual stream [B][T][C]
+  float* out_raw;       // fp32 residual stream after the unit (may alias skip), or null
+  void* out_act;        // activated output, bf16 (fp32 if act_f32): NOT the buffer x lives in (neighbouring tiles read x's halo rows)
+  int act_f32;
+  const float* alpha_in;  // XIN instances: [alpha | 1 / (alpha + 1e-9)] of the Snake that turns the fp32 stream `a.x` into this unit's input activation
+};
+
+// dynamic LDS of resunit_lds_kernel<NW>: the two slab buffers of phase A, overlaid by the y tile [128 frames][C bf16 + pad] of phase B
+// (NW = 8, C = 384: 100 KB - above the 64 KB a static __shared__ array may declare, hence dynamic for every instance)
+template <int NW> struct ResunitLds {
+  static constexpr int C = NW * 3 * 16, slabs = 2 * (128 + 54) * 96, ytile = 128 * (C * 2 + 32);
+  static constexpr int etile = 64 * (C * 4 + 16);  // epilogue: half of the output tile as fp32 rows (16 bytes of padding: the 16 frames of one store hit 16 different bank groups)
+  static constexpr int ain = slabs + 2 * C * 4;  // XIN instances: the input Snake's [alpha | 1 / alpha] behind the two slabs
+  static constexpr int bytes0 = ain > ytile ? ain : ytile;
+  static constexpr int bytes = bytes0 > etile ? bytes0 : etile;
+};
+// WD: how many k-steps ahead a wave requests its weight fragments (slab_mfma_loop: 3, or 1 for the XIN instances at C = 96).
+// RAW / F32 (round 5): does the launch write the fp32 stream, and is the activation written as fp32 (the unit feeding the final conv)? Compile-time,
+// so that the epilogue's pass over a whole half tile is ONE straight-line block (see there).
+// XIN / ACT (round 6): the codec is HBM-bound at batch 32 (profiles/r06_pmc_dac_bs32.txt: 195.7 GB per decode, the C = 96 units at 4.5-4.6 TB/s), so bytes
+// are what is left to cut. An XIN unit takes its input straight from the fp32 residual stream (`a.x` = `skip`): the Snake of the PREVIOUS layer's
+// output is evaluated on the way into the LDS slab (same function on the same fp32 values, rounded to bf16 once: bit-identical to reading the bf16
+// activation the producer would have written), and a producer whose consumer is an XIN unit does not write that activation at all (ACT = false):
+// per element and unit 12 C -> ~9.7 C bytes (halo rows of the stream are fp32 now, the bf16 copy is neither written nor read).
+template <int NW, int WD = 3, bool RAW = true, bool F32 = false, bool XIN = false, bool ACT = true>
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) resunit_lds_kernel(ResArgs ra) {
+  constexpr int CSW = 3, FT = 8, TF = FT * 16, MAXHALO = 54;
+  constexpr int C = NW * CSW * 16;
+  constexpr int RS = 96, NT = NW * 64, MAXROWS = TF + MAXHALO;  // slab_mfma_loop's at KS = 1: 32-channel chunks, 64-byte slab rows + 32
+  constexpr int RS2 = C * 2 + 32;  // y tile row stride: an odd multiple of 32 bytes, conflict-free ds_read_b128 like the slab
+  constexpr int NK1 = C / 32;      // k-steps of the k1 GEMM
+  static_assert(ResunitLds<NW>::bytes >= 2 * MAXROWS * RS && ResunitLds<NW>::bytes >= TF * RS2, "LDS size");
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const ConvArgs& a = ra.a;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = lane >> 4, j = lane & 15;
+  const int ntile = (a.Tn + TF - 1) / TF;
+  const int tile = blockIdx.x % ntile, b = blockIdx.x / ntile;
+  const int strip0 = wave * CSW;
+  const int nk = a.ntaps * (C / 32);
+  const int t0 = tile * TF;
+  const int Tv = valid_rows(a, b);  // ragged decode: this utterance's rows (workgroup-uniform)
+  if (t0 >= Tv) return;
+  const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)b * a.Tin * C * (XIN ? 4 : 2);
+  float* s_ain = reinterpret_cast<float*>(lds + 2 * MAXROWS * RS);  // XIN: [2][C]
+  if constexpr (XIN) {
+    for (int i = tid; i < 2 * C / 4; i += NT) reinterpret_cast<float4*>(s_ain)[i] = reinterpret_cast<const float4*>(ra.alpha_in)[i];
+    __syncthreads();
+  }
+  const float4* Wp = reinterpret_cast<const float4*>(a.Wp) + (size_t)strip0 * nk * 64 + lane;
+
+  f32x4 acc[CSW][FT];
+#pragma unroll
+  for (int s = 0; s < CSW; ++s)
+#pragma unroll
+    for (int f = 0; f < FT; ++f) acc[s][f] = f32x4{0, 0, 0, 0};
+  // ---- phase A: the k7 conv (the unit's first conv is k7: run_resunit), k-steps and chunks known at compile time
+  slab_mfma_loop<CSW, NW, 1, FT, MAXHALO, WD, XIN, C>(acc, lds, s_ain, a, xb, Wp, nk, t0, Tv, 0);
   // ---- phase A epilogue: y = Snake(acc + b7) as bf16 into the LDS tile [frame][C] (the loop's last barrier has retired every slab read)
   unsigned char* ytile = lds;
   auto put_y = [&](const f32x4 av, const int s, const int f) {
@@ -688,98 +590,71 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2,
     }
   }
   // ---- phase B epilogue: + bias + residual, fp32 stream out, Snake of the unit's output.
-  // Through LDS (default): a lane's accumulators are 4 channels of ONE frame, so the direct form below moves the fp32 stream in 64-byte pieces
-  // (rows C * 4 bytes apart) and ran the three fused units at 2.3-2.9 TB/s, 68 % of the batch-32 decode (profiles/r03_dac_kernels_bs32.txt).
-  // Here the output tile goes through LDS in two halves of 64 frames ([64][C fp32], rows padded by 16 bytes) and every lane then owns 16
-  // CONSECUTIVE bytes of a row: the residual read, the stream write and the activation write are whole rows (tools/epilogue_probe.hip on
-  // MI355X: 2.5-2.8 -> 3.9-5.1 TB/s with 64-frame tiles; 128-frame tiles do not pay). Same fp32 operations in the same order: bit-identical.
-  if (!ra.epi_direct) {
-    constexpr int RSE = C * 4 + 16, VPR = C / 4;
-    unsigned char* et = lds;
-    // The output Snake's [alpha | 1 / (alpha + 1e-9)] go through LDS (round 5): fetched from global memory inside the loop below, every iteration's
-    // s_waitcnt vmcnt() for them also waited for the STORES of the iteration before (loads and stores retire in order on one counter) - 24 store
-    // round trips in a row per workgroup, ~2/3 of the time the three fused units spent outside their MFMA loops (found in the ISA, not in a counter).
-    static_assert(ResunitLds<NW, KS>::bytes >= 64 * RSE + 2 * C * 4, "LDS: half output tile + the output Snake's parameters");
-    float* s_al = reinterpret_cast<float*>(lds + 64 * RSE);  // [2][C]
-    __syncthreads();  // every wave has finished reading the y tile
-    if constexpr (ACT)
-      for (int i = tid; i < 2 * C / 4; i += NT) reinterpret_cast<float4*>(s_al)[i] = reinterpret_cast<const float4*>(ra.alpha1)[i];
-    // (requesting the residual rows before the transposition, and the second half's as the first half's registers free up, measured SLOWER:
-    //  C = 96 unit 4228 -> 4735 us, profiles/r04_experiments.txt call 7; they are requested after the tile's barrier, 12 loads at once)
+  // Through LDS: a lane's accumulators are 4 channels of ONE frame, so stored straight from them the fp32 stream moves in 64-byte pieces
+  // (rows C * 4 bytes apart; that form and its figures: DESIGN.md §5). Here the output tile goes through LDS in two halves of 64 frames
+  // ([64][C fp32], rows padded by 16 bytes) and every lane then owns 16 CONSECUTIVE bytes of a row: the residual read, the stream write and
+  // the activation write are whole rows (tools/epilogue_probe.hip: 64-frame halves; 128-frame tiles do not pay).
+  constexpr int RSE = C * 4 + 16, VPR = C / 4;
+  unsigned char* et = lds;
+  // The output Snake's [alpha | 1 / (alpha + 1e-9)] go through LDS (round 5): fetched from global memory inside the loop below, every iteration's
+  // s_waitcnt vmcnt() for them also waited for the STORES of the iteration before (loads and stores retire in order on one counter) - 24 store
+  // round trips in a row per workgroup, ~2/3 of the time the three fused units spent outside their MFMA loops (found in the ISA, not in a counter).
+  static_assert(ResunitLds<NW>::bytes >= 64 * RSE + 2 * C * 4, "LDS: half output tile + the output Snake's parameters");
+  float* s_al = reinterpret_cast<float*>(lds + 64 * RSE);  // [2][C]
+  __syncthreads();  // every wave has finished reading the y tile
+  if constexpr (ACT)
+    for (int i = tid; i < 2 * C / 4; i += NT) reinterpret_cast<float4*>(s_al)[i] = reinterpret_cast<const float4*>(ra.alpha1)[i];
+  // (requesting the residual rows before the transposition, and the second half's as the first half's registers free up, measured SLOWER:
+  //  C = 96 unit 4228 -> 4735 us, profiles/r04_experiments.txt call 7; they are requested after the tile's barrier, 12 loads at once)
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
+  for (int hh = 0; hh < 2; ++hh) {
 #pragma unroll
-      for (int s = 0; s < CSW; ++s) {
-        const int co = (strip0 + s) * 16 + q * 4;
-        const float4 bs = *reinterpret_cast<const float4*>(ra.bias1 + co);
+    for (int s = 0; s < CSW; ++s) {
+      const int co = (strip0 + s) * 16 + q * 4;
+      const float4 bs = *reinterpret_cast<const float4*>(ra.bias1 + co);
 #pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          const f32x4 av = acc[s][hh * 4 + f];
-          *reinterpret_cast<float4*>(et + (f * 16 + j) * RSE + co * 4) = make_float4(av[0] + bs.x, av[1] + bs.y, av[2] + bs.z, av[3] + bs.w);
-        }
+      for (int f = 0; f < 4; ++f) {
+        const f32x4 av = acc[s][hh * 4 + f];
+        *reinterpret_cast<float4*>(et + (f * 16 + j) * RSE + co * 4) = make_float4(av[0] + bs.x, av[1] + bs.y, av[2] + bs.z, av[3] + bs.w);
       }
-      __syncthreads();
-      const int r0 = t0 + hh * 64;
-      const int rows = min(64, Tv - r0);
-      const size_t base = ((size_t)b * a.Tn + r0) * C;
-      // A whole half tile (every tile but an utterance's last) is ONE straight-line block: 12 unconditional residual loads, then per row piece
-      // LDS reads -> add -> store(s) -> Snake -> store, no load from global memory and no branch in between. With the stream / activation format
-      // decided by branches inside the loop (and the Snake parameters loaded from global memory there), the compiler's wait-count bookkeeping
-      // put an s_waitcnt vmcnt(0) - "until my last STORES are acknowledged", loads and stores retire in order on one counter - in front of every
-      // row piece: 24 store round trips in a row per workgroup.
-      auto piece = [&](const int k, const float4 sk) __attribute__((always_inline)) {
-        const int i = tid + k * NT;
-        const int rr = i / VPR, cv = i - rr * VPR;
-        const float4 av = *reinterpret_cast<const float4*>(et + rr * RSE + cv * 16);
-        const size_t o = base + (size_t)i * 4;  // the rows of a tile are contiguous in memory: i * 4 == rr * C + cv * 4
-        const float4 v = make_float4(av.x + sk.x, av.y + sk.y, av.z + sk.z, av.w + sk.w);
-        if constexpr (RAW) *reinterpret_cast<float4*>(ra.out_raw + o) = v;
-        if constexpr (ACT) {  // ACT = false: the consumer is an XIN unit and evaluates this Snake itself, out of the stream
-          const float4 al = *reinterpret_cast<const float4*>(s_al + cv * 4), ia = *reinterpret_cast<const float4*>(s_al + C + cv * 4);
-          const float4 sv = make_float4(snake_f<true>(v.x, al.x, ia.x), snake_f<true>(v.y, al.y, ia.y), snake_f<true>(v.z, al.z, ia.z), snake_f<true>(v.w, al.w, ia.w));
-          if constexpr (!F32) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(ra.out_act) + o) = make_uint2(pack_bf16x2(sv.x, sv.y), pack_bf16x2(sv.z, sv.w));
-          else *reinterpret_cast<float4*>(reinterpret_cast<float*>(ra.out_act) + o) = sv;
-        }
-      };
-      if (rows == 64) {
-        const float* sb_ = ra.skip + base;
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) skp[k] = *reinterpret_cast<const float4*>(sb_ + (size_t)(tid + k * NT) * 4);
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) piece(k, skp[k]);
-      } else {
-        load_skip(hh);
-#pragma unroll
-        for (int k = 0; k < NPT; ++k)
-          if ((tid + k * NT) / VPR < rows) piece(k, skp[k]);
-      }
-      if (hh == 0) __syncthreads();  // the tile is rewritten by the second half
     }
-    return;
+    __syncthreads();
+    const int r0 = t0 + hh * 64;
+    const int rows = min(64, Tv - r0);
+    const size_t base = ((size_t)b * a.Tn + r0) * C;
+    // A whole half tile (every tile but an utterance's last) is ONE straight-line block: 12 unconditional residual loads, then per row piece
+    // LDS reads -> add -> store(s) -> Snake -> store, no load from global memory and no branch in between. With the stream / activation format
+    // decided by branches inside the loop (and the Snake parameters loaded from global memory there), the compiler's wait-count bookkeeping
+    // put an s_waitcnt vmcnt(0) - "until my last STORES are acknowledged", loads and stores retire in order on one counter - in front of every
+    // row piece: 24 store round trips in a row per workgroup.
+    auto piece = [&](const int k, const float4 sk) __attribute__((always_inline)) {
+      const int i = tid + k * NT;
+      const int rr = i / VPR, cv = i - rr * VPR;
+      const float4 av = *reinterpret_cast<const float4*>(et + rr * RSE + cv * 16);
+      const size_t o = base + (size_t)i * 4;  // the rows of a tile are contiguous in memory: i * 4 == rr * C + cv * 4
+      const float4 v = make_float4(av.x + sk.x, av.y + sk.y, av.z + sk.z, av.w + sk.w);
+      if constexpr (RAW) *reinterpret_cast<float4*>(ra.out_raw + o) = v;
+      if constexpr (ACT) {  // ACT = false: the consumer is an XIN unit and evaluates this Snake itself, out of the stream
+        const float4 al = *reinterpret_cast<const float4*>(s_al + cv * 4), ia = *reinterpret_cast<const float4*>(s_al + C + cv * 4);
+        const float4 sv = make_float4(snake_f<true>(v.x, al.x, ia.x), snake_f<true>(v.y, al.y, ia.y), snake_f<true>(v.z, al.z, ia.z), snake_f<true>(v.w, al.w, ia.w));
+        if constexpr (!F32) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(ra.out_act) + o) = make_uint2(pack_bf16x2(sv.x, sv.y), pack_bf16x2(sv.z, sv.w));
+        else *reinterpret_cast<float4*>(reinterpret_cast<float*>(ra.out_act) + o) = sv;
+      }
+    };
+    if (rows == 64) {
+      const float* sb_ = ra.skip + base;
+#pragma unroll
+      for (int k = 0; k < NPT; ++k) skp[k] = *reinterpret_cast<const float4*>(sb_ + (size_t)(tid + k * NT) * 4);
+#pragma unroll
+      for (int k = 0; k < NPT; ++k) piece(k, skp[k]);
+    } else {
+      load_skip(hh);
+#pragma unroll
+      for (int k = 0; k < NPT; ++k)
+        if ((tid + k * NT) / VPR < rows) piece(k, skp[k]);
+    }
+    if (hh == 0) __syncthreads();  // the tile is rewritten by the second half
   }
-  auto emit = [&](const f32x4 av, const int s, const int f) {
-    const int jj = t0 + f * 16 + j;
-    if (jj >= Tv) return;
-    const int co = (strip0 + s) * 16 + q * 4;
-    const float4 bs = *reinterpret_cast<const float4*>(ra.bias1 + co);
-    const size_t o = ((size_t)b * a.Tn + (size_t)jj) * C + co;
-    const float4 sk = *reinterpret_cast<const float4*>(ra.skip + o);
-    const float4 v = make_float4(av[0] + bs.x + sk.x, av[1] + bs.y + sk.y, av[2] + bs.z + sk.z, av[3] + bs.w + sk.w);
-    if (ra.out_raw) *reinterpret_cast<float4*>(ra.out_raw + o) = v;
-    if (ra.out_act) {
-      const float4 al = *reinterpret_cast<const float4*>(ra.alpha1 + co), ia = ld_inv4(ra.alpha1, C, co);
-      const float4 sv = make_float4(snake_f<true>(v.x, al.x, ia.x), snake_f<true>(v.y, al.y, ia.y), snake_f<true>(v.z, al.z, ia.z), snake_f<true>(v.w, al.w, ia.w));
-      if (!ra.act_f32) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(ra.out_act) + o) = make_uint2(pack_bf16x2(sv.x, sv.y), pack_bf16x2(sv.z, sv.w));
-      else *reinterpret_cast<float4*>(reinterpret_cast<float*>(ra.out_act) + o) = sv;
-    }
-  };
-#define RU_EMIT_ROW(S)                                                                                                  \
-  emit(acc[S][0], S, 0); emit(acc[S][1], S, 1); emit(acc[S][2], S, 2); emit(acc[S][3], S, 3);                             \
-  emit(acc[S][4], S, 4); emit(acc[S][5], S, 5); emit(acc[S][6], S, 6); emit(acc[S][7], S, 7);
-  RU_EMIT_ROW(0)
-  RU_EMIT_ROW(1)
-  RU_EMIT_ROW(2)
-#undef RU_EMIT_ROW
 }
 
 // final Conv1d(C -> 1, k7, pad 3) + tanh; weights [7][C] in LDS. One thread per OS = 4 consecutive output samples: the 10 input rows
@@ -1460,32 +1335,27 @@ static int run_conv(ptts_dac* d, const ConvLayer& L, const void* x, const float*
       return PTTS_OK;
     }
   }
+  // strips per wave: the largest of {8, 6, 4, 2, 1} that divides the layer (real DAC widths: 96/48/24/12/6 strips)
+  const int CS = nstrips % 8 == 0 ? 8 : (nstrips % 6 == 0 ? 6 : (nstrips % 4 == 0 ? 4 : (nstrips % 2 == 0 ? 2 : 1)));
   // waves per workgroup: fewer (finer tiles) when the launch would otherwise put < ~6 workgroups on each CU, so the
   // 256 CUs finish together (324 four-wave workgroups on 256 CUs = 63 % balance; 1296 one-wave ones = 84 %+)
   int nwb = 4;
-  {
-    const int CS0 = nstrips % 8 == 0 ? 8 : (nstrips % 6 == 0 ? 6 : (nstrips % 4 == 0 ? 4 : (nstrips % 2 == 0 ? 2 : 1)));
-    auto blocks = [&](int nw) { return (long long)((a.Tn + 32 * nw - 1) / (32 * nw)) * a.nphase * B * (nstrips / CS0); };
-    while (nwb > 1 && blocks(nwb) < 256LL * 6) nwb >>= 1;
-  }
+  auto blocks = [&](int nw) { return (long long)((a.Tn + 32 * nw - 1) / (32 * nw)) * a.nphase * B * (nstrips / CS); };
+  while (nwb > 1 && blocks(nwb) < 256LL * 6) nwb >>= 1;
   const int ntile = (a.Tn + 32 * nwb - 1) / (32 * nwb);
-  // strips per wave: the largest of {8, 6, 4, 2, 1} that divides the layer (real DAC widths: 96/48/24/12/6 strips)
-  const int CS = nstrips % 8 == 0 ? 8 : (nstrips % 6 == 0 ? 6 : (nstrips % 4 == 0 ? 4 : (nstrips % 2 == 0 ? 2 : 1)));
   const dim3 grid((unsigned)(ntile * a.nphase * B), (unsigned)(nstrips / CS));
   const dim3 blk(64 * nwb);
-  if (L.bf16) {
-    if (CS == 8) hipLaunchKernelGGL((conv_mfma_kernel<8, true>), grid, blk, 0, st, a);
-    else if (CS == 6) hipLaunchKernelGGL((conv_mfma_kernel<6, true>), grid, blk, 0, st, a);
-    else if (CS == 4) hipLaunchKernelGGL((conv_mfma_kernel<4, true>), grid, blk, 0, st, a);
-    else if (CS == 2) hipLaunchKernelGGL((conv_mfma_kernel<2, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((conv_mfma_kernel<1, true>), grid, blk, 0, st, a);
-  } else {
-    if (CS == 8) hipLaunchKernelGGL((conv_mfma_kernel<8, false>), grid, blk, 0, st, a);
-    else if (CS == 6) hipLaunchKernelGGL((conv_mfma_kernel<6, false>), grid, blk, 0, st, a);
-    else if (CS == 4) hipLaunchKernelGGL((conv_mfma_kernel<4, false>), grid, blk, 0, st, a);
-    else if (CS == 2) hipLaunchKernelGGL((conv_mfma_kernel<2, false>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((conv_mfma_kernel<1, false>), grid, blk, 0, st, a);
-  }
+#define PTTS_CONV_LAUNCH(CSV)                                                                     \
+  do {                                                                                            \
+    if (L.bf16) hipLaunchKernelGGL((conv_mfma_kernel<CSV, true>), grid, blk, 0, st, a);           \
+    else hipLaunchKernelGGL((conv_mfma_kernel<CSV, false>), grid, blk, 0, st, a);                 \
+  } while (0)
+  if (CS == 8) PTTS_CONV_LAUNCH(8);
+  else if (CS == 6) PTTS_CONV_LAUNCH(6);
+  else if (CS == 4) PTTS_CONV_LAUNCH(4);
+  else if (CS == 2) PTTS_CONV_LAUNCH(2);
+  else PTTS_CONV_LAUNCH(1);
+#undef PTTS_CONV_LAUNCH
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "conv launch failed: %s", hipGetErrorString(e));
   return PTTS_OK;
@@ -1532,9 +1402,9 @@ static int run_resunit(const ConvLayer& c7, const ConvLayer& c1, const void* x, 
     return ptts_fail(PTTS_E_INVALID, "residual unit on the stream: x must be the skip buffer, out_raw another one");
   if (act_f32 && c7.Cout != 96) return ptts_fail(PTTS_E_UNSUPPORTED, "residual unit: fp32 activations only at the last block's width");
 #define PTTS_RU_LAUNCH(NWV, RAWV, F32V) \
-  hipLaunchKernelGGL((resunit_lds_kernel<NWV, 1, 3, RAWV, F32V>), grid, dim3(NWV * 64), (ResunitLds<NWV, 1>::bytes), st, r)
+  hipLaunchKernelGGL((resunit_lds_kernel<NWV, 3, RAWV, F32V>), grid, dim3(NWV * 64), ResunitLds<NWV>::bytes, st, r)
 #define PTTS_RU_LAUNCH_XIN(NWV, RAWV, F32V, ACTV) \
-  hipLaunchKernelGGL((resunit_lds_kernel<NWV, 1, ResunitXinWD<NWV>::value, RAWV, F32V, true, ACTV>), grid, dim3(NWV * 64), (ResunitLds<NWV, 1>::bytes), st, r)
+  hipLaunchKernelGGL((resunit_lds_kernel<NWV, ResunitXinWD<NWV>::value, RAWV, F32V, true, ACTV>), grid, dim3(NWV * 64), ResunitLds<NWV>::bytes, st, r)
   // (stream written, activation written) of an XIN unit: (1, 0) units 1 and 2 of a block, (0, 1) unit 3, (1, 1) the parity probe's stop stage
 #define PTTS_RU_XIN_BY_OUT(NWV, F32V)                                   \
   do {                                                                  \
@@ -1547,12 +1417,12 @@ static int run_resunit(const ConvLayer& c7, const ConvLayer& c1, const void* x, 
     const int attr_dev = PttsPerDeviceOnce::device();
     if (attr_once.need(attr_dev)) {
       constexpr int WDX = ResunitXinWD<8>::value;
-      const void* fns[] = {reinterpret_cast<const void*>(&resunit_lds_kernel<8, 1, 3, true, false>), reinterpret_cast<const void*>(&resunit_lds_kernel<8, 1, 3, false, false>),
-                           reinterpret_cast<const void*>(&resunit_lds_kernel<8, 1, WDX, true, false, true, false>),
-                           reinterpret_cast<const void*>(&resunit_lds_kernel<8, 1, WDX, true, false, true, true>),
-                           reinterpret_cast<const void*>(&resunit_lds_kernel<8, 1, WDX, false, false, true, true>)};
+      const void* fns[] = {reinterpret_cast<const void*>(&resunit_lds_kernel<8, 3, true, false>), reinterpret_cast<const void*>(&resunit_lds_kernel<8, 3, false, false>),
+                           reinterpret_cast<const void*>(&resunit_lds_kernel<8, WDX, true, false, true, false>),
+                           reinterpret_cast<const void*>(&resunit_lds_kernel<8, WDX, true, false, true, true>),
+                           reinterpret_cast<const void*>(&resunit_lds_kernel<8, WDX, false, false, true, true>)};
       for (const void* fn : fns) {
-        const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ResunitLds<8, 1>::bytes);
+        const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ResunitLds<8>::bytes);
         if (ea != hipSuccess) return ptts_fail(PTTS_E_HIP, "hipFuncSetAttribute(max dynamic LDS) failed: %s", hipGetErrorString(ea));
       }
       attr_once.done(attr_dev);
