@@ -227,6 +227,190 @@ template <typename Op> __device__ __forceinline__ float wave_reduce(float v) {
 __device__ __forceinline__ float wave_sum(float v) { return wave_reduce<OpSum>(v); }
 __device__ __forceinline__ float wave_max(float v) { return wave_reduce<OpMax>(v); }
 
+// Both LayerNorm sums in ONE reduction tree: a permlane32 swap puts sum-halves of s1 in lanes 0-31 and of s2 in lanes
+// 32-63, five more steps finish both (6 dependent cross-lane ops instead of 12); read back with v_readlane.
+__device__ __forceinline__ void gv_pair_sum(float& s1, float& s2) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(s1), __float_as_uint(s2), false, false);
+  float t = __uint_as_float(r[0]) + __uint_as_float(r[1]);  // lanes 0-31: s1[l] + s1[l+32]; lanes 32-63: s2[l-32] + s2[l]
+  t = swap16_reduce<OpSum>(t);
+  t = group_reduce<OpSum, 16>(t);
+  s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
+  s2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+}
+
+// ---- phases the decode-step kernels share ------------------------------------------------------------------------------------------
+// One function per phase; the kernels of ptts_lm_kernels.h and ptts_gemv_kernels.h call it with values they have already loaded (where a
+// load is issued - row first, rendezvous, weights - is each kernel's own business) and store through a functor. Whatever changes a rounding
+// is a template parameter: two kernels that pass the same parameters compute the same bits. The few call sites where the call moved the
+// kernel's loop shape or register count keep the phase written out, under a comment that names the function here.
+
+// LayerNorm of a row (nn.LayerNorm, eps 1e-5): mean and variance from ONE pass of sum(x - c) and sum((x - c)^2) with the shift c = x[0]
+// (shifted-data variance: no catastrophic cancellation, error ~ eps * (1 + (mean - c)^2 / var)).
+__device__ __forceinline__ void ln_accum4(const float4& t, float c, float& s1, float& s2) {
+  const float d0 = t.x - c, d1 = t.y - c, d2 = t.z - c, d3 = t.w - c;
+  s1 += (d0 + d1) + (d2 + d3);
+  s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+}
+// the row in registers, NF4 float4 per lane (element (lane + 64 i) * 4); EXACT: K == NF4 * 256, otherwise the lanes at or beyond K count as zero
+template <int NF4, bool EXACT = true>
+__device__ __forceinline__ void ln_row_sums(const float4 (&v)[NF4], int lane, int K, float& c, float& s1, float& s2) {
+  c = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v[0].x)));
+  s1 = 0.f; s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < NF4; ++i) {
+    if constexpr (EXACT) {
+      ln_accum4(v[i], c, s1, s2);
+    } else {
+      const float msk = (lane + 64 * i) * 4 < K ? 1.f : 0.f;
+      const float d0 = (v[i].x - c) * msk, d1 = (v[i].y - c) * msk, d2 = (v[i].z - c) * msk, d3 = (v[i].w - c) * msk;
+      s1 += (d0 + d1) + (d2 + d3);
+      s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+  }
+}
+// The two reduction trees in use round differently: two full wave reductions (MFMA-strip kernels), or both sums in one tree (GEMV kernels).
+struct LnWaveSums { static __device__ __forceinline__ void reduce(float& s1, float& s2) { s1 = wave_sum(s1); s2 = wave_sum(s2); } };
+struct LnPairSum { static __device__ __forceinline__ void reduce(float& s1, float& s2) { gv_pair_sum(s1, s2); } };
+__device__ __forceinline__ void ln_mean_rstd(float c, float s1, float s2, float invK, float& mean, float& rstd) {
+  const float dm = s1 * invK;
+  mean = c + dm;
+  rstd = rsqrtf(fmaxf(s2 * invK - dm * dm, 0.f) + 1e-5f);
+}
+template <typename Tree, int NF4>
+__device__ __forceinline__ void ln_row_stats(const float4 (&v)[NF4], float invK, float& mean, float& rstd) {
+  float c, s1, s2;
+  ln_row_sums<NF4>(v, 0, 0, c, s1, s2);
+  Tree::reduce(s1, s2);
+  ln_mean_rstd(c, s1, s2, invK, mean, rstd);
+}
+__device__ __forceinline__ float ln_norm(float x, float mean, float rstd, float g, float b) { return (x - mean) * rstd * g + b; }
+// st(k, a, b, c, d): elements k .. k + 3 of the normalised row
+template <int NF4, typename Store>
+__device__ __forceinline__ void ln_row_store(const float4 (&v)[NF4], const float4 (&g)[NF4], const float4 (&bt)[NF4], float mean, float rstd, int lane, Store&& st) {
+#pragma unroll
+  for (int i = 0; i < NF4; ++i)
+    st((lane + 64 * i) * 4, ln_norm(v[i].x, mean, rstd, g[i].x, bt[i].x), ln_norm(v[i].y, mean, rstd, g[i].y, bt[i].y), ln_norm(v[i].z, mean, rstd, g[i].z, bt[i].z),
+       ln_norm(v[i].w, mean, rstd, g[i].w, bt[i].w));
+}
+
+// RW weight rows of this wave (chunk c * 64 + lane of each row, in registers) against the prepared row in LDS (engine dtype): chunk-parity
+// accumulators, one wave reduction per row, row rr's dot product in lane rr (gemv_kernel's order). Dot = GvDot<WT, W8> (ptts_gemv_kernels.h).
+template <typename Dot, int RW, int NCH, typename WV>
+__device__ __forceinline__ float wave_rows_dot(const WV (&wv)[RW][NCH], const char* s_x, int lane) {
+  uint4 xv[NCH];
+#pragma unroll
+  for (int cc = 0; cc < NCH; ++cc) xv[cc] = *reinterpret_cast<const uint4*>(s_x + (size_t)(cc * 64 + lane) * 16);
+  float acc[RW], acc2[RW];
+#pragma unroll
+  for (int rr = 0; rr < RW; ++rr) { acc[rr] = 0.f; acc2[rr] = 0.f; }
+#pragma unroll
+  for (int cc = 0; cc < NCH; ++cc)
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr) {
+      if (cc & 1) acc2[rr] = Dot::run(wv[rr][cc], xv[cc], acc2[rr]);
+      else acc[rr] = Dot::run(wv[rr][cc], xv[cc], acc[rr]);
+    }
+  float v = 0.f;
+#pragma unroll
+  for (int rr = 0; rr < RW; ++rr) {
+    const float t = wave_sum(acc[rr] + acc2[rr]);
+    v = lane == rr ? t : v;
+  }
+  return v;
+}
+
+// ---- single-query attention over K / V row groups (attn_kernel, qkv_attn_kernel, xq_attn_kernel, xattn_fused_kernel) --------------------------
+// A wave-load covers RPI = 64 / LPR rows of 64 elements: lane (r, c) = (lane / LPR, lane % LPR) holds chunk c (EPL elements) of row r.
+__device__ __forceinline__ void kv8_unpack8(const uint2& v, float (&o)[8]) {
+  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
+  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
+  o[0] = a[0]; o[1] = a[1]; o[2] = b[0]; o[3] = b[1]; o[4] = c[0]; o[5] = c[1]; o[6] = d[0]; o[7] = d[1];
+}
+struct AttnExp2 { static __device__ __forceinline__ float f(float x) { return __builtin_amdgcn_exp2f(x); } };  // scores in log2 units
+struct AttnExpE { static __device__ __forceinline__ float f(float x) { return expf(x); } };
+// Online-softmax update for one batch of U row groups already in registers: scores of the (scaled) query chunk qv, block maximum, rescale of the
+// running (m, l, o), accumulation. visible(u): the caller's predicate for row group u (an invisible row weighs 0 and its data is never used -
+// it may be NaN / garbage). KV8: rows are 64 e4m3 bytes, the K row's scale ksc multiplies the score, the V row's vsc rides on the probability.
+template <typename WT, typename Exp, bool KV8, int U, typename KVV, int NS, int EPL, typename Vis>
+__device__ __forceinline__ void attn_online_update(const KVV (&kf)[U], const KVV (&vf)[U], Vis&& visible, const float (&ksc)[NS], const float (&vsc)[NS],
+                                                   const float (&qv)[EPL], float& m_run, float& l_run, float (&o)[EPL]) {
+  constexpr int LPR = 64 / EPL;
+  bool ok[U];
+  float sc[U], bm = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    ok[u] = visible(u);
+    float kx[EPL];
+    if constexpr (KV8) kv8_unpack8(kf[u], kx);
+    else unpack16(kf[u], kx, WT());
+    float d = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) d = fmaf(qv[e], kx[e], d);
+    d = group_reduce<OpSum, LPR>(d);
+    if constexpr (KV8) d *= ksc[u];
+    sc[u] = ok[u] ? d : -INFINITY;
+    bm = fmaxf(bm, sc[u]);
+  }
+  bm = across_groups_reduce<OpMax, LPR>(bm);
+  const float m_new = fmaxf(m_run, bm);
+  if (m_new == -INFINITY) return;  // wave-uniform: nothing visible yet
+  const float alpha = (m_run == -INFINITY) ? 0.f : Exp::f(m_run - m_new);
+  l_run *= alpha;
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) o[e] *= alpha;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float p = ok[u] ? Exp::f(sc[u] - m_new) : 0.f;
+    float vx[EPL];
+    if constexpr (KV8) kv8_unpack8(vf[u], vx);
+    else unpack16(vf[u], vx, WT());
+    l_run += p;
+    const float pv = KV8 ? p * vsc[KV8 ? u : 0] : p;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) o[e] = ok[u] ? fmaf(pv, vx[e], o[e]) : o[e];
+  }
+  m_run = m_new;
+}
+template <typename WT, typename Exp, int U, int EPL, typename Vis>  // rows in the engine dtype: no row scales
+__device__ __forceinline__ void attn_online_update(const uint4 (&kf)[U], const uint4 (&vf)[U], Vis&& visible, const float (&qv)[EPL], float& m_run, float& l_run, float (&o)[EPL]) {
+  const float none[1] = {1.f};
+  attn_online_update<WT, Exp, false>(kf, vf, visible, none, none, qv, m_run, l_run, o);
+}
+// sum over the RPI row slots of the wave (lanes sharing chunk c), result in every lane
+template <int EPL>
+__device__ __forceinline__ void attn_row_slots_sum(float& l_run, float (&o)[EPL]) {
+  l_run = across_groups_reduce<OpSum, 64 / EPL>(l_run);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) o[e] = across_groups_reduce<OpSum, 64 / EPL>(o[e]);
+}
+// this wave's partial context and (max, sumexp) into its slots so[64] / sml[2] of the workgroup's merge buffers
+template <int EPL>
+__device__ __forceinline__ void attn_wave_publish(float* so, float* sml, int r, int c, float m_run, float l_run, const float (&o)[EPL]) {
+  if (r == 0) {
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) so[c * EPL + e] = o[e];
+    if (c == 0) { sml[0] = m_run; sml[1] = l_run; }
+  }
+}
+// merge of NW consecutive waves' partials (fixed order: deterministic): columns col0 .. col0 + NC - 1 of the context, the maximum and the sum
+template <typename Exp, int NW, int NC>
+__device__ __forceinline__ void attn_waves_merge(const float* so, const float* sml, int col0, float& M, float& l, float (&o)[NC]) {
+  M = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) M = fmaxf(M, sml[i * 2]);
+  l = 0.f;
+#pragma unroll
+  for (int e = 0; e < NC; ++e) o[e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    const float mi = sml[i * 2];
+    const float wgt = (mi == -INFINITY) ? 0.f : Exp::f(mi - M);
+    l += wgt * sml[i * 2 + 1];
+#pragma unroll
+    for (int e = 0; e < NC; ++e) o[e] += wgt * so[i * 64 + col0 + e];
+  }
+}
+
 // ---- 64-key block of the f32-MFMA attention kernels (prefill_attn_mfma_kernel, t5_attn_mfma_kernel) ----------------------------------
 // K / V tiles in LDS as fp32 [64 keys][16 slots of 16 B], slot XOR-swizzled by key & 15; lane (j = l & 15, g = l >> 4).
 // Round 6, call 46: the compiler had scheduled each fragment read directly in front of its MFMAs - ds_read -> s_waitcnt lgkmcnt(0) -> MFMA, 16 + 64 LDS

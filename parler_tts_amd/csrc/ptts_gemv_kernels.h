@@ -78,15 +78,12 @@ template <> __device__ __forceinline__ void gv_lds_store4<bf16_t>(char* base, in
   *reinterpret_cast<uint2*>(base + (size_t)k * 2) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
 }
 
-// Both LayerNorm sums in ONE reduction tree: a permlane32 swap puts sum-halves of s1 in lanes 0-31 and of s2 in lanes
-// 32-63, five more steps finish both (6 dependent cross-lane ops instead of 12); read back with v_readlane.
-__device__ __forceinline__ void gv_pair_sum(float& s1, float& s2) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(s1), __float_as_uint(s2), false, false);
-  float t = __uint_as_float(r[0]) + __uint_as_float(r[1]);  // lanes 0-31: s1[l] + s1[l+32]; lanes 32-63: s2[l-32] + s2[l]
-  t = swap16_reduce<OpSum>(t);
-  t = group_reduce<OpSum, 16>(t);
-  s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
-  s2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+// LayerNorm of a row in a wave's registers into the prepared row in LDS, with the one-tree sums of the GEMV kernels (ptts_common.h)
+template <typename WT, int NF4>
+__device__ __forceinline__ void gv_ln_regs(const float4 (&v)[NF4], const float4 (&g)[NF4], const float4 (&bt)[NF4], float invK, char* s_x, int lane) {
+  float mean, rstd;
+  ln_row_stats<LnPairSum, NF4>(v, invK, mean, rstd);
+  ln_row_store<NF4>(v, g, bt, mean, rstd, lane, [&](int k, float a, float b, float c, float d) { gv_lds_store4<WT>(s_x, k, a, b, c, d); });
 }
 
 // prologue wave, LayerNorm of one row: row held in registers (K == NF4 * 256), shifted one-pass mean / variance
@@ -101,19 +98,10 @@ __device__ __forceinline__ void gv_ln_row(const float* xr, const float* gamma, c
     bt[i] = *reinterpret_cast<const float4*>(beta + (lane + 64 * i) * 4);
   }
   __builtin_amdgcn_sched_barrier(0);  // all 3 * NF4 loads are issued before the first wait (gamma / beta were sunk otherwise)
-  const float c = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v[0].x)));
-  float s1 = 0.f, s2 = 0.f;
+  float mean, rstd;
+  ln_row_stats<LnPairSum, NF4>(v, invK, mean, rstd);
 #pragma unroll
-  for (int i = 0; i < NF4; ++i) {
-    const float d0 = v[i].x - c, d1 = v[i].y - c, d2 = v[i].z - c, d3 = v[i].w - c;
-    s1 += (d0 + d1) + (d2 + d3);
-    s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-  }
-  gv_pair_sum(s1, s2);
-  const float dm = s1 * invK, mean = c + dm;
-  const float rstd = rsqrtf(fmaxf(s2 * invK - dm * dm, 0.f) + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < NF4; ++i)
+  for (int i = 0; i < NF4; ++i)  // ln_row_store (ptts_common.h) written out: called from here, gemv_kernel's register count moves by one
     gv_lds_store4<WT>(s_x, (lane + 64 * i) * 4, (v[i].x - mean) * rstd * g[i].x + bt[i].x, (v[i].y - mean) * rstd * g[i].y + bt[i].y,
                       (v[i].z - mean) * rstd * g[i].z + bt[i].z, (v[i].w - mean) * rstd * g[i].w + bt[i].w);
 }
@@ -429,8 +417,9 @@ __global__ void __launch_bounds__(((PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * 
 //                (first batch of K/V rows requested at kernel start, before q exists) -> unnormalised partial + (max, sumexp);
 //   role S, S+1: q rows and k rows of head dimensions [0,32) / [32,64) -> half of q . k_new, K cache row of the new position;
 //   role S + 2 : the 64 v rows -> V cache row, and the row as the new position's partial (weight exp2(score - max) in the combine).
-// The combine (gv_attn2_wave, prologue of the out_proj node) merges the S + 1 slots. Dot products run in gemv_kernel's order (chunk
-// parity accumulators, one wave reduction per row): q / k / v are bit-identical to the two-node path; only the association of the
+// The combine (gv_attn2_wave, prologue of the out_proj node) merges the S + 1 slots. The row is normalised with gv_ln_row's statistics
+// (gv_ln_regs: ln_row_stats<LnPairSum>) and the dot products run in gemv_kernel's order (wave_rows_dot: chunk parity accumulators, one wave reduction per row):
+// q / k / v are bit-identical to the two-node path; only the association of the
 // softmax sums differs (the new position is a slot of its own instead of a row inside a split).
 // ------------------------------------------------------------------------------------------------------
 template <typename WT, int NCH, bool W8, int U>
@@ -509,46 +498,12 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(PTTS_KPARAMS(QkvAttnArgs)
   }
   __builtin_amdgcn_sched_barrier(0);  // the loads stay above the barrier
   if (w == 0) GV_STAMP(a, 1);  // every load issued
-  if (w == 0) {  // LayerNorm of the row (gv_ln_row's arithmetic: shifted one-pass mean / variance), engine dtype into LDS
-    const float c0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lv[0].x)));
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NF4; ++i) {
-      const float d0 = lv[i].x - c0, d1 = lv[i].y - c0, d2 = lv[i].z - c0, d3 = lv[i].w - c0;
-      s1 += (d0 + d1) + (d2 + d3);
-      s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-    gv_pair_sum(s1, s2);
-    const float dm = s1 * a.invK, mean = c0 + dm;
-    const float rstd = rsqrtf(fmaxf(s2 * a.invK - dm * dm, 0.f) + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < NF4; ++i)
-      gv_lds_store4<WT>(s_x, (lane + 64 * i) * 4, (lv[i].x - mean) * rstd * lg[i].x + lb[i].x, (lv[i].y - mean) * rstd * lg[i].y + lb[i].y,
-                        (lv[i].z - mean) * rstd * lg[i].z + lb[i].z, (lv[i].w - mean) * rstd * lg[i].w + lb[i].w);
-  }
+  if (w == 0) gv_ln_regs<WT, NF4>(lv, lg, lb, a.invK, s_x, lane);  // LayerNorm of the row, engine dtype into LDS
   if (w == 0) GV_STAMP(a, 2);         // residual row landed, normalised, in LDS
   __syncthreads();                    // normalised row in LDS
   // ---- the wave's 8 projection rows ---------------------------------------------------------------------------------------------
   {
-    uint4 xv[NCH];
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc) xv[cc] = *reinterpret_cast<const uint4*>(s_x + (size_t)(cc * 64 + lane) * 16);
-    float acc[RW], acc2[RW];
-#pragma unroll
-    for (int rr = 0; rr < RW; ++rr) { acc[rr] = 0.f; acc2[rr] = 0.f; }
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc)
-#pragma unroll
-      for (int rr = 0; rr < RW; ++rr) {
-        if (cc & 1) acc2[rr] = GvDot<WT, W8>::run(wv[rr][cc], xv[cc], acc2[rr]);
-        else acc[rr] = GvDot<WT, W8>::run(wv[rr][cc], xv[cc], acc[rr]);
-      }
-    float v = 0.f;
-#pragma unroll
-    for (int rr = 0; rr < RW; ++rr) {
-      const float t = wave_sum(acc[rr] + acc2[rr]);
-      v = lane == rr ? t : v;
-    }
+    const float v = wave_rows_dot<GvDot<WT, W8>>(wv, s_x, lane);
     if (lane < RW) s_r[w * RW + lane] = W8 ? v * wsc : v;
   }
   if (w == 0) GV_STAMP(a, 3);  // weight rows landed, 8 dot products + reductions done
@@ -582,7 +537,6 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(PTTS_KPARAMS(QkvAttnArgs)
 #pragma unroll
   for (int e = 0; e < EPL; ++e) o[e] = 0.f;
   for (int g0 = wvid; g0 < G; g0 += TW * U) {
-    bool ok[U];
     if (g0 != wvid) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -593,61 +547,17 @@ __global__ void __launch_bounds__(512) qkv_attn_kernel(PTTS_KPARAMS(QkvAttnArgs)
         mk[u] = (mrow && tc < P) ? mrow[tc] : 1;
       }
     }
-    float sc[U], bm = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int t = (g0 + u * TW) * RPI + r;
-      ok[u] = t < L && (t >= P || mk[u] != 0);
-      float kx[EPL];
-      unpack16(kf[u], kx, WT());
-      float d = 0.f;
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) d = fmaf(qv[e], kx[e], d);
-      d = group_reduce<OpSum, LPR>(d);
-      sc[u] = ok[u] ? d : -INFINITY;
-      bm = fmaxf(bm, sc[u]);
-    }
-    bm = across_groups_reduce<OpMax, LPR>(bm);
-    const float m_new = fmaxf(m_run, bm);
-    if (m_new == -INFINITY) continue;  // wave-uniform: nothing visible yet
-    const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
-    l_run *= alpha;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) o[e] *= alpha;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const float p = ok[u] ? __builtin_amdgcn_exp2f(sc[u] - m_new) : 0.f;
-      float vx[EPL];
-      unpack16(vf[u], vx, WT());
-      l_run += p;
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) o[e] = ok[u] ? fmaf(p, vx[e], o[e]) : o[e];  // masked rows may hold NaN/garbage V
-    }
-    m_run = m_new;
+    attn_online_update<WT, AttnExp2>(kf, vf, [&](int u) { const int t = (g0 + u * TW) * RPI + r; return t < L && (t >= P || mk[u] != 0); }, qv, m_run, l_run, o);
   }
-  l_run = across_groups_reduce<OpSum, LPR>(l_run);
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) o[e] = across_groups_reduce<OpSum, LPR>(o[e]);
+  attn_row_slots_sum(l_run, o);
   if (w == 0) GV_STAMP(a, 4);  // K / V rows landed, attention loop of this wave done
-  if (r == 0) {
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) s_o[w][c * EPL + e] = o[e];
-    if (c == 0) { s_ml[w][0] = m_run; s_ml[w][1] = l_run; }
-  }
+  attn_wave_publish(s_o[w], s_ml[w], r, c, m_run, l_run, o);
   __syncthreads();
   if (w == 0) {
-    float M = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) M = fmaxf(M, s_ml[i][0]);
-    float ov = 0.f, lv = 0.f;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-      const float wgt = (s_ml[i][0] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(s_ml[i][0] - M);
-      ov += wgt * s_o[i][lane];
-      lv += wgt * s_ml[i][1];
-    }
+    float M, lv, ov[1];
+    attn_waves_merge<AttnExp2, NW>(&s_o[0][0], &s_ml[0][0], lane, M, lv, ov);
     GV_STAMP(a, 5);  // cross-wave combine done, stores next
-    part[(size_t)role * a.H + h * 64 + lane] = ov;
+    part[(size_t)role * a.H + h * 64 + lane] = ov[0];
     if (lane == 0) {
       float* st = stats + ((size_t)role * a.nheads + h) * 2;
       st[0] = M;
@@ -716,45 +626,11 @@ __global__ void __launch_bounds__(512) xfold_attn_kernel(PTTS_KPARAMS(XfoldAttnA
   PTTS_KTOUCH(nv);       // the dependent scalar load and the epilogue's tail arguments are fetched here, in the shadow of the burst
   PTTS_KTOUCH(a.xpart);
   if (w == 0) GV_STAMP(a, 1);  // every load issued
-  if (w == 0) {  // gv_ln_row's arithmetic
-    const float c0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lv[0].x)));
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NF4; ++i) {
-      const float d0 = lv[i].x - c0, d1 = lv[i].y - c0, d2 = lv[i].z - c0, d3 = lv[i].w - c0;
-      s1 += (d0 + d1) + (d2 + d3);
-      s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-    gv_pair_sum(s1, s2);
-    const float dm = s1 * a.invK, mean = c0 + dm;
-    const float rstd = rsqrtf(fmaxf(s2 * a.invK - dm * dm, 0.f) + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < NF4; ++i)
-      gv_lds_store4<WT>(s_x, (lane + 64 * i) * 4, (lv[i].x - mean) * rstd * lg[i].x + lb[i].x, (lv[i].y - mean) * rstd * lg[i].y + lb[i].y,
-                        (lv[i].z - mean) * rstd * lg[i].z + lb[i].z, (lv[i].w - mean) * rstd * lg[i].w + lb[i].w);
-  }
+  if (w == 0) gv_ln_regs<WT, NF4>(lv, lg, lb, a.invK, s_x, lane);
   if (w == 0) GV_STAMP(a, 2);         // residual row landed, normalised, in LDS
   __syncthreads();                    // normalised row in LDS
   {
-    uint4 xv[NCH];
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc) xv[cc] = *reinterpret_cast<const uint4*>(s_x + (size_t)(cc * 64 + lane) * 16);
-    float acc[RW], acc2[RW];
-#pragma unroll
-    for (int rr = 0; rr < RW; ++rr) { acc[rr] = 0.f; acc2[rr] = 0.f; }
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc)
-#pragma unroll
-      for (int rr = 0; rr < RW; ++rr) {
-        if (cc & 1) acc2[rr] = GvDot<WT, false>::run(wv[rr][cc], xv[cc], acc2[rr]);
-        else acc[rr] = GvDot<WT, false>::run(wv[rr][cc], xv[cc], acc[rr]);
-      }
-    float v = 0.f;
-#pragma unroll
-    for (int rr = 0; rr < RW; ++rr) {
-      const float t = wave_sum(acc[rr] + acc2[rr]);
-      v = lane == rr ? t : v;
-    }
+    const float v = wave_rows_dot<GvDot<WT, false>>(wv, s_x, lane);
     if (lane < RW) s_r[w * RW + lane] = v;
   }
   if (w == 0) GV_STAMP(a, 3);  // rows of M landed, 8 dot products + reductions done
@@ -842,44 +718,10 @@ __global__ void __launch_bounds__(512) xq_attn_kernel(XqAttnArgs a) {
     mk[u] = (mrow && t < a.mask_ld) ? mrow[t] : 1;
   }
   __builtin_amdgcn_sched_barrier(0);  // the loads stay above the barrier
-  if (w == 0) {  // gv_ln_row's arithmetic
-    const float c0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(lv[0].x)));
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NF4; ++i) {
-      const float d0 = lv[i].x - c0, d1 = lv[i].y - c0, d2 = lv[i].z - c0, d3 = lv[i].w - c0;
-      s1 += (d0 + d1) + (d2 + d3);
-      s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-    gv_pair_sum(s1, s2);
-    const float dm = s1 * a.invK, mean = c0 + dm;
-    const float rstd = rsqrtf(fmaxf(s2 * a.invK - dm * dm, 0.f) + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < NF4; ++i)
-      gv_lds_store4<WT>(s_x, (lane + 64 * i) * 4, (lv[i].x - mean) * rstd * lg[i].x + lb[i].x, (lv[i].y - mean) * rstd * lg[i].y + lb[i].y,
-                        (lv[i].z - mean) * rstd * lg[i].z + lb[i].z, (lv[i].w - mean) * rstd * lg[i].w + lb[i].w);
-  }
+  if (w == 0) gv_ln_regs<WT, NF4>(lv, lg, lb, a.invK, s_x, lane);
   __syncthreads();  // normalised row in LDS
   {
-    uint4 xv[NCH];
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc) xv[cc] = *reinterpret_cast<const uint4*>(s_x + (size_t)(cc * 64 + lane) * 16);
-    float acc[RW], acc2[RW];
-#pragma unroll
-    for (int rr = 0; rr < RW; ++rr) { acc[rr] = 0.f; acc2[rr] = 0.f; }
-#pragma unroll
-    for (int cc = 0; cc < NCH; ++cc)
-#pragma unroll
-      for (int rr = 0; rr < RW; ++rr) {
-        if (cc & 1) acc2[rr] = GvDot<WT, W8>::run(wv[rr][cc], xv[cc], acc2[rr]);
-        else acc[rr] = GvDot<WT, W8>::run(wv[rr][cc], xv[cc], acc[rr]);
-      }
-    float v = 0.f;
-#pragma unroll
-    for (int rr = 0; rr < RW; ++rr) {
-      const float t = wave_sum(acc[rr] + acc2[rr]);
-      v = lane == rr ? t : v;
-    }
+    const float v = wave_rows_dot<GvDot<WT, W8>>(wv, s_x, lane);
     if (lane < RW) s_r[w * RW + lane] = W8 ? v * wsc : v;
   }
   __syncthreads();  // the head's 64 q values in LDS
@@ -903,7 +745,7 @@ __global__ void __launch_bounds__(512) xq_attn_kernel(XqAttnArgs a) {
         mk[u] = mrow ? mrow[tc] : 1;
       }
     }
-    float sc[U], bm = -INFINITY;
+    float sc[U], bm = -INFINITY;  // attn_online_update<WT, AttnExp2> (ptts_common.h) written out: called, the first-batch peel of this loop is lost
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = (g0 + u * NW) * RPI + r;
@@ -935,26 +777,12 @@ __global__ void __launch_bounds__(512) xq_attn_kernel(XqAttnArgs a) {
     }
     m_run = m_new;
   }
-  l_run = across_groups_reduce<OpSum, LPR>(l_run);
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) o[e] = across_groups_reduce<OpSum, LPR>(o[e]);
-  if (r == 0) {
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) s_o[w][c * EPL + e] = o[e];
-    if (c == 0) { s_ml[w][0] = m_run; s_ml[w][1] = l_run; }
-  }
+  attn_row_slots_sum(l_run, o);
+  attn_wave_publish(s_o[w], s_ml[w], r, c, m_run, l_run, o);
   __syncthreads();
   if (w == 0) {
-    float M = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) M = fmaxf(M, s_ml[i][0]);
-    float ov = 0.f, lsum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-      const float wgt = (s_ml[i][0] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(s_ml[i][0] - M);
-      ov += wgt * s_o[i][lane];
-      lsum += wgt * s_ml[i][1];
-    }
-    gv_store<WT>(reinterpret_cast<WT*>(a.out) + (size_t)b * a.out_ld + h * 64 + lane, lsum > 0.f ? ov / lsum : 0.f);  // every key masked: 0 (attn_kernel)
+    float M, lsum, ov[1];
+    attn_waves_merge<AttnExp2, NW>(&s_o[0][0], &s_ml[0][0], lane, M, lsum, ov);
+    gv_store<WT>(reinterpret_cast<WT*>(a.out) + (size_t)b * a.out_ld + h * 64 + lane, lsum > 0.f ? ov[0] / lsum : 0.f);  // every key masked: 0 (attn_kernel)
   }
 }

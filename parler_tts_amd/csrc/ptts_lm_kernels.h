@@ -322,34 +322,23 @@ __device__ __forceinline__ void ln_rows(const Args& a, const float* const (&xr)[
   PTTS_LN_STAMP(a, 7);
   float c[R], s1[R], s2[R];
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
-    c[r] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v[r][0].x)));
-    s1[r] = 0.f; s2[r] = 0.f;
-#pragma unroll
-    for (int i = 0; i < NF4; ++i) {
-      const float msk = (EXACT || (lane + 64 * i) * 4 < a.K) ? 1.f : 0.f;
-      const float d0 = (v[r][i].x - c[r]) * msk, d1 = (v[r][i].y - c[r]) * msk, d2 = (v[r][i].z - c[r]) * msk, d3 = (v[r][i].w - c[r]) * msk;
-      s1[r] += (d0 + d1) + (d2 + d3);
-      s2[r] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-  }
-#pragma unroll
+  for (int r = 0; r < R; ++r) ln_row_sums<NF4, EXACT>(v[r], lane, a.K, c[r], s1[r], s2[r]);
   PTTS_LN_STAMP(a, 8);
-  for (int r = 0; r < R; ++r) { s1[r] = wave_sum(s1[r]); s2[r] = wave_sum(s2[r]); }
+#pragma unroll
+  for (int r = 0; r < R; ++r) LnWaveSums::reduce(s1[r], s2[r]);
   PTTS_LN_STAMP(a, 9);
   // normalise in registers (consumes gamma/beta: every load of this wave has landed), THEN start this wave's weight
   // stream, then write LDS: no wait on a row/gamma/beta load can end up behind the weight loads
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const float dm = s1[r] * a.invK;
-    const float mean = c[r] + dm;
-    const float rstd = rsqrtf(fmaxf(s2[r] * a.invK - dm * dm, 0.f) + 1e-5f);
+    float mean, rstd;
+    ln_mean_rstd(c[r], s1[r], s2[r], a.invK, mean, rstd);
 #pragma unroll
     for (int i = 0; i < NF4; ++i) {
-      v[r][i].x = (v[r][i].x - mean) * rstd * g[i].x + bt[i].x;
-      v[r][i].y = (v[r][i].y - mean) * rstd * g[i].y + bt[i].y;
-      v[r][i].z = (v[r][i].z - mean) * rstd * g[i].z + bt[i].z;
-      v[r][i].w = (v[r][i].w - mean) * rstd * g[i].w + bt[i].w;
+      v[r][i].x = ln_norm(v[r][i].x, mean, rstd, g[i].x, bt[i].x);
+      v[r][i].y = ln_norm(v[r][i].y, mean, rstd, g[i].y, bt[i].y);
+      v[r][i].z = ln_norm(v[r][i].z, mean, rstd, g[i].z, bt[i].z);
+      v[r][i].w = ln_norm(v[r][i].w, mean, rstd, g[i].w, bt[i].w);
     }
   }
   PTTS_LN_STAMP(a, 10);
@@ -453,7 +442,7 @@ __device__ __forceinline__ void lns_stage(const GemmArgs& a, int nrows, char* s_
         const float rstd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rstd_l), (i0 + i) * 8));
         char* row = s_x + (size_t)(wave + W * (i0 + i)) * row_bytes;
 #pragma unroll
-        for (int f = 0; f < NF4; ++f)
+        for (int f = 0; f < NF4; ++f)  // ln_row_store (ptts_common.h) written out: called, the paired LDS stores of two column slabs are split
           lds_store4<WT>(row, (lane + 64 * f) * 4, (v[i][f].x - mean) * rstd * g[f].x + bt[f].x, (v[i][f].y - mean) * rstd * g[f].y + bt[f].y,
                          (v[i][f].z - mean) * rstd * g[f].z + bt[f].z, (v[i][f].w - mean) * rstd * g[f].w + bt[f].w);
       }
@@ -1125,20 +1114,10 @@ __device__ __forceinline__ void prep_ln_row_regs(const GemmArgs& a, int m, WT* d
     g[i] = *reinterpret_cast<const float4*>(a.gamma + (lane + 64 * i) * 4);
     bt[i] = *reinterpret_cast<const float4*>(a.beta + (lane + 64 * i) * 4);
   }
-  const float c = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v[0].x)));
-  float s1 = 0.f, s2 = 0.f;
+  float mean, rstd;
+  ln_row_stats<LnWaveSums, NF4>(v, a.invK, mean, rstd);
 #pragma unroll
-  for (int i = 0; i < NF4; ++i) {
-    const float d0 = v[i].x - c, d1 = v[i].y - c, d2 = v[i].z - c, d3 = v[i].w - c;
-    s1 += (d0 + d1) + (d2 + d3);
-    s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-  }
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  const float dm = s1 * a.invK, mean = c + dm;
-  const float rstd = rsqrtf(fmaxf(s2 * a.invK - dm * dm, 0.f) + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < NF4; ++i)
+  for (int i = 0; i < NF4; ++i)  // ln_row_store (ptts_common.h) written out: called, rows_prep_kernel<float>'s register count moves
     act_store4<WT>(dst, m, (lane + 64 * i) * 4, a.K, a.out_fo, (v[i].x - mean) * rstd * g[i].x + bt[i].x, (v[i].y - mean) * rstd * g[i].y + bt[i].y,
                    (v[i].z - mean) * rstd * g[i].z + bt[i].z, (v[i].w - mean) * rstd * g[i].w + bt[i].w);
 }
@@ -1226,22 +1205,16 @@ __global__ void __launch_bounds__(256) rows_prep_kernel(PTTS_KPARAMS(RowsPrepHea
     const float* xr = a.x + (size_t)(m * a.x_row_mul + a.x_row_off) * a.x_ld;
     float s1 = 0.f, s2 = 0.f;
     const float c = xr[0];
-    for (int k = lane * 4; k < a.K; k += 256) {
-      const float4 t = *reinterpret_cast<const float4*>(xr + k);
-      const float d0 = t.x - c, d1 = t.y - c, d2 = t.z - c, d3 = t.w - c;
-      s1 += (d0 + d1) + (d2 + d3);
-      s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const float dm = s1 * a.invK, mean = c + dm;
-    const float rstd = rsqrtf(fmaxf(s2 * a.invK - dm * dm, 0.f) + 1e-5f);
+    for (int k = lane * 4; k < a.K; k += 256) ln_accum4(*reinterpret_cast<const float4*>(xr + k), c, s1, s2);
+    LnWaveSums::reduce(s1, s2);
+    float mean, rstd;
+    ln_mean_rstd(c, s1, s2, a.invK, mean, rstd);
     for (int k = lane * 4; k < a.K; k += 256) {
       const float4 t = *reinterpret_cast<const float4*>(xr + k);
       const float4 g = *reinterpret_cast<const float4*>(a.gamma + k);
       const float4 bt = *reinterpret_cast<const float4*>(a.beta + k);
-      act_store4<WT>(dst, m, k, a.K, a.out_fo, (t.x - mean) * rstd * g.x + bt.x, (t.y - mean) * rstd * g.y + bt.y, (t.z - mean) * rstd * g.z + bt.z,
-                     (t.w - mean) * rstd * g.w + bt.w);
+      act_store4<WT>(dst, m, k, a.K, a.out_fo, ln_norm(t.x, mean, rstd, g.x, bt.x), ln_norm(t.y, mean, rstd, g.y, bt.y), ln_norm(t.z, mean, rstd, g.z, bt.z),
+                     ln_norm(t.w, mean, rstd, g.w, bt.w));
     }
   } else {
     for (int k = lane * 4; k < a.K; k += 256) {
@@ -1402,11 +1375,6 @@ __device__ __forceinline__ uint2 kv8_pack8(const float (&x)[8], float inv_scale)
   w1 = __builtin_amdgcn_cvt_pk_fp8_f32(x[6] * inv_scale, x[7] * inv_scale, w1, true);
   return make_uint2((unsigned)w0, (unsigned)w1);
 }
-__device__ __forceinline__ void kv8_unpack8(const uint2& v, float (&o)[8]) {
-  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
-  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
-  o[0] = a[0]; o[1] = a[1]; o[2] = b[0]; o[3] = b[1]; o[4] = c[0]; o[5] = c[1]; o[6] = d[0]; o[7] = d[1];
-}
 template <bool KV8> struct KvVec { typedef uint4 T; };
 template <> struct KvVec<true> { typedef uint2 T; };
 
@@ -1507,7 +1475,6 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(AttnArgs a) {
   PTTS_WSTAMP(a, 2);  // the query chunk (the dependent operand: the previous node wrote it) is usable: rotated, scaled
 
   for (int g0 = wv; g0 < G; g0 += TW * U) {
-    bool ok[U];
     if (g0 != wv) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {  // loads only: clamped addresses, validity applied afterwards
@@ -1519,7 +1486,8 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(AttnArgs a) {
         mk[u] = (mrow && tc < mask_len) ? mrow[tc] : 1;
       }
     }
-    float sc[U], bm = -INFINITY;
+    bool ok[U];
+    float sc[U], bm = -INFINITY;  // attn_online_update<WT, AttnExp2, KV8> (ptts_common.h) written out: called, the kernel's register count moves
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = (g0 + u * TW) * RPI + r;
@@ -1560,27 +1528,13 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(AttnArgs a) {
     m_run = m_new;
   }
   PTTS_WSTAMP(a, 3);  // K / V loop done
-  // reduce over the RPI row slots of the wave (lanes sharing chunk c)
-  l_run = across_groups_reduce<OpSum, LPR>(l_run);
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) o[e] = across_groups_reduce<OpSum, LPR>(o[e]);
-  if (r == 0) {
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) s_o[w][c * EPL + e] = o[e];
-    if (c == 0) { s_ml[w][0] = m_run; s_ml[w][1] = l_run; }
-  }
+  attn_row_slots_sum(l_run, o);
+  attn_wave_publish(s_o[w], s_ml[w], r, c, m_run, l_run, o);
   __syncthreads();
   if (tid < 64) {
-    float M = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) M = fmaxf(M, s_ml[i][0]);
-    float ov = 0.f, lv = 0.f;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-      const float wgt = (s_ml[i][0] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(s_ml[i][0] - M);
-      ov += wgt * s_o[i][tid];
-      lv += wgt * s_ml[i][1];
-    }
+    float M, lv, ov1[1];
+    attn_waves_merge<AttnExp2, NW>(&s_o[0][0], &s_ml[0][0], tid, M, lv, ov1);
+    const float ov = ov1[0];
     if (a.direct_out) {  // unsplit launch: this workgroup saw every key, finish the softmax here
       const int kcol = h * 64 + tid;
       WT* dst = reinterpret_cast<WT*>(a.direct_out);
@@ -2057,7 +2011,7 @@ __global__ void __launch_bounds__(512) xattn_fused_kernel(PTTS_KPARAMS(XAttnArgs
         mk[u] = mrow ? mrow[tc] : 1;
       }
     }
-    float sc[UA], bm = -INFINITY;
+    float sc[UA], bm = -INFINITY;  // attn_online_update<WT, AttnExpE> (ptts_common.h) written out: called, this loop loses its peeled first batch
 #pragma unroll
     for (int u = 0; u < UA; ++u) {
       ok[u] = ((g0 + u * WPU + sub) * RPI + r) < N && mk[u] != 0;
@@ -2091,7 +2045,8 @@ __global__ void __launch_bounds__(512) xattn_fused_kernel(PTTS_KPARAMS(XAttnArgs
   l_run = across_groups_reduce<OpSum, LPR>(l_run);
 #pragma unroll
   for (int e = 0; e < EPL; ++e) o[e] = across_groups_reduce<OpSum, LPR>(o[e]);
-  if constexpr (WPU > 1) {  // merge the WPU partial softmaxes of an utterance (fixed wave order: deterministic)
+  if constexpr (WPU > 1) {  // merge the WPU partial softmaxes of an utterance: attn_wave_publish / attn_waves_merge<AttnExpE, WPU> (ptts_common.h)
+                            // written out (called, one LDS read of the merge is folded away)
     if (r == 0) {
 #pragma unroll
       for (int e = 0; e < EPL; ++e) s_o[wave * 64 + c * EPL + e] = o[e];
@@ -2134,7 +2089,7 @@ __global__ void __launch_bounds__(512) xattn_fused_kernel(PTTS_KPARAMS(XAttnArgs
 // front of the GEMM: 4.9 + ~1.5 (boundary) us per layer at batch 32, 2 x 5.0 + gaps at 128. Tiled over N AND M (64 rows x G utterances, full K)
 // a workgroup normalises only its own G rows (redundant over the N / 64 row blocks: G x 4 KB each, from the L2) and re-streams its 128 KB of
 // weights once per utterance group, also from the L2: the prep node and its boundary are gone and the arithmetic per row is prep_ln_row_regs'
-// (same fold order, same one-pass shifted statistics), so the normalised rows are bit-identical to the two-node path.
+// (ln_row_stats<LnWaveSums> of ptts_common.h, written out below), so the normalised rows are bit-identical to the two-node path.
 // 8 waves = 4 weight strips x 2 K halves; wave w < nb normalises row b0 + w first.
 // EPI_STORE: fp32 [M][out_ld] (QKV); EPI_GELU_WT: gelu_erf in the engine dtype, row-major or MFMA B-fragment order (fc1 -> fc2).
 // ------------------------------------------------------------------------------------------------------
@@ -2205,7 +2160,9 @@ __global__ void __launch_bounds__(512) lnproj_fused_kernel(PTTS_KPARAMS(LnProjAr
 #pragma unroll
       for (int uu = 0; uu < UW; ++uu) afr[uu] = ld_nt16(Wp + (size_t)(t0 + uu) * 64);
       __builtin_amdgcn_sched_barrier(0);
-      auto norm_row = [&](float4 (&v)[NF4], char* row) __attribute__((always_inline)) {  // prep_ln_row_regs' arithmetic
+      // ln_row_stats<LnWaveSums> + ln_row_store (ptts_common.h) written out, here and in the one-row branch below: on the shared functions the
+      // batch-32 Large-v1 step measured 3 us above the parent's two runs at one reading (profiles/shared_phases_ab.txt)
+      auto norm_row = [&](float4 (&v)[NF4], char* row) __attribute__((always_inline)) {
         const float c = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v[0].x)));
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll

@@ -5,12 +5,14 @@ their instruction streams are identical.
   python tools/isa_compare.py OLD/libptts_hip.so [NEW/libptts_hip.so] ['OLD NAME=NEW NAME' ...] > profiles/<name>.txt
 
 A change that only ADDS kernels must leave every kernel of the old build in place with the same instructions: a different stream in an
-existing kernel means its code generation moved (a shared device function, a struct layout, an inlining decision) and is listed by name.
+existing kernel means its code generation moved (a shared device function, a struct layout, an inlining decision) and is listed by name,
+with the opcodes whose counts differ (old -> new): none for renamed registers or instructions that only moved, many for a reshaped loop.
 A kernel that only changed its name (a template parameter added, a non-template made a template) is missing under its old name: where
 its instruction stream equals that of an added kernel it is listed as "renamed, identical" with both names and not counted as missing.
 'OLD NAME=NEW NAME' (substrings of the listed names) pairs a kernel that is gone on purpose with the one that replaces it, so that the two
 instruction counts stand next to each other; it stays counted as missing.
 Addresses and the disassembler's comments are ignored; branch offsets are relative, so identical code compares equal wherever it is placed."""
+import collections
 import os
 import re
 import shutil
@@ -83,6 +85,10 @@ def main():
             print(f"\n## {title}")
             for k in sorted(ks, key=names.get):
                 print(f"{names[k]}" + (f"  ({len(old[k])} -> {len(new[k])} instructions)" if both else f"  ({len((new if k in new else old)[k])} instructions)"))
+                if both:  # a renamed register or a moved instruction changes no count; a reshaped loop does
+                    co, cn = (collections.Counter(line.split()[0] for line in b[k]) for b in (old, new))
+                    moved = [f"{op} {co[op]} -> {cn[op]}" for op in sorted(set(co) | set(cn)) if co[op] != cn[op]]
+                    print("    opcode counts: " + (", ".join(moved) if moved else "all equal"))
     if pairs:
         print("\n## replaced (old -> new instructions)")
         for o, n in pairs:
