@@ -186,6 +186,8 @@ int ptts_ids(ptts_engine* e, int64_t** ids_dev, int32_t* row_stride);
  *   PTTS_E_INVALID (the checks of ptts_set_gen_params): temperature not finite or <= 0, top_p outside (0, 1], top_k < 0, min_new_tokens < 0.
  *   With `sample` == 0 the record is stored and only a later device tail (ptts_decode_steps) would read it. No step graph is captured again:
  *   the records live in one device array the graphs already point to.
+ * Group admissions (n requests into n idle slots with ONE prefill pass, ptts_admit_rows) are declared in ptts_session.h, which this header
+ *   includes at its end: the 46 declarations of this file are the ABI v8 set, that header is additive to it.
  * ptts_row_state (SYNCHRONISES): per slot, columns written so far (incl. BOS; 1 when idle) and whether it is still generating.
  * ptts_retire_row: makes a slot idle, whatever its state (cancel, or after its ids were read), and drops its sampler record: a later
  *   ptts_admit_row into the slot samples on the session's parameters.
@@ -347,4 +349,7 @@ int ptts_t5_debug_graph_nodes(ptts_t5* e, int32_t* nodes);
 #ifdef __cplusplus
 }
 #endif
+
+#include "ptts_session.h" /* additive to ABI v8: group admissions into a continuous session */
+
 #endif /* PTTS_H_ */

@@ -110,6 +110,11 @@ SYMBOLS = {
     "ptts_dac_debug_decode_upto": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32)]),
 }
 
+# include/ptts_session.h, additive to the ABI v8 set above: name -> (restype, argtypes)
+SESSION_SYMBOLS = {
+    "ptts_admit_rows": (C.c_int, [_VP, _I32, C.POINTER(_I32), _VP, _VP, _VP, _VP, C.POINTER(_I32), _I32, C.POINTER(C.POINTER(PttsGenParams)), _VP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -131,7 +136,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib = C.CDLL(p)
     except OSError as e:  # e.g. libamdhip64 missing
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -52,10 +52,17 @@ class ContinuousBatcher:
     default the same), ``last`` is True exactly once per ticket, and ``__iter__`` / ``run()`` raise. ``cancel(ticket)`` drops a request in either
     mode. The stream table lives in ONE codec engine, sized at construction for ``slots`` windows; should another call replace that engine
     (``DACModel._get_engine`` does when it needs more capacity), the next codec pass raises ``RuntimeError`` - the requests in flight are lost,
-    nothing is restarted silently."""
+    nothing is restarted silently.
+
+    ``admit_batch`` (default 1: one ``ptts_admit_row`` per request): with N > 1, the requests that find an idle slot at the same poll are
+    admitted in groups of up to N through one prefill pass each (``ptts_admit_rows``). The engine is then created with that many spare rows
+    behind the slots (``spare_rows``: clamped to the batch-size class of ``slots``; fewer than 2 left = single admissions). A request admitted
+    in a group is within the engine's tolerance of the reference, not bit-identical to the same request admitted alone."""
 
     def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16,
-                 stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, **generation_kwargs):
+                 stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, admit_batch: int = 1, **generation_kwargs):
+        if int(admit_batch) < 1:
+            raise ValueError("`admit_batch` must be >= 1")
         if slots < 1 or max_description_tokens < 1 or max_prompt_tokens < 0 or poll_steps < 1:
             raise ValueError("slots, max_description_tokens and poll_steps must be >= 1 and max_prompt_tokens >= 0")
         if stream_chunk_frames is None and stream_first_chunk_frames is not None:
@@ -94,7 +101,10 @@ class ContinuousBatcher:
         d = model.config.decoder
         self.K, self.bos = d.num_codebooks, d.bos_token_id
         self.pad = gc.pad_token_id if gc.pad_token_id is not None else d.pad_token_id
-        self.eng = model._get_engine(self.slots, self.N, self.P, self.max_length)
+        # admit_batch > 1: the engine carries `spare` arena rows behind the slots, where a group of requests is prefilled in one pass
+        self.spare = self.spare_rows(self.slots, int(admit_batch))
+        self.admissions, self.admission_groups = 0, []  # requests admitted; sizes of the groups that went through admit_rows
+        self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length)
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
         self.eng.begin_session(self.slots, self.N, self.P)
@@ -122,6 +132,17 @@ class ContinuousBatcher:
             self._first_out = [False] * self.slots  # the request's first chunk is still outstanding
             self._out: Deque[Tuple[int, torch.Tensor, bool]] = collections.deque()
             self.codec_passes, self.codec_rows, self.whole_requests = 0, 0, 0  # passes, listed rows, requests that ended below 2K - 1 columns
+
+    @staticmethod
+    def spare_rows(slots: int, admit_batch: int) -> int:
+        """Spare engine rows of a batcher of ``slots`` slots asked for groups of ``admit_batch``: clamped so that ``slots + spare`` stays in the
+        batch-size class of ``slots`` (<= 4, <= 8, wider: the class decides the kernels of the decode step, which must not change), and 0 -
+        single admissions - where fewer than 2 would be left."""
+        if admit_batch <= 1:
+            return 0
+        top = 4 if slots <= 4 else (8 if slots <= 8 else None)
+        spare = admit_batch if top is None else min(admit_batch, top - slots)
+        return spare if spare >= 2 else 0
 
     # -- requests ---------------------------------------------------------------------------------------------------------------
     def _pad_ids(self, ids, mask, width: int, what: str):
@@ -207,12 +228,46 @@ class ContinuousBatcher:
         kw = {} if r.gen is None else {"gen": dict(r.gen)}
         self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True, **kw)
         self._slot[s], self._cols[s] = r, 2
+        self.admissions += 1
+
+    def _admit_group(self, group):
+        """[(slot, request), ...] of 2 .. spare pairs through ONE prefill pass (``admit_rows``)."""
+        reqs = [r for _, r in group]
+        stack = lambda ts: None if ts[0] is None else torch.stack(list(ts))
+        gens = None if all(r.gen is None for r in reqs) else [None if r.gen is None else dict(r.gen) for r in reqs]
+        self.eng.admit_rows([s for s, _ in group], stack([r.enc for r in reqs]), stack([r.enc_mask for r in reqs]), stack([r.prompt for r in reqs]),
+                            stack([r.prompt_mask for r in reqs]), max_lengths=[r.max_length for r in reqs], sample=True, gens=gens)
+        for s, r in group:
+            self._slot[s], self._cols[s] = r, 2
+        self.admissions += len(group)
+        self.admission_groups.append(len(group))
+
+    def _admit_queued(self, admitted=None):
+        """Idle slots in ascending order take the queue in FIFO order; ``admitted(slot)`` runs behind each admission. Without spare rows
+        (``admit_batch=1``) every pair is one ``admit_row``; with them the pairs go in groups of at most ``spare`` through ``admit_rows``
+        (a group of one: ``admit_row``)."""
+        if not self.spare:
+            for s in range(self.slots):
+                if self._slot[s] is None and self._queue:
+                    self._admit_into(s, self._queue.popleft())
+                    if admitted is not None:
+                        admitted(s)
+            return
+        idle = [s for s in range(self.slots) if self._slot[s] is None][: len(self._queue)]
+        pairs = [(s, self._queue.popleft()) for s in idle]
+        for g0 in range(0, len(pairs), self.spare):
+            group = pairs[g0:g0 + self.spare]
+            if len(group) == 1:
+                self._admit_into(*group[0])
+            else:
+                self._admit_group(group)
+            if admitted is not None:
+                for s, _ in group:
+                    admitted(s)
 
     def _poll(self):
         """Admit FIFO into idle slots, run the live slots up to the next boundary, collect what finished."""
-        for s in range(self.slots):
-            if self._slot[s] is None and self._queue:
-                self._admit_into(s, self._queue.popleft())
+        self._admit_queued()
         busy = [s for s in range(self.slots) if self._slot[s] is not None]
         if not busy:
             return
@@ -234,12 +289,12 @@ class ContinuousBatcher:
 
     # -- streaming ----------------------------------------------------------------------------------------------------------------
     def _admit(self):
-        for s in range(self.slots):
-            if self._slot[s] is None and self._queue:
-                self._admit_into(s, self._queue.popleft())
-                self.model.audio_encoder.stream_reset(s)
-                self._absorbed[s] = self._kept[s] = self._emitted[s] = 0
-                self._first_out[s] = True
+        def fresh_stream(s):
+            self.model.audio_encoder.stream_reset(s)
+            self._absorbed[s] = self._kept[s] = self._emitted[s] = 0
+            self._first_out[s] = True
+
+        self._admit_queued(fresh_stream)
 
     def _streams(self, s: int, cur: int) -> bool:
         """Whether slot s's frames can be named yet: below 2K - 1 columns build_delay_pattern_mask applies no pattern at all, and `cur` alone

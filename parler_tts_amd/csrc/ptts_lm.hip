@@ -129,6 +129,8 @@ struct ptts_engine {
   SlotGen* slot_gen = nullptr;           // [max_batch] device: sampler record of the request in each slot (ptts_admit_row_gen); own = 0: the session's
   float* h_adm = nullptr;                // [max_prompt][H] residual rows of a row prefill: the step input h[B][H] of the other slots is live between steps
   KvLayer* kv_layers_rows = nullptr;     // [max_batch][layers] operands of the batched cross K/V projection with each slot's arena rows as base
+  float* h_adm_rows = nullptr;           // [(max_batch - 1) * max_prompt][H] residual rows of a group prefill (ptts_admit_rows), allocated at its first use
+  AdmitMoveLayer* move_layers = nullptr; // [layers] arena bases of admit_move_rows_kernel, written with h_adm_rows
   std::vector<char> slot_busy;           // host: admitted and not yet retired
   std::vector<int> slot_ub, slot_maxlen; // host: upper bound of the slot's self-KV positions (P + 1 + steps since admission), its max_length
 #ifdef PTTS_TIMING
@@ -1344,16 +1346,12 @@ static void session_row_view(ptts_engine* e, int row, bool enter) {
   std::swap(e->h, e->h_adm);
 }
 
-extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
-                                  const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, const ptts_gen_params* gp, void* stream) {
-  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
-  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_row: no continuous session (ptts_session_begin)");
+// the checks of one admission (ptts_admit_row_gen, and every entry of ptts_admit_rows); *L_out = the request's max_length
+static int check_admission(const ptts_engine* e, int row, const float* prompt_dev, int max_length, const ptts_gen_params* gp, int* L_out) {
   PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
   PTTS_CHECK(!e->slot_busy[row], PTTS_E_INVALID, "slot %d still holds a request (ptts_retire_row first)", row);
   PTTS_CHECK(e->pending_T == 0, PTTS_E_UNSUPPORTED, "a voice prompt is pending (ptts_set_audio_prefix): sessions take none");
-  const ptts_config& c = e->cfg;
-  const int P = e->P, N = e->N, H = c.hidden_size, K = c.num_codebooks;
-  PTTS_CHECK(P == 0 || prompt_dev, PTTS_E_INVALID, "prompt_dev is null but the session's P > 0");
+  PTTS_CHECK(e->P == 0 || prompt_dev, PTTS_E_INVALID, "prompt_dev is null but the session's P > 0");
   const int L = max_length == 0 ? e->session_max_length : max_length;
   PTTS_CHECK(L >= 2, PTTS_E_INVALID, "max_length must be 0 (the session's) or >= 2");
   PTTS_CHECK(L <= e->session_max_length, PTTS_E_CAPACITY, "max_length %d exceeds the session's %d", L, e->session_max_length);
@@ -1362,6 +1360,18 @@ extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_
     PTTS_CHECK(gp->max_length == 0 || gp->max_length == max_length, PTTS_E_INVALID,
                "gen params max_length %d differs from the max_length argument %d (which rules the slot's end)", gp->max_length, max_length);
   }
+  *L_out = L;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                                  const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, const ptts_gen_params* gp, void* stream) {
+  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_row: no continuous session (ptts_session_begin)");
+  int L = 0;
+  PTTS_TRY(check_admission(e, row, prompt_dev, max_length, gp, &L));
+  const ptts_config& c = e->cfg;
+  const int P = e->P, N = e->N, H = c.hidden_size, K = c.num_codebooks;
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
@@ -1394,6 +1404,83 @@ extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_
 extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
                               const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream) {
   return ptts_admit_row_gen(e, row, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_length, sample, nullptr, stream);
+}
+
+// A group of n requests in one prefill pass: the static prefill forward of a batch of n on the spare arena rows B .. B + n - 1 (every array of the
+// engine is batch-outermost and sized for max_batch, so the row view entered at row B with e->B = n is an n-utterance engine), then ONE launch that
+// moves each spare row to its slot (admit_move_rows_kernel), then per slot what ptts_admit_row_gen does: reset, record, tail. The tail runs on the
+// slot itself: the draw hash of a slot without a record of its own uses the slot index.
+extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                               const int32_t* prompt_mask_dev, const int32_t* max_lengths, int32_t sample, const ptts_gen_params* const* gps,
+                               void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_rows: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(n >= 1, PTTS_E_INVALID, "ptts_admit_rows: n = %d requests (at least 1)", n);
+  PTTS_CHECK(enc_dev && rows && max_lengths, PTTS_E_INVALID, "null argument");
+  const ptts_config& c = e->cfg;
+  const int B = e->B, P = e->P, N = e->N, H = c.hidden_size, K = c.num_codebooks;
+  std::vector<int> Ls(n);
+  for (int j = 0; j < n; ++j) {
+    PTTS_TRY(check_admission(e, rows[j], prompt_dev, max_lengths[j], gps ? gps[j] : nullptr, &Ls[j]));
+    for (int i = 0; i < j; ++i) PTTS_CHECK(rows[i] != rows[j], PTTS_E_INVALID, "slot %d listed twice", rows[j]);
+  }
+  PTTS_CHECK(n <= c.max_batch - B, PTTS_E_CAPACITY, "%d requests exceed the %d spare rows behind the session's %d slots (engine max_batch %d)", n,
+             c.max_batch - B, B, c.max_batch);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = pick_stream(e, stream);
+  if (!e->h_adm_rows) {
+    std::vector<AdmitMoveLayer> ml(c.num_layers);
+    for (int l = 0; l < c.num_layers; ++l) ml[l] = AdmitMoveLayer{e->L[l].k_self, e->L[l].v_self, e->L[l].k_cross, e->L[l].v_cross};
+    PTTS_TRY(e->alloc(&e->move_layers, (size_t)c.num_layers));
+    PTTS_HIP(hipMemcpy(e->move_layers, ml.data(), ml.size() * sizeof(AdmitMoveLayer), hipMemcpyHostToDevice));
+    PTTS_TRY(e->alloc(&e->h_adm_rows, (size_t)(c.max_batch - 1) * e->max_prompt * H));
+  }
+  // the spare rows as ptts_prefill prepares a batch of n: sampler state (the prefill's embedding reads the BOS column and the clock), masks, staging
+  hipLaunchKernelGGL(session_reset_rows_kernel, dim3((n * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
+                     e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
+  int* em = e->enc_mask + (size_t)B * c.max_enc;
+  int* pm = e->prompt_mask + (size_t)B * e->max_prompt;
+  if (enc_mask_dev) PTTS_HIP(hipMemcpy2DAsync(em, (size_t)c.max_enc * 4, enc_mask_dev, (size_t)N * 4, (size_t)N * 4, n, hipMemcpyDeviceToDevice, st));
+  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, em, 1, (size_t)n * c.max_enc);
+  if (prompt_mask_dev && P > 0) PTTS_HIP(hipMemcpy2DAsync(pm, (size_t)e->max_prompt * 4, prompt_mask_dev, (size_t)P * 4, (size_t)P * 4, n, hipMemcpyDeviceToDevice, st));
+  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, pm, 1, (size_t)n * e->max_prompt);
+  PTTS_HIP(hipMemcpyAsync(e->qc, enc_dev, (size_t)n * N * H * 4, hipMemcpyDeviceToDevice, st));
+  if (P > 0) PTTS_HIP(hipMemcpyAsync(e->ffn, prompt_dev, (size_t)n * P * H * 4, hipMemcpyDeviceToDevice, st));
+  float* h_one = e->h_adm;
+  e->h_adm = e->h_adm_rows;  // n * (P + 1) residual rows; the step graphs do not reference it
+  session_row_view(e, B, true);
+  e->B = n;
+  const int rc_fwd = forward_dispatch(e, true, st);
+  e->B = B;
+  session_row_view(e, B, false);
+  e->h_adm = h_one;
+  PTTS_TRY(rc_fwd);
+  const int ru = (int)(64 * e->esize / 16);  // 16-byte units of an arena row
+  for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
+    const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
+    AdmitMoveArgs a = {};
+    a.layers = e->move_layers; a.logits = e->logits; a.enc_mask = e->enc_mask; a.prompt_mask = e->prompt_mask;
+    a.src0 = B + j0; a.nlayers = c.num_layers; a.nkv = e->nkv; a.nkc = e->nkc;
+    a.self_u = (P + 1) * ru; a.self_cap_u = c.max_ctx * ru; a.cross_u = N * ru; a.cross_cap_u = c.max_enc * ru;
+    a.logit_u = K * c.vocab_size / 4;
+    a.enc_n = enc_mask_dev ? N : c.max_enc; a.enc_ld = c.max_enc;  // what ptts_admit_row writes of each mask row
+    a.prompt_n = (prompt_mask_dev && P > 0) ? P : e->max_prompt; a.prompt_ld = e->max_prompt;
+    for (int j = 0; j < nj; ++j) a.rows[j] = rows[j0 + j];
+    const int units = 2 * (e->nkv * a.self_u + e->nkc * a.cross_u);
+    hipLaunchKernelGGL(admit_move_rows_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, a);
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "admit_move_rows launch failed: %s", hipGetErrorString(err));
+  for (int j = 0; j < n; ++j) {
+    const int row = rows[j];
+    hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
+                       e->row_maxlen, row, 1, K, c.bos_token_id, 1, Ls[j]);
+    e->slot_busy[row] = 1; e->slot_ub[row] = P + 1; e->slot_maxlen[row] = Ls[j];
+    if (gps && gps[j]) hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, st, e->slot_gen, row, 1, SlotGen{dev_gen_of(*gps[j], Ls[j]), 1, 0});
+    if (sample) PTTS_TRY(launch_tail(e, st, true, row));
+  }
+  if (!sample) e->h_ready = false;
+  return PTTS_OK;
 }
 
 extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {

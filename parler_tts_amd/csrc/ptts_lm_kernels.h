@@ -2937,3 +2937,51 @@ static __global__ void set_slot_gen_kernel(SlotGen* recs, int row0, int nrows, S
 static __global__ void fill_int_kernel(int* p, int v, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
+
+// ptts_admit_rows: a group of n requests is prefilled as a static batch of n on the spare arena rows behind the session's slots (rows
+// src0 .. src0 + n - 1 of every batch-outermost array); this kernel then moves request j from spare row src0 + j to its slot rows[j], in one
+// launch: per layer and K/V head the self K/V rows [0, P + 1) and the cross K/V rows [0, N), and (blockIdx.y == nlayers) the K * V step-0
+// logits and both mask rows. Arena rows are 128 or 256 bytes and a slot's logits a multiple of 64, so everything but the masks moves in
+// 16-byte units. The slot list travels by value as a kernel argument (no staging buffer, no copy to wait on). grid (pieces, layers + 1, n).
+constexpr int ADMIT_ROWS_MAX = 64;  // slots per launch; a longer list takes several
+struct AdmitMoveLayer { void *k_self, *v_self, *k_cross, *v_cross; };  // one layer's arenas (slot 0)
+struct AdmitMoveArgs {
+  const AdmitMoveLayer* layers;  // [nlayers], device memory, written once
+  float* logits;
+  int *enc_mask, *prompt_mask;
+  int src0;                    // first spare row of this launch
+  int nlayers, nkv, nkc;       // self / cross K/V heads
+  int self_u, self_cap_u;      // 16-byte units per (slot, head): the P + 1 rows to move, the head's capacity (max_ctx rows)
+  int cross_u, cross_cap_u;    // the N rows to move, max_enc rows
+  int logit_u;                 // K * V * 4 / 16
+  int enc_n, enc_ld, prompt_n, prompt_ld;  // mask positions to move and the row strides
+  int rows[ADMIT_ROWS_MAX];
+};
+static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveArgs a) {
+  const size_t src = (size_t)(a.src0 + (int)blockIdx.z), dst = (size_t)a.rows[blockIdx.z];
+  const int tid = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256, l = blockIdx.y;
+  if (l == a.nlayers) {
+    uint4* lg = reinterpret_cast<uint4*>(a.logits);
+    for (int u = tid; u < a.logit_u; u += stride) lg[dst * a.logit_u + u] = lg[src * a.logit_u + u];
+    for (int i = tid; i < a.enc_n; i += stride) a.enc_mask[dst * a.enc_ld + i] = a.enc_mask[src * a.enc_ld + i];
+    for (int i = tid; i < a.prompt_n; i += stride) a.prompt_mask[dst * a.prompt_ld + i] = a.prompt_mask[src * a.prompt_ld + i];
+    return;
+  }
+  const AdmitMoveLayer L = a.layers[l];
+  const int su = a.nkv * a.self_u, cu = a.nkc * a.cross_u;
+  for (int u = tid; u < 2 * (su + cu); u += stride) {
+    uint4* base;
+    size_t heads, cap;
+    int head, off;
+    if (u < 2 * su) {
+      const int v = u >= su, r = u - v * su;
+      base = reinterpret_cast<uint4*>(v ? L.v_self : L.k_self);
+      head = r / a.self_u; off = r - head * a.self_u; heads = a.nkv; cap = a.self_cap_u;
+    } else {
+      const int r0 = u - 2 * su, v = r0 >= cu, r = r0 - v * cu;
+      base = reinterpret_cast<uint4*>(v ? L.v_cross : L.k_cross);
+      head = r / a.cross_u; off = r - head * a.cross_u; heads = a.nkc; cap = a.cross_cap_u;
+    }
+    base[(dst * heads + head) * cap + off] = base[(src * heads + head) * cap + off];
+  }
+}

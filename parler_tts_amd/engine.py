@@ -287,6 +287,59 @@ class DecoderEngine:
             self._keep_rows = {}
         self._keep_rows[int(row)] = keep  # consumed asynchronously by the enqueued kernels
 
+    def admit_rows(self, rows, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
+                   prompt_mask: Optional[torch.Tensor], max_lengths=None, sample: bool = True, gens=None):
+        """Prefills ``n = len(rows)`` requests into ``n`` distinct idle slots with ONE prefill pass (``ptts_admit_rows``): request ``j``
+        (``enc[j]`` [N, H], ``prompt[j]`` [P, H], ``max_lengths[j]``, ``gens[j]``) goes into slot ``rows[j]``, which afterwards is what
+        ``admit_row`` makes of it. The engine needs ``n`` spare rows behind the session's slots (``max_batch >= slots + n``).
+        ``max_lengths``: one per request (``None``: the session's for all); ``gens``: ``None``, or one entry per request, each ``None`` or
+        ``admit_row``'s ``gen``."""
+        rows = [int(r) for r in rows]
+        n = len(rows)
+        max_lengths = [0] * n if max_lengths is None else [int(x) for x in max_lengths]
+        if len(max_lengths) != n or (gens is not None and len(gens) != n):
+            raise ValueError(f"{n} slots, {len(max_lengths)} max_lengths, {None if gens is None else len(gens)} gens")
+        gp_arr, gps = None, []
+        if gens is not None:
+            gp_arr = (C.POINTER(N.PttsGenParams) * max(n, 1))()
+            for j, gen in enumerate(gens):
+                if gen is None:
+                    continue
+                unknown = set(gen) - {"min_new_tokens", "do_sample", "temperature", "top_k", "top_p", "use_eos_gate", "seed"}
+                if unknown:
+                    raise ValueError(f"unknown per-request generation parameters {sorted(unknown)}")
+                gps.append(N.PttsGenParams(0, int(gen.get("min_new_tokens", 0)), int(bool(gen.get("do_sample", False))), float(gen.get("temperature", 1.0)),
+                                           int(gen.get("top_k", 0) or 0), float(gen.get("top_p", 1.0)), int(bool(gen.get("use_eos_gate", True))),
+                                           int(gen.get("seed", 0)) & (2 ** 64 - 1)))
+                gp_arr[j] = C.pointer(gps[-1])
+        enc = enc.to(self.device, torch.float32).contiguous()
+        if enc.dim() != 3 or tuple(enc.shape) != (n, self.session_N, self.H):
+            raise ValueError(f"encoder states {tuple(enc.shape)} do not match [{n}, {self.session_N}, {self.H}] ({n} slots at the session's widths)")
+        keep = [enc]
+        pr = em = pm = None
+        if self.P > 0:
+            if prompt is None or tuple(prompt.shape) != (n, self.P, self.H):
+                raise ValueError(f"prompt embeddings {None if prompt is None else tuple(prompt.shape)} do not match [{n}, {self.P}, {self.H}]")
+            pr = prompt.to(self.device, torch.float32).contiguous()
+            keep.append(pr)
+        if enc_mask is not None:
+            em = enc_mask.to(self.device, torch.int32).contiguous()
+            if tuple(em.shape) != (n, self.session_N):
+                raise ValueError(f"attention_mask {tuple(em.shape)} does not match [{n}, {self.session_N}]")
+            keep.append(em)
+        if prompt_mask is not None and self.P > 0:
+            pm = prompt_mask.to(self.device, torch.int32).contiguous()
+            if tuple(pm.shape) != (n, self.P):
+                raise ValueError(f"prompt_attention_mask {tuple(pm.shape)} does not match [{n}, {self.P}]")
+            keep.append(pm)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+        N.check(self.lib.ptts_admit_rows(self._h, n, (C.c_int32 * max(n, 1))(*rows), ptr(enc), ptr(em), ptr(pr), ptr(pm), (C.c_int32 * max(n, 1))(*max_lengths),
+                                         int(sample), gp_arr, _stream_ptr(device=self.device)), "ptts_admit_rows")
+        if not hasattr(self, "_keep_rows"):
+            self._keep_rows = {}
+        for r in rows:
+            self._keep_rows[r] = keep  # consumed asynchronously by the enqueued kernels
+
     def row_state(self) -> Tuple[list, list]:
         """(cur_len, live) per slot: columns written so far incl. BOS, and whether the slot is still generating. Synchronises."""
         cur, live = (C.c_int32 * self.B)(), (C.c_int32 * self.B)()

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Continuous batching against static batching on a request stream of mixed lengths (Mini-v1 shapes, bf16, synthetic weights).
 
-  python tools/continuous_bench.py [--repeats 5] [--static-only] [--per-request] [--stream [--stream-chunks 43,86]] [--out FILE]
+  python tools/continuous_bench.py [--repeats 5] [--static-only] [--per-request] [--stream [--stream-chunks 43,86]]
+                                   [--admit-batch 4,8 [--slots 64] [--burst-only]] [--out FILE]
 
 256 requests whose lengths come from a fixed seeded list (uniform 150..860 frames, set through per-request max_new_tokens; EOS is blocked,
 so lengths are exact), 32 slots. Reports
@@ -21,7 +22,16 @@ one and a sampled one with a seed (temperature 0.7, top-k 50), min_new_tokens as
 
 --stream measures the streaming mode instead of (a), (d), (e): (b) and the streaming batcher (`stream_chunk_frames`) alternate on the same list;
 per chunk size it reports audio-s/s next to (b), the codec passes and the mean rows per pass, and per request the host time from its admission
-and from its submission to its first chunk (p50 / p90 / max), next to admission -> whole waveform of the non-streaming batcher."""
+and from its submission to its first chunk (p50 / p90 / max), next to admission -> whole waveform of the non-streaming batcher.
+
+--admit-batch N[,M..] measures group admissions (ptts_admit_rows) instead of (a), (d), (e): (b) and the batcher with `admit_batch=N` alternate on
+the same list (--slots sets the slot count of both); per N it reports audio-s/s next to (b), the total time in admissions (one run with a sync around
+each phase) and the groups formed, and
+  (g) group    : GPU time of one admission of n requests into n retired slots beside the other live slots, as ONE ptts_admit_rows and as n
+                 ptts_admit_row
+  (u) burst    : wall time from the first admission of a full session until every slot holds its first token, with one ptts_row_state after the
+                 admissions - in groups of n, and one by one (n = 1)
+--burst-only runs (g) and (u) alone (a short run, e.g. under a kernel trace)."""
 import argparse
 import ctypes as C
 import json
@@ -94,14 +104,15 @@ def request_options(i):
     return {"do_sample": False} if i % 4 == 1 else {"do_sample": True, "temperature": 0.7, "top_k": 50, "seed": 1000 + i}
 
 
-def run_batcher(model, desc, prompt, frames, per_request=False):
+def run_batcher(model, desc, prompt, frames, per_request=False, admit_batch=1):
     import parler_tts_amd as P
 
     new_max = FRAMES_HI + K - 1
+    kw = {"admit_batch": admit_batch} if admit_batch > 1 else {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     cb = P.ContinuousBatcher(model, slots=SLOTS, max_description_tokens=bench.N_DESC, max_prompt_tokens=bench.N_PROMPT, poll_steps=16, do_sample=False,
-                             max_new_tokens=new_max, min_new_tokens=new_max)
+                             max_new_tokens=new_max, min_new_tokens=new_max, **kw)
     tickets = [cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1, **(request_options(i) if per_request else {}))
                for i in range(N_REQ)]
     torch.cuda.synchronize()
@@ -195,13 +206,14 @@ def stream_report(model, desc, prompt, frames, audio_s, chunks, repeats, say):
     return res
 
 
-def batcher_breakdown(model, desc, prompt, frames):
+def batcher_breakdown(model, desc, prompt, frames, admit_batch=1):
     """One extra run with a device synchronisation around each phase (so phases no longer overlap host work: an attribution, not a throughput)."""
     import parler_tts_amd as P
 
     new_max = FRAMES_HI + K - 1
+    kw = {"admit_batch": admit_batch} if admit_batch > 1 else {}
     cb = P.ContinuousBatcher(model, slots=SLOTS, max_description_tokens=bench.N_DESC, max_prompt_tokens=bench.N_PROMPT, poll_steps=16, do_sample=False,
-                             max_new_tokens=new_max, min_new_tokens=new_max)
+                             max_new_tokens=new_max, min_new_tokens=new_max, **kw)
     acc = {"admit": 0.0, "steps": 0.0, "poll": 0.0, "ids+retire": 0.0, "codec": 0.0}
     count = {k: 0 for k in acc}
 
@@ -219,6 +231,8 @@ def batcher_breakdown(model, desc, prompt, frames):
     eng = cb.eng
     saved = (eng.admit_row, eng.decode_steps, eng.row_state, eng.row_ids)
     eng.admit_row, eng.decode_steps = timed("admit", eng.admit_row), timed("steps", eng.decode_steps)
+    if admit_batch > 1:
+        eng.admit_rows = timed("admit", eng.admit_rows)
     eng.row_state, eng.row_ids = timed("poll", eng.row_state), timed("ids+retire", eng.row_ids)
     cb._decode_group = timed("codec", cb._decode_group)
     try:
@@ -231,6 +245,9 @@ def batcher_breakdown(model, desc, prompt, frames):
         total = time.perf_counter() - t0
     finally:
         eng.admit_row, eng.decode_steps, eng.row_state, eng.row_ids = saved
+        eng.__dict__.pop("admit_rows", None)
+    if admit_batch > 1:
+        count["groups"] = list(cb.admission_groups)
     return total, acc, count
 
 
@@ -277,6 +294,96 @@ def step_session(model, enc, pr, ev, live):
     return step, admit
 
 
+def group_admission(model, enc, pr, ev, n):
+    """(g): every slot live, then slots 5 .. 5 + n - 1 retired and re-admitted - as one ptts_admit_rows, and one by one. GPU time, ms."""
+    import parler_tts_amd as P
+
+    spare = P.ContinuousBatcher.spare_rows(SLOTS, n)
+    eng = model._get_engine(SLOTS + spare, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1)
+    eng.set_gen_params(max_length=bench.NEW_TOKENS + 1, min_new_tokens=bench.NEW_TOKENS)
+    eng.begin_session(SLOTS, bench.N_DESC, bench.N_PROMPT)
+    for s in range(SLOTS):
+        eng.admit_row(s, enc[s], None, pr[s], None)
+    eng.decode_steps(WARM_STEPS)
+    rows = list(range(5, 5 + spare))
+    out = []
+    for grouped in (True, False):
+        for s in rows:
+            eng.retire_row(s)
+        if grouped:
+            out.append(ev.ms(lambda: eng.admit_rows(rows, enc[8:8 + spare], None, pr[8:8 + spare], None)))
+        else:
+            out.append(ev.ms(lambda: [eng.admit_row(s, enc[8 + j], None, pr[8 + j], None) for j, s in enumerate(rows)]))
+        eng.decode_steps(4)
+    return spare, out[0], out[1]
+
+
+def burst(model, enc, pr, n):
+    """(u): a full session start. Wall time from the first admission until ptts_row_state returns behind the last one, ms."""
+    import parler_tts_amd as P
+
+    spare = P.ContinuousBatcher.spare_rows(SLOTS, n)
+    eng = model._get_engine(SLOTS + spare, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1)
+    eng.set_gen_params(max_length=bench.NEW_TOKENS + 1, min_new_tokens=bench.NEW_TOKENS)
+    eng.begin_session(SLOTS, bench.N_DESC, bench.N_PROMPT)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if spare:
+        for g0 in range(0, SLOTS, spare):
+            g1 = min(g0 + spare, SLOTS)
+            eng.admit_rows(list(range(g0, g1)), enc[g0:g1], None, pr[g0:g1], None)
+    else:
+        for s in range(SLOTS):
+            eng.admit_row(s, enc[s], None, pr[s], None)
+    cur, live = eng.row_state()
+    dt = time.perf_counter() - t0
+    assert cur == [2] * SLOTS and all(live), "a slot is without its first token"
+    return dt * 1e3
+
+
+def admit_batch_report(model, desc, prompt, frames, audio_s, sizes, repeats, burst_only, say):
+    res = {}
+    enc = model._encode_description(desc[:max(64, SLOTS)], None).float()
+    pr = model.embed_prompts(prompt[:max(64, SLOTS)]).float()
+    ev = Events()
+    if not burst_only:
+        run_batcher(model, desc, prompt, frames)
+        for n in sizes:
+            run_batcher(model, desc, prompt, frames, admit_batch=n)  # warm: the engine with spare rows, its step graphs
+        base, runs = [], {n: [] for n in sizes}
+        for r in range(repeats):
+            base.append(run_batcher(model, desc, prompt, frames)[0])
+            for n in sizes:
+                runs[n].append(run_batcher(model, desc, prompt, frames, admit_batch=n)[0])
+            say(f"  repeat {r}: batcher {base[-1]:.3f} s, " + ", ".join(f"admit_batch {n} {runs[n][-1]:.3f} s" for n in sizes))
+        mb, lob, hib = med_spread(base)
+        say(f"(b) ContinuousBatcher: median {mb:.3f} s = {audio_s / mb:.1f} audio-s/s (spread {audio_s / hib:.1f} .. {audio_s / lob:.1f})")
+        total, acc, count = batcher_breakdown(model, desc, prompt, frames)
+        say(f"    admissions of (b), one run with a sync around each phase: {acc['admit']:.3f} s in {count['admit']} calls of {total:.3f} s")
+        res.update(batcher_s=mb, batcher_audio_s_per_s=audio_s / mb, admit_s=acc["admit"])
+        for n in sizes:
+            m, lo, hi = med_spread(runs[n])
+            total, acc, count = batcher_breakdown(model, desc, prompt, frames, admit_batch=n)
+            groups = count.get("groups", [])
+            say(f"(n) admit_batch {n}: median {m:.3f} s = {audio_s / m:.1f} audio-s/s (spread {audio_s / hi:.1f} .. {audio_s / lo:.1f}) = {mb / m:.3f} of (b); "
+                f"admissions {acc['admit']:.3f} s in {count['admit']} calls of {total:.3f} s; {len(groups)} groups, sizes " +
+                ", ".join(f"{k}: {groups.count(k)}" for k in sorted(set(groups))))
+            res[f"admit_batch{n}"] = {"s": m, "audio_s_per_s": audio_s / m, "of_b": mb / m, "admit_s": acc["admit"], "admit_calls": count["admit"]}
+    for r in range(2):  # the first round warms the prefill kernels of these row counts
+        singles = burst(model, enc, pr, 1)
+        groups = {n: burst(model, enc, pr, n) for n in sizes}
+        adm = {n: group_admission(model, enc, pr, ev, n) for n in sizes}
+    say(f"(u) session start, {SLOTS} slots, first admission -> every slot holds its first token: one by one {singles:.2f} ms = {SLOTS} x {singles / SLOTS:.3f} ms; " +
+        "; ".join(f"in groups of {n} {groups[n]:.2f} ms ({singles / groups[n]:.2f} x)" for n in sizes))
+    for n in sizes:
+        spare, g, one = adm[n]
+        say(f"(g) {spare} requests beside {SLOTS - spare} live slots: one ptts_admit_rows {g:.3f} ms, {spare} x ptts_admit_row {one:.3f} ms ({one / spare:.3f} ms each): "
+            f"{one / g:.2f} x")
+        res[f"group{n}"] = {"rows": spare, "group_ms": g, "singles_ms": one}
+    res.update(burst_single_ms=singles, burst_ms={str(n): groups[n] for n in sizes})
+    return res
+
+
 def med_spread(xs):
     return statistics.median(xs), min(xs), max(xs)
 
@@ -288,8 +395,15 @@ def main():
     ap.add_argument("--per-request", action="store_true", help="also measure (p): every second request with its own sampler record")
     ap.add_argument("--stream", action="store_true", help="measure the streaming mode against (b) instead of (a), (d), (e)")
     ap.add_argument("--stream-chunks", default="43,86", help="stream_chunk_frames values to measure")
+    ap.add_argument("--admit-batch", default=None, help="admit_batch values to measure against single admissions, e.g. 4,8")
+    ap.add_argument("--slots", type=int, default=SLOTS, help="slots of the session (with --admit-batch)")
+    ap.add_argument("--burst-only", action="store_true", help="with --admit-batch: only the session start and the group admission")
     ap.add_argument("--out", default=None, help="also append the report to this file")
     a = ap.parse_args()
+    if a.slots != SLOTS:
+        if not a.admit_batch:
+            ap.error("--slots goes with --admit-batch")
+        globals()["SLOTS"] = a.slots
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     frames = request_frames()
@@ -307,6 +421,15 @@ def main():
     st_steps, cb_steps = schedule_steps(frames)
     say(f"  decode steps of the schedules themselves: static {st_steps}, FIFO slots {cb_steps} (ratio {st_steps / cb_steps:.3f}: (c) less the drain of the "
         f"last requests, when nothing is left to admit)")
+    if a.admit_batch:
+        with torch.no_grad():
+            res = admit_batch_report(model, desc, prompt, frames, audio_s, [int(n) for n in a.admit_batch.split(",")], a.repeats, a.burst_only, say)
+        say(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.stream:
         with torch.no_grad():
             res = stream_report(model, desc, prompt, frames, audio_s, [int(c) for c in a.stream_chunks.split(",")], a.repeats, say)
