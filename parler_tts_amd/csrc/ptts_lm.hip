@@ -1,12 +1,12 @@
 // Decoder-LM engine behind the C ABI of include/ptts.h: packed weights, static KV arena, device-resident
 // sampler state, one captured hipGraph per batch size. Replaces ParlerTTSForCausalLM.forward + the
 // transformers `_sample` loop of the reference (modeling_parler_tts.py:1865, :3564).
+#include <array>
 #include <map>
 #include <set>
 #include <string>
 #include <type_traits>
 #include <vector>
-#include <string.h>
 
 #include "ptts_common.h"
 #include "ptts_lm_kernels.h"
@@ -83,10 +83,9 @@ struct ptts_engine {
   int nkv = 0, nkc = 0;                // self / cross K/V heads (== num_heads unless grouped-query attention)
   long long* prefix = nullptr;         // voice-prompt codes [max_batch*K][max_ctx], valid for the next prefill when pending_T > 0
   int pending_T = 0;
-  int prefill_T = 0;                   // voice-prompt columns folded into the current prefill pass (batched multi-column prefill)
   float* lnstat = nullptr;             // strip statistics of the residual rows (EPI_RESID -> PRO_LNS), [max_batch][H/16][2]
   bool use_lns = true;                 // 8 < batch <= 32 decode: LayerNorm fused into the consumer GEMM (no rows_prep node)
-  int S_self = 4, S_cross = 1;
+  int S_self = 4;
   int cross_waves = 4; // waves per cross-attention workgroup on the GEMV step: one 8-deep batch of row groups per wave covers max_enc
   // state
   long long* ids = nullptr;
@@ -155,10 +154,59 @@ struct ptts_engine {
 
 namespace {
 
+// What one forward pass addresses: the whole engine (whole_view) or a few arena rows of it (rows_view). A caller that wants a pass somewhere
+// else builds another view; the engine itself is never edited to aim one.
+struct FwdView {
+  int B, N, P;
+  int T;                         // voice-prompt columns folded into this prefill pass (batched multi-column prefill)
+  int kv_bound;                  // attention fetch bound of a decode forward
+  bool session, xfold_valid;
+  float *h, *logits;             // residual rows [B * Q][H]; logits [B][K * V]
+  long long* ids;
+  int *cur_len, *unfinished, *has_eos, *first_unf, *enc_mask, *prompt_mask;
+  const KvLayer* kv_layers;      // [layers] operands of the batched cross K/V projection
+  size_t self_off, cross_off;    // bytes from a layer's self / cross K/V arena to utterance 0 of this view (sessions refuse kv_fp8: the scales need none)
+};
+
+// the whole engine, now
+FwdView whole_view(const ptts_engine* e) {
+  FwdView v = {};
+  v.B = e->B; v.N = e->N; v.P = e->P; v.kv_bound = e->kv_bound; v.session = e->session; v.xfold_valid = e->xfold_valid;
+  v.h = e->h; v.logits = e->logits; v.ids = e->ids; v.cur_len = e->cur_len; v.unfinished = e->unfinished; v.has_eos = e->has_eos;
+  v.first_unf = e->first_unf; v.enc_mask = e->enc_mask; v.prompt_mask = e->prompt_mask; v.kv_layers = e->kv_layers;
+  return v;
+}
+
+// Rows [row, row + n) of a session's engine as an n-utterance engine: the prefill kernels address utterance 0 of what they are given. The
+// residual rows go to `h` (h_adm, h_adm_rows), because e->h[B][H] holds the other slots' next step input.
+FwdView rows_view(const ptts_engine* e, int row, int n, float* h) {
+  const ptts_config& c = e->cfg;
+  const size_t r = (size_t)row, K = (size_t)c.num_codebooks;
+  FwdView v = whole_view(e);
+  v.B = n; v.h = h; v.kv_layers = e->kv_layers_rows + r * c.num_layers;
+  v.ids += r * K * e->ids_ld; v.cur_len += r; v.first_unf += r; v.unfinished += r * K; v.has_eos += r * K;
+  v.logits += r * K * c.vocab_size; v.enc_mask += r * c.max_enc; v.prompt_mask += r * e->max_prompt;
+  v.self_off = r * e->nkv * c.max_ctx * 64 * e->esize; v.cross_off = r * e->nkc * c.max_enc * 64 * e->esize;
+  return v;
+}
+
+inline void* at(void* p, size_t off) { return static_cast<char*>(p) + off; }
+
+#ifdef PTTS_TIMING  // measurement build: node number `node_` of the decode step stamps into its own 48 slots of e->dbg_stamps
+#define PTTS_DBG_STAMP(args, on_, node_) (args).dbg = (e->dbg_stamps && (on_)) ? e->dbg_stamps + (node_) * 48 : nullptr
+#else
+#define PTTS_DBG_STAMP(args, on_, node_) do { } while (0)
+#endif
+
+// behind a run of launches: the first error any of them left
+int launch_status(const char* what) {
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? PTTS_OK : ptts_fail(PTTS_E_HIP, "%s launch failed: %s", what, hipGetErrorString(err));
+}
 
 // LayerNorm (+ fold of pending fc2 partials) + projection, tiled over 64 weight rows x G utterances (lnproj_fused_kernel): decode at batch > 8
 template <typename WT, int EPI>
-int launch_lnproj(ptts_engine* e, LnProjArgs p, hipStream_t st, int g) {
+int launch_lnproj(const ptts_engine* e, LnProjArgs p, hipStream_t st, int g) {
   constexpr int KT = Elem<WT>::KT;
   const int H = p.K;
   p.invK = 1.0f / (float)H;
@@ -191,15 +239,34 @@ int launch_lnproj(ptts_engine* e, LnProjArgs p, hipStream_t st, int g) {
   else PTTS_LNPROJ_LAUNCH(8, 6);
 #undef PTTS_LNPROJ_LAUNCH
 #undef PTTS_LNPROJ_ONE
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "lnproj launch failed: %s", hipGetErrorString(err));
-  return PTTS_OK;
+  return launch_status("lnproj");
+}
+
+// LN2 + cross q projection + cross-attention of x.B rows as one node (xattn_fused_kernel), gsz utterances per workgroup: heads x ceil(B / gsz)
+// workgroups, the 8 / gsz waves of an utterance split the description's row groups
+template <typename WT>
+void launch_xattn_fused(XAttnArgs x, int gsz, hipStream_t st) {
+  const int H = x.K, M = x.B, KTw = Elem<WT>::KT;
+  const int mg = M < gsz ? M : gsz;
+  const size_t sh = (size_t)mg * (H * sizeof(WT) + 16) + 8 * 1024 + (size_t)gsz * 64 * 4 + 8 * 64 * 4 + 64;
+  const dim3 xg(x.nheads, (M + gsz - 1) / gsz);
+  const bool u16 = ((H / KTw) / 2) % 16 == 0;
+  if (H == 1024 && u16) {  // Mini-v1
+    if (gsz == 4) ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 4>, xg, dim3(512), sh, st, x);
+    else if (gsz == 2) ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 2>, xg, dim3(512), sh, st, x);
+    else ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 8>, xg, dim3(512), sh, st, x);
+  } else if (H == 1024) ptts_klaunch(xattn_fused_kernel<WT, 8, 4>, xg, dim3(512), sh, st, x);
+  else if (H == 1536) {  // Large-v1
+    if (gsz == 4) ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 4>, xg, dim3(512), sh, st, x);
+    else if (gsz == 2) ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 2>, xg, dim3(512), sh, st, x);
+    else ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 8>, xg, dim3(512), sh, st, x);
+  } else ptts_klaunch(xattn_fused_kernel<WT, 8, 2>, xg, dim3(512), sh, st, x);                            // hidden 512
 }
 
 // LN -> GEMM and split-KV-combine -> GEMM: fused prologue at M <= 8 rows, prep kernel + copy staging above (the
 // redundant per-workgroup prologue is 88 % of the GEMM at M = 32: tools/phase_probe, profiles/).
 template <typename WT, int PRO, int EPI>
-int gemm_with_prologue(ptts_engine* e, GemmArgs g, hipStream_t st) {
+int gemm_with_prologue(const ptts_engine* e, GemmArgs g, hipStream_t st) {
   if (g.M <= 8) return launch_gemm<WT, PRO, EPI>(g, st);
   if constexpr (PRO == PRO_LN) {
     // statistics came with the residual rows and all M normalised rows fit in LDS beside the reduction buffer
@@ -214,186 +281,208 @@ int gemm_with_prologue(ptts_engine* e, GemmArgs g, hipStream_t st) {
   return launch_gemm<WT, PRO_COPY, EPI>(g, st);
 }
 
-// One decoder forward over Q positions per utterance (Q = P+1 at prefill, 1 at decode) up to the logits.
-template <typename WT>
-int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true) {
+// Causal self-attention of layer `w` over the view's rows of the KV arena, Q positions per utterance from the QKV rows in e->qkv, RoPE fused: a
+// decode pass appends the new position and splits the context S_self ways; a prefill reads the rows written before it and never splits (strip_path)
+AttnArgs self_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w, int Q, bool prefill, int fo) {
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, B = e->B;
+  const int H = c.hidden_size, nh = c.num_heads, nkv = e->nkv, Hkv = nkv * 64, QKV = H + 2 * Hkv, S = prefill ? 1 : e->S_self;
+  AttnArgs a = {};
+  a.q = e->qkv; a.q_ld = QKV; a.knew = e->qkv + H; a.vnew = e->qkv + H + Hkv; a.kv_ld = QKV; a.kv_heads = nkv; a.n_rep = nh / nkv;
+  a.kcache = at(w.k_self, v.self_off); a.vcache = at(w.v_self, v.self_off); a.cap = c.max_ctx; a.kv_bound = prefill ? c.max_ctx : v.kv_bound;
+  a.cur_len = prefill ? nullptr : v.cur_len; a.dims = e->dims;
+  a.mask = v.prompt_mask; a.mask_ld = e->max_prompt;
+  a.cos = c.rope ? e->rope_cos : nullptr; a.sin = c.rope ? e->rope_sin : nullptr;
+  a.part = e->part; a.stats = e->stats; a.S = S; a.Q = Q; a.nheads = nh; a.H = H; a.cross = 0;
+  a.fused_append = prefill ? 0 : 1; a.scale = 1.0f / sqrtf((float)(H / nh)); a.kscale = w.ks_self; a.vscale = w.vs_self;
+  a.direct_out = S == 1 ? e->xw : nullptr; a.out_fo = fo;
+  return a;
+}
+
+// Cross-attention of layer `w` against the static description K/V, queries in e->qc. The description is short: never split, softmax finished
+// in the attention kernel.
+AttnArgs cross_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w, int Q, bool prefill, int fo) {
+  const ptts_config& c = e->cfg;
+  const int H = c.hidden_size, nh = c.num_heads, nkc = e->nkc;
+  AttnArgs a = {};
+  a.q = e->qc; a.q_ld = H; a.kcache = at(w.k_cross, v.cross_off); a.vcache = at(w.v_cross, v.cross_off); a.cap = c.max_enc; a.kv_bound = c.max_enc;
+  a.cur_len = prefill ? nullptr : v.cur_len; a.dims = e->dims; a.mask = v.enc_mask; a.mask_ld = c.max_enc;
+  a.cos = c.rope ? e->rope_cos : nullptr; a.sin = c.rope ? e->rope_sin : nullptr;  // quirk: q rotated, keys not (:858 vs :880)
+  a.part = e->part; a.stats = e->stats; a.S = 1; a.Q = Q; a.nheads = nh; a.H = H; a.cross = 1; a.kv_heads = nkc; a.n_rep = nh / nkc;
+  a.fused_append = 0; a.scale = 1.0f / sqrtf((float)(H / nh)); a.direct_out = e->xw; a.out_fo = fo;
+  return a;
+}
+
+// cross-attention K/V of the description, once per prefill (:877-878 then reused :872-875)
+template <typename WT>
+int project_cross_kv(const ptts_engine* e, FwdView v, hipStream_t st) {
+  const ptts_config& c = e->cfg;
+  const int H = c.hidden_size, nkc = e->nkc, B = v.B;
+  // encoder states were staged into qc by stage_inputs (fp32 row-major [B*N][H]); convert once to the engine dtype
+  const size_t n = (size_t)B * v.N * H;
+  hipLaunchKernelGGL((convert_kernel<WT, float>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, e->qc,
+                     reinterpret_cast<WT*>(e->xw2), n);
+  // every layer's K/V projection in ONE launch (blockIdx.z = layer): the strip kernel up to 256 rows, the bf16 engine's LDS-DMA GEMM above (round 6:
+  // 24 launches of ~17 us at 32 descriptions x 64 tokens were one tenth of that prefill; a shape the GEMM declines falls back to the strips)
+  const bool one_launch = (B * v.N <= 256 || (sizeof(WT) == 2 && H % 64 == 0 && (2 * nkc * 64) % 64 == 0));
+  for (int l = 0; l < (one_launch ? 1 : c.num_layers); ++l) {
+    GemmArgs g = {};
+    g.W = e->L[l].ckv; g.M = B * v.N; g.N = 2 * nkc * 64; g.K = H;
+    g.x = reinterpret_cast<const float*>(e->xw2); g.x_ld = H; g.x_row_mul = 1; g.x_row_off = 0;
+    g.kcache = at(e->L[l].k_cross, v.cross_off); g.vcache = at(e->L[l].v_cross, v.cross_off); g.kv_rows_per_b = v.N; g.kv_cap = c.max_enc; g.nheads = nkc;
+    if (one_launch) { g.kv_layers = v.kv_layers; g.kv_nlayers = c.num_layers; }
+    PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_KV>(g, st)));
+  }
+  return PTTS_OK;
+}
+
+// the residual-stream input: Q positions per utterance at prefill (prompt rows staged in ffn + the BOS / voice-prompt columns), the last column at decode
+template <typename WT>
+void launch_embed(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStream_t st) {
+  const ptts_config& c = e->cfg;
+  EmbedArgs ea = {};
+  ea.tables = e->embed; ea.pos_table = c.rope ? nullptr : e->pos_table; ea.prompt = prefill ? e->ffn : nullptr;
+  ea.ids = v.ids; ea.ids_ld = e->ids_ld; ea.cur_len = v.cur_len; ea.dims = e->dims; ea.h = v.h;
+  ea.H = c.hidden_size; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.bos = c.bos_token_id; ea.pad = c.pad_token_id;
+  ea.prefill = prefill ? 1 : 0;
+  if (v.session && !prefill)  // every slot under its own request's delay pattern
+    hipLaunchKernelGGL((embed_kernel<WT, true>), dim3(1, v.B), dim3(256), 0, st, EmbedSessionArgs{ea, e->row_maxlen});
+  else
+    hipLaunchKernelGGL((embed_kernel<WT, false>), dim3(Q, v.B), dim3(256), 0, st, ea);
+}
+
+// Decode step of 1..gemv_rows utterances up to the logits: 8 row-per-wave GEMV / attention nodes per layer, every weight matrix spread over all
+// CUs and read once
+template <typename WT>
+int gemv_step(const ptts_engine* e, FwdView v, hipStream_t st) {
+  const ptts_config& c = e->cfg;
+  const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, M = v.B;
+  const int nkv = e->nkv, nkc = e->nkc, QKV = H + 2 * nkv * 64;  // grouped-query attention: fewer K/V heads
+  const float scale = 1.0f / sqrtf((float)(H / nh));
+  const int mode = c.dtype == PTTS_F32 ? GV_F32 : (e->w8 ? GV_BF16_W8 : GV_BF16);
+  // single utterance, sinusoidal positions: the two nodes of the self-attention block's first half as one (PTTS_NO_FUSE_QA=1: two nodes)
+  // (round 5: 2..8 utterances too - one grid slice per utterance, the slices of a head share its weight rows in the L2; PTTS_FUSE_QA_MAX=1: one only)
+  // measured, Mini-v1 us per step at contexts ~210 / ~460 / ~710, fused | two nodes (profiles/r05_experiments.txt call 2): 2 utterances 720 / 756 / 791 |
+  // 769 / 777 / 791; 3: 741 / 788 / 862 | 780 / 796 / 821; 4: 777 / 864 / 923 | 803 / 832 / 862; 8: 966 / 1010 / 1068 | 907 / 965 / 1023 (the slices of
+  // a head re-read its q / k / v rows from the L2 once per utterance and split): on up to fuse_qa_max utterances (3), PTTS_FUSE_QA_MAX forces a bound
+  const bool fuse_qa = e->fuse_qa && (M == 1 || (M <= e->fuse_qa_max && mode != GV_F32)) && !c.rope && ptts_qkvattn_ok(H, mode);
+  // KV splits of the fused node: the smallest count whose FIRST batch of row groups (8 waves x 4 groups x 8 bf16 / 4 fp32 rows per split,
+  // requested before q exists) covers the context bucket this graph is captured for - fewer workgroups recompute the head's q rows, and no
+  // split needs a second, dependent K/V batch (context ~210 / ~460 / ~710: 2 splits 554 / 562 / 586 us per step, 4 splits 575 / 577 / 579,
+  // 8 splits 645 / 646 / 648; profiles/r04_experiments.txt call 15)
+  int S_f = 1;
+  const int S_cap = M == 1 ? 8 : (M <= 4 ? 4 : 2);  // the combine prologue of the out_proj node holds S + 1 slots per lane: 12-wave workgroups (5..8 utterances) fit 2 splits
+  while (S_f < S_cap && S_f * ptts_qkvattn_rows_per_split(mode) < v.kv_bound) S_f *= 2;
+  auto gv = [&](int pro, int epi, int S, GemvArgs g, const char* what) -> int {
+    g.M = M;
+    const int rc_ = ptts_gemv_launch(mode, pro, epi, S, g, st);
+    if (rc_ == -1) return ptts_fail(PTTS_E_UNSUPPORTED, "gemv: no instance for %s (N=%d K=%d M=%d)", what, g.N, g.K, M);
+    if (rc_ != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (%s)", what);
+    return PTTS_OK;
+  };
+#define PTTS_DBG_NODE(args, l_, k_) PTTS_DBG_STAMP(args, M == 1, (size_t)(l_) * 5 + (k_))
+  for (int l = 0; l < c.num_layers; ++l) {
+    const LayerW& w = e->L[l];
+    if (fuse_qa) {  // LN1 + the head's q / k / v rows + split-KV self-attention + append in ONE node (qkv_attn_kernel), then combine + out_proj
+      QkvAttnArgs q = {};
+      q.W = w.qkv_rm; q.wscale = w.qkv_sc; q.x = v.h; q.gamma = w.ln1_g; q.beta = w.ln1_b;
+      q.kcache = at(w.k_self, v.self_off); q.vcache = at(w.v_self, v.self_off); q.cur_len = v.cur_len; q.P = &e->dims->P; q.mask = v.prompt_mask;
+      q.part = e->part; q.stats = e->stats; q.cap = c.max_ctx; q.kv_bound = v.kv_bound; q.mask_ld = e->max_prompt;
+      q.S = S_f; q.nheads = nh; q.H = H; q.kv_heads = nkv; q.scale = scale; q.M = M; q.x_ld = H;
+      PTTS_DBG_NODE(q, l, 0);
+      if (ptts_qkvattn_launch(mode, q, st) != 0) return ptts_fail(PTTS_E_HIP, "qkv_attn launch failed");
+      GemvArgs g = {};
+      g.W = w.o_rm; g.wscale = w.o_sc; g.out = v.h; g.out_ld = H; g.N = H; g.K = H; g.part = e->part; g.stats = e->stats; g.nheads = nh;
+      PTTS_DBG_NODE(g, l, 1);
+      PTTS_TRY(gv(GV_ATTN2, GV_RESID, S_f, g, "combine+out_proj"));
+    } else {
+    {  // LN1 + fused QKV projection (:1020-1021, :848-850)
+      GemvArgs g = {};
+      g.W = w.qkv_rm; g.wscale = w.qkv_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln1_g; g.beta = w.ln1_b; g.out = e->qkv; g.out_ld = QKV; g.N = QKV; g.K = H;
+      PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "LN1+QKV"));
+    }
+    // causal self-attention over the KV arena, fused RoPE + append
+    PTTS_TRY((launch_attn<WT>(self_attn_args(e, v, w, 1, false, 0), M, st)));
+    {  // [combine splits] + out_proj + residual (:1034)
+      GemvArgs g = {};
+      g.W = w.o_rm; g.wscale = w.o_sc; g.out = v.h; g.out_ld = H; g.N = H; g.K = H;
+      if (e->S_self == 1) { g.xw = e->xw; g.xw_ld = H; PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g, "out_proj")); }
+      else { g.part = e->part; g.stats = e->stats; g.nheads = nh; PTTS_TRY(gv(GV_ATTN, GV_RESID, e->S_self, g, "combine+out_proj")); }
+    }
+    }
+    bool x_fused = false;  // the cross block left its output as per-head partial rows (summed by the LN3 + fc1 node)
+    if (v.xfold_valid && M == 1 && (e->fuse_x < 0 ? H <= 1024 : e->fuse_x != 0) && e->xfold_ne == 64 && ptts_xfoldattn_ok(H, nh, c.dtype == PTTS_F32 ? GV_F32 : GV_BF16)) {
+      // folded cross block as ONE node: LN2 + the head's rows of M + softmax + the head's columns of U -> xpart[h][:]
+      XfoldAttnArgs x = {};
+      x.Mw = w.xM; x.Uw = w.xU; x.x = v.h; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.mask = v.enc_mask; x.n_valid = &e->dims->N;
+      x.xpart = e->xpart; x.nheads = nh; x.H = H; x.nur = e->fuse_x_nur;
+      PTTS_DBG_NODE(x, l, 2);
+      if (ptts_xfoldattn_launch(c.dtype == PTTS_F32 ? GV_F32 : GV_BF16, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xfold_attn launch failed");
+      x_fused = true;
+    } else if (v.xfold_valid && M == 1) {
+      // folded cross block (xfold_*_kernel at prefill): LN2 + (K Wq) x -> base-2 scores; per-head softmax + (Wo V^T) p + residual
+      const int K2 = nh * e->xfold_ne, gm = c.dtype == PTTS_F32 ? GV_F32 : GV_BF16;  // M / U are in the engine dtype, never e4m3
+      GemvArgs g = {};
+      g.W = w.xM; g.x = v.h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = K2; g.N = K2; g.K = H; g.M = 1;
+      if (ptts_gemv_launch(gm, GV_LN, GV_STORE, 1, g, st) != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (LN2 + folded scores)");
+      GemvArgs g2 = {};
+      g2.W = w.xU; g2.x = e->qc; g2.mask = v.enc_mask; g2.n_valid = &e->dims->N; g2.ne = e->xfold_ne;
+      g2.out = v.h; g2.out_ld = H; g2.N = H; g2.K = K2; g2.M = 1;
+      if (ptts_gemv_launch(gm, GV_SOFTMAX, GV_RESID, 1, g2, st) != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (softmax + folded out_proj)");
+    } else {
+    if (e->fuse_xq && !c.rope && ptts_xqattn_ok(H, mode)) {
+      // LN2 + the head's cross-q rows + cross-attention of one (head, utterance) as ONE node (xq_attn_kernel): 1..8 utterances without the static fold
+      XqAttnArgs x = {};
+      x.W = w.cq_rm; x.wscale = w.cq_sc; x.x = v.h; x.x_ld = H; x.gamma = w.ln2_g; x.beta = w.ln2_b;
+      x.kcache = at(w.k_cross, v.cross_off); x.vcache = at(w.v_cross, v.cross_off); x.mask = v.enc_mask; x.mask_ld = c.max_enc; x.cap = c.max_enc; x.n_valid = &e->dims->N;
+      x.out = e->xw; x.out_ld = H; x.nheads = nh; x.H = H; x.kv_heads = nkc; x.M = M; x.scale = scale;
+      if (ptts_xqattn_launch(mode, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xq_attn launch failed");
+    } else {
+    {  // LN2 + cross q projection (:1040, :855)
+      GemvArgs g = {};
+      g.W = w.cq_rm; g.wscale = w.cq_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = H; g.N = H; g.K = H;
+      PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "LN2+cross q"));
+    }
+    // cross-attention against the static description K/V: one workgroup per head, softmax finished in the kernel
+    PTTS_TRY((launch_attn<WT>(cross_attn_args(e, v, w, 1, false, 0), M, st, e->cross_waves)));
+    }
+    {  // cross out_proj + residual (:1052)
+      GemvArgs g = {};
+      g.W = w.co_rm; g.wscale = w.co_sc; g.xw = e->xw; g.xw_ld = H; g.out = v.h; g.out_ld = H; g.N = H; g.K = H;
+      PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g, "cross out_proj"));
+    }
+    }
+    {  // LN3 + fc1 + GELU (engine dtype), fc2 + residual (:1059-1064)
+      GemvArgs g = {};
+      g.W = w.fc1_rm; g.wscale = w.fc1_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln3_g; g.beta = w.ln3_b;
+      g.out = reinterpret_cast<float*>(e->xw2); g.out_ld = F; g.N = F; g.K = H;
+      PTTS_DBG_NODE(g, l, 3);
+      if (x_fused) { g.part = e->xpart; g.npart = nh; g.hsum = e->h2; PTTS_TRY(gv(GV_LNP, GV_GELU_WT, 1, g, "partial rows+LN3+fc1")); }
+      else PTTS_TRY(gv(GV_LN, GV_GELU_WT, 1, g, "LN3+fc1"));
+      GemvArgs g2 = {};
+      g2.W = w.fc2_rm; g2.wscale = w.fc2_sc; g2.xw = e->xw2; g2.xw_ld = F; g2.out = v.h; g2.out_ld = H; g2.N = H; g2.K = F;
+      if (x_fused) g2.resid = e->h2;  // h = (x + partial rows) + fc2(...)
+      PTTS_DBG_NODE(g2, l, 4);
+      PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g2, "fc2"));
+    }
+  }
+  GemvArgs g = {};  // final LayerNorm + all K LM heads (:1632, :1917-1960)
+  g.W = e->heads_rm; g.wscale = e->heads_sc; g.x = v.h; g.x_ld = H; g.gamma = e->lnf_g; g.beta = e->lnf_b; g.out = v.logits;
+  g.out_ld = c.num_codebooks * c.vocab_size; g.N = c.num_codebooks * c.vocab_size; g.K = H;
+  PTTS_DBG_NODE(g, c.num_layers, 0);
+  PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "final LN + LM heads"));
+  return launch_status("forward");
+}
+
+// The MFMA strip path up to the logits: every prefill (Q positions per utterance), and the decode step above gemv_rows utterances
+template <typename WT>
+int strip_path(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStream_t st) {
+  const ptts_config& c = e->cfg;
+  const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, B = v.B;
   const int nkv = e->nkv, nkc = e->nkc, Hkv = nkv * 64, QKV = H + 2 * Hkv;  // grouped-query attention: fewer K/V heads
-  const int Q = prefill ? e->P + 1 + e->prefill_T : 1;  // prompt positions + BOS column [+ the voice-prompt columns, run in the same pass]
   const int M = B * Q;
   const bool big = M > 8;
   const int dec = prefill ? 0 : 1;  // GemmArgs::decode: rows per M pass of the strip GEMMs (msplit_rows)
   const float scale = 1.0f / sqrtf((float)(H / nh));
-
-  if (prefill) {  // cross-attention K/V of the description, once per call (:877-878 then reused :872-875)
-    // encoder states were staged into qc by ptts_prefill (fp32 row-major [B*N][H]); convert once to the engine dtype
-    const size_t n = (size_t)B * e->N * H;
-    hipLaunchKernelGGL((convert_kernel<WT, float>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, e->qc,
-                       reinterpret_cast<WT*>(e->xw2), n);
-    // every layer's K/V projection in ONE launch (blockIdx.z = layer): the strip kernel up to 256 rows, the bf16 engine's LDS-DMA GEMM above (round 6:
-    // 24 launches of ~17 us at 32 descriptions x 64 tokens were one tenth of that prefill; a shape the GEMM declines falls back to the strips)
-    const bool one_launch = (B * e->N <= 256 || (sizeof(WT) == 2 && H % 64 == 0 && (2 * nkc * 64) % 64 == 0));
-    for (int l = 0; l < (one_launch ? 1 : c.num_layers); ++l) {
-      GemmArgs g = {};
-      g.W = e->L[l].ckv; g.M = B * e->N; g.N = 2 * nkc * 64; g.K = H;
-      g.x = reinterpret_cast<const float*>(e->xw2); g.x_ld = H; g.x_row_mul = 1; g.x_row_off = 0;
-      g.kcache = e->L[l].k_cross; g.vcache = e->L[l].v_cross; g.kv_rows_per_b = e->N; g.kv_cap = c.max_enc; g.nheads = nkc;
-      if (one_launch) { g.kv_layers = e->kv_layers; g.kv_nlayers = c.num_layers; }
-      PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_KV>(g, st)));
-    }
-  }
-  if (with_embed) {
-    EmbedArgs ea = {};
-    ea.tables = e->embed; ea.pos_table = c.rope ? nullptr : e->pos_table; ea.prompt = prefill ? e->ffn : nullptr;
-    ea.ids = e->ids; ea.ids_ld = e->ids_ld; ea.cur_len = e->cur_len; ea.dims = e->dims; ea.h = e->h;
-    ea.H = H; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.bos = c.bos_token_id; ea.pad = c.pad_token_id;
-    ea.prefill = prefill ? 1 : 0;
-    if (e->session && !prefill)  // every slot under its own request's delay pattern
-      hipLaunchKernelGGL((embed_kernel<WT, true>), dim3(1, B), dim3(256), 0, st, EmbedSessionArgs{ea, e->row_maxlen});
-    else
-      hipLaunchKernelGGL((embed_kernel<WT, false>), dim3(Q, B), dim3(256), 0, st, ea);
-  }
-  if (e->use_gemv && !prefill && M <= e->gemv_rows) {
-    // batch 1..4: 8 row-per-wave GEMV / attention nodes per layer, every weight matrix spread over all CUs and read once
-    const float* rc = c.rope ? e->rope_cos : nullptr;
-    const float* rs = c.rope ? e->rope_sin : nullptr;
-    const int mode = c.dtype == PTTS_F32 ? GV_F32 : (e->w8 ? GV_BF16_W8 : GV_BF16);
-    // single utterance, sinusoidal positions: the two nodes of the self-attention block's first half as one (PTTS_NO_FUSE_QA=1: two nodes)
-    // (round 5: 2..8 utterances too - one grid slice per utterance, the slices of a head share its weight rows in the L2; PTTS_FUSE_QA_MAX=1: one only)
-    // measured, Mini-v1 us per step at contexts ~210 / ~460 / ~710, fused | two nodes (profiles/r05_experiments.txt call 2): 2 utterances 720 / 756 / 791 |
-    // 769 / 777 / 791; 3: 741 / 788 / 862 | 780 / 796 / 821; 4: 777 / 864 / 923 | 803 / 832 / 862; 8: 966 / 1010 / 1068 | 907 / 965 / 1023 (the slices of
-    // a head re-read its q / k / v rows from the L2 once per utterance and split): on up to fuse_qa_max utterances (3), PTTS_FUSE_QA_MAX forces a bound
-    const bool fuse_qa = e->fuse_qa && (M == 1 || (M <= e->fuse_qa_max && mode != GV_F32)) && !c.rope && ptts_qkvattn_ok(H, mode);
-    // KV splits of the fused node: the smallest count whose FIRST batch of row groups (8 waves x 4 groups x 8 bf16 / 4 fp32 rows per split,
-    // requested before q exists) covers the context bucket this graph is captured for - fewer workgroups recompute the head's q rows, and no
-    // split needs a second, dependent K/V batch (context ~210 / ~460 / ~710: 2 splits 554 / 562 / 586 us per step, 4 splits 575 / 577 / 579,
-    // 8 splits 645 / 646 / 648; profiles/r04_experiments.txt call 15)
-    int S_f = 1;
-    const int S_cap = M == 1 ? 8 : (M <= 4 ? 4 : 2);  // the combine prologue of the out_proj node holds S + 1 slots per lane: 12-wave workgroups (5..8 utterances) fit 2 splits
-    while (S_f < S_cap && S_f * ptts_qkvattn_rows_per_split(mode) < e->kv_bound) S_f *= 2;
-    auto gv = [&](int pro, int epi, int S, GemvArgs g, const char* what) -> int {
-      g.M = M;
-      const int rc_ = ptts_gemv_launch(mode, pro, epi, S, g, st);
-      if (rc_ == -1) return ptts_fail(PTTS_E_UNSUPPORTED, "gemv: no instance for %s (N=%d K=%d M=%d)", what, g.N, g.K, M);
-      if (rc_ != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (%s)", what);
-      return PTTS_OK;
-    };
-#ifdef PTTS_TIMING
-#define PTTS_DBG_NODE(args, l_, k_) (args).dbg = (e->dbg_stamps && M == 1) ? e->dbg_stamps + ((size_t)(l_) * 5 + (k_)) * 48 : nullptr
-#else
-#define PTTS_DBG_NODE(args, l_, k_) do { } while (0)
-#endif
-    for (int l = 0; l < c.num_layers; ++l) {
-      const LayerW& w = e->L[l];
-      if (fuse_qa) {  // LN1 + the head's q / k / v rows + split-KV self-attention + append in ONE node (qkv_attn_kernel), then combine + out_proj
-        QkvAttnArgs q = {};
-        q.W = w.qkv_rm; q.wscale = w.qkv_sc; q.x = e->h; q.gamma = w.ln1_g; q.beta = w.ln1_b;
-        q.kcache = w.k_self; q.vcache = w.v_self; q.cur_len = e->cur_len; q.P = &e->dims->P; q.mask = e->prompt_mask;
-        q.part = e->part; q.stats = e->stats; q.cap = c.max_ctx; q.kv_bound = e->kv_bound; q.mask_ld = e->max_prompt;
-        q.S = S_f; q.nheads = nh; q.H = H; q.kv_heads = nkv; q.scale = scale; q.M = M; q.x_ld = H;
-        PTTS_DBG_NODE(q, l, 0);
-        if (ptts_qkvattn_launch(mode, q, st) != 0) return ptts_fail(PTTS_E_HIP, "qkv_attn launch failed");
-        GemvArgs g = {};
-        g.W = w.o_rm; g.wscale = w.o_sc; g.out = e->h; g.out_ld = H; g.N = H; g.K = H; g.part = e->part; g.stats = e->stats; g.nheads = nh;
-        PTTS_DBG_NODE(g, l, 1);
-        PTTS_TRY(gv(GV_ATTN2, GV_RESID, S_f, g, "combine+out_proj"));
-      } else {
-      {  // LN1 + fused QKV projection (:1020-1021, :848-850)
-        GemvArgs g = {};
-        g.W = w.qkv_rm; g.wscale = w.qkv_sc; g.x = e->h; g.x_ld = H; g.gamma = w.ln1_g; g.beta = w.ln1_b; g.out = e->qkv; g.out_ld = QKV; g.N = QKV; g.K = H;
-        PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "LN1+QKV"));
-      }
-      {  // causal self-attention over the KV arena, fused RoPE + append
-        AttnArgs a = {};
-        a.q = e->qkv; a.q_ld = QKV; a.knew = e->qkv + H; a.vnew = e->qkv + H + Hkv; a.kv_ld = QKV;
-        a.kv_heads = nkv; a.n_rep = nh / nkv;
-        a.kcache = w.k_self; a.vcache = w.v_self; a.cap = c.max_ctx; a.kv_bound = e->kv_bound; a.cur_len = e->cur_len; a.dims = e->dims;
-        a.mask = e->prompt_mask; a.mask_ld = e->max_prompt; a.cos = rc; a.sin = rs;
-        a.part = e->part; a.stats = e->stats; a.S = e->S_self; a.Q = 1; a.nheads = nh; a.H = H; a.cross = 0;
-        a.fused_append = 1; a.scale = scale;
-        a.direct_out = e->S_self == 1 ? e->xw : nullptr;
-        PTTS_TRY((launch_attn<WT>(a, B, st)));
-      }
-      {  // [combine splits] + out_proj + residual (:1034)
-        GemvArgs g = {};
-        g.W = w.o_rm; g.wscale = w.o_sc; g.out = e->h; g.out_ld = H; g.N = H; g.K = H;
-        if (e->S_self == 1) { g.xw = e->xw; g.xw_ld = H; PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g, "out_proj")); }
-        else { g.part = e->part; g.stats = e->stats; g.nheads = nh; PTTS_TRY(gv(GV_ATTN, GV_RESID, e->S_self, g, "combine+out_proj")); }
-      }
-      }
-      bool x_fused = false;  // the cross block left its output as per-head partial rows (summed by the LN3 + fc1 node)
-      if (e->xfold_valid && M == 1 && (e->fuse_x < 0 ? H <= 1024 : e->fuse_x != 0) && e->xfold_ne == 64 && ptts_xfoldattn_ok(H, nh, c.dtype == PTTS_F32 ? GV_F32 : GV_BF16)) {
-        // folded cross block as ONE node: LN2 + the head's rows of M + softmax + the head's columns of U -> xpart[h][:]
-        XfoldAttnArgs x = {};
-        x.Mw = w.xM; x.Uw = w.xU; x.x = e->h; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.mask = e->enc_mask; x.n_valid = &e->dims->N;
-        x.xpart = e->xpart; x.nheads = nh; x.H = H; x.nur = e->fuse_x_nur;
-        PTTS_DBG_NODE(x, l, 2);
-        if (ptts_xfoldattn_launch(c.dtype == PTTS_F32 ? GV_F32 : GV_BF16, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xfold_attn launch failed");
-        x_fused = true;
-      } else if (e->xfold_valid && M == 1) {
-        // folded cross block (xfold_*_kernel at prefill): LN2 + (K Wq) x -> base-2 scores; per-head softmax + (Wo V^T) p + residual
-        const int K2 = nh * e->xfold_ne, gm = c.dtype == PTTS_F32 ? GV_F32 : GV_BF16;  // M / U are in the engine dtype, never e4m3
-        GemvArgs g = {};
-        g.W = w.xM; g.x = e->h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = K2; g.N = K2; g.K = H; g.M = 1;
-        if (ptts_gemv_launch(gm, GV_LN, GV_STORE, 1, g, st) != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (LN2 + folded scores)");
-        GemvArgs g2 = {};
-        g2.W = w.xU; g2.x = e->qc; g2.mask = e->enc_mask; g2.n_valid = &e->dims->N; g2.ne = e->xfold_ne;
-        g2.out = e->h; g2.out_ld = H; g2.N = H; g2.K = K2; g2.M = 1;
-        if (ptts_gemv_launch(gm, GV_SOFTMAX, GV_RESID, 1, g2, st) != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (softmax + folded out_proj)");
-      } else {
-      if (e->fuse_xq && !c.rope && ptts_xqattn_ok(H, mode)) {
-        // LN2 + the head's cross-q rows + cross-attention of one (head, utterance) as ONE node (xq_attn_kernel): 1..8 utterances without the static fold
-        XqAttnArgs x = {};
-        x.W = w.cq_rm; x.wscale = w.cq_sc; x.x = e->h; x.x_ld = H; x.gamma = w.ln2_g; x.beta = w.ln2_b;
-        x.kcache = w.k_cross; x.vcache = w.v_cross; x.mask = e->enc_mask; x.mask_ld = c.max_enc; x.cap = c.max_enc; x.n_valid = &e->dims->N;
-        x.out = e->xw; x.out_ld = H; x.nheads = nh; x.H = H; x.kv_heads = nkc; x.M = M; x.scale = scale;
-        if (ptts_xqattn_launch(mode, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xq_attn launch failed");
-      } else {
-      {  // LN2 + cross q projection (:1040, :855)
-        GemvArgs g = {};
-        g.W = w.cq_rm; g.wscale = w.cq_sc; g.x = e->h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = H; g.N = H; g.K = H;
-        PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "LN2+cross q"));
-      }
-      {  // cross-attention against the static description K/V: one workgroup per head, softmax finished in the kernel
-        AttnArgs a = {};
-        a.q = e->qc; a.q_ld = H; a.kcache = w.k_cross; a.vcache = w.v_cross; a.cap = c.max_enc; a.kv_bound = c.max_enc;
-        a.cur_len = e->cur_len; a.dims = e->dims; a.mask = e->enc_mask; a.mask_ld = c.max_enc;
-        a.cos = rc; a.sin = rs;  // quirk: q rotated, keys not (:858 vs :880)
-        a.part = e->part; a.stats = e->stats; a.S = 1; a.Q = 1; a.nheads = nh; a.H = H; a.cross = 1;
-        a.kv_heads = nkc; a.n_rep = nh / nkc; a.fused_append = 0; a.scale = scale; a.direct_out = e->xw;
-        PTTS_TRY((launch_attn<WT>(a, B, st, e->cross_waves)));
-      }
-      }
-      {  // cross out_proj + residual (:1052)
-        GemvArgs g = {};
-        g.W = w.co_rm; g.wscale = w.co_sc; g.xw = e->xw; g.xw_ld = H; g.out = e->h; g.out_ld = H; g.N = H; g.K = H;
-        PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g, "cross out_proj"));
-      }
-      }
-      {  // LN3 + fc1 + GELU (engine dtype), fc2 + residual (:1059-1064)
-        GemvArgs g = {};
-        g.W = w.fc1_rm; g.wscale = w.fc1_sc; g.x = e->h; g.x_ld = H; g.gamma = w.ln3_g; g.beta = w.ln3_b;
-        g.out = reinterpret_cast<float*>(e->xw2); g.out_ld = F; g.N = F; g.K = H;
-        PTTS_DBG_NODE(g, l, 3);
-        if (x_fused) { g.part = e->xpart; g.npart = nh; g.hsum = e->h2; PTTS_TRY(gv(GV_LNP, GV_GELU_WT, 1, g, "partial rows+LN3+fc1")); }
-        else PTTS_TRY(gv(GV_LN, GV_GELU_WT, 1, g, "LN3+fc1"));
-        GemvArgs g2 = {};
-        g2.W = w.fc2_rm; g2.wscale = w.fc2_sc; g2.xw = e->xw2; g2.xw_ld = F; g2.out = e->h; g2.out_ld = H; g2.N = H; g2.K = F;
-        if (x_fused) g2.resid = e->h2;  // h = (x + partial rows) + fc2(...)
-        PTTS_DBG_NODE(g2, l, 4);
-        PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g2, "fc2"));
-      }
-    }
-    GemvArgs g = {};  // final LayerNorm + all K LM heads (:1632, :1917-1960)
-    g.W = e->heads_rm; g.wscale = e->heads_sc; g.x = e->h; g.x_ld = H; g.gamma = e->lnf_g; g.beta = e->lnf_b; g.out = e->logits;
-    g.out_ld = c.num_codebooks * c.vocab_size; g.N = c.num_codebooks * c.vocab_size; g.K = H;
-    PTTS_DBG_NODE(g, c.num_layers, 0);
-    PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "final LN + LM heads"));
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "forward launch failed: %s", hipGetErrorString(err));
-    return PTTS_OK;
-  }
   // KV splits of the self-attention: the engine's split factor at decode (long context, few rows); ONE at prefill - the context is the
   // prompt (tens of positions) and there is one workgroup per (head, position) anyway: splitting 4 ways + a combine kernel cost
   // 15 + 9 us per layer on the time-to-first-token path against ~7 us unsplit (profiles/r03_prefill_kernels.txt)
@@ -405,13 +494,13 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
   const int fo = (M > 8 && (!prefill || M <= 256)) ? 1 : 0;
   // LayerNorm + projection as one node (lnproj_fused_kernel): decode, batch > 8, Mini / Large widths, weights in the engine dtype (e4m3 strips keep
   // streaming bytes through the strip GEMMs)
-  const int KTf = Elem<WT>::KT;
+  const int KT = Elem<WT>::KT;
   const int lnproj = e->lnproj >= 0 ? e->lnproj : 3;
   // utterances per workgroup of that node: 8 (one row per wave) up to 40, 16 (two rows per wave, the whole MFMA tile, half the weight re-reads) above
   const int lnproj_g = e->lnproj_g > 0 ? e->lnproj_g : (M <= 40 ? 8 : 16);
   // (round 5: the prefill rows of a short prompt, 8 < M <= 40, run the same fused nodes - three rows_prep nodes less per layer on the
   //  time-to-first-token path: prefill 1.41 -> 1.29 ms, first token 2.41 -> 2.28 ms at 33 rows, profiles/r05_experiments.txt call 2)
-  const bool lnproj_ok = lnproj > 0 && (!prefill || M <= 40) && M > 8 && !e->w8_strips && (H == 1024 || H == 1536) && ((H / KTf) / 2) % 8 == 0 && QKV % 64 == 0 && F % 64 == 0;
+  const bool lnproj_ok = lnproj > 0 && (!prefill || M <= 40) && M > 8 && !e->w8_strips && (H == 1024 || H == 1536) && ((H / KT) / 2) % 8 == 0 && QKV % 64 == 0 && F % 64 == 0;
   // prefill attention on the tiled kernel (8 query rows per workgroup share the K / V tile; PTTS_PREFILL_ATTN=0: one workgroup per query row, attn_kernel)
   const int prefill_attn_mode = getenv("PTTS_PREFILL_ATTN") ? atoi(getenv("PTTS_PREFILL_ATTN")) : 3;  // 0: one workgroup per query row, 1: tiled VALU kernel, 2: f32-MFMA kernel, 3: by batch
   const bool prefill_attn = prefill_attn_mode != 0;
@@ -422,50 +511,39 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
   // 24 kv_append launches of ~6 us + their boundaries off the time-to-first-token path of a batch. Between 41 and 256 rows the kv_append node stays
   // (fragment-order rows_prep + strips: measured path of round 5).
   const bool kv_in_gemm = prefill && !kv_in_qkv && !lnproj_ok && M > 256 && !c.rope && !e->L[0].ks_self;
-#ifdef PTTS_TIMING
-#define PTTS_DBG_BIG(args, l_, k_) (args).dbg = (e->dbg_stamps && !prefill && M > 8) ? e->dbg_stamps + ((size_t)(l_) * 7 + (k_)) * 48 : nullptr
-#else
-#define PTTS_DBG_BIG(args, l_, k_) do { } while (0)
-#endif
+#define PTTS_DBG_BIG(args, l_, k_) PTTS_DBG_STAMP(args, !prefill && M > 8, (size_t)(l_) * 7 + (k_))
   for (int l = 0; l < c.num_layers; ++l) {
     const LayerW& w = e->L[l];
+    void *const k_self = at(w.k_self, v.self_off), *const v_self = at(w.v_self, v.self_off);
     if (lnproj_ok) {  // LN1 + fused QKV projection in one node
       LnProjArgs p = {};
       PTTS_DBG_BIG(p, l, 0);
-      p.W = w.qkv; p.x = e->h; p.x_ld = H; p.gamma = w.ln1_g; p.beta = w.ln1_b; p.K = H; p.out = e->qkv; p.out_ld = QKV; p.M = M; p.N = QKV;
-      if (kv_in_qkv) { p.kcache = w.k_self; p.vcache = w.v_self; p.kv_Q = Q; p.kv_cap = c.max_ctx; p.kv_heads = nkv; p.kv_H = H; }
+      p.W = w.qkv; p.x = v.h; p.x_ld = H; p.gamma = w.ln1_g; p.beta = w.ln1_b; p.K = H; p.out = e->qkv; p.out_ld = QKV; p.M = M; p.N = QKV;
+      if (kv_in_qkv) { p.kcache = k_self; p.vcache = v_self; p.kv_Q = Q; p.kv_cap = c.max_ctx; p.kv_heads = nkv; p.kv_H = H; }
       PTTS_TRY((launch_lnproj<WT, EPI_STORE>(e, p, st, lnproj_g)));
     } else {  // LN1 + fused QKV projection
       GemmArgs g = {}; g.decode = dec;
-      g.W = w.qkv; g.W8 = w.qkv_p8; g.wscale = w.qkv_sc; g.x = e->h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln1_g; g.beta = w.ln1_b;
+      g.W = w.qkv; g.W8 = w.qkv_p8; g.wscale = w.qkv_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln1_g; g.beta = w.ln1_b;
       g.out = e->qkv; g.out_ld = QKV; g.M = M; g.N = QKV; g.K = H; g.x_fo = fo;
-      if (kv_in_gemm) { g.kcache = w.k_self; g.vcache = w.v_self; g.kv_rows_per_b = Q; g.kv_cap = c.max_ctx; g.nheads = nkv; g.kv_col0 = H; }
+      if (kv_in_gemm) { g.kcache = k_self; g.vcache = v_self; g.kv_rows_per_b = Q; g.kv_cap = c.max_ctx; g.nheads = nkv; g.kv_col0 = H; }
       PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_STORE>(e, g, st)));
     }
     if (prefill && !kv_in_qkv && !kv_in_gemm) {
       bool done8 = false;
       if constexpr (sizeof(WT) == 2) {
         if (w.ks_self) {
-          hipLaunchKernelGGL((kv_append_kernel<WT, true>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, w.k_self, w.v_self, c.max_ctx,
+          hipLaunchKernelGGL((kv_append_kernel<WT, true>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, k_self, v_self, c.max_ctx,
                              Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr, w.ks_self, w.vs_self);
           done8 = true;
         }
       }
       if (!done8)
-      hipLaunchKernelGGL((kv_append_kernel<WT>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, w.k_self,
-                         w.v_self, c.max_ctx, Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr);
+      hipLaunchKernelGGL((kv_append_kernel<WT>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, k_self,
+                         v_self, c.max_ctx, Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr);
     }
     {  // causal self-attention over the KV arena
-      AttnArgs a = {};
-      a.q = e->qkv; a.q_ld = QKV; a.knew = e->qkv + H; a.vnew = e->qkv + H + Hkv; a.kv_ld = QKV;
-      a.kv_heads = nkv; a.n_rep = nh / nkv;
-      a.kcache = w.k_self; a.vcache = w.v_self; a.cap = c.max_ctx; a.kv_bound = prefill ? c.max_ctx : e->kv_bound; a.cur_len = prefill ? nullptr : e->cur_len; a.dims = e->dims;
-      a.mask = e->prompt_mask; a.mask_ld = e->max_prompt;
-      a.cos = c.rope ? e->rope_cos : nullptr; a.sin = c.rope ? e->rope_sin : nullptr;
-      a.part = e->part; a.stats = e->stats; a.S = S_used; a.Q = Q; a.nheads = nh; a.H = H; a.cross = 0;
-      a.fused_append = prefill ? 0 : 1; a.scale = scale;
-      a.kscale = w.ks_self; a.vscale = w.vs_self; a.hostP = e->P; a.hostN = e->N;
-      a.direct_out = S_used == 1 ? e->xw : nullptr; a.out_fo = fo;
+      AttnArgs a = self_attn_args(e, v, w, Q, prefill, fo);
+      a.hostP = v.P; a.hostN = v.N;  // the prefill kernels' preloaded head (PrefillAttnHead::pack)
       PTTS_DBG_BIG(a, l, 1);
       if (prefill && prefill_attn) PTTS_TRY((launch_prefill_attn<WT>(a, B, st, prefill_attn_mode)));
       else PTTS_TRY((launch_attn<WT>(a, B, st)));
@@ -473,7 +551,7 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     {  // [combine splits] + out_proj + residual
       GemmArgs g = {}; g.decode = dec;
       g.W = w.o; g.W8 = w.o_p8; g.wscale = w.o_sc; g.part = e->part; g.stats = e->stats; g.S = S_used; g.nheads = nh;
-      g.out = e->h; g.out_ld = H; g.M = M; g.N = H; g.K = H; g.x_fo = fo;
+      g.out = v.h; g.out_ld = H; g.M = M; g.N = H; g.K = H; g.x_fo = fo;
       if (lns) g.stats_out = e->lnstat;  // strip statistics of the new residual rows for LN2 (PRO_LNS)
       PTTS_DBG_BIG(g, l, 2);
       if (S_used == 1) {
@@ -483,55 +561,35 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
         PTTS_TRY((gemm_with_prologue<WT, PRO_ATTN, EPI_RESID>(e, g, st)));
       }
     }
-    const int KTw = Elem<WT>::KT;
-    if (!prefill && (M <= 8 || (e->xattn_groups && M <= 256)) && (H / KTw) % 16 == 0 && (H == 512 || H == 1024 || H == 1536)) {
+    if (!prefill && (M <= 8 || (e->xattn_groups && M <= 256)) && (H / KT) % 16 == 0 && (H == 512 || H == 1024 || H == 1536)) {
       // decode, small batch: LN2 + cross q projection + cross-attention fused, one workgroup per head
       XAttnArgs x = {};
-      x.W = w.cq; x.x = e->h; x.x_ld = H; x.x_row_mul = 1; x.x_row_off = 0; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.K = H;
-      x.invK = 1.0f / (float)H; x.kcache = w.k_cross; x.vcache = w.v_cross; x.cap = c.max_enc; x.cur_len = e->cur_len; x.dims = e->dims;
-      x.mask = e->enc_mask; x.mask_ld = c.max_enc; x.cos = c.rope ? e->rope_cos : nullptr; x.sin = c.rope ? e->rope_sin : nullptr;
+      x.W = w.cq; x.x = v.h; x.x_ld = H; x.x_row_mul = 1; x.x_row_off = 0; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.K = H;
+      x.invK = 1.0f / (float)H; x.kcache = at(w.k_cross, v.cross_off); x.vcache = at(w.v_cross, v.cross_off); x.cap = c.max_enc; x.cur_len = v.cur_len; x.dims = e->dims;
+      x.mask = v.enc_mask; x.mask_ld = c.max_enc; x.cos = c.rope ? e->rope_cos : nullptr; x.sin = c.rope ? e->rope_sin : nullptr;
       x.out = e->xw; x.B = M; x.nheads = nh; x.kv_heads = nkc; x.n_rep = nh / nkc; x.scale = scale; x.out_fo = fo;
       PTTS_DBG_BIG(x, l, 3);
       // utterances per workgroup: 8 (one per wave) up to 8 utterances; above, e->xattn_g (8 / 4 / 2: heads x ceil(M / g) workgroups, the 8 / g
       // waves of an utterance split the description's row groups)
       // measured (profiles/r04_experiments.txt, us per step at mid context, g = 8 / 4 / 2): batch 32 1432 / 1381 / 1360, batch 128 2596 / 2682 / 2860
       const int gsz = M <= 8 ? 8 : (e->xattn_g ? e->xattn_g : (e->xattn_g_ok ? (M <= 32 ? 2 : (M <= 64 ? 4 : 8)) : 8));
-      const int mg = M < gsz ? M : gsz;
-      const size_t sh = (size_t)mg * (H * sizeof(WT) + 16) + 8 * 1024 + (size_t)gsz * 64 * 4 + 8 * 64 * 4 + 64;
-      const dim3 xg(nh, (M + gsz - 1) / gsz);
-      const bool u16 = ((H / KTw) / 2) % 16 == 0;
-      if (H == 1024 && u16) {  // Mini-v1
-        if (gsz == 4) ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 4>, xg, dim3(512), sh, st, x);
-        else if (gsz == 2) ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 2>, xg, dim3(512), sh, st, x);
-        else ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 8>, xg, dim3(512), sh, st, x);
-      } else if (H == 1024) ptts_klaunch(xattn_fused_kernel<WT, 8, 4>, xg, dim3(512), sh, st, x);
-      else if (H == 1536) {  // Large-v1
-        if (gsz == 4) ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 4>, xg, dim3(512), sh, st, x);
-        else if (gsz == 2) ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 2>, xg, dim3(512), sh, st, x);
-        else ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 8>, xg, dim3(512), sh, st, x);
-      } else ptts_klaunch(xattn_fused_kernel<WT, 8, 2>, xg, dim3(512), sh, st, x);                            // hidden 512
+      launch_xattn_fused<WT>(x, gsz, st);
     } else {
     if (prefill && lnproj_ok) {  // LN2 + cross q projection as one node
       LnProjArgs p = {};
-      p.W = w.cq; p.x = e->h; p.x_ld = H; p.gamma = w.ln2_g; p.beta = w.ln2_b; p.K = H; p.out = e->qc; p.out_ld = H; p.M = M; p.N = H;
+      p.W = w.cq; p.x = v.h; p.x_ld = H; p.gamma = w.ln2_g; p.beta = w.ln2_b; p.K = H; p.out = e->qc; p.out_ld = H; p.M = M; p.N = H;
       PTTS_TRY((launch_lnproj<WT, EPI_STORE>(e, p, st, lnproj_g)));
     } else
     {  // LN2 + cross q projection
       GemmArgs g = {}; g.decode = dec;
-      g.W = w.cq; g.x = e->h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln2_g; g.beta = w.ln2_b;
+      g.W = w.cq; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln2_g; g.beta = w.ln2_b;
       g.out = e->qc; g.out_ld = H; g.M = M; g.N = H; g.K = H; g.x_fo = fo;
       if (lns) g.lnstat = e->lnstat;
       PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_STORE>(e, g, st)));
     }
     {  // cross-attention against the static description K/V
-      AttnArgs a = {};
-      a.q = e->qc; a.q_ld = H; a.kcache = w.k_cross; a.vcache = w.v_cross; a.cap = c.max_enc; a.kv_bound = c.max_enc;
-      a.cur_len = prefill ? nullptr : e->cur_len; a.dims = e->dims; a.mask = e->enc_mask; a.mask_ld = c.max_enc;
-      a.cos = c.rope ? e->rope_cos : nullptr; a.sin = c.rope ? e->rope_sin : nullptr;  // quirk: q rotated, keys not (:858 vs :880)
-      a.part = e->part; a.stats = e->stats; a.S = 1; a.Q = Q; a.nheads = nh; a.H = H; a.cross = 1;
-      a.kv_heads = nkc; a.n_rep = nh / nkc;
-      a.fused_append = 0; a.scale = scale; a.hostP = e->P; a.hostN = e->N;
-      a.direct_out = e->xw; a.out_fo = fo;  // the description is short: never split, softmax finished in the attention kernel
+      AttnArgs a = cross_attn_args(e, v, w, Q, prefill, fo);
+      a.hostP = v.P; a.hostN = v.N;
       if (prefill && prefill_attn) PTTS_TRY((launch_prefill_attn<WT>(a, B, st, prefill_attn_mode)));
       else PTTS_TRY((launch_attn<WT>(a, B, st, prefill ? 4 : e->cross_waves)));  // decode: as few waves as cover the description (no LDS combine at 1)
     }
@@ -539,7 +597,7 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     {  // cross out_proj + residual, activations read straight from the attention output
       GemmArgs g = {}; g.decode = dec;
       g.W = w.co; g.W8 = w.co_p8; g.wscale = w.co_sc; g.x = reinterpret_cast<const float*>(e->xw); g.x_ld = H; g.x_row_mul = 1; g.x_fo = fo;
-      g.out = e->h; g.out_ld = H; g.M = M; g.N = H; g.K = H;
+      g.out = v.h; g.out_ld = H; g.M = M; g.N = H; g.K = H;
       if (lns) g.stats_out = e->lnstat;  // for LN3
       PTTS_DBG_BIG(g, l, 4);
       PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_RESID>(g, st)));
@@ -547,16 +605,16 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
     {  // LN3 + fc1 + GELU, then fc2 + residual. Above 8 rows the GELU output is written in the engine dtype so fc2
        // stages it with plain copies too.
       GemmArgs g = {}; g.decode = dec;
-      g.W = w.fc1; g.W8 = w.fc1_p8; g.wscale = w.fc1_sc; g.x = e->h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln3_g; g.beta = w.ln3_b;
+      g.W = w.fc1; g.W8 = w.fc1_p8; g.wscale = w.fc1_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln3_g; g.beta = w.ln3_b;
       g.out_ld = F; g.M = M; g.N = F; g.K = H;
       GemmArgs g2 = {}; g2.decode = dec;
-      g2.W = w.fc2; g2.W8 = w.fc2_p8; g2.wscale = w.fc2_sc; g2.x_ld = F; g2.x_row_mul = 1; g2.out = e->h; g2.out_ld = H; g2.M = M; g2.N = H; g2.K = F;
+      g2.W = w.fc2; g2.W8 = w.fc2_p8; g2.wscale = w.fc2_sc; g2.x_ld = F; g2.x_row_mul = 1; g2.out = v.h; g2.out_ld = H; g2.M = M; g2.N = H; g2.K = F;
       if (big) {
         g.out = reinterpret_cast<float*>(e->xw2); g.x_fo = fo; g.out_fo = fo;
         if (lns) g.lnstat = e->lnstat;
         if (lnproj_ok && (lnproj >= 3 || (lnproj == 2 && M > 32))) {  // LN3 + fc1 + GELU in one node
           LnProjArgs p = {};
-          p.W = w.fc1; p.x = e->h; p.x_ld = H; p.gamma = w.ln3_g; p.beta = w.ln3_b; p.K = H; p.out = e->xw2; p.out_ld = F; p.out_fo = fo; p.M = M; p.N = F;
+          p.W = w.fc1; p.x = v.h; p.x_ld = H; p.gamma = w.ln3_g; p.beta = w.ln3_b; p.K = H; p.out = e->xw2; p.out_ld = F; p.out_fo = fo; p.M = M; p.N = F;
           PTTS_DBG_BIG(p, l, 5);
           PTTS_TRY((launch_lnproj<WT, EPI_GELU_WT>(e, p, st, lnproj_g)));
         } else
@@ -579,32 +637,38 @@ int forward(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true
   //  re-read once per group of 8 utterances - profiles/r04_experiments.txt call 23; the rows_prep + strip GEMM pair stays)
   {  // final LayerNorm + all K LM heads as one [K*V, H] projection, last position of each utterance only
     GemmArgs g = {}; g.decode = dec;
-    g.W = e->heads; g.W8 = e->heads_p8; g.wscale = e->heads_sc; g.x = e->h; g.x_ld = H; g.x_row_mul = Q; g.x_row_off = Q - 1; g.gamma = e->lnf_g; g.beta = e->lnf_b;
-    g.out = e->logits; g.out_ld = c.num_codebooks * c.vocab_size; g.M = B; g.N = c.num_codebooks * c.vocab_size; g.K = H;
+    g.W = e->heads; g.W8 = e->heads_p8; g.wscale = e->heads_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = Q; g.x_row_off = Q - 1; g.gamma = e->lnf_g; g.beta = e->lnf_b;
+    g.out = v.logits; g.out_ld = c.num_codebooks * c.vocab_size; g.M = B; g.N = c.num_codebooks * c.vocab_size; g.K = H;
     g.x_fo = (B > 8 && (!prefill || B <= 256)) ? 1 : 0;
     PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_STORE>(e, g, st)));
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "forward launch failed: %s", hipGetErrorString(err));
-  return PTTS_OK;
+  return launch_status("forward");
 }
 
-// row >= 0 (sessions only): the tail of that one slot (ptts_admit_row)
-int launch_tail(ptts_engine* e, hipStream_t st, bool embed_next, int row = -1) {
+// One decoder forward over Q positions per utterance (Q = P+1 at prefill, 1 at decode) up to the logits.
+template <typename WT>
+int forward(const ptts_engine* e, FwdView v, bool prefill, hipStream_t st, bool with_embed = true) {
+  const int Q = prefill ? v.P + 1 + v.T : 1;  // prompt positions + BOS column [+ the voice-prompt columns, run in the same pass]
+  if (prefill) PTTS_TRY(project_cross_kv<WT>(e, v, st));
+  if (with_embed) launch_embed<WT>(e, v, prefill, Q, st);
+  if (e->use_gemv && !prefill && v.B <= e->gemv_rows) return gemv_step<WT>(e, v, st);  // batch 1..4 (fp32: 1)
+  return strip_path<WT>(e, v, prefill, Q, st);
+}
+
+// the sampler tail over the view's utterances; row >= 0 (sessions only): the tail of that one slot (ptts_admit_row)
+int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next, int row = -1) {
   TailArgs t = {};
   if (embed_next) {
-    t.tables = e->embed; t.pos_table = e->cfg.rope ? nullptr : e->pos_table; t.dims = e->dims; t.h = e->h;
+    t.tables = e->embed; t.pos_table = e->cfg.rope ? nullptr : e->pos_table; t.dims = e->dims; t.h = v.h;
     t.H = e->cfg.hidden_size; t.bos = e->cfg.bos_token_id; t.bf16_tables = e->cfg.dtype == PTTS_BF16;
   }
-  t.logits = e->logits; t.ids = e->ids; t.ids_ld = e->ids_ld; t.cur_len = e->cur_len; t.unfinished = e->unfinished;
-  t.has_eos = e->has_eos; t.first_unf = e->first_unf; t.gen = e->gen; t.sort_buf = e->sort_buf;
-  t.B = e->B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
+  t.logits = v.logits; t.ids = v.ids; t.ids_ld = e->ids_ld; t.cur_len = v.cur_len; t.unfinished = v.unfinished;
+  t.has_eos = v.has_eos; t.first_unf = v.first_unf; t.gen = e->gen; t.sort_buf = e->sort_buf;
+  t.B = v.B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
   // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
-  if (e->session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? e->B : 1), st, e->slot_gen);
-  else tail_launch(t, nullptr, 0, dim3(e->B), st);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "tail launch failed: %s", hipGetErrorString(err));
-  return PTTS_OK;
+  if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen);
+  else tail_launch(t, nullptr, 0, dim3(v.B), st);
+  return launch_status("tail");
 }
 
 // static cross-attention folding for the utterance just prefilled (xfold_*_kernel): 2 launches covering every layer
@@ -622,18 +686,19 @@ int fold_cross(ptts_engine* e, hipStream_t st) {
                        e->dims, qscale);
     hipLaunchKernelGGL((xfold_u_kernel<WT, W8>), dim3((nh * NE + 63) / 64, H, L), dim3(64), 0, st, e->fold_layers, H, NE, nh, c.max_enc, n_rep, e->dims);
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "cross-attention fold launch failed: %s", hipGetErrorString(err));
-  return PTTS_OK;
+  return launch_status("cross-attention fold");
 }
 
-int forward_dispatch(ptts_engine* e, bool prefill, hipStream_t st, bool with_embed = true) {
-  return e->cfg.dtype == PTTS_BF16 ? forward<bf16_t>(e, prefill, st, with_embed) : forward<float>(e, prefill, st, with_embed);
+int forward_dispatch(const ptts_engine* e, FwdView v, bool prefill, hipStream_t st, bool with_embed = true) {
+  return e->cfg.dtype == PTTS_BF16 ? forward<bf16_t>(e, v, prefill, st, with_embed) : forward<float>(e, v, prefill, st, with_embed);
 }
+
+// attention fetch bound of a decode forward behind `ub` written self-KV positions: ub + 1 rounded up to 64, <= max_ctx
+static int kv_bound_of(const ptts_engine* e, int ub) { return std::min(e->cfg.max_ctx, (ub + 1 + 63) / 64 * 64); }
 
 // every decode forward appends one self-KV position: advance the host's bound before launching it (eagerly or as a graph)
 // (session: one bound per busy slot, capped by the end of its request; the step's bound is their maximum, so it falls when a long request retires)
-static int advance_kv(ptts_engine* e) {
+static void advance_kv(ptts_engine* e) {
   if (e->session) {
     int ub = e->P + 1;
     for (int b = 0; b < e->B; ++b)
@@ -645,14 +710,7 @@ static int advance_kv(ptts_engine* e) {
   } else {
     e->kv_ub += 1;
   }
-  const int cap = e->cfg.max_ctx;
-  e->kv_bound = std::min(cap, (e->kv_ub + 1 + 63) / 64 * 64);
-  return e->kv_bound;
-}
-
-bool ends_with(const std::string& s, const char* suf) {
-  const size_t n = strlen(suf);
-  return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
+  e->kv_bound = kv_bound_of(e, e->kv_ub);
 }
 
 // copy/convert a plain tensor into engine storage
@@ -686,6 +744,39 @@ int rowmajor_dispatch(ptts_engine* e, void* dst, const void* src, int src_dtype,
   const size_t off = (size_t)row0 * K, n = (size_t)N * K;
   if (e->cfg.dtype == PTTS_BF16) return convert_into<bf16_t>(reinterpret_cast<bf16_t*>(dst) + off, src, src_dtype, n, st);
   return convert_into<float>(reinterpret_cast<float*>(dst) + off, src, src_dtype, n, st);
+}
+
+// The tensors of a decoder layer by name suffix. A projection matrix is rows [row0, row0 + N) of its packed destination, of the row-major copy
+// (GEMV step), of the e4m3 strip copy and of the row scales (weights_fp8) - null where this engine holds none; K = -1: an fp32 vector of N
+struct LayerTensor { const char* name; void *dst, *rm, *p8; float* sc; int N, K, row0; };
+std::array<LayerTensor, 16> layer_tensors(const ptts_engine* e, const LayerW& w) {
+  const int H = e->cfg.hidden_size, F = e->cfg.ffn_dim, kv = e->nkv * 64, kc = e->nkc * 64;
+  return {{{"self_attn.q_proj.weight", w.qkv, w.qkv_rm, w.qkv_p8, w.qkv_sc, H, H, 0},
+           {"self_attn.k_proj.weight", w.qkv, w.qkv_rm, w.qkv_p8, w.qkv_sc, kv, H, H},
+           {"self_attn.v_proj.weight", w.qkv, w.qkv_rm, w.qkv_p8, w.qkv_sc, kv, H, H + kv},
+           {"self_attn.out_proj.weight", w.o, w.o_rm, w.o_p8, w.o_sc, H, H, 0},
+           {"encoder_attn.q_proj.weight", w.cq, w.cq_rm, nullptr, w.cq_sc, H, H, 0},
+           {"encoder_attn.k_proj.weight", w.ckv, nullptr, nullptr, nullptr, kc, H, 0},
+           {"encoder_attn.v_proj.weight", w.ckv, nullptr, nullptr, nullptr, kc, H, kc},
+           {"encoder_attn.out_proj.weight", w.co, w.co_rm, w.co_p8, w.co_sc, H, H, 0},
+           {"fc1.weight", w.fc1, w.fc1_rm, w.fc1_p8, w.fc1_sc, F, H, 0},
+           {"fc2.weight", w.fc2, w.fc2_rm, w.fc2_p8, w.fc2_sc, H, F, 0},
+           {"self_attn_layer_norm.weight", w.ln1_g, nullptr, nullptr, nullptr, H, -1, 0}, {"self_attn_layer_norm.bias", w.ln1_b, nullptr, nullptr, nullptr, H, -1, 0},
+           {"encoder_attn_layer_norm.weight", w.ln2_g, nullptr, nullptr, nullptr, H, -1, 0}, {"encoder_attn_layer_norm.bias", w.ln2_b, nullptr, nullptr, nullptr, H, -1, 0},
+           {"final_layer_norm.weight", w.ln3_g, nullptr, nullptr, nullptr, H, -1, 0}, {"final_layer_norm.bias", w.ln3_b, nullptr, nullptr, nullptr, H, -1, 0}}};
+}
+
+// The engine's environment switches, read once when it is created. PTTS_PREFILL_ATTN alone is read per forward (strip_path).
+void read_env_switches(ptts_engine* e) {
+  if (const char* ev = getenv("PTTS_FUSE_X")) e->fuse_x = atoi(ev) ? 1 : 0;
+  if (const char* ev = getenv("PTTS_FUSE_X_NUR")) { const int v = atoi(ev); if (v == 2 || v == 4) e->fuse_x_nur = v; }
+  e->fuse_qa = !(getenv("PTTS_NO_FUSE_QA") && atoi(getenv("PTTS_NO_FUSE_QA")));
+  if (const char* ev = getenv("PTTS_FUSE_QA_MAX")) e->fuse_qa_max = std::max(1, std::min(GV_MAX_ROWS, atoi(ev)));
+  e->fuse_xq = !(getenv("PTTS_NO_FUSE_XQ") && atoi(getenv("PTTS_NO_FUSE_XQ")));
+  if (const char* ev = getenv("PTTS_LNPROJ")) e->lnproj = std::max(0, std::min(3, atoi(ev)));
+  if (const char* ev = getenv("PTTS_LNPROJ_G")) e->lnproj_g = atoi(ev) == 4 ? 4 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 8 ? 8 : 0));
+  if (const char* ev = getenv("PTTS_XATTN_G")) { const int g = atoi(ev); if (g == 2 || g == 4 || g == 8) e->xattn_g = e->xattn_g_ok ? g : 8; }  // after xattn_g_ok
+  e->xattn_groups = !(getenv("PTTS_NO_XATTN_GROUPS") && atoi(getenv("PTTS_NO_XATTN_GROUPS")));  // measured: 1386 -> 1360 us per batch-32 step (profiles/r03_experiments.txt)
 }
 
 // NULL is the legacy default stream (what torch.cuda.current_stream() is on ROCm unless the caller switched): pass through.
@@ -742,18 +833,15 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   if (e->use_gemv && !c.rope && c.max_enc <= 64 && ptts_gemv_k_ok(nh * 64, gmode))
     e->xfold_ne = 64;
   e->w8_strips = e->w8 && !e->use_gemv;
-  if (c.kv_fp8 && (c.dtype != PTTS_BF16 || c.max_batch <= GV_MAX_ROWS)) {  // by capacity, not by path (a width without GEMV instances runs strips at 1..8 too)
-    ptts_engine_destroy(e);
-    return ptts_fail(PTTS_E_UNSUPPORTED, "kv_fp8 (e4m3 self-attention cache) needs the bf16 engine created for more than %d utterances (the MFMA strip step)", GV_MAX_ROWS);
-  }
-  if (e->w8 && (c.dtype != PTTS_BF16 || H % 512 || F % 512 || H > 2048)) {
-    ptts_engine_destroy(e);
-    return ptts_fail(PTTS_E_UNSUPPORTED, "weights_fp8 needs the bf16 engine and hidden / ffn sizes that are multiples of 512 (hidden <= 2048)");
-  }
+  if (c.kv_fp8 && (c.dtype != PTTS_BF16 || c.max_batch <= GV_MAX_ROWS))  // by capacity, not by path (a width without GEMV instances runs strips at 1..8 too)
+    return fail(ptts_fail(PTTS_E_UNSUPPORTED, "kv_fp8 (e4m3 self-attention cache) needs the bf16 engine created for more than %d utterances (the MFMA strip step)", GV_MAX_ROWS));
+  if (e->w8 && (c.dtype != PTTS_BF16 || H % 512 || F % 512 || H > 2048))
+    return fail(ptts_fail(PTTS_E_UNSUPPORTED, "weights_fp8 needs the bf16 engine and hidden / ffn sizes that are multiples of 512 (hidden <= 2048)"));
 #define A(expr) if ((rc = (expr)) != PTTS_OK) return fail(rc)
   for (int l = 0; l < c.num_layers; ++l) {
     LayerW& w = e->L[l];
-    A(e->alloc_bytes(&w.qkv, (size_t)(H + 2 * e->nkv * 64) * H * es));
+    const int nq = H + 2 * e->nkv * 64;
+    A(e->alloc_bytes(&w.qkv, (size_t)nq * H * es));
     A(e->alloc_bytes(&w.o, (size_t)H * H * es));
     A(e->alloc_bytes(&w.cq, (size_t)H * H * es));
     A(e->alloc_bytes(&w.ckv, (size_t)2 * e->nkc * 64 * H * es));
@@ -762,7 +850,6 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
     A(e->alloc_bytes(&w.fc2, (size_t)F * H * es));
     if (e->use_gemv) {
       const size_t res = e->w8 ? 1 : es;  // row-major element size: e4m3 bytes or the engine dtype
-      const int nq = H + 2 * e->nkv * 64;
       A(e->alloc_bytes(&w.qkv_rm, (size_t)nq * H * res)); A(e->alloc_bytes(&w.o_rm, (size_t)H * H * res));
       A(e->alloc_bytes(&w.cq_rm, (size_t)H * H * res)); A(e->alloc_bytes(&w.co_rm, (size_t)H * H * res));
       A(e->alloc_bytes(&w.fc1_rm, (size_t)F * H * res)); A(e->alloc_bytes(&w.fc2_rm, (size_t)F * H * res));
@@ -771,12 +858,8 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
       }
     }
     if (e->w8) {  // row scales serve both e4m3 layouts (row-major for the GEMV step, strips for the MFMA step)
-      const int nq = H + 2 * e->nkv * 64;
       A(e->alloc(&w.qkv_sc, nq)); A(e->alloc(&w.o_sc, H)); A(e->alloc(&w.cq_sc, H)); A(e->alloc(&w.co_sc, H));
       A(e->alloc(&w.fc1_sc, F)); A(e->alloc(&w.fc2_sc, H));
-      const char* qm[] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "encoder_attn.q_proj",
-                          "encoder_attn.out_proj", "fc1", "fc2"};
-      for (const char* m : qm) { char nm[160]; snprintf(nm, sizeof nm, "model.decoder.layers.%d.%s.weight", l, m); e->required_fp8.insert(nm); }
       if (e->w8_strips) {
         A(e->alloc_bytes(&w.qkv_p8, (size_t)nq * H)); A(e->alloc_bytes(&w.o_p8, (size_t)H * H)); A(e->alloc_bytes(&w.co_p8, (size_t)H * H));
         A(e->alloc_bytes(&w.fc1_p8, (size_t)F * H)); A(e->alloc_bytes(&w.fc2_p8, (size_t)F * H));
@@ -789,13 +872,9 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
     if (c.kv_fp8) { A(e->alloc(&w.ks_self, (size_t)c.max_batch * e->nkv * c.max_ctx)); A(e->alloc(&w.vs_self, (size_t)c.max_batch * e->nkv * c.max_ctx)); }
     A(e->alloc_bytes(&w.k_cross, kvc)); A(e->alloc_bytes(&w.v_cross, kvc));
     char nm[160];
-    const char* mats[] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "encoder_attn.q_proj",
-                          "encoder_attn.k_proj", "encoder_attn.v_proj", "encoder_attn.out_proj", "fc1", "fc2"};
-    for (const char* m : mats) { snprintf(nm, sizeof nm, "model.decoder.layers.%d.%s.weight", l, m); e->required.insert(nm); }
-    const char* lns[] = {"self_attn_layer_norm", "encoder_attn_layer_norm", "final_layer_norm"};
-    for (const char* m : lns) {
-      snprintf(nm, sizeof nm, "model.decoder.layers.%d.%s.weight", l, m); e->required.insert(nm);
-      snprintf(nm, sizeof nm, "model.decoder.layers.%d.%s.bias", l, m); e->required.insert(nm);
+    for (const LayerTensor& m : layer_tensors(e, w)) {
+      snprintf(nm, sizeof nm, "model.decoder.layers.%d.%s", l, m.name); e->required.insert(nm);
+      if (m.sc) e->required_fp8.insert(nm);  // weights_fp8: a matrix with row scales has an e4m3 copy to load
     }
   }
   {
@@ -847,12 +926,9 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
     if (s > 8) s = 8;
     while (s > 1 && (s - 1) * 4 * 8 * 8 >= c.max_ctx) --s;  // do not split below one 8-deep batch of row groups per wave
     e->S_self = s;
-    e->S_cross = 1;
-    {
-      const int rows_per_wave = (c.dtype == PTTS_BF16 ? 8 : 4) * 8;  // RPI row groups x 8 loads in flight
-      const int need = (c.max_enc + rows_per_wave - 1) / rows_per_wave;
-      e->cross_waves = need <= 1 ? 1 : (need <= 2 ? 2 : 4);
-    }
+    const int rows_per_wave = (c.dtype == PTTS_BF16 ? 8 : 4) * 8;  // RPI row groups x 8 loads in flight
+    const int need = (c.max_enc + rows_per_wave - 1) / rows_per_wave;
+    e->cross_waves = need <= 1 ? 1 : (need <= 2 ? 2 : 4);
     if (e->use_gemv) while (e->S_self & (e->S_self - 1)) --e->S_self;  // the GEMV combine prologue is instantiated for 2 / 4 / 8 splits
   }
   const size_t rows = (size_t)c.max_batch * e->max_prompt;
@@ -866,11 +942,6 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   A(e->alloc(&e->stats, part_rows * nh * 2));
   A(e->alloc(&e->xpart, (size_t)nh * H));
   A(e->alloc(&e->h2, (size_t)H));
-  if (const char* ev = getenv("PTTS_FUSE_X")) e->fuse_x = atoi(ev) ? 1 : 0;
-  if (const char* ev = getenv("PTTS_FUSE_X_NUR")) { const int v = atoi(ev); if (v == 2 || v == 4) e->fuse_x_nur = v; }
-  e->fuse_qa = !(getenv("PTTS_NO_FUSE_QA") && atoi(getenv("PTTS_NO_FUSE_QA")));
-  if (const char* ev = getenv("PTTS_FUSE_QA_MAX")) e->fuse_qa_max = std::max(1, std::min(GV_MAX_ROWS, atoi(ev)));
-  e->fuse_xq = !(getenv("PTTS_NO_FUSE_XQ") && atoi(getenv("PTTS_NO_FUSE_XQ")));
   A(e->alloc(&e->ffn, std::max(rows * F, rows * (size_t)H)));
   A(e->alloc(&e->logits, (size_t)c.max_batch * K * V));
   A(e->alloc(&e->sort_buf, 16));
@@ -878,11 +949,8 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   A(e->alloc_bytes(&e->xw2, std::max((rows + 16) * F, enc_rows * (size_t)H) * es));
   A(e->alloc(&e->lnstat, (size_t)c.max_batch * (H / 16) * 2 + 16));
   e->use_lns = H == 1024 || H == 1536;
-  if (const char* ev = getenv("PTTS_LNPROJ")) e->lnproj = std::max(0, std::min(3, atoi(ev)));
-  if (const char* ev = getenv("PTTS_LNPROJ_G")) e->lnproj_g = atoi(ev) == 4 ? 4 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 8 ? 8 : 0));
   e->xattn_g_ok = (H == 1024 && ((H / (c.dtype == PTTS_BF16 ? 32 : 16)) / 2) % 16 == 0) || H == 1536;
-  if (const char* ev = getenv("PTTS_XATTN_G")) { const int g = atoi(ev); if (g == 2 || g == 4 || g == 8) e->xattn_g = e->xattn_g_ok ? g : 8; }
-  e->xattn_groups = !(getenv("PTTS_NO_XATTN_GROUPS") && atoi(getenv("PTTS_NO_XATTN_GROUPS")));  // measured: 1386 -> 1360 us per batch-32 step (profiles/r03_experiments.txt)
+  read_env_switches(e);
   A(e->alloc(&e->prefix, (size_t)c.max_batch * K * c.max_ctx));
   e->ids_ld = c.max_ctx + 8;
   A(e->alloc(&e->ids, (size_t)c.max_batch * K * e->ids_ld));
@@ -929,7 +997,7 @@ extern "C" int ptts_load_weight(ptts_engine* e, const char* name_c, const void* 
   PTTS_DEVICE(e->cfg.device);
   hipStream_t st = pick_stream(e, stream);
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, F = c.ffn_dim, K = c.num_codebooks, V = c.vocab_size;
+  const int H = c.hidden_size, K = c.num_codebooks, V = c.vocab_size;
   const std::string name(name_c);
   auto want = [&](int64_t a, int64_t b) -> int {
     if (b < 0) { if (ndim != 1 || shape[0] != a) return ptts_fail(PTTS_E_INVALID, "%s: expected shape [%lld]", name_c, (long long)a); }
@@ -940,30 +1008,13 @@ extern "C" int ptts_load_weight(ptts_engine* e, const char* name_c, const void* 
   char tail[128] = {0};
   if (sscanf(name_c, "model.decoder.layers.%d.%127s", &l, tail) == 2) {
     PTTS_CHECK(l >= 0 && l < c.num_layers, PTTS_E_INVALID, "%s: layer index out of range", name_c);
-    LayerW& w = e->L[l];
     const std::string t(tail);
-    struct { const char* n; void* dst; void* rm; int N, Kd, row0; } mats[] = {
-        {"self_attn.q_proj.weight", w.qkv, w.qkv_rm, H, H, 0},       {"self_attn.k_proj.weight", w.qkv, w.qkv_rm, e->nkv * 64, H, H},
-        {"self_attn.v_proj.weight", w.qkv, w.qkv_rm, e->nkv * 64, H, H + e->nkv * 64}, {"self_attn.out_proj.weight", w.o, w.o_rm, H, H, 0},
-        {"encoder_attn.q_proj.weight", w.cq, w.cq_rm, H, H, 0},     {"encoder_attn.k_proj.weight", w.ckv, nullptr, e->nkc * 64, H, 0},
-        {"encoder_attn.v_proj.weight", w.ckv, nullptr, e->nkc * 64, H, e->nkc * 64}, {"encoder_attn.out_proj.weight", w.co, w.co_rm, H, H, 0},
-        {"fc1.weight", w.fc1, w.fc1_rm, F, H, 0},                    {"fc2.weight", w.fc2, w.fc2_rm, H, F, 0}};
-    for (auto& m : mats)
-      if (t == m.n) {
-        PTTS_TRY(want(m.N, m.Kd));
-        PTTS_TRY(pack_dispatch(e, m.dst, dev_ptr, src_dtype, m.N, m.Kd, m.row0, st));
-        if (m.rm && !e->w8) PTTS_TRY(rowmajor_dispatch(e, m.rm, dev_ptr, src_dtype, m.N, m.Kd, m.row0, st));
-        e->loaded.insert(name);
-        return PTTS_OK;
-      }
-    struct { const char* n; float* dst; } vecs[] = {
-        {"self_attn_layer_norm.weight", w.ln1_g}, {"self_attn_layer_norm.bias", w.ln1_b},
-        {"encoder_attn_layer_norm.weight", w.ln2_g}, {"encoder_attn_layer_norm.bias", w.ln2_b},
-        {"final_layer_norm.weight", w.ln3_g}, {"final_layer_norm.bias", w.ln3_b}};
-    for (auto& v : vecs)
-      if (t == v.n) {
-        PTTS_TRY(want(H, -1));
-        PTTS_TRY(convert_into<float>(v.dst, dev_ptr, src_dtype, H, st));
+    for (const LayerTensor& m : layer_tensors(e, e->L[l]))
+      if (t == m.name) {
+        PTTS_TRY(want(m.N, m.K));
+        if (m.K < 0) PTTS_TRY(convert_into<float>((float*)m.dst, dev_ptr, src_dtype, m.N, st));
+        else PTTS_TRY(pack_dispatch(e, m.dst, dev_ptr, src_dtype, m.N, m.K, m.row0, st));
+        if (m.rm && !e->w8) PTTS_TRY(rowmajor_dispatch(e, m.rm, dev_ptr, src_dtype, m.N, m.K, m.row0, st));
         e->loaded.insert(name);
         return PTTS_OK;
       }
@@ -995,7 +1046,7 @@ extern "C" int ptts_load_weight(ptts_engine* e, const char* name_c, const void* 
   }
   if (name == "model.decoder.layer_norm.weight" || name == "model.decoder.layer_norm.bias") {
     PTTS_TRY(want(H, -1));
-    PTTS_TRY(convert_into<float>(ends_with(name, ".weight") ? e->lnf_g : e->lnf_b, dev_ptr, src_dtype, H, st));
+    PTTS_TRY(convert_into<float>(name == "model.decoder.layer_norm.weight" ? e->lnf_g : e->lnf_b, dev_ptr, src_dtype, H, st));
     e->loaded.insert(name);
     return PTTS_OK;
   }
@@ -1040,37 +1091,30 @@ extern "C" int ptts_load_weight_fp8(ptts_engine* e, const char* name_c, const ui
   PTTS_DEVICE(e->cfg.device);
   hipStream_t st = pick_stream(e, stream);
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, F = c.ffn_dim, K = c.num_codebooks, V = c.vocab_size;
-  uint8_t *dst = nullptr, *p8 = nullptr;
-  float* sc = nullptr;
-  bool known = false;
-  int N = 0, Kd = 0, row0 = 0, l = -1, k = -1;
+  const int H = c.hidden_size, K = c.num_codebooks, V = c.vocab_size;
+  LayerTensor m = {};  // the matrix named: rows of the row-major / strip copies and of the scales (no name: none found)
+  int l = -1, k = -1;
   char tail[128] = {0};
   if (sscanf(name_c, "model.decoder.layers.%d.%127s", &l, tail) == 2) {
     PTTS_CHECK(l >= 0 && l < c.num_layers, PTTS_E_INVALID, "%s: layer index out of range", name_c);
-    LayerW& w = e->L[l];
     const std::string t(tail);
-    struct { const char* n; void* rm; void* p8; float* sc; int N, Kd, row0; } mats[] = {
-        {"self_attn.q_proj.weight", w.qkv_rm, w.qkv_p8, w.qkv_sc, H, H, 0}, {"self_attn.k_proj.weight", w.qkv_rm, w.qkv_p8, w.qkv_sc, e->nkv * 64, H, H},
-        {"self_attn.v_proj.weight", w.qkv_rm, w.qkv_p8, w.qkv_sc, e->nkv * 64, H, H + e->nkv * 64}, {"self_attn.out_proj.weight", w.o_rm, w.o_p8, w.o_sc, H, H, 0},
-        {"encoder_attn.q_proj.weight", w.cq_rm, nullptr, w.cq_sc, H, H, 0}, {"encoder_attn.out_proj.weight", w.co_rm, w.co_p8, w.co_sc, H, H, 0},
-        {"fc1.weight", w.fc1_rm, w.fc1_p8, w.fc1_sc, F, H, 0}, {"fc2.weight", w.fc2_rm, w.fc2_p8, w.fc2_sc, H, F, 0}};
-    for (auto& m : mats)
-      if (t == m.n) { dst = (uint8_t*)m.rm; p8 = (uint8_t*)m.p8; sc = m.sc; N = m.N; Kd = m.Kd; row0 = m.row0; known = true; }
+    for (const LayerTensor& x : layer_tensors(e, e->L[l]))  // (the cross K/V projections and the vectors have no scales: refused below)
+      if (t == x.name) m = x;
   } else if (sscanf(name_c, "lm_heads.%d.weight", &k) == 1) {
     PTTS_CHECK(k >= 0 && k < K, PTTS_E_INVALID, "%s: codebook index out of range", name_c);
-    dst = (uint8_t*)e->heads_rm; p8 = (uint8_t*)e->heads_p8; sc = e->heads_sc; N = V; Kd = H; row0 = k * V; known = true;
+    m = LayerTensor{name_c, e->heads, e->heads_rm, e->heads_p8, e->heads_sc, V, H, k * V};
   }
-  PTTS_CHECK(known && sc, PTTS_E_INVALID, "%s has no e4m3 copy (only the decode-step projection matrices do)", name_c);
+  const int N = m.N, Kd = m.K, row0 = m.row0;
+  PTTS_CHECK(m.name && m.sc, PTTS_E_INVALID, "%s has no e4m3 copy (only the decode-step projection matrices do)", name_c);
   PTTS_CHECK(shape[0] == N && shape[1] == Kd, PTTS_E_INVALID, "%s: expected shape [%d, %d]", name_c, N, Kd);
   // row-major bytes for the GEMV step (engines of <= GV_MAX_ROWS utterances), strip order for the MFMA step (wider engines)
-  if (dst) PTTS_HIP(hipMemcpyAsync(dst + (size_t)row0 * Kd, q_dev, (size_t)N * Kd, hipMemcpyDeviceToDevice, st));
-  if (p8) {
+  if (m.rm) PTTS_HIP(hipMemcpyAsync((uint8_t*)m.rm + (size_t)row0 * Kd, q_dev, (size_t)N * Kd, hipMemcpyDeviceToDevice, st));
+  if (m.p8) {
     PTTS_CHECK(N % 16 == 0 && Kd % 64 == 0 && row0 % 16 == 0, PTTS_E_INVALID, "%s: [%d, %d] at row %d is not a whole number of 16 x 64 e4m3 strips", name_c, N, Kd, row0);
     const size_t total = (size_t)(N / 16) * (Kd / 64) * 64;
-    hipLaunchKernelGGL(pack_w8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q_dev, reinterpret_cast<uint4*>(p8), N, Kd, row0 / 16, Kd / 64);
+    hipLaunchKernelGGL(pack_w8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q_dev, reinterpret_cast<uint4*>(m.p8), N, Kd, row0 / 16, Kd / 64);
   }
-  PTTS_HIP(hipMemcpyAsync(sc + row0, scale_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+  PTTS_HIP(hipMemcpyAsync(m.sc + row0, scale_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
   e->loaded_fp8.insert(name_c);
   return PTTS_OK;
 }
@@ -1136,6 +1180,24 @@ static void launch_set_params(ptts_engine* e, int T_prefix, hipStream_t st) {
   hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, st, e->dims, e->gen, hd, dev_gen_of(e->gp, e->gp.max_length));
 }
 
+// Inputs of a prefill over arena rows [row0, row0 + n). Masks: all-ones when absent, so that the captured graph never changes shape - the N / P
+// given entries of each row, or the whole row (AdmitMoveArgs::enc_n / prompt_n move exactly that). Encoder states -> qc (consumed by the cross
+// K/V projection), prompt embeddings -> ffn: both are scratch of a forward, dead between the steps of a session.
+static int stage_inputs(const ptts_engine* e, int row0, int n, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                        const int32_t* prompt_mask_dev, hipStream_t st) {
+  const ptts_config& c = e->cfg;
+  const size_t N = e->N, P = e->P, H = c.hidden_size, enc_ld = c.max_enc, prompt_ld = e->max_prompt;
+  int* em = e->enc_mask + row0 * enc_ld;
+  int* pm = e->prompt_mask + row0 * prompt_ld;
+  if (enc_mask_dev) PTTS_HIP(hipMemcpy2DAsync(em, enc_ld * 4, enc_mask_dev, N * 4, N * 4, n, hipMemcpyDeviceToDevice, st));
+  else hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, em, 1, n * enc_ld);
+  if (prompt_mask_dev && P > 0) PTTS_HIP(hipMemcpy2DAsync(pm, prompt_ld * 4, prompt_mask_dev, P * 4, P * 4, n, hipMemcpyDeviceToDevice, st));
+  else hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, pm, 1, n * prompt_ld);
+  PTTS_HIP(hipMemcpyAsync(e->qc, enc_dev, n * N * H * 4, hipMemcpyDeviceToDevice, st));
+  if (P > 0) PTTS_HIP(hipMemcpyAsync(e->ffn, prompt_dev, n * P * H * 4, hipMemcpyDeviceToDevice, st));
+  return PTTS_OK;
+}
+
 extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
                             const int32_t* prompt_mask_dev, int32_t B, int32_t N, int32_t P, int32_t sample, void* stream) {
   PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
@@ -1146,21 +1208,14 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
   PTTS_CHECK(e->pending_T + 2 <= e->gp.max_length, PTTS_E_INVALID, "voice prompt of %d frames leaves no room below max_length %d", e->pending_T, e->gp.max_length);
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
-  const int H = c.hidden_size, K = c.num_codebooks;
+  const int K = c.num_codebooks;
   e->B = B; e->N = N; e->P = P;
   e->session = false;  // a static batch ends a continuous session
   if (sample) PTTS_HIP(hipEventRecord(e->ev_pre0, st));
   launch_set_params(e, e->pending_T, st);
-  // masks (all-ones when absent so the captured graph never changes shape)
-  if (enc_mask_dev) PTTS_HIP(hipMemcpy2DAsync(e->enc_mask, (size_t)c.max_enc * 4, enc_mask_dev, (size_t)N * 4, (size_t)N * 4, B, hipMemcpyDeviceToDevice, st));
-  else hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, e->enc_mask, 1, (size_t)B * c.max_enc);
-  if (prompt_mask_dev && P > 0) PTTS_HIP(hipMemcpy2DAsync(e->prompt_mask, (size_t)e->max_prompt * 4, prompt_mask_dev, (size_t)P * 4, (size_t)P * 4, B, hipMemcpyDeviceToDevice, st));
-  else hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, e->prompt_mask, 1, (size_t)B * e->max_prompt);
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished,
                      e->has_eos, e->first_unf, (int*)nullptr, 0, B, K, c.bos_token_id, 1, 0);  // every row live; no per-row end
-  // stage inputs: encoder states -> qc (consumed by the cross K/V projection), prompt embeddings -> ffn
-  PTTS_HIP(hipMemcpyAsync(e->qc, enc_dev, (size_t)B * N * H * 4, hipMemcpyDeviceToDevice, st));
-  if (P > 0) PTTS_HIP(hipMemcpyAsync(e->ffn, prompt_dev, (size_t)B * P * H * 4, hipMemcpyDeviceToDevice, st));
+  PTTS_TRY(stage_inputs(e, 0, B, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
   // voice prompt (ptts_set_audio_prefix): the reference runs BOS + the T given code columns in ONE multi-column forward
   // (:3136-3194, causal attention); so does this prefill whenever the row capacity (max_prompt) holds P + 1 + T positions
   // per utterance. Otherwise the T columns are teacher-forced one position at a time through the decode path (same numbers:
@@ -1168,23 +1223,20 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
   const int T = e->pending_T;
   e->pending_T = 0;
   const bool batched = T > 0 && P + 1 + T <= e->max_prompt;
-  if (batched) {
-    hipLaunchKernelGGL(push_prefix_all_kernel, dim3((B * K * T + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->dims, T, B, K, c.bos_token_id);
-    e->prefill_T = T;
-  }
+  if (batched) hipLaunchKernelGGL(push_prefix_all_kernel, dim3((B * K * T + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->dims, T, B, K, c.bos_token_id);
   e->xfold_valid = false;  // the prefill itself (and anything before the fold below) runs the un-folded cross-attention
-  const int rc_fwd = forward_dispatch(e, true, st);
-  e->prefill_T = 0;
-  PTTS_TRY(rc_fwd);
+  FwdView v = whole_view(e);
+  v.T = batched ? T : 0;
+  PTTS_TRY(forward_dispatch(e, v, true, st));
   e->kv_ub = P + 1 + (batched ? T : 0);  // self-KV positions written by this pass
   if (batched) hipLaunchKernelGGL(set_len_kernel, dim3((B + 255) / 256), dim3(256), 0, st, e->cur_len, B, T + 1);
   for (int j = 1; j <= (batched ? 0 : T); ++j) {  // (un-folded cross block: the fold below has not run yet)
     hipLaunchKernelGGL(push_prefix_col_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->dims, j, B, K, c.bos_token_id);
     hipLaunchKernelGGL(set_len_kernel, dim3((B + 255) / 256), dim3(256), 0, st, e->cur_len, B, j + 1);
     advance_kv(e);
-    PTTS_TRY(forward_dispatch(e, false, st, true));
+    PTTS_TRY(forward_dispatch(e, whole_view(e), false, st, true));
   }
-  if (sample) { PTTS_HIP(hipEventRecord(e->ev_tail0, st)); PTTS_TRY(launch_tail(e, st, true)); }  // also embeds the sampled column for the first decode step
+  if (sample) { PTTS_HIP(hipEventRecord(e->ev_tail0, st)); PTTS_TRY(launch_tail(e, whole_view(e), st, true)); }  // also embeds the sampled column for the first decode step
   e->first_recorded = false;
   if (sample) { PTTS_HIP(hipEventRecord(e->ev_first, st)); e->first_recorded = true; }
   if (e->xfold_ne && B == 1) {
@@ -1206,27 +1258,27 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
 
 // The decode step (170 kernel nodes for Mini-v1 at batch <= 8) is captured ONCE per batch size on the engine's private stream
 // (capture records, it does not execute; the legacy NULL stream cannot be captured) and replayed into the caller's.
-static int get_graph(ptts_engine* e, hipGraphExec_t* out) {
+static int get_graph(ptts_engine* e, int kv_bound, hipGraphExec_t* out) {
   // the node set of the step depends on the batch size and on the folded cross block; the attention fetch bound (a kernel argument)
-  // on the 64-position bucket of the context (forward<> reads it from e->kv_bound while capturing). (Several steps of one bucket per
+  // on the 64-position bucket of the context this graph is captured for (`kv_bound`). (Several steps of one bucket per
   // graph launch - round 4's PTTS_GRAPH_STEPS - measured 0.3-0.7 %, profiles/r04_experiments.txt call 19: removed in round 6.)
-  const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (e->kv_bound / 64) + (e->session ? 1LL << 40 : 0);  // session steps end in their own tail
+  const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (kv_bound / 64) + (e->session ? 1LL << 40 : 0);  // session steps end in their own tail
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) { if (out) *out = it->second; return PTTS_OK; }
   hipGraph_t g = nullptr;
   hipStream_t st = e->own_stream;
   PTTS_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
   // decode step = layers + heads + tail; the tail embeds the column it just sampled for the NEXT replay (no embed node)
-  int rc = forward_dispatch(e, false, st, false);
-  if (rc == PTTS_OK) rc = launch_tail(e, st, true);
+  FwdView v = whole_view(e);
+  v.kv_bound = kv_bound;
+  int rc = forward_dispatch(e, v, false, st, false);
+  if (rc == PTTS_OK) rc = launch_tail(e, v, st, true);
   hipError_t ce = hipStreamEndCapture(st, &g);
   if (rc != PTTS_OK) { if (g) hipGraphDestroy(g); return rc; }
   if (ce != hipSuccess) return ptts_fail(PTTS_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
   hipGraphExec_t ex = nullptr;
-  {
-    size_t nn = 0;
-    if (hipGraphGetNodes(g, nullptr, &nn) == hipSuccess) e->last_graph_nodes = (int)nn;
-  }
+  size_t nn = 0;
+  if (hipGraphGetNodes(g, nullptr, &nn) == hipSuccess) e->last_graph_nodes = (int)nn;
   hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
   hipGraphDestroy(g);
   if (ie != hipSuccess) return ptts_fail(PTTS_E_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
@@ -1243,15 +1295,13 @@ static int get_graph(ptts_engine* e, hipGraphExec_t* out) {
 // the first decode_steps of the first call of every batch size. Graphs are cached for the engine's life, so only the first call of a
 // (batch, fold, bucket) pays.
 static int precapture_graphs(ptts_engine* e, int max_buckets) {
-  const int cap = e->cfg.max_ctx, saved_ub = e->kv_ub, saved_bound = e->kv_bound;
-  const int last_ub = std::min(cap - 1, e->P + (e->session ? e->session_max_length : e->gp.max_length));  // positions the longest run of this call writes
+  const int last_ub = std::min(e->cfg.max_ctx - 1, e->P + (e->session ? e->session_max_length : e->gp.max_length));  // positions the longest run of this call writes
   int rc = PTTS_OK, done = 0;
-  for (int ub = saved_ub + 1; ub <= last_ub && rc == PTTS_OK && done < max_buckets; ++done) {
-    e->kv_bound = std::min(cap, (ub + 1 + 63) / 64 * 64);
-    rc = get_graph(e, nullptr);
-    ub = e->kv_bound;  // first upper bound of the next bucket: (ub + 1 + 63) / 64 * 64 > kv_bound
+  for (int ub = e->kv_ub + 1; ub <= last_ub && rc == PTTS_OK && done < max_buckets; ++done) {
+    const int bound = kv_bound_of(e, ub);
+    rc = get_graph(e, bound, nullptr);
+    ub = bound;  // first upper bound of the next bucket: kv_bound_of(ub) > bound
   }
-  e->kv_ub = saved_ub; e->kv_bound = saved_bound;
   return rc;
 }
 
@@ -1263,18 +1313,16 @@ extern "C" int ptts_decode_steps(ptts_engine* e, int32_t n_steps, void* stream) 
   hipStream_t st = pick_stream(e, stream);
   if (n_steps > 0 && !e->h_ready) {  // previous column came from ptts_push_tokens / an un-sampled prefill: embed it once, eagerly
     advance_kv(e);
-    PTTS_TRY(forward_dispatch(e, false, st, true));
-    PTTS_TRY(launch_tail(e, st, true));
+    PTTS_TRY(forward_dispatch(e, whole_view(e), false, st, true));
+    PTTS_TRY(launch_tail(e, whole_view(e), st, true));
     e->h_ready = true;
     --n_steps;
   }
-  const int cap = e->cfg.max_ctx;
-  for (int i = 0; i < n_steps;) {
+  for (int i = 0; i < n_steps; ++i) {
     hipGraphExec_t ex = nullptr;
     advance_kv(e);
-    PTTS_TRY(get_graph(e, &ex));  // cached per (batch, fold, 64-position bucket)
+    PTTS_TRY(get_graph(e, e->kv_bound, &ex));  // cached per (batch, fold, 64-position bucket)
     PTTS_HIP(hipGraphLaunch(ex, st));
-    ++i;
   }
   if (n_steps > 0) PTTS_TRY(precapture_graphs(e, 2));  // the current bucket and the next one, while the GPU works through what was just enqueued
   return PTTS_OK;
@@ -1295,7 +1343,7 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
     PTTS_TRY(e->alloc(&e->row_maxlen, (size_t)c.max_batch));
     PTTS_TRY(e->alloc(&e->slot_gen, (size_t)c.max_batch));  // with row_maxlen: the step graphs hold a pointer that never changes
     PTTS_TRY(e->alloc(&e->h_adm, (size_t)e->max_prompt * H));
-    PTTS_TRY(e->alloc(&e->kv_layers_rows, (size_t)c.max_batch * c.num_layers));
+    PTTS_TRY(e->alloc(&e->kv_layers_rows, (size_t)c.max_batch * c.num_layers));  // rows_view points into it
     std::vector<KvLayer> kl((size_t)c.max_batch * c.num_layers);
     const size_t kvc = (size_t)e->nkc * c.max_enc * 64 * e->esize;  // one slot's cross K (or V) rows of a layer
     for (int b = 0; b < c.max_batch; ++b)
@@ -1318,32 +1366,11 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
   PTTS_HIP(hipMemsetAsync(e->h, 0, (size_t)B * H * 4, st));
   PTTS_HIP(hipMemsetAsync(e->logits, 0, (size_t)B * K * c.vocab_size * 4, st));
   e->kv_ub = P + 1;
-  e->kv_bound = std::min(c.max_ctx, (e->kv_ub + 1 + 63) / 64 * 64);
+  e->kv_bound = kv_bound_of(e, e->kv_ub);
   e->first_recorded = false;
   e->h_ready = true;  // nothing to embed: no slot is live
   e->prefilled = true;
   return PTTS_OK;
-}
-
-// The engine seen as a one-utterance engine whose arenas, masks, ids and logits are those of `row` (enter = true), and back. The prefill
-// kernels address utterance 0 of what they are given; the residual rows go to h_adm, because h[B][H] holds the other slots' next step input.
-static void session_row_view(ptts_engine* e, int row, bool enter) {
-  const ptts_config& c = e->cfg;
-  const long long d = enter ? row : -row;
-  const int K = c.num_codebooks;
-  const long long kvs = (long long)e->nkv * c.max_ctx * 64 * e->esize, kvc = (long long)e->nkc * c.max_enc * 64 * e->esize;
-  for (LayerW& w : e->L) {
-    w.k_self = (char*)w.k_self + d * kvs; w.v_self = (char*)w.v_self + d * kvs;
-    w.k_cross = (char*)w.k_cross + d * kvc; w.v_cross = (char*)w.v_cross + d * kvc;
-  }
-  e->logits += d * K * c.vocab_size;
-  e->ids += d * K * e->ids_ld;
-  e->cur_len += d; e->first_unf += d; e->unfinished += d * K; e->has_eos += d * K;
-  e->enc_mask += d * c.max_enc; e->prompt_mask += d * e->max_prompt;
-  if (enter) e->kv_layers_rows += d * c.num_layers;
-  std::swap(e->kv_layers, e->kv_layers_rows);
-  if (!enter) e->kv_layers_rows += d * c.num_layers;
-  std::swap(e->h, e->h_adm);
 }
 
 // the checks of one admission (ptts_admit_row_gen, and every entry of ptts_admit_rows); *L_out = the request's max_length
@@ -1364,6 +1391,16 @@ static int check_admission(const ptts_engine* e, int row, const float* prompt_de
   return PTTS_OK;
 }
 
+// The per-slot end of an admission, once nothing can refuse it any more: the host's bookkeeping, the request's own sampler record (a slot admitted
+// without one kept own = 0 from session begin / its last ptts_retire_row; a refused admission leaves the slot's record cleared), and its tail
+static int finish_admission(ptts_engine* e, int row, int L, const ptts_gen_params* gp, bool sample, hipStream_t st) {
+  e->slot_busy[row] = 1; e->slot_ub[row] = e->P + 1; e->slot_maxlen[row] = L;
+  if (gp) hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, st, e->slot_gen, row, 1, SlotGen{dev_gen_of(*gp, L), 1, 0});
+  if (sample) return launch_tail(e, whole_view(e), st, true, row);  // first token of the request + the embedding of its next column into h[row]
+  e->h_ready = false;                                               // manual path: the next forward embeds every slot's last column
+  return PTTS_OK;
+}
+
 extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
                                   const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, const ptts_gen_params* gp, void* stream) {
   PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
@@ -1371,34 +1408,13 @@ extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_
   int L = 0;
   PTTS_TRY(check_admission(e, row, prompt_dev, max_length, gp, &L));
   const ptts_config& c = e->cfg;
-  const int P = e->P, N = e->N, H = c.hidden_size, K = c.num_codebooks;
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
-                     e->row_maxlen, row, 1, K, c.bos_token_id, 1, L);
-  int* em = e->enc_mask + (size_t)row * c.max_enc;
-  int* pm = e->prompt_mask + (size_t)row * e->max_prompt;
-  if (enc_mask_dev) PTTS_HIP(hipMemcpyAsync(em, enc_mask_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, em, 1, (size_t)c.max_enc);
-  if (prompt_mask_dev && P > 0) PTTS_HIP(hipMemcpyAsync(pm, prompt_mask_dev, (size_t)P * 4, hipMemcpyDeviceToDevice, st));
-  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, pm, 1, (size_t)e->max_prompt);
-  // staging as in ptts_prefill: qc and ffn are scratch of a forward, dead between steps
-  PTTS_HIP(hipMemcpyAsync(e->qc, enc_dev, (size_t)N * H * 4, hipMemcpyDeviceToDevice, st));
-  if (P > 0) PTTS_HIP(hipMemcpyAsync(e->ffn, prompt_dev, (size_t)P * H * 4, hipMemcpyDeviceToDevice, st));
-  const int B = e->B;
-  session_row_view(e, row, true);
-  e->B = 1;
-  const int rc_fwd = forward_dispatch(e, true, st);
-  e->B = B;
-  session_row_view(e, row, false);
-  PTTS_TRY(rc_fwd);
-  e->slot_busy[row] = 1; e->slot_ub[row] = P + 1; e->slot_maxlen[row] = L;
-  // the request's own sampler record, written once nothing can refuse the admission any more (a refused one leaves the slot's record cleared);
-  // a slot admitted without one kept own = 0 from session begin / its last ptts_retire_row
-  if (gp) hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, st, e->slot_gen, row, 1, SlotGen{dev_gen_of(*gp, L), 1, 0});
-  if (sample) PTTS_TRY(launch_tail(e, st, true, row));  // first token of the request + the embedding of its next column into h[row]
-  else e->h_ready = false;                             // manual path: the next forward embeds every slot's last column
-  return PTTS_OK;
+                     e->row_maxlen, row, 1, c.num_codebooks, c.bos_token_id, 1, L);  // before the forward: its embedding reads the BOS column and the clock
+  PTTS_TRY(stage_inputs(e, row, 1, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
+  PTTS_TRY(forward_dispatch(e, rows_view(e, row, 1, e->h_adm), true, st));
+  return finish_admission(e, row, L, gp, sample != 0, st);
 }
 
 extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
@@ -1407,9 +1423,9 @@ extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev,
 }
 
 // A group of n requests in one prefill pass: the static prefill forward of a batch of n on the spare arena rows B .. B + n - 1 (every array of the
-// engine is batch-outermost and sized for max_batch, so the row view entered at row B with e->B = n is an n-utterance engine), then ONE launch that
-// moves each spare row to its slot (admit_move_rows_kernel), then per slot what ptts_admit_row_gen does: reset, record, tail. The tail runs on the
-// slot itself: the draw hash of a slot without a record of its own uses the slot index.
+// engine is batch-outermost and sized for max_batch, so rows_view(e, B, n) is an n-utterance engine), then ONE launch that moves each spare row to its
+// slot (admit_move_rows_kernel), then per slot what ptts_admit_row_gen does: reset, record, tail. The tail runs on the slot itself: the draw hash of a
+// slot without a record of its own uses the slot index.
 extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
                                const int32_t* prompt_mask_dev, const int32_t* max_lengths, int32_t sample, const ptts_gen_params* const* gps,
                                void* stream) {
@@ -1438,23 +1454,8 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
   // the spare rows as ptts_prefill prepares a batch of n: sampler state (the prefill's embedding reads the BOS column and the clock), masks, staging
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((n * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
-  int* em = e->enc_mask + (size_t)B * c.max_enc;
-  int* pm = e->prompt_mask + (size_t)B * e->max_prompt;
-  if (enc_mask_dev) PTTS_HIP(hipMemcpy2DAsync(em, (size_t)c.max_enc * 4, enc_mask_dev, (size_t)N * 4, (size_t)N * 4, n, hipMemcpyDeviceToDevice, st));
-  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, em, 1, (size_t)n * c.max_enc);
-  if (prompt_mask_dev && P > 0) PTTS_HIP(hipMemcpy2DAsync(pm, (size_t)e->max_prompt * 4, prompt_mask_dev, (size_t)P * 4, (size_t)P * 4, n, hipMemcpyDeviceToDevice, st));
-  else hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, pm, 1, (size_t)n * e->max_prompt);
-  PTTS_HIP(hipMemcpyAsync(e->qc, enc_dev, (size_t)n * N * H * 4, hipMemcpyDeviceToDevice, st));
-  if (P > 0) PTTS_HIP(hipMemcpyAsync(e->ffn, prompt_dev, (size_t)n * P * H * 4, hipMemcpyDeviceToDevice, st));
-  float* h_one = e->h_adm;
-  e->h_adm = e->h_adm_rows;  // n * (P + 1) residual rows; the step graphs do not reference it
-  session_row_view(e, B, true);
-  e->B = n;
-  const int rc_fwd = forward_dispatch(e, true, st);
-  e->B = B;
-  session_row_view(e, B, false);
-  e->h_adm = h_one;
-  PTTS_TRY(rc_fwd);
+  PTTS_TRY(stage_inputs(e, B, n, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
+  PTTS_TRY(forward_dispatch(e, rows_view(e, B, n, e->h_adm_rows), true, st));  // n * (P + 1) residual rows; the step graphs do not reference them
   const int ru = (int)(64 * e->esize / 16);  // 16-byte units of an arena row
   for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
     const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
@@ -1469,17 +1470,12 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
     const int units = 2 * (e->nkv * a.self_u + e->nkc * a.cross_u);
     hipLaunchKernelGGL(admit_move_rows_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, a);
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return ptts_fail(PTTS_E_HIP, "admit_move_rows launch failed: %s", hipGetErrorString(err));
+  PTTS_TRY(launch_status("admit_move_rows"));
   for (int j = 0; j < n; ++j) {
-    const int row = rows[j];
     hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
-                       e->row_maxlen, row, 1, K, c.bos_token_id, 1, Ls[j]);
-    e->slot_busy[row] = 1; e->slot_ub[row] = P + 1; e->slot_maxlen[row] = Ls[j];
-    if (gps && gps[j]) hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, st, e->slot_gen, row, 1, SlotGen{dev_gen_of(*gps[j], Ls[j]), 1, 0});
-    if (sample) PTTS_TRY(launch_tail(e, st, true, row));
+                       e->row_maxlen, rows[j], 1, K, c.bos_token_id, 1, Ls[j]);
+    PTTS_TRY(finish_admission(e, rows[j], Ls[j], gps ? gps[j] : nullptr, sample != 0, st));
   }
-  if (!sample) e->h_ready = false;
   return PTTS_OK;
 }
 
@@ -1562,7 +1558,7 @@ extern "C" int ptts_step_forward(ptts_engine* e, void* stream) {
   PTTS_CHECK(e->prefilled, PTTS_E_INVALID, "ptts_step_forward called before ptts_prefill");
   PTTS_DEVICE(e->cfg.device);
   advance_kv(e);
-  return forward_dispatch(e, false, pick_stream(e, stream));
+  return forward_dispatch(e, whole_view(e), false, pick_stream(e, stream));
 }
 
 extern "C" int ptts_logits(ptts_engine* e, float** logits_dev) {

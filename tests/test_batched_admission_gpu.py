@@ -13,6 +13,7 @@ Shapes: the pool of tests/test_continuous_batching_gpu.py (cases.batch_case(20),
 engines of 12 slots + 4 spare rows (MFMA-strip step) and 3 slots + 2 spare rows (max_batch 5, the class of up to 8 utterances). Into the 2
 spare rows of the small engine a group has at most 2 requests (3 would be PTTS_E_CAPACITY, which the refusal test pins), so its groups are
 [2, 0] - unsorted, slot 0 and the last slot - and [1]."""
+import ctypes
 import functools
 
 import numpy as np
@@ -25,6 +26,7 @@ import slot_gen_cases as GC
 import test_continuous_batching_gpu as TB
 from helpers import make_engine
 from oracle import decoder_oracle as DO
+from parler_tts_amd import _native
 
 pytestmark = pytest.mark.gpu
 
@@ -330,6 +332,57 @@ def test_refusals_admit_nothing():
         assert refs[r].min_margin >= C.MARGIN
         assert torch.equal(eng.row_ids(s, cur[s]).cpu(), refs[r].sequences), (s, r)
     eng.close()
+
+
+def _engine_addresses(eng):
+    """The device addresses behind ptts_logits, ptts_ids and ptts_debug_hidden."""
+    logits, hidden, rows = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
+    _native.check(eng.lib.ptts_logits(eng._h, ctypes.byref(logits)), "ptts_logits")
+    _native.check(eng.lib.ptts_debug_hidden(eng._h, ctypes.byref(hidden), ctypes.byref(rows)), "ptts_debug_hidden")
+    return logits.value, eng.ids_buffer()[0], hidden.value
+
+
+def test_the_engine_does_not_move():
+    """An admission runs its prefill on a view of the engine, and no call - accepted or refused - leaves the engine itself aimed anywhere else:
+    the addresses behind ptts_logits, ptts_ids and ptts_debug_hidden are the same after session begin, admit_row, admit_rows of 2, refused
+    group and single admissions, retire_row and decode_steps, and the live slots end on the ids of the same sequence without the refused calls.
+    The capacity refusal (3 requests into 2 spare rows) comes right after session begin: the per-entry checks run before it and a 3-slot
+    session has three distinct idle slots only then; after the admissions the same group of 3 is refused on its busy slots instead."""
+    pool = TB._pool()
+    spec, sd = pool[0], pool[1]
+    slots, spare = 3, 2
+
+    def run(refusals):
+        eng = make_engine(spec, sd, torch.float32, max_batch=slots + spare)
+        eng.set_gen_params(max_length=20, min_new_tokens=19)
+        where = _engine_addresses(eng)
+        assert all(where)
+
+        def call(what, fn, refused=None):
+            if refused is None:
+                fn()
+            elif refusals:
+                with pytest.raises(ValueError, match=refused):
+                    fn()
+            assert _engine_addresses(eng) == where, what
+
+        call("begin_session", lambda: eng.begin_session(slots, N_ENC, N_PROMPT))
+        call("admit_rows of 3, refused", lambda: _admit_rows(eng, [0, 1, 2], pool, [1, 2, 3]), refused="spare rows")
+        call("admit_row", lambda: TB._admit(eng, 1, pool, 0))
+        call("admit_rows of 2", lambda: _admit_rows(eng, [2, 0], pool, [1, 2]))
+        call("admit_rows of 3 into busy slots, refused", lambda: _admit_rows(eng, [0, 1, 2], pool, [1, 2, 3]), refused="still holds a request")
+        call("admit_row into a busy slot, refused", lambda: TB._admit(eng, 1, pool, 3), refused="still holds a request")
+        call("retire_row", lambda: eng.retire_row(1))
+        call("decode_steps", lambda: eng.decode_steps(3))
+        cur, live = eng.row_state()
+        ids = [eng.row_ids(s, cur[s]).cpu() for s in (0, 2)]
+        eng.close()
+        return cur, live, ids
+
+    cur_a, live_a, ids_a = run(True)
+    cur_b, live_b, ids_b = run(False)
+    assert cur_a == cur_b == [5, 1, 5] and live_a == live_b == [True, False, True]
+    assert all(torch.equal(a, b) for a, b in zip(ids_a, ids_b))
 
 
 # ---- end to end: ContinuousBatcher(admit_batch=4) on the tiny model ---------------------------------------------------------------------
