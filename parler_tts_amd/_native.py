@@ -115,6 +115,13 @@ SESSION_SYMBOLS = {
     "ptts_admit_rows": (C.c_int, [_VP, _I32, C.POINTER(_I32), _VP, _VP, _VP, _VP, C.POINTER(_I32), _I32, C.POINTER(C.POINTER(PttsGenParams)), _VP]),
 }
 
+# include/ptts_session_kv8.h, additive likewise: sessions on the e4m3 self-attention cache, and a view of the self K/V arena
+SESSION_KV8_SYMBOLS = {
+    "ptts_session_begin_kv8": (C.c_int, [_VP, _I32, _I32, _I32, _VP]),
+    "ptts_debug_self_kv": (C.c_int, [_VP, _I32, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32),
+                                      C.POINTER(_I32)]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -136,7 +143,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib = C.CDLL(p)
     except OSError as e:  # e.g. libamdhip64 missing
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
-    for name, (res, args) in list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -57,7 +57,11 @@ class ContinuousBatcher:
     ``admit_batch`` (default 1: one ``ptts_admit_row`` per request): with N > 1, the requests that find an idle slot at the same poll are
     admitted in groups of up to N through one prefill pass each (``ptts_admit_rows``). The engine is then created with that many spare rows
     behind the slots (``spare_rows``: clamped to the batch-size class of ``slots``; fewer than 2 left = single admissions). A request admitted
-    in a group is within the engine's tolerance of the reference, not bit-identical to the same request admitted alone."""
+    in a group is within the engine's tolerance of the reference, not bit-identical to the same request admitted alone.
+
+    A model with ``enable_fp8_kv_cache()`` runs the session on the e4m3 self-attention cache whenever the engine holds more than 8 rows
+    (slots + spare; ``ptts_session_begin_kv8``), half the self-attention arena per slot; with 8 rows or fewer it keeps the bf16 cache, as
+    ``generate()`` does. There is no argument for it here: the model's switch is the opt-in, and ``self.eng.kv_fp8`` says which cache runs."""
 
     def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16,
                  stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, admit_batch: int = 1, **generation_kwargs):
@@ -107,7 +111,10 @@ class ContinuousBatcher:
         self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length)
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
-        self.eng.begin_session(self.slots, self.N, self.P)
+        if getattr(self.eng, "kv_fp8", False):  # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
+            self.eng.begin_session(self.slots, self.N, self.P, kv_fp8=True)
+        else:
+            self.eng.begin_session(self.slots, self.N, self.P)
         # what a request's own record starts from (submit): the session's values as the caller gave them (top_k is not zeroed for a greedy session)
         self._gen = dict(min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0), top_k=int(gc.top_k or 0),
                          top_p=float(gc.top_p if gc.top_p is not None else 1.0))

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ptts_common.h"
+#include "../../include/ptts_session_kv8.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
 #include "ptts_strip_w8.h"
@@ -130,6 +131,7 @@ struct ptts_engine {
   KvLayer* kv_layers_rows = nullptr;     // [max_batch][layers] operands of the batched cross K/V projection with each slot's arena rows as base
   float* h_adm_rows = nullptr;           // [(max_batch - 1) * max_prompt][H] residual rows of a group prefill (ptts_admit_rows), allocated at its first use
   AdmitMoveLayer* move_layers = nullptr; // [layers] arena bases of admit_move_rows_kernel, written with h_adm_rows
+  AdmitScaleLayer* move_scales = nullptr; // [layers] kv_fp8 engines: scale arrays of admit_move_scales_kernel, written with h_adm_rows
   std::vector<char> slot_busy;           // host: admitted and not yet retired
   std::vector<int> slot_ub, slot_maxlen; // host: upper bound of the slot's self-KV positions (P + 1 + steps since admission), its max_length
 #ifdef PTTS_TIMING
@@ -165,7 +167,8 @@ struct FwdView {
   long long* ids;
   int *cur_len, *unfinished, *has_eos, *first_unf, *enc_mask, *prompt_mask;
   const KvLayer* kv_layers;      // [layers] operands of the batched cross K/V projection
-  size_t self_off, cross_off;    // bytes from a layer's self / cross K/V arena to utterance 0 of this view (sessions refuse kv_fp8: the scales need none)
+  size_t self_off, cross_off;    // bytes from a layer's self / cross K/V arena to utterance 0 of this view
+  size_t scale_off;              // kv_fp8 engines: floats from a layer's K / V scale array (LayerW::ks_self, vs_self) to utterance 0 of this view
 };
 
 // the whole engine, now
@@ -186,11 +189,14 @@ FwdView rows_view(const ptts_engine* e, int row, int n, float* h) {
   v.B = n; v.h = h; v.kv_layers = e->kv_layers_rows + r * c.num_layers;
   v.ids += r * K * e->ids_ld; v.cur_len += r; v.first_unf += r; v.unfinished += r * K; v.has_eos += r * K;
   v.logits += r * K * c.vocab_size; v.enc_mask += r * c.max_enc; v.prompt_mask += r * e->max_prompt;
-  v.self_off = r * e->nkv * c.max_ctx * 64 * e->esize; v.cross_off = r * e->nkc * c.max_enc * 64 * e->esize;
+  // an e4m3 self row is 64 bytes with one scale beside it; the cross arena stays in the engine dtype
+  v.self_off = r * e->nkv * c.max_ctx * 64 * (c.kv_fp8 ? 1 : e->esize); v.cross_off = r * e->nkc * c.max_enc * 64 * e->esize;
+  v.scale_off = r * e->nkv * c.max_ctx;
   return v;
 }
 
 inline void* at(void* p, size_t off) { return static_cast<char*>(p) + off; }
+inline float* scale_at(float* p, size_t off) { return p ? p + off : nullptr; }  // null = engine-dtype cache: stays null
 
 #ifdef PTTS_TIMING  // measurement build: node number `node_` of the decode step stamps into its own 48 slots of e->dbg_stamps
 #define PTTS_DBG_STAMP(args, on_, node_) (args).dbg = (e->dbg_stamps && (on_)) ? e->dbg_stamps + (node_) * 48 : nullptr
@@ -293,7 +299,7 @@ AttnArgs self_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w,
   a.mask = v.prompt_mask; a.mask_ld = e->max_prompt;
   a.cos = c.rope ? e->rope_cos : nullptr; a.sin = c.rope ? e->rope_sin : nullptr;
   a.part = e->part; a.stats = e->stats; a.S = S; a.Q = Q; a.nheads = nh; a.H = H; a.cross = 0;
-  a.fused_append = prefill ? 0 : 1; a.scale = 1.0f / sqrtf((float)(H / nh)); a.kscale = w.ks_self; a.vscale = w.vs_self;
+  a.fused_append = prefill ? 0 : 1; a.scale = 1.0f / sqrtf((float)(H / nh)); a.kscale = scale_at(w.ks_self, v.scale_off); a.vscale = scale_at(w.vs_self, v.scale_off);
   a.direct_out = S == 1 ? e->xw : nullptr; a.out_fo = fo;
   return a;
 }
@@ -533,7 +539,7 @@ int strip_path(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStream_t
       if constexpr (sizeof(WT) == 2) {
         if (w.ks_self) {
           hipLaunchKernelGGL((kv_append_kernel<WT, true>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, k_self, v_self, c.max_ctx,
-                             Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr, w.ks_self, w.vs_self);
+                             Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr, scale_at(w.ks_self, v.scale_off), scale_at(w.vs_self, v.scale_off));
           done8 = true;
         }
       }
@@ -1329,11 +1335,13 @@ extern "C" int ptts_decode_steps(ptts_engine* e, int32_t n_steps, void* stream) 
 }
 
 // ---- continuous session ---------------------------------------------------------------------------------------------------------------
-extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream) {
+// one body behind both entry points: ptts_session_begin refuses a kv_fp8 engine (its documented behaviour), ptts_session_begin_kv8 any other
+static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool kv8_entry) {
   PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
   PTTS_TRY(ptts_weights_ready(e));
   const ptts_config& c = e->cfg;
-  PTTS_CHECK(!c.kv_fp8, PTTS_E_UNSUPPORTED, "continuous sessions do not run on the e4m3 KV cache (kv_fp8)");
+  if (kv8_entry) PTTS_CHECK(c.kv_fp8, PTTS_E_INVALID, "ptts_session_begin_kv8: the engine was created without kv_fp8 (its entry point is ptts_session_begin)");
+  else PTTS_CHECK(!c.kv_fp8, PTTS_E_UNSUPPORTED, "continuous sessions do not run on the e4m3 KV cache (kv_fp8)");
   PTTS_CHECK(e->pending_T == 0, PTTS_E_UNSUPPORTED, "a voice prompt is pending (ptts_set_audio_prefix): sessions take none");
   PTTS_TRY(check_call_shape(e, B, N, P, true));
   PTTS_DEVICE(c.device);
@@ -1365,6 +1373,17 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
   hipLaunchKernelGGL(fill_int_kernel, dim3(64), dim3(256), 0, st, e->prompt_mask, 1, (size_t)B * e->max_prompt);
   PTTS_HIP(hipMemsetAsync(e->h, 0, (size_t)B * H * 4, st));
   PTTS_HIP(hipMemsetAsync(e->logits, 0, (size_t)B * K * c.vocab_size * 4, st));
+  if (c.kv_fp8) {
+    // ... and the K/V rows an idle slot's step attends over: the e4m3 rows and scales of positions [0, P] of its own self arena rows, and the
+    // cross rows [0, N) (engine dtype; what a recycled allocation holds may read as NaN). The fused append of an idle or finished slot keeps
+    // rewriting its own row (position P, or where the request ended) every step: harmless, an admission rewrites rows [0, P + 1)
+    for (const LayerW& w : e->L) {
+      hipLaunchKernelGGL(kv8_zero_rows_kernel, dim3(B * e->nkv), dim3(256), 0, st, w.k_self, w.v_self, w.ks_self, w.vs_self, c.max_ctx, P + 1, 4);
+      hipLaunchKernelGGL(kv8_zero_rows_kernel, dim3(B * e->nkc), dim3(256), 0, st, w.k_cross, w.v_cross, (float*)nullptr, (float*)nullptr, c.max_enc, N,
+                         (int)(64 * e->esize / 16));
+    }
+    PTTS_TRY(launch_status("kv8_zero_rows"));
+  }
   e->kv_ub = P + 1;
   e->kv_bound = kv_bound_of(e, e->kv_ub);
   e->first_recorded = false;
@@ -1372,6 +1391,9 @@ extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t 
   e->prefilled = true;
   return PTTS_OK;
 }
+
+extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream) { return session_begin(e, B, N, P, stream, false); }
+extern "C" int ptts_session_begin_kv8(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream) { return session_begin(e, B, N, P, stream, true); }
 
 // the checks of one admission (ptts_admit_row_gen, and every entry of ptts_admit_rows); *L_out = the request's max_length
 static int check_admission(const ptts_engine* e, int row, const float* prompt_dev, int max_length, const ptts_gen_params* gp, int* L_out) {
@@ -1449,6 +1471,12 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
     for (int l = 0; l < c.num_layers; ++l) ml[l] = AdmitMoveLayer{e->L[l].k_self, e->L[l].v_self, e->L[l].k_cross, e->L[l].v_cross};
     PTTS_TRY(e->alloc(&e->move_layers, (size_t)c.num_layers));
     PTTS_HIP(hipMemcpy(e->move_layers, ml.data(), ml.size() * sizeof(AdmitMoveLayer), hipMemcpyHostToDevice));
+    if (c.kv_fp8) {
+      std::vector<AdmitScaleLayer> sl(c.num_layers);
+      for (int l = 0; l < c.num_layers; ++l) sl[l] = AdmitScaleLayer{e->L[l].ks_self, e->L[l].vs_self};
+      PTTS_TRY(e->alloc(&e->move_scales, (size_t)c.num_layers));
+      PTTS_HIP(hipMemcpy(e->move_scales, sl.data(), sl.size() * sizeof(AdmitScaleLayer), hipMemcpyHostToDevice));
+    }
     PTTS_TRY(e->alloc(&e->h_adm_rows, (size_t)(c.max_batch - 1) * e->max_prompt * H));
   }
   // the spare rows as ptts_prefill prepares a batch of n: sampler state (the prefill's embedding reads the BOS column and the clock), masks, staging
@@ -1456,19 +1484,25 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
                      e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
   PTTS_TRY(stage_inputs(e, B, n, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
   PTTS_TRY(forward_dispatch(e, rows_view(e, B, n, e->h_adm_rows), true, st));  // n * (P + 1) residual rows; the step graphs do not reference them
-  const int ru = (int)(64 * e->esize / 16);  // 16-byte units of an arena row
+  const int ru = (int)(64 * e->esize / 16), sru = c.kv_fp8 ? 4 : ru;  // 16-byte units of an arena row: engine dtype; self rows (e4m3: 64 bytes)
   for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
     const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
     AdmitMoveArgs a = {};
     a.layers = e->move_layers; a.logits = e->logits; a.enc_mask = e->enc_mask; a.prompt_mask = e->prompt_mask;
     a.src0 = B + j0; a.nlayers = c.num_layers; a.nkv = e->nkv; a.nkc = e->nkc;
-    a.self_u = (P + 1) * ru; a.self_cap_u = c.max_ctx * ru; a.cross_u = N * ru; a.cross_cap_u = c.max_enc * ru;
+    a.self_u = (P + 1) * sru; a.self_cap_u = c.max_ctx * sru; a.cross_u = N * ru; a.cross_cap_u = c.max_enc * ru;
     a.logit_u = K * c.vocab_size / 4;
     a.enc_n = enc_mask_dev ? N : c.max_enc; a.enc_ld = c.max_enc;  // what ptts_admit_row writes of each mask row
     a.prompt_n = (prompt_mask_dev && P > 0) ? P : e->max_prompt; a.prompt_ld = e->max_prompt;
     for (int j = 0; j < nj; ++j) a.rows[j] = rows[j0 + j];
     const int units = 2 * (e->nkv * a.self_u + e->nkc * a.cross_u);
     hipLaunchKernelGGL(admit_move_rows_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, a);
+    if (c.kv_fp8) {  // the rows' scales travel with them
+      AdmitScaleArgs sa = {};
+      sa.layers = e->move_scales; sa.src0 = B + j0; sa.nkv = e->nkv; sa.n = P + 1; sa.cap = c.max_ctx;
+      for (int j = 0; j < nj; ++j) sa.rows[j] = rows[j0 + j];
+      hipLaunchKernelGGL(admit_move_scales_kernel, dim3(1, c.num_layers, nj), dim3(256), 0, st, sa);
+    }
   }
   PTTS_TRY(launch_status("admit_move_rows"));
   for (int j = 0; j < n; ++j) {
@@ -1599,6 +1633,16 @@ extern "C" int ptts_debug_stamps(ptts_engine* e, long long** stamps_dev, int32_t
 extern "C" int ptts_debug_graph_nodes(ptts_engine* e, int32_t* nodes) {
   PTTS_CHECK(e && nodes, PTTS_E_INVALID, "null argument");
   *nodes = e->last_graph_nodes;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_debug_self_kv(ptts_engine* e, int32_t layer, void** k_dev, void** v_dev, float** kscale_dev, float** vscale_dev, int32_t* row_bytes,
+                                  int32_t* kv_heads, int32_t* cap) {
+  PTTS_CHECK(e && k_dev && v_dev && kscale_dev && vscale_dev && row_bytes && kv_heads && cap, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(layer >= 0 && layer < e->cfg.num_layers, PTTS_E_INVALID, "layer %d outside the engine's %d layers", layer, e->cfg.num_layers);
+  const LayerW& w = e->L[layer];
+  *k_dev = w.k_self; *v_dev = w.v_self; *kscale_dev = w.ks_self; *vscale_dev = w.vs_self;
+  *row_bytes = (int32_t)(64 * (e->cfg.kv_fp8 ? 1 : e->esize)); *kv_heads = e->nkv; *cap = e->cfg.max_ctx;
   return PTTS_OK;
 }
 

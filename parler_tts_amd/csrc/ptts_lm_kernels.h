@@ -2985,3 +2985,35 @@ static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveAr
     base[(dst * heads + head) * cap + off] = base[(src * heads + head) * cap + off];
   }
 }
+
+// kv_fp8 engines, beside admit_move_rows_kernel (which moves the 64-byte e4m3 self rows as 4 units each): the P + 1 K scales and V scales per
+// (layer, K/V head) from spare row src0 + j to slot rows[j]. P + 1 floats are in general no multiple of 16 bytes: one float per thread.
+// grid (1, layers, n). AdmitScaleArgs::layers: [nlayers] device memory, written once.
+struct AdmitScaleLayer { float *ks_self, *vs_self; };  // one layer's scale arrays (slot 0)
+struct AdmitScaleArgs {
+  const AdmitScaleLayer* layers;
+  int src0, nkv, n, cap;  // first spare row; K/V heads; scales to move per head (P + 1); scales per head (max_ctx)
+  int rows[ADMIT_ROWS_MAX];
+};
+static __global__ void __launch_bounds__(256) admit_move_scales_kernel(AdmitScaleArgs a) {
+  const size_t src = (size_t)(a.src0 + (int)blockIdx.z), dst = (size_t)a.rows[blockIdx.z];
+  const AdmitScaleLayer L = a.layers[blockIdx.y];
+  const int per = a.nkv * a.n;
+  for (int u = threadIdx.x; u < 2 * per; u += 256) {
+    const int v = u >= per, r = u - v * per, head = r / a.n, off = r - head * a.n;
+    float* base = v ? L.vs_self : L.ks_self;
+    base[(dst * a.nkv + head) * a.cap + off] = base[(src * a.nkv + head) * a.cap + off];
+  }
+}
+
+// kv_fp8 engines at session begin: positions [0, n) of every (slot, K/V head) of one layer's K and V cache to zero, rows of row_u 16-byte
+// units, and (self cache: kscale / vscale not null) their scales - an idle slot's discarded step attends over positions [0, P] of its own
+// self rows and [0, N) of its cross rows, and neither uninitialised scales nor the e4m3 bytes 0x7f / 0xff (NaN) nor whatever bf16 patterns a
+// recycled allocation holds are defined values. grid (slots * kv_heads).
+static __global__ void __launch_bounds__(256) kv8_zero_rows_kernel(void* kcache, void* vcache, float* kscale, float* vscale, int cap, int n, int row_u) {
+  const size_t row0 = (size_t)blockIdx.x * cap;
+  uint4 *k = reinterpret_cast<uint4*>(kcache) + row0 * row_u, *v = reinterpret_cast<uint4*>(vcache) + row0 * row_u;
+  for (int u = threadIdx.x; u < n * row_u; u += 256) { k[u] = uint4{0, 0, 0, 0}; v[u] = uint4{0, 0, 0, 0}; }
+  if (kscale)
+    for (int i = threadIdx.x; i < n; i += 256) { kscale[row0 + i] = 0.f; vscale[row0 + i] = 0.f; }
+}

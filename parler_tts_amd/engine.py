@@ -234,12 +234,31 @@ class DecoderEngine:
         self._keep2 = (tk, fn)
 
     # -- continuous batching (ptts_session_begin / ptts_admit_row / ptts_row_state / ptts_retire_row) -------------
-    def begin_session(self, slots: int, enc_width: int, prompt_width: int):
+    def begin_session(self, slots: int, enc_width: int, prompt_width: int, kv_fp8: bool = False):
         """Opens a continuous session: ``slots`` utterance slots, all idle; every request is padded to ``enc_width`` description and
         ``prompt_width`` prompt positions. Generation parameters are those of the last ``set_gen_params``, for every request that brings
-        none of its own (``admit_row(..., gen=...)``)."""
-        N.check(self.lib.ptts_session_begin(self._h, int(slots), int(enc_width), int(prompt_width), _stream_ptr(device=self.device)), "ptts_session_begin")
+        none of its own (``admit_row(..., gen=...)``).
+        ``kv_fp8=True`` opens it on an engine created with ``kv_fp8`` (``ptts_session_begin_kv8``; a ``ValueError`` on any other engine);
+        the default (``ptts_session_begin``) refuses such an engine with ``NotImplementedError``. The session is the same either way."""
+        if kv_fp8:
+            N.check(self.lib.ptts_session_begin_kv8(self._h, int(slots), int(enc_width), int(prompt_width), _stream_ptr(device=self.device)),
+                    "ptts_session_begin_kv8")
+        else:
+            N.check(self.lib.ptts_session_begin(self._h, int(slots), int(enc_width), int(prompt_width), _stream_ptr(device=self.device)), "ptts_session_begin")
         self.B, self.P, self.session_N = int(slots), int(prompt_width), int(enc_width)
+
+    def self_kv(self, layer: int):
+        """Copies of one layer's self-attention K/V arena (``ptts_debug_self_kv``; for tests): ``(k, v, kscale, vscale)``. ``k`` / ``v``
+        uint8 [max_batch, kv_heads, max_ctx, row_bytes] - 64 e4m3 bytes per row on a ``kv_fp8`` engine, else the 64 engine-dtype values
+        of the row as bytes; ``kscale`` / ``vscale`` float32 [max_batch, kv_heads, max_ctx] on a ``kv_fp8`` engine, else ``None``."""
+        k, v, ks, vs = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rb, nkv, cap = C.c_int32(), C.c_int32(), C.c_int32()
+        N.check(self.lib.ptts_debug_self_kv(self._h, int(layer), C.byref(k), C.byref(v), C.byref(ks), C.byref(vs), C.byref(rb), C.byref(nkv),
+                                            C.byref(cap)), "ptts_debug_self_kv")
+        shape = (self.cfg.max_batch, nkv.value, cap.value)
+        rows = [self._copy_out(p.value, shape + (rb.value,), torch.uint8) for p in (k, v)]
+        scales = [self._copy_out(p.value, shape, torch.float32) if p.value else None for p in (ks, vs)]
+        return rows[0], rows[1], scales[0], scales[1]
 
     def admit_row(self, row: int, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
                   prompt_mask: Optional[torch.Tensor], max_length: int = 0, sample: bool = True, gen: Optional[dict] = None):

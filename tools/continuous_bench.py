@@ -2,7 +2,7 @@
 """Continuous batching against static batching on a request stream of mixed lengths (Mini-v1 shapes, bf16, synthetic weights).
 
   python tools/continuous_bench.py [--repeats 5] [--static-only] [--per-request] [--stream [--stream-chunks 43,86]]
-                                   [--admit-batch 4,8 [--slots 64] [--burst-only]] [--out FILE]
+                                   [--admit-batch 4,8 [--slots 64] [--burst-only]] [--kv8 [--slots 32,64,128] [--cache bf16|kv8]] [--out FILE]
 
 256 requests whose lengths come from a fixed seeded list (uniform 150..860 frames, set through per-request max_new_tokens; EOS is blocked,
 so lengths are exact), 32 slots. Reports
@@ -31,7 +31,14 @@ each phase) and the groups formed, and
                  ptts_admit_row
   (u) burst    : wall time from the first admission of a full session until every slot holds its first token, with one ptts_row_state after the
                  admissions - in groups of n, and one by one (n = 1)
---burst-only runs (g) and (u) alone (a short run, e.g. under a kernel trace)."""
+--burst-only runs (g) and (u) alone (a short run, e.g. under a kernel trace).
+
+--kv8 measures the session on the e4m3 self-attention cache (model.enable_fp8_kv_cache(): ptts_session_begin_kv8) instead of (a), (d), (e): per
+slot count of --slots (a comma list here, e.g. 32,64,128) first the bf16-cache session, then the kv8 session, each after its own warm run (the
+model keeps ONE decoder engine per cache mode, so the two cannot alternate inside a process; alternate processes with --cache bf16 / --cache kv8
+for that), and every figure of the kv8 session beside the bf16-cache figure of the same run (--kv8-aggregate LABEL=FILE ... then gives medians with
+min .. max over the saved reports of such processes): (b) audio-s/s on the request list, (d) the step
+time with every slot live, (e) one admission and (g) one ptts_admit_rows of 8 beside the other live slots, and the K/V arena bytes per slot."""
 import argparse
 import ctypes as C
 import json
@@ -121,7 +128,7 @@ def run_batcher(model, desc, prompt, frames, per_request=False, admit_batch=1):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert [got[t] for t in tickets] == [f * 512 for f in frames], "the batcher returned other lengths than were asked for"
-    return dt, t_submit
+    return dt, t_submit, cb.eng
 
 
 def _quantiles(xs):
@@ -279,10 +286,15 @@ def step_static(model, enc, pr, ev):
     return ev.ms(lambda: eng.decode_steps(TIMED_STEPS)) / TIMED_STEPS
 
 
+def begin_session(eng):
+    """The session of SLOTS slots on whichever self-attention cache the engine was created with."""
+    eng.begin_session(SLOTS, bench.N_DESC, bench.N_PROMPT, **({"kv_fp8": True} if eng.kv_fp8 else {}))
+
+
 def step_session(model, enc, pr, ev, live):
     eng = model._get_engine(SLOTS, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1)
     eng.set_gen_params(max_length=bench.NEW_TOKENS + 1, min_new_tokens=bench.NEW_TOKENS)
-    eng.begin_session(SLOTS, bench.N_DESC, bench.N_PROMPT)
+    begin_session(eng)
     for s in range(live):
         eng.admit_row(s, enc[s], None, pr[s], None)
     eng.decode_steps(WARM_STEPS)
@@ -301,7 +313,7 @@ def group_admission(model, enc, pr, ev, n):
     spare = P.ContinuousBatcher.spare_rows(SLOTS, n)
     eng = model._get_engine(SLOTS + spare, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1)
     eng.set_gen_params(max_length=bench.NEW_TOKENS + 1, min_new_tokens=bench.NEW_TOKENS)
-    eng.begin_session(SLOTS, bench.N_DESC, bench.N_PROMPT)
+    begin_session(eng)
     for s in range(SLOTS):
         eng.admit_row(s, enc[s], None, pr[s], None)
     eng.decode_steps(WARM_STEPS)
@@ -325,7 +337,7 @@ def burst(model, enc, pr, n):
     spare = P.ContinuousBatcher.spare_rows(SLOTS, n)
     eng = model._get_engine(SLOTS + spare, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1)
     eng.set_gen_params(max_length=bench.NEW_TOKENS + 1, min_new_tokens=bench.NEW_TOKENS)
-    eng.begin_session(SLOTS, bench.N_DESC, bench.N_PROMPT)
+    begin_session(eng)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if spare:
@@ -384,6 +396,93 @@ def admit_batch_report(model, desc, prompt, frames, audio_s, sizes, repeats, bur
     return res
 
 
+def arena_bytes_per_slot(eng):
+    """(self, cross) K/V arena bytes one slot owns: e4m3 self rows are 64 bytes + one fp32 scale, the cross arena stays in the engine dtype."""
+    c = eng.cfg
+    nkv, nkc = c.num_kv_heads or c.num_heads, c.num_cross_kv_heads or c.num_heads
+    return c.num_layers * 2 * nkv * c.max_ctx * (64 + 4 if eng.kv_fp8 else 128), c.num_layers * 2 * nkc * c.max_enc * 128
+
+
+def kv8_report(model, desc, prompt, frames, audio_s, slot_counts, caches, repeats, say):
+    res = {}
+    enc = model._encode_description(desc[:max(slot_counts) + 8], None).float()
+    pr = model.embed_prompts(prompt[:max(slot_counts) + 8]).float()
+    ev = Events()
+    for slots in slot_counts:
+        globals()["SLOTS"] = slots
+        got = {}
+        for cache in caches:
+            model.enable_fp8_kv_cache(cache == "kv8")  # drops the other mode's engine: everything below is warmed again
+            run_batcher(model, desc, prompt, frames)
+            runs = []
+            for _ in range(repeats):
+                dt, _, eng = run_batcher(model, desc, prompt, frames)  # eng: the engine the batcher's session ran on
+                assert eng.kv_fp8 == (cache == "kv8"), "the batcher ran on the other cache"
+                runs.append(dt)
+            arena, max_ctx = arena_bytes_per_slot(eng), eng.cfg.max_ctx
+            steps, adm, grp = [], [], []
+            for r in range(repeats + 1):  # the first round warms the step graphs of these contexts and the prefill kernels of these row counts
+                y, ad = step_session(model, enc, pr, ev, slots)
+                if r:
+                    steps.append(y); adm.append(ad)
+            for r in range(repeats + 1):
+                spare, g, one = group_admission(model, enc, pr, ev, 8)
+                if r:
+                    grp.append(g)
+            m, lo, hi = med_spread(runs)
+            got[cache] = {"s": m, "audio_s_per_s": audio_s / m, "step_us": statistics.median(steps) * 1e3, "admit_ms": statistics.median(adm),
+                          "admit_rows8_ms": statistics.median(grp), "self_arena_bytes_per_slot": arena[0], "cross_arena_bytes_per_slot": arena[1]}
+            of = f"median of {repeats} runs {m:.3f} s" if repeats > 1 else f"one run {m:.3f} s"
+            spread = f" (spread {audio_s / hi:.1f} .. {audio_s / lo:.1f})" if repeats > 1 else ""
+            say(f"[{slots} slots, {cache} cache] (b) {of} = {audio_s / m:.1f} audio-s/s{spread}; "
+                f"(d) step, every slot live, context ~235..435: {got[cache]['step_us']:.1f} us; (e) one admission beside {slots - 1} live slots "
+                f"{got[cache]['admit_ms']:.3f} ms; (g) one ptts_admit_rows of {spare} beside {slots - spare} live slots {got[cache]['admit_rows8_ms']:.3f} ms; "
+                f"arena per slot at max_ctx {max_ctx}: self {arena[0] / 2 ** 20:.2f} MiB + cross {arena[1] / 2 ** 20:.2f} MiB")
+        if len(got) == 2:
+            a, b = got["bf16"], got["kv8"]
+            say(f"[{slots} slots] kv8 / bf16 cache: audio-s/s {b['audio_s_per_s'] / a['audio_s_per_s']:.3f}, step {b['step_us'] / a['step_us']:.3f}, admission "
+                f"{b['admit_ms'] / a['admit_ms']:.3f}, admit_rows of 8 {b['admit_rows8_ms'] / a['admit_rows8_ms']:.3f}, self arena "
+                f"{b['self_arena_bytes_per_slot'] / a['self_arena_bytes_per_slot']:.3f}")
+        res[str(slots)] = got
+    model.enable_fp8_kv_cache(False)
+    return res
+
+
+KV8_LINE = (r"\[(\d+) slots, (\w+) cache\] \(b\) .*? = ([\d.]+) audio-s/s.*?context ~235\.\.435: ([\d.]+) us; \(e\) one admission beside \d+ live slots "
+            r"([\d.]+) ms; \(g\) one ptts_admit_rows of \d+ beside \d+ live slots ([\d.]+) ms; arena per slot at max_ctx \d+: self ([\d.]+) MiB")
+
+
+def kv8_aggregate(specs):
+    """--kv8-aggregate LABEL=FILE ...: the per-process reports of --kv8 --cache X (several processes per label), as medians with min .. max per
+    label and slot count. No GPU needed: it reads what the processes printed."""
+    import re
+
+    data, labels = {}, []
+    for spec in specs:
+        label, path = spec.split("=", 1)
+        if label not in labels:
+            labels.append(label)
+        for m in re.finditer(KV8_LINE, open(path).read()):
+            data.setdefault((label, int(m.group(1))), []).append([float(x) for x in m.groups()[2:]])
+    names = (("audio-s/s", "{:.1f}"), ("step us", "{:.1f}"), ("admission ms", "{:.3f}"), ("admit_rows of 8 ms", "{:.3f}"), ("self arena MiB per slot", "{:.2f}"))
+    for slots in sorted({s for _, s in data}):
+        for label in labels:
+            v = data.get((label, slots))
+            if not v:
+                continue
+            cols = []
+            for j, (name, fmt) in enumerate(names):
+                xs = [x[j] for x in v]
+                cols.append(f"{name} {fmt.format(statistics.median(xs))} ({fmt.format(min(xs))} .. {fmt.format(max(xs))})")
+            print(f"[{slots} slots, {label}] {len(v)} processes: median (min .. max): " + "; ".join(cols))
+        base = data.get((labels[0], slots))
+        for label in labels[1:]:
+            v = data.get((label, slots))
+            if base and v:
+                r = [statistics.median(x[j] for x in v) / statistics.median(x[j] for x in base) for j in range(4)]
+                print(f"[{slots} slots] {label} / {labels[0]}: audio-s/s {r[0]:.3f}, step {r[1]:.3f}, admission {r[2]:.3f}, admit_rows of 8 {r[3]:.3f}")
+
+
 def med_spread(xs):
     return statistics.median(xs), min(xs), max(xs)
 
@@ -396,14 +495,22 @@ def main():
     ap.add_argument("--stream", action="store_true", help="measure the streaming mode against (b) instead of (a), (d), (e)")
     ap.add_argument("--stream-chunks", default="43,86", help="stream_chunk_frames values to measure")
     ap.add_argument("--admit-batch", default=None, help="admit_batch values to measure against single admissions, e.g. 4,8")
-    ap.add_argument("--slots", type=int, default=SLOTS, help="slots of the session (with --admit-batch)")
+    ap.add_argument("--slots", default=str(SLOTS), help="slots of the session (with --admit-batch; with --kv8 a comma list, e.g. 32,64,128)")
+    ap.add_argument("--kv8", action="store_true", help="measure the session on the e4m3 self-attention cache beside the bf16-cache session")
+    ap.add_argument("--cache", default="both", choices=["both", "bf16", "kv8"], help="with --kv8: one side only (for alternating processes)")
     ap.add_argument("--burst-only", action="store_true", help="with --admit-batch: only the session start and the group admission")
+    ap.add_argument("--kv8-aggregate", nargs="+", default=None, metavar="LABEL=FILE",
+                    help="no measurement: medians (min .. max) per label over the saved reports of several --kv8 --cache X processes")
     ap.add_argument("--out", default=None, help="also append the report to this file")
     a = ap.parse_args()
-    if a.slots != SLOTS:
-        if not a.admit_batch:
-            ap.error("--slots goes with --admit-batch")
-        globals()["SLOTS"] = a.slots
+    if a.kv8_aggregate:
+        kv8_aggregate(a.kv8_aggregate)
+        return
+    slot_counts = [int(n) for n in a.slots.split(",")]
+    if slot_counts != [SLOTS]:
+        if not (a.admit_batch or a.kv8) or (len(slot_counts) > 1 and not a.kv8):
+            ap.error("--slots goes with --admit-batch (one value) or --kv8 (a list)")
+        globals()["SLOTS"] = slot_counts[0]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     frames = request_frames()
@@ -421,6 +528,15 @@ def main():
     st_steps, cb_steps = schedule_steps(frames)
     say(f"  decode steps of the schedules themselves: static {st_steps}, FIFO slots {cb_steps} (ratio {st_steps / cb_steps:.3f}: (c) less the drain of the "
         f"last requests, when nothing is left to admit)")
+    if a.kv8:
+        with torch.no_grad():
+            res = kv8_report(model, desc, prompt, frames, audio_s, slot_counts, ["bf16", "kv8"] if a.cache == "both" else [a.cache], a.repeats, say)
+        say(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.admit_batch:
         with torch.no_grad():
             res = admit_batch_report(model, desc, prompt, frames, audio_s, [int(n) for n in a.admit_batch.split(",")], a.repeats, a.burst_only, say)
@@ -454,7 +570,7 @@ def main():
         for r in range(a.repeats):
             st.append(run_static(model, desc, prompt, frames))
             if not a.static_only:
-                dt, ts = run_batcher(model, desc, prompt, frames)
+                dt, ts, _ = run_batcher(model, desc, prompt, frames)
                 cb.append(dt); sub.append(ts)
             if per_request:
                 pr_t.append(run_batcher(model, desc, prompt, frames, per_request=True)[0])
