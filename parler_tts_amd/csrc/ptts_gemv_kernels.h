@@ -147,14 +147,16 @@ __device__ __forceinline__ void gv_attn_wave(const GemvArgs& a, const float* par
 
 // prologue wave, combine of qkv_attn_kernel's partials (single utterance): S cache splits as above + slot S = the new position, whose
 // base-2 score arrives as two half dot products (q . k over head dimensions 0-31 / 32-63, from two workgroups) and whose value row is
-// the partial itself (weight 1 before normalisation)
-template <typename WT, int NF4, int S>
-__device__ __forceinline__ void gv_attn2_wave(const GemvArgs& a, const float* part, const float* stats, char* s_x, int lane) {
-  float4 p[NF4][S + 1];
-  float2 st[NF4][S + 1];
+// the partial itself (weight 1 before normalisation).
+// The wave prepares NI slabs of 256 columns from slab i0 on: the whole row (NI = NF4, one wave per utterance), or one slab of it (NI = 1,
+// single utterance: NF4 waves, wave w takes slab w = 4 heads). A column's arithmetic does not depend on which wave holds it: bit-identical.
+template <typename WT, int NF4, int S, int NI = NF4>
+__device__ __forceinline__ void gv_attn2_wave(const GemvArgs& a, const float* part, const float* stats, char* s_x, int lane, int i0 = 0) {
+  float4 p[NI][S + 1];
+  float2 st[NI][S + 1];
 #pragma unroll
-  for (int i = 0; i < NF4; ++i) {
-    const int k = (lane + 64 * i) * 4, head = k >> 6;
+  for (int i = 0; i < NI; ++i) {
+    const int k = (lane + 64 * (i0 + i)) * 4, head = k >> 6;
 #pragma unroll
     for (int sp = 0; sp <= S; ++sp) {
       st[i][sp] = *reinterpret_cast<const float2*>(stats + ((size_t)sp * a.nheads + head) * 2);
@@ -163,7 +165,7 @@ __device__ __forceinline__ void gv_attn2_wave(const GemvArgs& a, const float* pa
   }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int i = 0; i < NF4; ++i) {
+  for (int i = 0; i < NI; ++i) {
     const float m_new = st[i][S].x + st[i][S].y;
     float mx = m_new;
 #pragma unroll
@@ -180,7 +182,7 @@ __device__ __forceinline__ void gv_attn2_wave(const GemvArgs& a, const float* pa
     den += wn;
     o.x += wn * p[i][S].x; o.y += wn * p[i][S].y; o.z += wn * p[i][S].z; o.w += wn * p[i][S].w;
     const float inv = __frcp_rn(den);  // den >= the weight of the larger of (cache maximum, new position) = 1
-    gv_lds_store4<WT>(s_x, (lane + 64 * i) * 4, o.x * inv, o.y * inv, o.z * inv, o.w * inv);
+    gv_lds_store4<WT>(s_x, (lane + 64 * (i0 + i)) * 4, o.x * inv, o.y * inv, o.z * inv, o.w * inv);
   }
 }
 
@@ -251,18 +253,24 @@ __device__ __forceinline__ void gv_softmax_wave(const GemvArgs& a, char* s_x, in
   }
 }
 
+// Prologue waves of an instance: none (GV_COPY); one per 256 columns of the single row (nf4 = K / 256) for GV_LNP and for the single-utterance
+// combine GV_ATTN2 (one wave issued (S + 1) * nf4 float4 + as many float2 loads per lane in front of the barrier the four weight waves wait at);
+// one per utterance otherwise.
+template <int PRO, int MB>
+constexpr int gv_prologue_waves(int nf4) { return PRO == GV_COPY ? 0 : ((PRO == GV_LNP || (PRO == GV_ATTN2 && MB == 1)) ? nf4 : MB); }
+
 // NCH = chunks per lane per row (K = NCH * 64 * EPL), R = weight rows per wave, S = KV splits (GV_ATTN), MB = utterances the
 // instance is built for (1, 4 or GV_MAX_ROWS = 8; a.M <= MB of them are live), W8 = e4m3 weights + per-row scale.
 // MB = 8 (batch 5..8): the activation chunks of MG utterances sit in registers at a time (MG * NCH <= 40 vectors), the wave's weight
 // registers are reused for every group; groups past the live batch are skipped (workgroup-uniform).
 template <typename WT, int NCH, int R, int PRO, int EPI, int S, int MB, bool W8, bool STG = false>
-__global__ void __launch_bounds__(((PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * Elem<WT>::EPL / 4 : MB)) + 4) * 64) gemv_kernel(PTTS_KPARAMS(GemvArgs)) {
+__global__ void __launch_bounds__((gv_prologue_waves<PRO, MB>(NCH * Elem<WT>::EPL / 4) + 4) * 64) gemv_kernel(PTTS_KPARAMS(GemvArgs)) {
   PTTS_KJOIN(GemvArgs, a)
   static_assert(!STG || (PRO == GV_COPY && MB == 8), "staged activation rows: GV_COPY nodes of the 5..8-utterance instances only");
   constexpr bool HASPRO = PRO != GV_COPY;
   constexpr int EPL = Elem<WT>::EPL;
   constexpr int NF4 = NCH * EPL / 4;  // float4 per lane of one fp32 row (K / 256)
-  constexpr int NPW = PRO == GV_LNP ? NF4 : (HASPRO ? MB : 0);  // prologue waves (GV_LNP: one per 256 columns of the single row)
+  constexpr int NPW = gv_prologue_waves<PRO, MB>(NF4);
   static_assert(PRO != GV_LNP || MB == 1, "GV_LNP: single utterance");
   __shared__ float s_st[PRO == GV_LNP ? 2 * NF4 : 1];
   constexpr int MG = (MB <= 4 || MB * NCH <= 40) ? MB : ((MB / 2) * NCH <= 40 ? MB / 2 : MB / 4);  // utterances per register group
@@ -276,6 +284,8 @@ __global__ void __launch_bounds__(((PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * 
     __builtin_amdgcn_s_setprio(3);
     if constexpr (PRO == GV_LNP) {
       gv_lnp_waves<WT, NF4>(a, s_x, s_st, wave, lane);
+    } else if constexpr (PRO == GV_ATTN2 && NPW == NF4 && MB == 1) {
+      gv_attn2_wave<WT, NF4, S, 1>(a, a.part, a.stats, s_x, lane, wave);  // slab `wave` of the row: 4 heads, no cross-wave step
     } else if (MB == 1 || wave < a.M) {
       constexpr int KK = NF4 * 256;              // = a.K
       const size_t pw = MB == 1 ? 0 : wave;      // single utterance: no tail argument (x_ld) in front of the row's loads

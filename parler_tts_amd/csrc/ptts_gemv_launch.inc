@@ -23,7 +23,7 @@ int launch_inst(const GemvArgs& a, hipStream_t st) {
   // MB = 8 runs 12 waves per workgroup (168 VGPRs per lane): at most 4 weight rows per wave (3 with the e4m3 convert temporaries) stay spill-free
   if constexpr (R * NCH <= 40 && R <= RCAP && MB * R <= 64 && (MB < 8 || R <= (GV_W8 ? 3 : 4)) && (PRO == GV_COPY || NCH * Elem<GV_WT>::EPL <= 32)) {
     const int waves = (a.N + R - 1) / R;
-    const int npw = PRO == GV_COPY ? 0 : (PRO == GV_LNP ? NCH * Elem<GV_WT>::EPL / 4 : MB);
+    const int npw = gv_prologue_waves<PRO, MB>(NCH * Elem<GV_WT>::EPL / 4);
     const dim3 grid((waves + 3) / 4), block((npw + 4) * 64);
     const size_t sh = PRO == GV_COPY ? 0 : (size_t)MB * a.K * sizeof(GV_WT);
     if constexpr (PRO == GV_COPY && MB == 8 && MB * NCH > 40 && MB * NCH * 1024 <= 64 * 1024) {

@@ -5,7 +5,9 @@
 //
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -Iinclude tools/cabi_probe.hip -o tools/cabi_probe \
 //         -Lparler_tts_amd -lptts_hip -Wl,-rpath,'$ORIGIN/../parler_tts_amd'
-//   tools/cabi_probe lm  <batch> [large] [fp32] [fp8] [kv8] [layers=<n>] [ctx=<prompt positions>] [tag=<text>] [dump=<file> [steps=<n>]] [eager=<n>]
+//   tools/cabi_probe lm  <batch> [large] [fp32] [fp8] [kv8] [layers=<n>] [ctx=<prompt positions>] [tag=<text>] [dump=<file> [steps=<n>]] [eager=<n>] [run=<n>]
+//        run=<n>: n graph replays per reading (and at most n warm-up steps) instead of 250 (50): the three readings end at context ctx + 1 + 4 n (n <= 50), so a
+//        short run stays inside one KV-split range of the fused self-attention node (the stamp build reports the node phases of the LAST bucket)
 //        eager=<n>: only a prefill + n EAGER decode forwards (ptts_push_tokens + ptts_step_forward), no hipGraph is captured or launched:
 //        the target of `rocprofv3 --pmc ...` passes (which crash on graph replays in this image; tools/prof_eager.py without torch),
 //        e.g. `rocprofv3 --pmc FETCH_SIZE --kernel-trace -d out -- tools/cabi_probe lm 1 ctx=431 eager=24` = the bench's timed context
@@ -19,7 +21,7 @@
 // flips, first differing id): the seconds-long A/B check that a kernel variant behind an environment knob computes what the default
 // path computes, before the oracle-backed parity tests are spent on it.
 //
-// `lm` prints three readings of 250 graph replays each at growing context, like tools/step_probe2.py; `dac` prints ms per decode and
+// `lm` prints three readings of 250 (run=<n>: n) graph replays each at growing context, like tools/step_probe2.py; `dac` prints ms per decode and
 // TFLOP/s at 1.608 GFLOP per frame.
 #include <hip/hip_runtime.h>
 
@@ -133,6 +135,7 @@ static int run_lm(int argc, char** argv) {
   const int dump_steps = opt(argc, argv, "steps") ? atoi(opt(argc, argv, "steps")) : 6;
   const char* tag = opt(argc, argv, "tag") ? opt(argc, argv, "tag") : "";
   const int P = opt(argc, argv, "ctx") ? atoi(opt(argc, argv, "ctx")) : 32;
+  const int run = opt(argc, argv, "run") ? std::max(1, std::min(250, atoi(opt(argc, argv, "run")))) : 250;
   // layers=<n>: the same widths with n layers (n = 2: every weight stays in the L2s / Infinity Cache between replays, n = 8: 240 MB, Infinity
   // Cache only): per-layer step time against the 24-layer model = what cold weights cost a dependent node
   const int H = large ? 1536 : 1024, L = opt(argc, argv, "layers") ? atoi(opt(argc, argv, "layers")) : (large ? 30 : 24), F = large ? 6144 : 4096,
@@ -245,7 +248,7 @@ static int run_lm(int argc, char** argv) {
   PT(ptts_prefill(e, enc, nullptr, prompt, nullptr, B, NE, P, 1, st));
   PT(ptts_first_token_sync(e));
   const double ttft2 = now_s() - t0;
-  PT(ptts_decode_steps(e, 50, st));
+  PT(ptts_decode_steps(e, std::min(50, run), st));
   HIPCHK(hipStreamSynchronize(st));
   double us[3];
   hipEvent_t ev0, ev1;
@@ -253,12 +256,12 @@ static int run_lm(int argc, char** argv) {
   HIPCHK(hipEventCreate(&ev1));
   for (int r = 0; r < 3; ++r) {
     HIPCHK(hipEventRecord(ev0, st));
-    PT(ptts_decode_steps(e, 250, st));
+    PT(ptts_decode_steps(e, run, st));
     HIPCHK(hipEventRecord(ev1, st));
     HIPCHK(hipEventSynchronize(ev1));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-    us[r] = ms * 1e3 / 250;
+    us[r] = ms * 1e3 / run;
   }
   int32_t cur = 0, fin = 0;
   PT(ptts_state(e, &cur, &fin, st));
@@ -605,7 +608,7 @@ static int run_t5(int argc, char** argv) {
 int main(int argc, char** argv) {
   if (argc >= 4 && !strcmp(argv[1], "cmp")) return run_cmp(argv[2], argv[3]);
   if (argc < 3 || (strcmp(argv[1], "lm") && strcmp(argv[1], "dac") && strcmp(argv[1], "t5"))) {
-    fprintf(stderr, "usage: %s lm <batch> [large] [fp32] [fp8] [kv8] [ctx=<prompt positions>] [tag=<text>] [dump=<file> [steps=<n>]] [eager=<n>]\n"
+    fprintf(stderr, "usage: %s lm <batch> [large] [fp32] [fp8] [kv8] [ctx=<prompt positions>] [tag=<text>] [dump=<file> [steps=<n>]] [eager=<n>] [run=<n>]\n"
                     "       %s dac <batch> [frames=<n>] [f32] [reps=<n>] [tag=<text>] [dump=<file>]\n"
                     "       %s t5 <batch> [tokens=<n>] [layers=<n>] [fp32] [reps=<n>] [tag=<text>]\n       %s cmp <file a> <file b>\n", argv[0], argv[0], argv[0], argv[0]);
     return 1;
