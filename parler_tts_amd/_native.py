@@ -122,6 +122,12 @@ SESSION_KV8_SYMBOLS = {
                                       C.POINTER(_I32)]),
 }
 
+# include/ptts_session_voice.h, additive likewise: a request that continues a voice prompt inside a continuous session
+SESSION_VOICE_SYMBOLS = {
+    "ptts_admit_row_voice": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, C.POINTER(PttsGenParams), _VP]),
+    "ptts_debug_slot_voice": (C.c_int, [_VP, C.POINTER(_I32), _VP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -143,7 +149,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib = C.CDLL(p)
     except OSError as e:  # e.g. libamdhip64 missing
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
-    for name, (res, args) in list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items()):
+    for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
+                              + list(SESSION_VOICE_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -30,11 +30,16 @@ _VOICE_ARGUMENTS = ("input_values", "decoder_input_ids")
 
 
 class _Request:
-    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen")
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice")
 
-    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None):
+    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None):
         self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
         self.gen = gen  # the request's own sampler record (DecoderEngine.admit_row's `gen`), or None: the session's
+        self.voice = voice  # un-delayed codes [K, T >= 1] of the voice prompt the request continues (admit_row's `voice`), or None
+
+    @property
+    def T(self) -> int:
+        return 0 if self.voice is None else int(self.voice.shape[1])
 
 
 class ContinuousBatcher:
@@ -43,8 +48,8 @@ class ContinuousBatcher:
 
     ``generation_kwargs`` are ``generate()``'s: ``max_new_tokens`` / ``max_length`` (the session's limit; a request may ask for less),
     ``min_new_tokens``, ``do_sample``, ``temperature``, ``top_k``, ``top_p``: the session's values, which ``submit`` may override per request
-    (with a ``seed`` of its own, see there). Everything that needs the host loop, a streamer or a voice
-    prompt raises ``NotImplementedError``. ``poll_steps``: decode steps between two looks at the slots (each look is one host sync);
+    (with a ``seed`` of its own, see there). Everything that needs the host loop or a streamer raises ``NotImplementedError``; so does a
+    voice prompt given HERE: it belongs to a request (``submit(input_values=...)`` / ``submit(decoder_input_ids=...)``). ``poll_steps``: decode steps between two looks at the slots (each look is one host sync);
     a request that ends by its own ``max_new_tokens`` is known in advance and is met exactly.
 
     ``stream_chunk_frames`` (default ``None``: off) switches to streaming: ``chunks()`` yields ``(ticket, chunk 1-D float32, last)`` as soon as
@@ -61,12 +66,22 @@ class ContinuousBatcher:
 
     A model with ``enable_fp8_kv_cache()`` runs the session on the e4m3 self-attention cache whenever the engine holds more than 8 rows
     (slots + spare; ``ptts_session_begin_kv8``), half the self-attention arena per slot; with 8 rows or fewer it keeps the bf16 cache, as
-    ``generate()`` does. There is no argument for it here: the model's switch is the opt-in, and ``self.eng.kv_fp8`` says which cache runs."""
+    ``generate()`` does. There is no argument for it here: the model's switch is the opt-in, and ``self.eng.kv_fp8`` says which cache runs.
+
+    ``max_voice_frames`` (default 0: no request brings a voice prompt, and every call on the model and the engine is the one made without
+    this argument): the longest voice prompt, in codec frames, a request may bring. The engine's prefill is then sized for
+    ``max_prompt_tokens + 1 + max_voice_frames`` positions. A limit given as ``max_new_tokens`` counts NEW tokens, as in ``generate()``: the
+    session's ``max_length`` grows by ``max_voice_frames`` and a request with T frames gets ``max_new_tokens + 1 + T`` columns; a limit
+    given as ``max_length`` stays the total. A request with a voice prompt is admitted alone (``ptts_admit_row_voice``), also with
+    ``admit_batch > 1``, and not in streaming mode (``submit`` raises ``NotImplementedError`` there)."""
 
     def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16,
-                 stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, admit_batch: int = 1, **generation_kwargs):
+                 stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, admit_batch: int = 1, max_voice_frames: int = 0,
+                 **generation_kwargs):
         if int(admit_batch) < 1:
             raise ValueError("`admit_batch` must be >= 1")
+        if int(max_voice_frames) < 0:
+            raise ValueError("`max_voice_frames` must be >= 0")
         if slots < 1 or max_description_tokens < 1 or max_prompt_tokens < 0 or poll_steps < 1:
             raise ValueError("slots, max_description_tokens and poll_steps must be >= 1 and max_prompt_tokens >= 0")
         if stream_chunk_frames is None and stream_first_chunk_frames is not None:
@@ -79,7 +94,7 @@ class ContinuousBatcher:
             generation_kwargs.pop(name, None)
         for name in _VOICE_ARGUMENTS:
             if generation_kwargs.get(name) is not None:
-                raise NotImplementedError(f"`{name}` (voice prompt): a continuous session takes no audio prefix")
+                raise NotImplementedError(f"`{name}` (voice prompt): a continuous session takes no audio prefix of its own; give it to submit()")
             generation_kwargs.pop(name, None)
         if getattr(model, "prompt_cross_attention", False):
             raise NotImplementedError("prompt_cross_attention models: the prompt joins the cross-attention context, which a session keeps at a fixed width")
@@ -94,7 +109,10 @@ class ContinuousBatcher:
         if int(getattr(gc, "num_return_sequences", 1) or 1) != 1:
             raise NotImplementedError("num_return_sequences > 1: submit the request several times")
         self.model, self.slots, self.N, self.P, self.poll_steps = model, int(slots), int(max_description_tokens), int(max_prompt_tokens), int(poll_steps)
-        self.max_length = int(gc.max_new_tokens) + 1 if gc.max_new_tokens is not None else int(gc.max_length)
+        self.max_voice_frames = int(max_voice_frames)
+        # new tokens of a request that names no limit of its own (None: the session's limit is a total, `max_length`)
+        self._max_new = int(gc.max_new_tokens) if gc.max_new_tokens is not None else None
+        self.max_length = self._max_new + 1 + self.max_voice_frames if self._max_new is not None else int(gc.max_length)
         if self.max_length < 2:
             raise ValueError("`max_length` / `max_new_tokens` leave no room for a generated token")
         min_new = int(gc.min_new_tokens or 0)
@@ -108,7 +126,10 @@ class ContinuousBatcher:
         # admit_batch > 1: the engine carries `spare` arena rows behind the slots, where a group of requests is prefilled in one pass
         self.spare = self.spare_rows(self.slots, int(admit_batch))
         self.admissions, self.admission_groups = 0, []  # requests admitted; sizes of the groups that went through admit_rows
-        self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length)
+        if self.max_voice_frames:  # the prefill of one slot runs P + 1 + T positions
+            self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length, self.max_voice_frames)
+        else:
+            self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length)
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
         if getattr(self.eng, "kv_fp8", False):  # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
@@ -195,17 +216,27 @@ class ContinuousBatcher:
     @torch.no_grad()
     def submit(self, input_ids, attention_mask=None, prompt_input_ids=None, prompt_attention_mask=None, max_new_tokens: Optional[int] = None,
                do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
-               min_new_tokens: Optional[int] = None, seed: Optional[int] = None) -> int:
+               min_new_tokens: Optional[int] = None, seed: Optional[int] = None, input_values=None, decoder_input_ids=None) -> int:
         """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path).
         ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_new_tokens``: the request's own sampler settings; an option left ``None``
         takes the session's value. A request that sets any of them (or ``seed``) draws from its own stream ``(seed, column, codebook)``: with a
         ``seed`` it gives the same tokens in whichever slot and at whatever time it runs, with ``seed=None`` one is drawn from torch's RNG here
-        (``torch.manual_seed`` governs the run). A request that sets none is admitted on the session's parameters and draw stream."""
-        max_length = self.max_length if max_new_tokens is None else int(max_new_tokens) + 1
-        if max_length < 2:
-            raise ValueError("`max_new_tokens` leaves no room for a generated token")
-        if max_length > self.max_length:
-            raise ValueError(f"max_new_tokens {max_length - 1} exceeds the session's {self.max_length - 1}")
+        (``torch.manual_seed`` governs the run). A request that sets none is admitted on the session's parameters and draw stream.
+        ``input_values`` (a waveform [1, 1, samples], encoded on the model's own DAC encoder) or ``decoder_input_ids`` (codes [K, T], a leading
+        BOS column is dropped): the voice prompt the request continues, as ``generate()`` takes it; needs ``max_voice_frames >= T``. The
+        request's waveform contains the prompt's frames, and ``max_new_tokens`` counts what follows them."""
+        voice = self._voice(input_values, decoder_input_ids)
+        T = 0 if voice is None else int(voice.shape[1])
+        if max_new_tokens is not None:
+            max_length = int(max_new_tokens) + 1 + T
+        else:
+            max_length = self.max_length if self._max_new is None else self._max_new + 1 + T
+        if max_length < T + 2:
+            raise ValueError("`max_new_tokens` leaves no room for a generated token" if T == 0 or max_new_tokens is not None else
+                             f"a voice prompt of {T} frames leaves no room for a generated token below the session's max_length {self.max_length}")
+        room = self.max_length - 1 - T if self._max_new is None else self._max_new  # new tokens the session grants this request
+        if max_length - 1 - T > room:
+            raise ValueError(f"max_new_tokens {max_length - 1 - T} exceeds the session's {room}")
         gen = self._request_gen(do_sample, temperature, top_k, top_p, min_new_tokens, seed)
         dev = self.model.device
         ids, mask = self._pad_ids(input_ids, attention_mask, self.N, "description")
@@ -222,8 +253,30 @@ class ContinuousBatcher:
             gen["seed"] = int(torch.randint(0, 2 ** 62, (1,)).item()) if gen["do_sample"] else 0
         ticket = self._next_ticket
         self._next_ticket += 1
-        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen))
+        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice))
         return ticket
+
+    def _voice(self, input_values, decoder_input_ids) -> Optional[torch.Tensor]:
+        """The voice prompt of one request as un-delayed codes [K, T >= 1], or None: generate()'s own preparation (``input_values`` through
+        the model's DAC encoder and over ``decoder_input_ids`` when both are given, a leading BOS column dropped), then this session's limits."""
+        if input_values is None and decoder_input_ids is None:
+            return None
+        if self.chunk is not None:
+            raise NotImplementedError("a voice prompt in streaming mode: the windowed codec pass reads the slot's raw ids, which hold the delay pattern "
+                                      "behind the prompt; submit it to a batcher without `stream_chunk_frames`")
+        if input_values is not None:
+            decoder_input_ids = self.model._voice_prompt_codes(torch.as_tensor(input_values))
+        else:
+            decoder_input_ids = torch.as_tensor(decoder_input_ids)
+            if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] != self.K:
+                raise ValueError(f"decoder_input_ids: one request at a time, [{self.K} codebooks, frames]; got {tuple(decoder_input_ids.shape)}")
+        codes = self.model._voice_prompt_rows(decoder_input_ids)
+        if codes.shape[0] != self.K:
+            raise ValueError(f"voice prompt: one request at a time, [{self.K} codebooks, frames]; got {tuple(codes.shape)}")
+        T = int(codes.shape[1])
+        if T > self.max_voice_frames:
+            raise ValueError(f"voice prompt of {T} frames, the session was opened for {self.max_voice_frames} (`max_voice_frames`)")
+        return codes.contiguous() if T > 0 else None
 
     # -- scheduler ----------------------------------------------------------------------------------------------------------------
     def pending(self) -> int:
@@ -233,8 +286,10 @@ class ContinuousBatcher:
     def _admit_into(self, s: int, r: _Request):
         """The one admission of both modes. A request without a record of its own goes through the same call as ever (no `gen` keyword)."""
         kw = {} if r.gen is None else {"gen": dict(r.gen)}
+        if r.voice is not None:
+            kw["voice"] = r.voice
         self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True, **kw)
-        self._slot[s], self._cols[s] = r, 2
+        self._slot[s], self._cols[s] = r, 2 + r.T  # BOS + the given columns + the first token
         self.admissions += 1
 
     def _admit_group(self, group):
@@ -252,7 +307,8 @@ class ContinuousBatcher:
     def _admit_queued(self, admitted=None):
         """Idle slots in ascending order take the queue in FIFO order; ``admitted(slot)`` runs behind each admission. Without spare rows
         (``admit_batch=1``) every pair is one ``admit_row``; with them the pairs go in groups of at most ``spare`` through ``admit_rows``
-        (a group of one: ``admit_row``)."""
+        (a group of one: ``admit_row``). A request with a voice prompt ends the group before it and goes alone (``admit_rows`` takes none);
+        which request meets which slot does not change."""
         if not self.spare:
             for s in range(self.slots):
                 if self._slot[s] is None and self._queue:
@@ -262,8 +318,15 @@ class ContinuousBatcher:
             return
         idle = [s for s in range(self.slots) if self._slot[s] is None][: len(self._queue)]
         pairs = [(s, self._queue.popleft()) for s in idle]
-        for g0 in range(0, len(pairs), self.spare):
-            group = pairs[g0:g0 + self.spare]
+        groups = [[]]
+        for pair in pairs:
+            if pair[1].voice is not None:
+                groups += [[pair], []]
+            else:
+                if len(groups[-1]) == self.spare:
+                    groups.append([])
+                groups[-1].append(pair)
+        for group in [g for g in groups if g]:
             if len(group) == 1:
                 self._admit_into(*group[0])
             else:
@@ -411,10 +474,13 @@ class ContinuousBatcher:
                 self._out = collections.deque(c for c in self._out if c[0] != ticket)
         return found
 
-    def _codes(self, ids: torch.Tensor, max_length: int) -> torch.Tensor:
-        """Raw ids [K, columns] of one request -> its un-delayed audio codes [K, frames] (generate()'s tail, modeling_parler_tts.py:3585-3600)."""
+    def _codes(self, ids: torch.Tensor, max_length: int, voice: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Raw ids [K, columns] of one request -> its un-delayed audio codes [K, frames] (generate()'s tail, modeling_parler_tts.py:3585-3600).
+        ``voice``: the request's voice prompt; the pattern is then built over BOS + prefix, as generate() builds it (:3523-3530), and the
+        prompt's frames are part of the codes."""
         bos_col = ids[:, :1]
-        _, pattern = build_delay_pattern_mask(bos_col, self.bos, self.pad, max_length, self.K)
+        given = bos_col if voice is None else torch.cat([bos_col, voice.to(ids.device)], dim=-1)
+        _, pattern = build_delay_pattern_mask(given, self.bos, self.pad, max_length, self.K)
         out = apply_delay_pattern_mask(ids, pattern)
         _, m2 = build_delay_pattern_mask(bos_col, self.bos, self.pad, out.shape[1], self.K)
         keep = (m2 != self.bos) & (m2 != self.pad)
@@ -423,7 +489,7 @@ class ContinuousBatcher:
     def _decode_group(self, group):
         """The requests that finished at the same poll go through the codec as ONE ragged batch (special-id filter + ragged decode); the shorter
         ones are padded with an id outside the codebook, which the filter drops like any special id."""
-        codes = [self._codes(ids, r.max_length) for r, ids in group]
+        codes = [self._codes(ids, r.max_length, r.voice) for r, ids in group]
         T = max(int(c.shape[1]) for c in codes)
         if T == 0:
             for r, _ in group:

@@ -10,6 +10,7 @@
 
 #include "ptts_common.h"
 #include "../../include/ptts_session_kv8.h"
+#include "../../include/ptts_session_voice.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
 #include "ptts_strip_w8.h"
@@ -127,6 +128,8 @@ struct ptts_engine {
   int session_max_length = 0;            // max_length of the generation parameters the session was opened with
   int* row_maxlen = nullptr;             // [max_batch] device: max_length of the request in each slot
   SlotGen* slot_gen = nullptr;           // [max_batch] device: sampler record of the request in each slot (ptts_admit_row_gen); own = 0: the session's
+  int* slot_T = nullptr;                 // [max_batch] device: voice-prompt frames of the request in each slot (ptts_admit_row_voice); 0: none
+  DevDims* dims_adm = nullptr;           // [max_batch] device: per slot, the DevDims a voice admission's prefill embedding reads (the request's max_length, T, prefix rows)
   float* h_adm = nullptr;                // [max_prompt][H] residual rows of a row prefill: the step input h[B][H] of the other slots is live between steps
   KvLayer* kv_layers_rows = nullptr;     // [max_batch][layers] operands of the batched cross K/V projection with each slot's arena rows as base
   float* h_adm_rows = nullptr;           // [(max_batch - 1) * max_prompt][H] residual rows of a group prefill (ptts_admit_rows), allocated at its first use
@@ -167,6 +170,7 @@ struct FwdView {
   long long* ids;
   int *cur_len, *unfinished, *has_eos, *first_unf, *enc_mask, *prompt_mask;
   const KvLayer* kv_layers;      // [layers] operands of the batched cross K/V projection
+  const DevDims* embed_dims;     // what the embedding reads its delay pattern from: the engine's, or a voice admission's own (ptts_admit_row_voice)
   size_t self_off, cross_off;    // bytes from a layer's self / cross K/V arena to utterance 0 of this view
   size_t scale_off;              // kv_fp8 engines: floats from a layer's K / V scale array (LayerW::ks_self, vs_self) to utterance 0 of this view
 };
@@ -177,6 +181,7 @@ FwdView whole_view(const ptts_engine* e) {
   v.B = e->B; v.N = e->N; v.P = e->P; v.kv_bound = e->kv_bound; v.session = e->session; v.xfold_valid = e->xfold_valid;
   v.h = e->h; v.logits = e->logits; v.ids = e->ids; v.cur_len = e->cur_len; v.unfinished = e->unfinished; v.has_eos = e->has_eos;
   v.first_unf = e->first_unf; v.enc_mask = e->enc_mask; v.prompt_mask = e->prompt_mask; v.kv_layers = e->kv_layers;
+  v.embed_dims = e->dims;
   return v;
 }
 
@@ -347,11 +352,11 @@ void launch_embed(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStrea
   const ptts_config& c = e->cfg;
   EmbedArgs ea = {};
   ea.tables = e->embed; ea.pos_table = c.rope ? nullptr : e->pos_table; ea.prompt = prefill ? e->ffn : nullptr;
-  ea.ids = v.ids; ea.ids_ld = e->ids_ld; ea.cur_len = v.cur_len; ea.dims = e->dims; ea.h = v.h;
+  ea.ids = v.ids; ea.ids_ld = e->ids_ld; ea.cur_len = v.cur_len; ea.dims = v.embed_dims; ea.h = v.h;
   ea.H = c.hidden_size; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.bos = c.bos_token_id; ea.pad = c.pad_token_id;
   ea.prefill = prefill ? 1 : 0;
   if (v.session && !prefill)  // every slot under its own request's delay pattern
-    hipLaunchKernelGGL((embed_kernel<WT, true>), dim3(1, v.B), dim3(256), 0, st, EmbedSessionArgs{ea, e->row_maxlen});
+    hipLaunchKernelGGL((embed_kernel<WT, true>), dim3(1, v.B), dim3(256), 0, st, EmbedSessionArgs{ea, e->row_maxlen, e->slot_T});
   else
     hipLaunchKernelGGL((embed_kernel<WT, false>), dim3(Q, v.B), dim3(256), 0, st, ea);
 }
@@ -672,7 +677,7 @@ int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next
   t.has_eos = v.has_eos; t.first_unf = v.first_unf; t.gen = e->gen; t.sort_buf = e->sort_buf;
   t.B = v.B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
   // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
-  if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen);
+  if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen, e->slot_T);
   else tail_launch(t, nullptr, 0, dim3(v.B), st);
   return launch_status("tail");
 }
@@ -1350,6 +1355,8 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
   if (!e->row_maxlen) {  // first session of this engine: the row prefill's own residual rows and per-slot operand tables
     PTTS_TRY(e->alloc(&e->row_maxlen, (size_t)c.max_batch));
     PTTS_TRY(e->alloc(&e->slot_gen, (size_t)c.max_batch));  // with row_maxlen: the step graphs hold a pointer that never changes
+    PTTS_TRY(e->alloc(&e->slot_T, (size_t)c.max_batch));    // likewise: a voice admission captures nothing
+    PTTS_TRY(e->alloc(&e->dims_adm, (size_t)c.max_batch));  // one per slot: admissions into different slots on different streams share nothing
     PTTS_TRY(e->alloc(&e->h_adm, (size_t)e->max_prompt * H));
     PTTS_TRY(e->alloc(&e->kv_layers_rows, (size_t)c.max_batch * c.num_layers));  // rows_view points into it
     std::vector<KvLayer> kl((size_t)c.max_batch * c.num_layers);
@@ -1366,6 +1373,7 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
   e->slot_busy.assign(B, 0); e->slot_ub.assign(B, P + 1); e->slot_maxlen.assign(B, e->gp.max_length);
   launch_set_params(e, 0, st);
   hipLaunchKernelGGL(set_slot_gen_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->slot_gen, 0, c.max_batch, SlotGen{});  // no slot has a record of its own
+  hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, e->slot_T, 0, (size_t)c.max_batch);  // ... nor a voice prompt
   // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);
@@ -1415,8 +1423,8 @@ static int check_admission(const ptts_engine* e, int row, const float* prompt_de
 
 // The per-slot end of an admission, once nothing can refuse it any more: the host's bookkeeping, the request's own sampler record (a slot admitted
 // without one kept own = 0 from session begin / its last ptts_retire_row; a refused admission leaves the slot's record cleared), and its tail
-static int finish_admission(ptts_engine* e, int row, int L, const ptts_gen_params* gp, bool sample, hipStream_t st) {
-  e->slot_busy[row] = 1; e->slot_ub[row] = e->P + 1; e->slot_maxlen[row] = L;
+static int finish_admission(ptts_engine* e, int row, int L, const ptts_gen_params* gp, bool sample, hipStream_t st, int T = 0) {
+  e->slot_busy[row] = 1; e->slot_ub[row] = e->P + 1 + T; e->slot_maxlen[row] = L;  // T voice-prompt positions: the step's fetch bound includes them
   if (gp) hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, st, e->slot_gen, row, 1, SlotGen{dev_gen_of(*gp, L), 1, 0});
   if (sample) return launch_tail(e, whole_view(e), st, true, row);  // first token of the request + the embedding of its next column into h[row]
   e->h_ready = false;                                               // manual path: the next forward embeds every slot's last column
@@ -1442,6 +1450,54 @@ extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_
 extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
                               const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream) {
   return ptts_admit_row_gen(e, row, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_length, sample, nullptr, stream);
+}
+
+// A request that continues a voice prompt of T frames: the slot is admitted with 1 + T given columns. What ptts_set_audio_prefix + ptts_prefill do
+// for a static batch, for ONE slot: the codes go to the slot's rows of e->prefix, the delay pattern of (BOS + prefix, the request's max_length) to
+// its id columns 1..T, and P + 1 + T positions run in one pass through rows_view with T set - the ordinary prefill kernels, chosen by row count.
+// The prefill embedding reads the request's own DevDims (dims_adm: its max_length, T and prefix rows), so it feeds the model what the static
+// prefill of the same request feeds it; the decode steps read the slot's T from slot_T, which stays set until ptts_retire_row.
+extern "C" int ptts_admit_row_voice(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                                    const int32_t* prompt_mask_dev, const int64_t* codes_dev, int32_t T, int32_t max_length, int32_t sample,
+                                    const ptts_gen_params* gp, void* stream) {
+  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_row_voice: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(T >= 0 && (T == 0 || codes_dev), PTTS_E_INVALID, "bad voice prompt (T = %d frames, codes %s)", T, codes_dev ? "given" : "null");
+  if (T == 0) return ptts_admit_row_gen(e, row, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_length, sample, gp, stream);
+  int L = 0;
+  PTTS_TRY(check_admission(e, row, prompt_dev, max_length, gp, &L));
+  const ptts_config& c = e->cfg;
+  const int P = e->P, K = c.num_codebooks;
+  PTTS_CHECK(P + 1 + T <= e->max_prompt, PTTS_E_CAPACITY, "P + 1 + T = %d positions exceed the engine's prefill capacity %d (max_prompt)", P + 1 + T, e->max_prompt);
+  PTTS_CHECK(T + 2 <= L, PTTS_E_INVALID, "voice prompt of %d frames leaves no room below max_length %d", T, L);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = pick_stream(e, stream);
+  long long* pre = e->prefix + (size_t)row * K * c.max_ctx;
+  FwdView v = rows_view(e, row, 1, e->h_adm);
+  v.T = T; v.embed_dims = e->dims_adm + row;
+  hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
+                     e->row_maxlen, row, 1, K, c.bos_token_id, 1, L);
+  PTTS_HIP(hipMemcpy2DAsync(pre, (size_t)c.max_ctx * 8, codes_dev, (size_t)T * 8, (size_t)T * 8, (size_t)K, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(push_prefix_slot_kernel, dim3((K * T + 255) / 256), dim3(256), 0, st, v.ids, e->ids_ld, pre, c.max_ctx, T, K, c.bos_token_id,
+                     c.pad_token_id, L);
+  hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, st, e->slot_T + row, T, (size_t)1);  // before the prefill; read by every step from here on
+  DevDims hd; hd.P = P; hd.N = e->N; hd.max_length = L; hd.T_prefix = T; hd.prefix = pre; hd.prefix_ld = c.max_ctx;
+  hipLaunchKernelGGL(set_dims_kernel, dim3(1), dim3(1), 0, st, e->dims_adm + row, hd);
+  PTTS_TRY(stage_inputs(e, row, 1, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
+  PTTS_TRY(forward_dispatch(e, v, true, st));
+  hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(64), 0, st, v.cur_len, 1, T + 1);  // the slot's clock: BOS + T given columns
+  return finish_admission(e, row, L, gp, sample != 0, st, T);
+}
+
+extern "C" int ptts_debug_slot_voice(ptts_engine* e, int32_t* frames_host, void* stream) {
+  PTTS_CHECK(e && frames_host, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_debug_slot_voice: no continuous session (ptts_session_begin)");
+  PTTS_DEVICE(e->cfg.device);
+  hipStream_t st = pick_stream(e, stream);
+  PTTS_HIP(hipMemcpyAsync(e->host_pinned, e->slot_T, (size_t)e->B * 4, hipMemcpyDeviceToHost, st));
+  PTTS_HIP(hipStreamSynchronize(st));
+  for (int b = 0; b < e->B; ++b) frames_host[b] = e->host_pinned[b];
+  return PTTS_OK;
 }
 
 // A group of n requests in one prefill pass: the static prefill forward of a batch of n on the spare arena rows B .. B + n - 1 (every array of the
@@ -1521,6 +1577,7 @@ extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, pick_stream(e, stream), e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, row, 1, e->cfg.num_codebooks, e->cfg.bos_token_id, 0, e->session_max_length);
   hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_gen, row, 1, SlotGen{});  // the next plain admission samples on the session's
+  hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_T + row, 0, (size_t)1);  // ... and continues no voice prompt
   e->slot_busy[row] = 0; e->slot_ub[row] = e->P + 1;
   return PTTS_OK;
 }

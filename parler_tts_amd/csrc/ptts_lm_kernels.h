@@ -2486,11 +2486,12 @@ struct EmbedArgs {
 // manual path inside a session (ptts_step_forward): embedding of every slot's last column under the slot's own delay pattern
 struct EmbedSessionArgs : EmbedArgs {
   const int* row_maxlen;
+  const int* slot_tprefix = nullptr;  // [B] voice-prompt frames of the request in each slot (ptts_admit_row_voice), or null: no slot has a prefix
 };
 template <bool SESSION> struct EmbedK { using T = EmbedArgs; };
 template <> struct EmbedK<true> { using T = EmbedSessionArgs; };
 
-// SESSION: decode only (grid (1, B)), max_length from the slot's request and no voice prompt
+// SESSION: decode only (grid (1, B)), max_length and the voice-prompt length from the slot's request
 template <typename WT, bool SESSION>
 __global__ void embed_kernel(typename EmbedK<SESSION>::T p) {
   const EmbedArgs& a = p;
@@ -2513,7 +2514,7 @@ __global__ void embed_kernel(typename EmbedK<SESSION>::T p) {
     if constexpr (SESSION) {
       DevDims dd = *a.dims;
       dd.max_length = p.row_maxlen[b];
-      dd.T_prefix = 0;
+      dd.T_prefix = p.slot_tprefix ? p.slot_tprefix[b] : 0;  // the codes themselves: rows b * K + k of dd.prefix, as on the static path
       s_tok[threadIdx.x] = (int)delayed_token(a.ids, a.ids_ld, b * a.K + threadIdx.x, threadIdx.x, j, a.K, dd, a.bos, a.pad);
     } else {
       s_tok[threadIdx.x] = (int)delayed_token(a.ids, a.ids_ld, b * a.K + threadIdx.x, threadIdx.x, j, a.K, *a.dims, a.bos, a.pad);
@@ -2730,6 +2731,7 @@ struct TailSessionArgs : TailArgs {
   const int* row_maxlen;  // [B] max_length of the request in each slot
   int row0;               // first slot of this launch: grid (B) with 0 for a decode step, grid (1) with the slot for an admission
   const SlotGen* slot_gen = nullptr;  // [B] per-slot records, or null: every slot on *gen
+  const int* slot_tprefix = nullptr;  // [B] voice-prompt frames of the request in each slot (ptts_admit_row_voice), or null: no slot has a prefix
 };
 template <bool SESSION> struct TailK { using T = TailArgs; };
 template <> struct TailK<true> { using T = TailSessionArgs; };
@@ -2765,7 +2767,6 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
   DevDims dd = *a.dims;  // the embedding of the next column needs P / max_length / the voice-prompt prefix: fetched now, not after the argmax
   if constexpr (SESSION) {
     dd.max_length = p.row_maxlen[b];  // the pad triangle (and whether there is a pattern at all) follows the request's own length
-    dd.T_prefix = 0;                  // no voice prompt inside a session
   }
   if constexpr (SESSION) {
     // the slot's own record rides in the same batch of loads as *gen: both addresses come from kernel arguments alone (without records they
@@ -2783,6 +2784,13 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
     g.temperature = own ? sg.temperature : g.temperature; g.top_p = own ? sg.top_p : g.top_p;
     g.seed = own ? sg.seed : g.seed;
     hrow0 = own ? sbase : hrow0;
+    // the slot's voice-prompt length, the same way: a load of this batch whose address needs the kernel arguments alone (without the array
+    // one more read of *gen), the zero of "no prefix" chosen in a register. What follows it: the min_new_tokens count and what the model is
+    // fed for the next column (s_tok below); the ids written stay the raw sampled tokens
+    const bool pres = p.slot_tprefix != nullptr;
+    const int* tpp = pres ? &p.slot_tprefix[b] : &a.gen->max_length;
+    const int stp = *tpp;
+    dd.T_prefix = pres ? stp : 0;
   }
   const int t_prefix = dd.T_prefix;
   const int he = lane < a.K ? a.has_eos[b * a.K + lane] : 0;  // every wave: the K EOS flags of this utterance
@@ -2837,6 +2845,18 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
       const int nxt = unf ? widx : a.pad;  // next_tokens * unfinished + pad * (1 - unfinished)
       a.ids[(size_t)row * a.ids_ld + t] = nxt;
       s_tok[k] = nxt;
+      if constexpr (SESSION) {
+        // behind a voice prompt the model is FED the shifted prompt code while the pattern holds one for this codebook (the first K - 1 steps of
+        // such a slot; BOS / PAD still win in tail_embed_rows); what is stored stays the raw token. Resolved here, by the one lane that owns the
+        // codebook and only for such a slot, so that the embedding below keeps its one batch of table-row loads (see there)
+        // (the pointer and the stride are read HERE, through volatile, not taken from the prologue's copy of *dims: kept live from there through
+        // the token loop they cost the prologue its load groups - profiles/session_voice_isa_compare.txt)
+        if (t - k - 1 < t_prefix && t > k && dd.max_length >= 2 * a.K - 1) {
+          const long long* pf = *reinterpret_cast<const long long* const volatile*>(&a.dims->prefix);
+          const int pld = *reinterpret_cast<const volatile int*>(&a.dims->prefix_ld);
+          s_tok[k] = (int)pf[(size_t)row * pld + (t - k - 1)];
+        }
+      }
       if (nxt == a.eos) a.has_eos[row] = 1;
       // EosTokenCriteria | MaxLengthCriteria (the slot's own length in a session)
       if (unf && ((nxt == a.eos) || (t + 1 >= (SESSION ? dd.max_length : g.max_length)))) a.unfinished[row] = -(t + 1);
@@ -2844,6 +2864,7 @@ __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p
   }
   __syncthreads();
   if (tid == 0) a.cur_len[b] = t + 1;
+  if constexpr (SESSION) dd.T_prefix = 0;  // s_tok already holds the prompt codes: no load of them between the table rows' loads
   tail_embed_next(a, dd, b, t, s_tok, tid);
 }
 
@@ -2919,6 +2940,23 @@ static __global__ void push_prefix_all_kernel(long long* ids, int ids_ld, const 
   const DevDims dd = *dims;
   ids[(size_t)row * ids_ld + j] = j <= k ? (long long)bos : dd.prefix[(size_t)row * dd.prefix_ld + (j - k - 1)];
 }
+// ptts_admit_row_voice: columns 1..T of ONE slot's raw ids = what build_delay_pattern_mask holds there for (BOS + prefix, the request's own
+// max_length): BOS for j <= k, PAD for j - k >= max_length - K + 1, prefix[j - k - 1] otherwise; the prefix un-shifted below 2K - 1, where there
+// is no pattern. ids / prefix: the slot's first row. One thread per cell; T >= 1
+static __global__ void push_prefix_slot_kernel(long long* ids, int ids_ld, const long long* prefix, int prefix_ld, int T, int K, int bos, int pad,
+                                               int max_length) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= K * T) return;
+  const int k = i / T, j = 1 + i % T;
+  long long v;
+  if (max_length < 2 * K - 1) v = prefix[(size_t)k * prefix_ld + (j - 1)];
+  else if (j <= k) v = bos;
+  else if (j - k >= max_length - K + 1) v = pad;
+  else v = prefix[(size_t)k * prefix_ld + (j - k - 1)];
+  ids[(size_t)k * ids_ld + j] = v;
+}
+// the DevDims the prefill embedding of such an admission reads (the request's max_length, T and prefix rows; by value, as set_params_kernel's)
+static __global__ void set_dims_kernel(DevDims* dd, DevDims d) { *dd = d; }
 static __global__ void set_len_kernel(int* cur_len, int B, int v) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) cur_len[b] = v;

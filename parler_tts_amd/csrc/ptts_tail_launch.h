@@ -10,9 +10,11 @@
 // row_maxlen null: the static instances (every utterance on the shared clock, stop on DevGen::max_length; row0 unused).
 // row_maxlen set: the session instances, slot b = row0 + blockIdx.x under its own max_length - grid (B) with row0 0 for a
 // decode step, grid (1) with row0 = the slot for an admission. slot_gen (session only): the per-slot sampler records, or null.
+// slot_tprefix (session only): the per-slot voice-prompt lengths, or null: no slot has a prefix.
 // NV = logits per lane: 8 up to vocab 512, 18 up to 1152, 32 up to PTTS_SORT_N. One wave per codebook row (greedy arg-max or the
 // sort-free sampler), at least 4 waves for the embedding of the next column, at most 16 (more codebooks loop).
-static inline void tail_launch(const TailArgs& t, const int* row_maxlen, int row0, dim3 grid, hipStream_t st, const SlotGen* slot_gen = nullptr) {
+static inline void tail_launch(const TailArgs& t, const int* row_maxlen, int row0, dim3 grid, hipStream_t st, const SlotGen* slot_gen = nullptr,
+                               const int* slot_tprefix = nullptr) {
   const int nw = std::min(std::max(t.K, 4), 16);
   auto launch = [&](auto session, const auto& args) {  // one NV dispatch for both instances
     constexpr bool S = decltype(session)::value;
@@ -20,6 +22,6 @@ static inline void tail_launch(const TailArgs& t, const int* row_maxlen, int row
     else if (t.V <= 1152) hipLaunchKernelGGL((tail_kernel<18, S>), grid, dim3(nw * 64), 0, st, args);
     else hipLaunchKernelGGL((tail_kernel<32, S>), grid, dim3(nw * 64), 0, st, args);
   };
-  if (row_maxlen) launch(std::true_type{}, TailSessionArgs{t, row_maxlen, row0, slot_gen});  // per-slot clocks
+  if (row_maxlen) launch(std::true_type{}, TailSessionArgs{t, row_maxlen, row0, slot_gen, slot_tprefix});  // per-slot clocks
   else launch(std::false_type{}, t);
 }

@@ -261,12 +261,20 @@ class DecoderEngine:
         return rows[0], rows[1], scales[0], scales[1]
 
     def admit_row(self, row: int, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
-                  prompt_mask: Optional[torch.Tensor], max_length: int = 0, sample: bool = True, gen: Optional[dict] = None):
+                  prompt_mask: Optional[torch.Tensor], max_length: int = 0, sample: bool = True, gen: Optional[dict] = None,
+                  voice: Optional[torch.Tensor] = None):
         """Prefills ONE request (``enc`` [N, H], ``prompt`` [P, H] at the session's widths) into the idle slot ``row``; the other slots
         keep their state. ``max_length`` = the request's own 1 + max_new_tokens (0: the session's).
         ``gen``: the request's own sampler settings and seed (``ptts_admit_row_gen``) - keys ``min_new_tokens, do_sample, temperature, top_k,
         top_p, use_eos_gate, seed``, a key left out takes ``set_gen_params``'s default; the slot then draws from ``(seed, column, codebook)``,
-        whichever slot it is. ``None``: the session's parameters and draw stream (``ptts_admit_row``)."""
+        whichever slot it is. ``None``: the session's parameters and draw stream (``ptts_admit_row``).
+        ``voice``: un-delayed audio codes int64 [K, T] the request continues (``ptts_admit_row_voice``): the slot starts with 1 + T given
+        columns and ``max_length`` counts them, as ``set_audio_prefix`` + ``prefill`` do for a static batch. ``None`` or T == 0: the call made
+        without it."""
+        if voice is not None:
+            if voice.dim() != 2 or voice.shape[0] != self.K:
+                raise ValueError(f"voice prompt codes {tuple(voice.shape)}: expected [{self.K}, frames]")
+            voice = voice.to(self.device, torch.int64).contiguous() if voice.shape[1] > 0 else None
         gp = None
         if gen is not None:
             unknown = set(gen) - {"min_new_tokens", "do_sample", "temperature", "top_k", "top_p", "use_eos_gate", "seed"}
@@ -296,7 +304,12 @@ class DecoderEngine:
                 raise ValueError(f"prompt_attention_mask of {pm.numel()} positions does not match the session's {self.P}")
             keep.append(pm)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
-        if gp is None:
+        if voice is not None:
+            keep.append(voice)
+            N.check(self.lib.ptts_admit_row_voice(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), ptr(voice), int(voice.shape[1]), int(max_length),
+                                                  int(sample), C.byref(gp) if gp is not None else None, _stream_ptr(device=self.device)),
+                    "ptts_admit_row_voice")
+        elif gp is None:
             N.check(self.lib.ptts_admit_row(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), int(max_length), int(sample),
                                             _stream_ptr(device=self.device)), "ptts_admit_row")
         else:
@@ -367,6 +380,12 @@ class DecoderEngine:
 
     def retire_row(self, row: int):
         N.check(self.lib.ptts_retire_row(self._h, int(row), _stream_ptr(device=self.device)), "ptts_retire_row")
+
+    def slot_voice(self) -> list:
+        """Voice-prompt frames per slot as the device holds them (``ptts_debug_slot_voice``; for tests). Synchronises."""
+        t = (C.c_int32 * self.B)()
+        N.check(self.lib.ptts_debug_slot_voice(self._h, t, _stream_ptr(device=self.device)), "ptts_debug_slot_voice")
+        return list(t)
 
     def row_ids(self, row: int, cols: int) -> torch.Tensor:
         """Raw ids [K, cols] of one slot (a copy)."""

@@ -723,6 +723,31 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         graph.replay()
         return static_out.clone()
 
+    def _voice_prompt_codes(self, input_values):
+        """`input_values` (a waveform) -> DAC codes [batch * num_codebooks, frames] on the model's own codec encoder (:3136-3194); shared by
+        generate() and ContinuousBatcher.submit."""
+        K = self.config.decoder.num_codebooks
+        enc_out = self.audio_encoder.encode(input_values.to(self.device), n_quantizers=K)
+        audio_codes = enc_out.audio_codes
+        if audio_codes.dim() == 4:
+            if audio_codes.shape[0] != 1:  # :3182-3186
+                raise ValueError(f"Expected 1 frame in the audio code outputs, got {audio_codes.shape[0]} frames. Ensure chunking is "
+                                 "disabled by setting `chunk_length=None` in the audio encoder.")
+            audio_codes = audio_codes[0]
+        return audio_codes.reshape(audio_codes.shape[0] * K, audio_codes.shape[-1])
+
+    def _voice_prompt_rows(self, decoder_input_ids):
+        """`decoder_input_ids` as generate() takes them -> int64 [batch * num_codebooks, frames] on the model's device, without a leading BOS
+        column; shared by generate() and ContinuousBatcher.submit."""
+        d = self.config.decoder
+        K, bos = d.num_codebooks, d.bos_token_id
+        decoder_input_ids = decoder_input_ids.to(self.device).long()
+        if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] % K:
+            raise ValueError(f"decoder_input_ids must be [batch * num_codebooks, frames], got {tuple(decoder_input_ids.shape)}")
+        if not bool((decoder_input_ids[..., 0] != bos).all()):  # already starts with the BOS column (:3017-3018)
+            decoder_input_ids = decoder_input_ids[:, 1:]
+        return decoder_input_ids
+
     @torch.no_grad()
     def generate(self, inputs: Optional[torch.Tensor] = None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  synced_gpus: Optional[bool] = None, streamer=None, **kwargs):
@@ -797,21 +822,10 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         bos = d.bos_token_id
         # --- voice prompt (:3136-3194): `input_values` -> DAC codes -> `decoder_input_ids`, continued by the decoder --------------
         if input_values is not None:
-            enc_out = self.audio_encoder.encode(input_values.to(dev), n_quantizers=K)
-            audio_codes = enc_out.audio_codes
-            if audio_codes.dim() == 4:
-                if audio_codes.shape[0] != 1:  # :3182-3186
-                    raise ValueError(f"Expected 1 frame in the audio code outputs, got {audio_codes.shape[0]} frames. Ensure chunking is "
-                                     "disabled by setting `chunk_length=None` in the audio encoder.")
-                audio_codes = audio_codes[0]
-            decoder_input_ids = audio_codes.reshape(audio_codes.shape[0] * K, audio_codes.shape[-1])
+            decoder_input_ids = self._voice_prompt_codes(input_values)
         prefix = None
         if decoder_input_ids is not None:
-            decoder_input_ids = decoder_input_ids.to(dev).long()
-            if decoder_input_ids.dim() != 2 or decoder_input_ids.shape[0] % K:
-                raise ValueError(f"decoder_input_ids must be [batch * num_codebooks, frames], got {tuple(decoder_input_ids.shape)}")
-            if not bool((decoder_input_ids[..., 0] != bos).all()):  # already starts with the BOS column (:3017-3018)
-                decoder_input_ids = decoder_input_ids[:, 1:]
+            decoder_input_ids = self._voice_prompt_rows(decoder_input_ids)
             if decoder_input_ids.shape[0] // K == B // num_return and num_return > 1:
                 decoder_input_ids = decoder_input_ids.reshape(-1, K, decoder_input_ids.shape[-1]).repeat_interleave(num_return, 0).reshape(B * K, -1)
             if decoder_input_ids.shape[0] != B * K:

@@ -2,7 +2,8 @@
 """Continuous batching against static batching on a request stream of mixed lengths (Mini-v1 shapes, bf16, synthetic weights).
 
   python tools/continuous_bench.py [--repeats 5] [--static-only] [--per-request] [--stream [--stream-chunks 43,86]]
-                                   [--admit-batch 4,8 [--slots 64] [--burst-only]] [--kv8 [--slots 32,64,128] [--cache bf16|kv8]] [--out FILE]
+                                   [--admit-batch 4,8 [--slots 64] [--burst-only]] [--kv8 [--slots 32,64,128] [--cache bf16|kv8]]
+                                   [--voice [--voice-frames 43] [--voice-share 0.5]] [--out FILE]
 
 256 requests whose lengths come from a fixed seeded list (uniform 150..860 frames, set through per-request max_new_tokens; EOS is blocked,
 so lengths are exact), 32 slots. Reports
@@ -38,7 +39,14 @@ slot count of --slots (a comma list here, e.g. 32,64,128) first the bf16-cache s
 model keeps ONE decoder engine per cache mode, so the two cannot alternate inside a process; alternate processes with --cache bf16 / --cache kv8
 for that), and every figure of the kv8 session beside the bf16-cache figure of the same run (--kv8-aggregate LABEL=FILE ... then gives medians with
 min .. max over the saved reports of such processes): (b) audio-s/s on the request list, (d) the step
-time with every slot live, (e) one admission and (g) one ptts_admit_rows of 8 beside the other live slots, and the K/V arena bytes per slot."""
+time with every slot live, (e) one admission and (g) one ptts_admit_rows of 8 beside the other live slots, and the K/V arena bytes per slot.
+
+--voice measures voice prompts per request (ContinuousBatcher(max_voice_frames=T), ptts_admit_row_voice) instead of (a), (d), (e): (b) and the
+batcher in which a seeded share (--voice-share) of the requests carries a prompt of T = --voice-frames frames alternate on the same list; it
+reports requests per second and audio-s/s with the prompt's frames NOT counted (a request still generates the frames it was asked for, behind
+its prompt), and
+  (w) voice admission: GPU time of one ptts_admit_row_voice beside the other live slots at T = 43 and T = 430 (P + 1 + T positions in one
+                 prefill pass), next to the plain admission of the same session."""
 import argparse
 import ctypes as C
 import json
@@ -111,23 +119,34 @@ def request_options(i):
     return {"do_sample": False} if i % 4 == 1 else {"do_sample": True, "temperature": 0.7, "top_k": 50, "seed": 1000 + i}
 
 
-def run_batcher(model, desc, prompt, frames, per_request=False, admit_batch=1):
+def voice_requests(share, seed=LIST_SEED + 1):
+    """--voice: which requests of the list carry a prompt - a seeded choice of about `share` of them."""
+    g = torch.Generator().manual_seed(seed)
+    return [bool(x) for x in torch.rand(N_REQ, generator=g) < share]
+
+
+def run_batcher(model, desc, prompt, frames, per_request=False, admit_batch=1, voice=None):
+    """voice: None, or (T, [request carries a prompt], codes int64 [K, T] on the device): the session is opened with max_voice_frames = T."""
     import parler_tts_amd as P
 
     new_max = FRAMES_HI + K - 1
     kw = {"admit_batch": admit_batch} if admit_batch > 1 else {}
+    if voice is not None:
+        kw["max_voice_frames"] = voice[0]
+    extra = lambda i: {"decoder_input_ids": voice[2]} if voice is not None and voice[1][i] else {}
+    given = lambda i: voice[0] if voice is not None and voice[1][i] else 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     cb = P.ContinuousBatcher(model, slots=SLOTS, max_description_tokens=bench.N_DESC, max_prompt_tokens=bench.N_PROMPT, poll_steps=16, do_sample=False,
                              max_new_tokens=new_max, min_new_tokens=new_max, **kw)
-    tickets = [cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1, **(request_options(i) if per_request else {}))
+    tickets = [cb.submit(desc[i], prompt_input_ids=prompt[i], max_new_tokens=frames[i] + K - 1, **(request_options(i) if per_request else {}), **extra(i))
                for i in range(N_REQ)]
     torch.cuda.synchronize()
     t_submit = time.perf_counter() - t0
     got = {t: n for t, w, n in cb}
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    assert [got[t] for t in tickets] == [f * 512 for f in frames], "the batcher returned other lengths than were asked for"
+    assert [got[t] for t in tickets] == [(f + given(i)) * 512 for i, f in enumerate(frames)], "the batcher returned other lengths than were asked for"
     return dt, t_submit, cb.eng
 
 
@@ -396,6 +415,53 @@ def admit_batch_report(model, desc, prompt, frames, audio_s, sizes, repeats, bur
     return res
 
 
+def voice_admission(model, enc, pr, ev, T, repeats):
+    """(w): every slot live, then slot 5 retired and re-admitted with a T-frame prompt (T = 0: the plain admission). GPU time, ms, per repeat."""
+    eng = model._get_engine(SLOTS, bench.N_DESC, bench.N_PROMPT, bench.NEW_TOKENS + 1 + T, T)
+    eng.set_gen_params(max_length=bench.NEW_TOKENS + 1 + T, min_new_tokens=bench.NEW_TOKENS)
+    begin_session(eng)
+    for s in range(SLOTS):
+        eng.admit_row(s, enc[s], None, pr[s], None)
+    eng.decode_steps(WARM_STEPS)
+    codes = torch.randint(0, 1024, (K, T), generator=torch.Generator().manual_seed(T), dtype=torch.long).to(enc.device) if T else None
+    out = []
+    for r in range(repeats + 1):  # the first one warms the prefill kernels of this row count
+        eng.retire_row(5)
+        out.append(ev.ms(lambda: eng.admit_row(5, enc[40], None, pr[40], None, **({"voice": codes} if T else {}))))
+        eng.decode_steps(4)
+    return out[1:]
+
+
+def voice_report(model, desc, prompt, frames, audio_s, T, share, repeats, say):
+    res = {}
+    who = voice_requests(share)
+    codes = torch.randint(0, 1024, (K, T), generator=torch.Generator().manual_seed(T), dtype=torch.long).to(desc.device)
+    voice = (T, who, codes)
+    run_batcher(model, desc, prompt, frames)
+    run_batcher(model, desc, prompt, frames, voice=voice)  # warm: the engine with P + 1 + T prefill rows, its step graphs
+    base, runs = [], []
+    for r in range(repeats):
+        base.append(run_batcher(model, desc, prompt, frames)[0])
+        runs.append(run_batcher(model, desc, prompt, frames, voice=voice)[0])
+        say(f"  repeat {r}: batcher {base[-1]:.3f} s, {sum(who)} of {N_REQ} requests with a {T}-frame prompt {runs[-1]:.3f} s")
+    mb, lob, hib = med_spread(base)
+    say(f"(b) ContinuousBatcher: median {mb:.3f} s = {N_REQ / mb:.2f} requests/s = {audio_s / mb:.1f} audio-s/s (spread {audio_s / hib:.1f} .. {audio_s / lob:.1f})")
+    m, lo, hi = med_spread(runs)
+    say(f"(v) max_voice_frames {T}, {sum(who)} of {N_REQ} requests (seeded share {share}) with a {T}-frame prompt: median {m:.3f} s = {N_REQ / m:.2f} requests/s = "
+        f"{audio_s / m:.1f} audio-s/s without the prompts' frames (spread {audio_s / hi:.1f} .. {audio_s / lo:.1f}) = {mb / m:.3f} of (b); with them "
+        f"{(audio_s + sum(who) * T * SEC_PER_FRAME) / m:.1f}")
+    res.update(batcher_s=mb, batcher_audio_s_per_s=audio_s / mb, voice_s=m, voice_audio_s_per_s=audio_s / m, voice_requests_per_s=N_REQ / m, voice_requests=sum(who))
+    enc = model._encode_description(desc[:64], None).float()
+    pr = model.embed_prompts(prompt[:64]).float()
+    ev = Events()
+    for t in (0, 43, 430):
+        mm, lo, hi = med_spread(voice_admission(model, enc, pr, ev, t, repeats))
+        what = "plain admission (33-position row prefill" if t == 0 else f"voice admission, T = {t} ({bench.N_PROMPT + 1 + t}-position row prefill"
+        say(f"(w) one {what} + cross K/V + first token) beside {SLOTS - 1} live slots: median {mm:.3f} ms ({lo:.3f} .. {hi:.3f})")
+        res[f"admit_T{t}_ms"] = mm
+    return res
+
+
 def arena_bytes_per_slot(eng):
     """(self, cross) K/V arena bytes one slot owns: e4m3 self rows are 64 bytes + one fp32 scale, the cross arena stays in the engine dtype."""
     c = eng.cfg
@@ -498,6 +564,9 @@ def main():
     ap.add_argument("--slots", default=str(SLOTS), help="slots of the session (with --admit-batch; with --kv8 a comma list, e.g. 32,64,128)")
     ap.add_argument("--kv8", action="store_true", help="measure the session on the e4m3 self-attention cache beside the bf16-cache session")
     ap.add_argument("--cache", default="both", choices=["both", "bf16", "kv8"], help="with --kv8: one side only (for alternating processes)")
+    ap.add_argument("--voice", action="store_true", help="measure requests with voice prompts against (b), and one voice admission at T = 43 and 430")
+    ap.add_argument("--voice-frames", type=int, default=43, help="with --voice: frames of a request's prompt (43 = 0.5 s)")
+    ap.add_argument("--voice-share", type=float, default=0.5, help="with --voice: seeded share of the requests that carry a prompt")
     ap.add_argument("--burst-only", action="store_true", help="with --admit-batch: only the session start and the group admission")
     ap.add_argument("--kv8-aggregate", nargs="+", default=None, metavar="LABEL=FILE",
                     help="no measurement: medians (min .. max) per label over the saved reports of several --kv8 --cache X processes")
@@ -540,6 +609,15 @@ def main():
     if a.admit_batch:
         with torch.no_grad():
             res = admit_batch_report(model, desc, prompt, frames, audio_s, [int(n) for n in a.admit_batch.split(",")], a.repeats, a.burst_only, say)
+        say(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if a.voice:
+        with torch.no_grad():
+            res = voice_report(model, desc, prompt, frames, audio_s, a.voice_frames, a.voice_share, a.repeats, say)
         say(json.dumps(res))
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

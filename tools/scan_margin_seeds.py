@@ -82,6 +82,17 @@ def main():
         for seed, n in TS.E2E_SCANNED:
             f = lambda s, n=n: TS.e2e_oracle(m, spec, sd, dsd, TS.e2e_request(s, n), "cpu")[0].min_margin
             scan(f"stream_e2e {n} tokens", seed, f, list(range(500, 700)), want=1)
+    if want("session_voice"):  # tests/session_voice_cases.py: one request per (T, max_length), each alone, with and without its prefix
+        import session_voice_cases as VC
+
+        sd = VC.weights()
+        for T, L, seed in VC.FREE_RUNNING:
+            scan(f"session_voice T={T} L={L}", seed, lambda s, T=T, L=L: VC.margin(T, L, s, sd), list(range(700, 900)), want=1)
+        sde = VC.weights(eos_gain=6.0)
+        L = VC.MIN_NEW_MAX_LENGTH
+        scan("session_voice min_new", VC.MIN_NEW_SEED,
+             lambda s: min(VC.margin(4, L, s, sde, min_new=3), VC.margin(0, L, s + 1, sde, min_new=5), VC.margin(4, L, s + 2, sde, min_new=4),
+                           VC.margin(4, L, s + 2, sde, min_new=5)), list(range(720, 1400, 3)), want=1)
     if want("gen_voice"):
         scan("gen_voice", C.GEN_VOICE_SEEDS, lambda s: gen_margin(s[0], s[1], "voice"), [(0, 100 + i) for i in range(40)])
 
