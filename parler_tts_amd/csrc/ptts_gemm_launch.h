@@ -1,5 +1,6 @@
-// Host-side launch helpers of the MFMA strip / block GEMMs and the rows_prep kernel (ptts_lm_kernels.h), shared by the decoder-LM engine
-// (ptts_lm.hip) and the T5 description encoder (ptts_t5.hip). Every function is internal to its translation unit (anonymous namespace).
+// Host-side launch helpers of the MFMA strip / block GEMMs, the rows_prep kernel and the fused LayerNorm + projection / cross-block nodes
+// (ptts_lm_kernels.h), shared by the decoder-LM engine (ptts_lm.hip), the T5 description encoder (ptts_t5.hip) and the test harnesses under
+// tests/native/, which launch what the engine launches. Every function is internal to its translation unit (anonymous namespace).
 #pragma once
 #include <algorithm>
 
@@ -223,6 +224,71 @@ int launch_prep(GemmArgs a, void* dst, hipStream_t st) {
   PTTS_TRY(RowsPrepHead::pack(a, dst, h));
   ptts_klaunch(rows_prep_kernel<WT, PRO>, dim3((a.M + 3) / 4), dim3(256), 0, st, h, a);
   return PTTS_OK;
+}
+
+// behind a run of launches: the first error any of them left
+int launch_status(const char* what) {
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? PTTS_OK : ptts_fail(PTTS_E_HIP, "%s launch failed: %s", what, hipGetErrorString(err));
+}
+
+// LayerNorm (+ fold of pending fc2 partials) + projection, tiled over 64 weight rows x G utterances (lnproj_fused_kernel): decode at batch > 8
+template <typename WT, int EPI>
+int launch_lnproj(const ptts_engine* e, LnProjArgs p, hipStream_t st, int g) {
+  constexpr int KT = Elem<WT>::KT;
+  const int H = p.K;
+  p.invK = 1.0f / (float)H;
+  const int mg = p.M < g ? p.M : g;
+  const size_t sh = (size_t)mg * (H * sizeof(WT) + 16) + 8 * 1024;
+  const dim3 grid(p.N / 64, (p.M + g - 1) / g);
+  const bool u16 = ((H / KT) / 2) % 16 == 0;
+  // > 64 KiB of dynamic LDS needs an explicit opt-in, once per instantiation and device (the fp32 engine's 16-row instances ask for 72 KiB at
+  // H = 1024 and 104 KiB at H = 1536): same pattern as launch_gemm_inst
+#define PTTS_LNPROJ_ONE(UW, NF4, G)                                                                                   \
+  do {                                                                                                                \
+    static PttsPerDeviceOnce attr_once;                                                                               \
+    const int attr_dev = PttsPerDeviceOnce::device();                                                                 \
+    if (sh > 64 * 1024 && attr_once.need(attr_dev)) {                                                                 \
+      hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnproj_fused_kernel<WT, UW, NF4, G, EPI>),  \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                    \
+      if (ea != hipSuccess) return ptts_fail(PTTS_E_HIP, "hipFuncSetAttribute(max dynamic LDS) failed: %s", hipGetErrorString(ea)); \
+      attr_once.done(attr_dev);                                                                                       \
+    }                                                                                                                 \
+    ptts_klaunch(lnproj_fused_kernel<WT, UW, NF4, G, EPI>, grid, dim3(512), sh, st, p);                      \
+  } while (0)
+#define PTTS_LNPROJ_LAUNCH(UW, NF4)                                                                                   \
+  do {                                                                                                                \
+    if (g == 16) PTTS_LNPROJ_ONE(UW, NF4, 16);                                                                        \
+    else if (g == 4) PTTS_LNPROJ_ONE(UW, NF4, 4);                                                                     \
+    else PTTS_LNPROJ_ONE(UW, NF4, 8);                                                                                 \
+  } while (0)
+  if (H == 1024 && u16) PTTS_LNPROJ_LAUNCH(16, 4);
+  else if (H == 1024) PTTS_LNPROJ_LAUNCH(8, 4);
+  else PTTS_LNPROJ_LAUNCH(8, 6);
+#undef PTTS_LNPROJ_LAUNCH
+#undef PTTS_LNPROJ_ONE
+  return launch_status("lnproj");
+}
+
+// LN2 + cross q projection + cross-attention of x.B rows as one node (xattn_fused_kernel), gsz utterances per workgroup: heads x ceil(B / gsz)
+// workgroups, the 8 / gsz waves of an utterance split the description's row groups
+template <typename WT>
+void launch_xattn_fused(XAttnArgs x, int gsz, hipStream_t st) {
+  const int H = x.K, M = x.B, KTw = Elem<WT>::KT;
+  const int mg = M < gsz ? M : gsz;
+  const size_t sh = (size_t)mg * (H * sizeof(WT) + 16) + 8 * 1024 + (size_t)gsz * 64 * 4 + 8 * 64 * 4 + 64;
+  const dim3 xg(x.nheads, (M + gsz - 1) / gsz);
+  const bool u16 = ((H / KTw) / 2) % 16 == 0;
+  if (H == 1024 && u16) {  // Mini-v1
+    if (gsz == 4) ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 4>, xg, dim3(512), sh, st, x);
+    else if (gsz == 2) ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 2>, xg, dim3(512), sh, st, x);
+    else ptts_klaunch(xattn_fused_kernel<WT, 16, 4, 8>, xg, dim3(512), sh, st, x);
+  } else if (H == 1024) ptts_klaunch(xattn_fused_kernel<WT, 8, 4>, xg, dim3(512), sh, st, x);
+  else if (H == 1536) {  // Large-v1
+    if (gsz == 4) ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 4>, xg, dim3(512), sh, st, x);
+    else if (gsz == 2) ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 2>, xg, dim3(512), sh, st, x);
+    else ptts_klaunch(xattn_fused_kernel<WT, 8, 6, 8>, xg, dim3(512), sh, st, x);
+  } else ptts_klaunch(xattn_fused_kernel<WT, 8, 2>, xg, dim3(512), sh, st, x);                            // hidden 512
 }
 
 }  // namespace

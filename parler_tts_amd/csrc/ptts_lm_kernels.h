@@ -260,6 +260,13 @@ template <typename A> __device__ __forceinline__ long long* ptts_dbg_of(const A&
 template <> __device__ __forceinline__ long long* ptts_dbg_of<GemmArgs>(const GemmArgs& a) { return a.dbg; }
 #endif
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+// The GELU behind an ENGINE-DTYPE output (EPI_GELU_WT; lnproj_fused_kernel's fc1 epilogue). bf16 engine: gelu_erf - its fp32 error vanishes in the
+// bf16 rounding (within one bf16 ulp of the exact function). fp32 engine: 1 + erff cancels for x < 0, so gelu_erf is 40 .. 90 fp32 ulps of the
+// (small) result away at x ~ -2.5; the output is held to ONE fp32 ulp (tests/test_step_kernels_gpu.py), so it is 0.5 x erfc(-x / sqrt 2) in
+// double - no cancellation - rounded once. A few hundred fp64 operations per output element of an fp32-engine fc1, beside K = 1024+ MFMA steps.
+template <typename WT> __device__ __forceinline__ float gelu_erf_wt(float x);
+template <> __device__ __forceinline__ float gelu_erf_wt<bf16_t>(float x) { return gelu_erf(x); }
+template <> __device__ __forceinline__ float gelu_erf_wt<float>(float x) { return (float)(0.5 * (double)x * erfc(-(double)x * 0.70710678118654752440)); }
 // transformers NewGELUActivation ("gelu_new", T5 v1.1 / flan-t5 gated-gelu): 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))
 __device__ __forceinline__ float gelu_new(float x) { return 0.5f * x * (1.0f + tanhf(0.79788456080286535588f * (x + 0.044715f * (x * x * x)))); }
 // two consecutive engine-dtype elements (k % 2 == 0) of row m: row-major [M][K] or fragment order
@@ -462,9 +469,12 @@ __device__ __forceinline__ float4 stage_elem(const GemmArgs& a, int m, int k) {
     float4 o = make_float4(0, 0, 0, 0);
     for (int sp = 0; sp < a.S; ++sp) {
       const float ms = st[(size_t)sp * a.nheads * 2], ls = st[(size_t)sp * a.nheads * 2 + 1];
-      const float w = (ms == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(ms - mx);  // statistics are in log2 units (attn_kernel)
-      den += w * ls;
-      const float4 t = *reinterpret_cast<const float4*>(a.part + ((size_t)m * a.S + sp) * a.K + k);
+      const bool live = ms != -INFINITY;  // an empty split contributes nothing, whatever its row holds: its values are selected away before the
+                                          // multiplication by weight 0 (0 * NaN would reach the output)
+      const float w = live ? __builtin_amdgcn_exp2f(ms - mx) : 0.f;  // statistics are in log2 units (attn_kernel)
+      den += w * (live ? ls : 0.f);
+      float4 t = *reinterpret_cast<const float4*>(a.part + ((size_t)m * a.S + sp) * a.K + k);
+      if (!live) t = make_float4(0.f, 0.f, 0.f, 0.f);
       o.x += w * t.x; o.y += w * t.y; o.z += w * t.z; o.w += w * t.w;
     }
     const float inv = den > 0.f ? __frcp_rn(den) : 0.f;
@@ -735,7 +745,7 @@ __device__ __forceinline__ void gemm_strip_body(GemmArgs& a) {
           *reinterpret_cast<float4*>(a.out + (size_t)m * a.out_ld + n) =
               make_float4(gelu_erf(r[0]), gelu_erf(r[1]), gelu_erf(r[2]), gelu_erf(r[3]));
         } else if (EPI == EPI_GELU_WT) {
-          act_store4<WT>(reinterpret_cast<WT*>(a.out), m, n, a.out_ld, a.out_fo, gelu_erf(r[0]), gelu_erf(r[1]), gelu_erf(r[2]), gelu_erf(r[3]));
+          act_store4<WT>(reinterpret_cast<WT*>(a.out), m, n, a.out_ld, a.out_fo, gelu_erf_wt<WT>(r[0]), gelu_erf_wt<WT>(r[1]), gelu_erf_wt<WT>(r[2]), gelu_erf_wt<WT>(r[3]));
         } else if (EPI == EPI_GATE_WT) {  // rows n .. n + 3 of the interleaved matrix = (wi_0, wi_1) of features n / 2, n / 2 + 1
           act_store2<WT>(reinterpret_cast<WT*>(a.out), m, n >> 1, a.out_ld, a.out_fo, gelu_new(r[0]) * r[1], gelu_new(r[2]) * r[3]);
         } else if (EPI == EPI_RESID) {
@@ -838,7 +848,7 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& a, int m, int n,
   } else if (EPI == EPI_GELU_WT) {
     WT* o = reinterpret_cast<WT*>(a.out) + (size_t)m * a.out_ld + n;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) store_from_f32<WT>(o + e, gelu_erf(r[e]));
+    for (int e = 0; e < 4; ++e) store_from_f32<WT>(o + e, gelu_erf_wt<WT>(r[e]));
   } else if (EPI == EPI_GATE_WT) {
     act_store2<WT>(reinterpret_cast<WT*>(a.out), m, n >> 1, a.out_ld, 0, gelu_new(r[0]) * r[1], gelu_new(r[2]) * r[3]);
   } else if (EPI == EPI_RESID) {
@@ -2276,7 +2286,7 @@ __global__ void __launch_bounds__(512) lnproj_fused_kernel(PTTS_KPARAMS(LnProjAr
         for (int e = 0; e < 4; ++e) store_from_f32<WT>(dst + e, rr[e]);
       }
     } else {
-      act_store4<WT>(reinterpret_cast<WT*>(a.out), m, n, a.out_ld, a.out_fo, gelu_erf(rr[0]), gelu_erf(rr[1]), gelu_erf(rr[2]), gelu_erf(rr[3]));
+      act_store4<WT>(reinterpret_cast<WT*>(a.out), m, n, a.out_ld, a.out_fo, gelu_erf_wt<WT>(rr[0]), gelu_erf_wt<WT>(rr[1]), gelu_erf_wt<WT>(rr[2]), gelu_erf_wt<WT>(rr[3]));
     }
   }
 }

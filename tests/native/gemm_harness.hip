@@ -68,7 +68,8 @@ int ptts_fail(int code, const char* fmt, ...) {
   g_ptts_err = buf;
   return code;
 }
-// the e4m3 strips (ptts_lm_w8.hip) are out of the harness's scope: launch_gemm never gets here without GemmArgs::W8
+// the e4m3 strips (ptts_lm_w8.hip) and the strips on fragment-order rows (x_fo, m_split) are tests/native/step_harness.hip's, which links the
+// product's ptts_lm_w8.hip; here launch_gemm never gets to this stand-in without GemmArgs::W8
 int ptts_strip_w8_launch(int, int, int, const GemmArgs&, dim3, dim3, size_t, hipStream_t) { return -1; }
 
 GH_API const char* gh_last_error(void) { return g_ptts_err.c_str(); }
