@@ -128,6 +128,13 @@ SESSION_VOICE_SYMBOLS = {
     "ptts_debug_slot_voice": (C.c_int, [_VP, C.POINTER(_I32), _VP]),
 }
 
+# include/ptts_dac_stream_voice.h, additive likewise: streaming a request that continues a voice prompt out of a continuous session
+DAC_STREAM_VOICE_SYMBOLS = {
+    "ptts_dac_stream_open_voice": (C.c_int, [_VP, _I32, _I32, _I32, _VP]),
+    "ptts_dac_stream_reset_voice": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP]),
+    "ptts_dac_stream_decode_capped": (C.c_int, [_VP, _VP, C.c_int64, _I32, _I32, C.POINTER(PttsDacStreamRow), _I32, _I32, _VP, C.c_int64, _VP, _VP, _I32]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -150,7 +157,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 missing
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
     for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
-                              + list(SESSION_VOICE_SYMBOLS.items())):
+                              + list(SESSION_VOICE_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

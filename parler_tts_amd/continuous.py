@@ -30,12 +30,14 @@ _VOICE_ARGUMENTS = ("input_values", "decoder_input_ids")
 
 
 class _Request:
-    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice")
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept")
 
-    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None):
+    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None):
         self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
         self.gen = gen  # the request's own sampler record (DecoderEngine.admit_row's `gen`), or None: the session's
         self.voice = voice  # un-delayed codes [K, T >= 1] of the voice prompt the request continues (admit_row's `voice`), or None
+        # stream_voice_prompts="skip": prompt_kept[n] = frames the special-id filter keeps of the prompt's first n, n = 0..T (else None)
+        self.prompt_kept = prompt_kept
 
     @property
     def T(self) -> int:
@@ -73,15 +75,27 @@ class ContinuousBatcher:
     ``max_prompt_tokens + 1 + max_voice_frames`` positions. A limit given as ``max_new_tokens`` counts NEW tokens, as in ``generate()``: the
     session's ``max_length`` grows by ``max_voice_frames`` and a request with T frames gets ``max_new_tokens + 1 + T`` columns; a limit
     given as ``max_length`` stays the total. A request with a voice prompt is admitted alone (``ptts_admit_row_voice``), also with
-    ``admit_batch > 1``, and not in streaming mode (``submit`` raises ``NotImplementedError`` there)."""
+    ``admit_batch > 1``, and in streaming mode only with ``stream_voice_prompts`` (without it ``submit`` raises ``NotImplementedError``).
+
+    ``stream_voice_prompts`` (default ``None``; needs ``stream_chunk_frames`` and ``max_voice_frames > 0``): a streaming session takes voice
+    prompts. ``"emit"``: a request's chunks concatenate to the waveform of the non-streaming mode, the prompt's frames included. ``"skip"``:
+    to that waveform without its leading ``hop * (kept prompt frames)`` samples - the continuation alone, for a caller who has the reference
+    audio already. The codec's stream table then keeps each slot's prompt (``ptts_dac_stream_open_voice`` / ``_reset_voice``) and no pass
+    emits more than ``max_emit = window_frames - 2 * halo`` frames per slot (``ptts_dac_stream_decode_capped``): a long prompt leaves in
+    several chunks, starting at the poll that admits it, and a finished slot is drained by repeated final passes before it is reused. A
+    request without a prompt never has that much ready: its chunks are the ones of a session without the option."""
 
     def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16,
                  stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, admit_batch: int = 1, max_voice_frames: int = 0,
-                 **generation_kwargs):
+                 stream_voice_prompts: Optional[str] = None, **generation_kwargs):
         if int(admit_batch) < 1:
             raise ValueError("`admit_batch` must be >= 1")
         if int(max_voice_frames) < 0:
             raise ValueError("`max_voice_frames` must be >= 0")
+        if stream_voice_prompts not in (None, "emit", "skip"):
+            raise ValueError(f"`stream_voice_prompts` must be None, 'emit' or 'skip', got {stream_voice_prompts!r}")
+        if stream_voice_prompts is not None and (stream_chunk_frames is None or int(max_voice_frames) < 1):
+            raise ValueError("`stream_voice_prompts` needs `stream_chunk_frames` (streaming mode) and `max_voice_frames` > 0")
         if slots < 1 or max_description_tokens < 1 or max_prompt_tokens < 0 or poll_steps < 1:
             raise ValueError("slots, max_description_tokens and poll_steps must be >= 1 and max_prompt_tokens >= 0")
         if stream_chunk_frames is None and stream_first_chunk_frames is not None:
@@ -145,6 +159,7 @@ class ContinuousBatcher:
         self._done: Deque[Tuple[int, torch.Tensor, int]] = collections.deque()
         self._next_ticket = 0
         self.chunk = None if stream_chunk_frames is None else int(stream_chunk_frames)
+        self.stream_voice = stream_voice_prompts
         if self.chunk is not None:
             from .streamer import receptive_halo_frames
 
@@ -155,7 +170,13 @@ class ContinuousBatcher:
             # without reading the device (ptts.h), which after dropped frames is looser by up to another chunk + halo
             big = max(self.chunk, self.first_chunk)
             self.window_frames = min(3 * self.halo + 2 * big + self.poll_steps + 8, max(self.max_length, 1))
-            ae.stream_open(self.slots, self.max_length, self.window_frames)
+            if self.stream_voice is None:
+                ae.stream_open(self.slots, self.max_length, self.window_frames)
+            else:
+                ae.stream_open(self.slots, self.max_length, self.window_frames, max_voice_frames=self.max_voice_frames)
+                # a capped window = halo + max_emit + halo frames. A request without a prompt has fewer than chunk + poll_steps frames to emit
+                # at a poll, which is below this cap; a window as long as the longest request needs none
+                self.max_emit = self.window_frames - 2 * self.halo if self.window_frames < self.max_length else self.max_length
             self._absorbed, self._kept, self._emitted = [0] * self.slots, [0] * self.slots, [0] * self.slots
             self._first_out = [False] * self.slots  # the request's first chunk is still outstanding
             self._out: Deque[Tuple[int, torch.Tensor, bool]] = collections.deque()
@@ -253,7 +274,11 @@ class ContinuousBatcher:
             gen["seed"] = int(torch.randint(0, 2 ** 62, (1,)).item()) if gen["do_sample"] else 0
         ticket = self._next_ticket
         self._next_ticket += 1
-        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice))
+        prompt_kept = None
+        if voice is not None and self.stream_voice == "skip":  # what the filter keeps of the prompt, known here: the codec's pairs do not say
+            cb = int(self.model.audio_encoder.config.codebook_size)
+            prompt_kept = [0] + ((voice >= 0) & (voice < cb)).all(dim=0).long().cumsum(0).tolist()
+        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept))
         return ticket
 
     def _voice(self, input_values, decoder_input_ids) -> Optional[torch.Tensor]:
@@ -261,9 +286,10 @@ class ContinuousBatcher:
         the model's DAC encoder and over ``decoder_input_ids`` when both are given, a leading BOS column dropped), then this session's limits."""
         if input_values is None and decoder_input_ids is None:
             return None
-        if self.chunk is not None:
+        if self.chunk is not None and self.stream_voice is None:
             raise NotImplementedError("a voice prompt in streaming mode: the windowed codec pass reads the slot's raw ids, which hold the delay pattern "
-                                      "behind the prompt; submit it to a batcher without `stream_chunk_frames`")
+                                      "behind the prompt; submit it to a batcher without `stream_chunk_frames`, or open this one with "
+                                      "`stream_voice_prompts`")
         if input_values is not None:
             decoder_input_ids = self.model._voice_prompt_codes(torch.as_tensor(input_values))
         else:
@@ -360,11 +386,24 @@ class ContinuousBatcher:
     # -- streaming ----------------------------------------------------------------------------------------------------------------
     def _admit(self):
         def fresh_stream(s):
-            self.model.audio_encoder.stream_reset(s)
+            r = self._slot[s]
+            if r.voice is None:
+                self.model.audio_encoder.stream_reset(s)
+            else:  # only with stream_voice_prompts: submit refuses the prompt otherwise
+                self.model.audio_encoder.stream_reset(s, voice=r.voice, emit_prompt=self.stream_voice == "emit")
             self._absorbed[s] = self._kept[s] = self._emitted[s] = 0
             self._first_out[s] = True
 
         self._admit_queued(fresh_stream)
+
+    def _skipped(self, s: int) -> int:
+        """Frames of slot s's prompt that are never emitted (stream_voice_prompts="skip"), else 0."""
+        return 0 if self._slot[s].prompt_kept is None else self._slot[s].T
+
+    def _new_raw(self, s: int, complete: int) -> int:
+        """Raw frames of [absorbed, complete) that may become ready: all of them, less those of a prompt that is not emitted."""
+        T = self._skipped(s)
+        return max(complete, T) - max(self._absorbed[s], T)
 
     def _streams(self, s: int, cur: int) -> bool:
         """Whether slot s's frames can be named yet: below 2K - 1 columns build_delay_pattern_mask applies no pattern at all, and `cur` alone
@@ -380,7 +419,8 @@ class ContinuousBatcher:
         if not self._first_out[s] or self._slot[s].max_length < 2 * self.K - 1:
             return None
         need = self.first_chunk + self.halo - (self._kept[s] - self._emitted[s])  # raw frames still to absorb
-        cols = max(2 * self.K - 1, self._absorbed[s] + need + self.K)
+        # the frames of a prompt that is not emitted do not count. A prompt that is emitted may hold the first chunk at admission: <= 0 then
+        cols = max(2 * self.K - 1, max(self._absorbed[s], self._skipped(s)) + need + self.K)
         return cols - self._cols[s]
 
     def _poll_stream(self):
@@ -395,6 +435,8 @@ class ContinuousBatcher:
             f = self._first_chunk_steps(s)
             if f is not None and f >= 1:
                 n = min(n, f)
+            elif f is not None and self._slot[s].voice is not None:
+                n = 0  # the prompt alone holds the first chunk: the codec pass comes before any further step
         n = max(0, n)
         if n > 0:
             self.eng.decode_steps(n)
@@ -411,25 +453,38 @@ class ContinuousBatcher:
             complete = min(cur[s], r.max_length) - self.K
             if done:
                 rows.append((s, complete, 1, 0))
-            elif self._kept[s] + (complete - self._absorbed[s]) - self._emitted[s] - self.halo >= self._want(s):
+            elif self._kept[s] + self._new_raw(s, complete) - self._emitted[s] - self.halo >= self._want(s):
                 rows.append((s, complete, 0, self._want(s)))
-        if rows:
+        while rows:  # more than once only under stream_voice_prompts: a finished slot that had more than max_emit frames ready is drained here
             ptr, ld = self.eng.ids_buffer()
-            wave, out = self.model.audio_encoder.stream_decode(ptr, ld, rows, self.halo, col0=1, delay=1)
+            if self.stream_voice is None:
+                wave, out = self.model.audio_encoder.stream_decode(ptr, ld, rows, self.halo, col0=1, delay=1)
+            else:
+                wave, out = self.model.audio_encoder.stream_decode(ptr, ld, rows, self.halo, col0=1, delay=1, max_emit=self.max_emit)
             self.codec_passes += 1
             self.codec_rows += len(rows)
             hop = self.model._codec_hop()
             pairs = out.tolist()  # the pass's one host read: (emit, kept) per row
+            again = []
             for i, (s, complete, final, _) in enumerate(rows):
                 emit, kept = int(pairs[i][0]), int(pairs[i][1])
+                pk = self._slot[s].prompt_kept
+                if pk is not None:  # the kept frames of a skipped prompt count as emitted when they are absorbed
+                    self._emitted[s] += pk[min(len(pk) - 1, complete)] - pk[min(len(pk) - 1, self._absorbed[s])]
                 self._absorbed[s], self._kept[s] = complete, kept
                 self._emitted[s] += emit
+                flushed = bool(final) and self._emitted[s] >= kept  # a capped final pass may leave frames behind
+                if final and not flushed:
+                    if emit == 0:
+                        raise RuntimeError(f"stream table of slot {s}: {kept - self._emitted[s]} frames left and none emitted")
+                    again.append(rows[i])
                 t = self._slot[s].ticket
                 if emit > 0:
-                    self._out.append((t, wave[i, : emit * hop].clone(), bool(final)))
+                    self._out.append((t, wave[i, : emit * hop].clone(), flushed))
                     self._first_out[s] = False
                 elif final:  # nothing left to flush: the flag alone, or the reference's torch.zeros(1) for a request without any valid frame (:3641)
                     self._out.append((t, torch.zeros(1 if self._emitted[s] == 0 else 0, device=wave.device), True))
+            rows = again
         group = [(self._slot[s], self.eng.row_ids(s, cur[s])) for s in whole]
         for s in busy:
             if not live[s]:
@@ -439,9 +494,18 @@ class ContinuousBatcher:
             self.whole_requests += len(group)
             done_before = len(self._done)
             self._decode_group(group)
+            # stream_voice_prompts="skip": the samples of the prompt's kept frames are dropped here, on the host
+            drop = {r.ticket: self._whole_prompt_kept(r, ids) * self.model._codec_hop() for r, ids in group if r.prompt_kept is not None}
             while len(self._done) > done_before:
                 t, w, _ = self._done.pop()
-                self._out.append((t, w, True))
+                self._out.append((t, w[drop[t]:] if drop.get(t) else w, True))
+
+    def _whole_prompt_kept(self, r: _Request, ids: torch.Tensor) -> int:
+        """Frames of r's prompt in the waveform of the whole-utterance path (a request that ended below 2K - 1 columns): there `_codes` strips
+        nothing, a frame is a column, and the prompt's frames are columns 1 .. T (un-shifted where the request's max_length is below 2K - 1)."""
+        c = self._codes(ids, r.max_length, r.voice)[:, 1: 1 + r.T]
+        cb = int(self.model.audio_encoder.config.codebook_size)
+        return int(((c >= 0) & (c < cb)).all(dim=0).sum())
 
     def chunks(self) -> Iterator[Tuple[int, torch.Tensor, bool]]:
         """Streaming mode: yields (ticket, chunk, last) in the order chunks become available, until nothing is queued or running. The chunks of

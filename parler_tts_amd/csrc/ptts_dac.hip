@@ -20,11 +20,13 @@
 #include <string>
 #include <vector>
 #include <string.h>
+#include <limits.h>
 
 #include <algorithm>
 #include <type_traits>
 
 #include "ptts_common.h"
+#include "../../include/ptts_dac_stream_voice.h"
 
 namespace {
 
@@ -1013,9 +1015,11 @@ struct ptts_dac {
   // stream table (ptts_dac_stream_open): kept codes [slots][K][cap], counters [slots][4] = absorbed, kept, emitted, -; the plan of the pass in
   // flight [5][slots] = window length (the ragged `lens`), window start, skip and end in samples, slot. Host side: what the host knows without
   // reading the device - the raw frames absorbed (exact) and an upper bound of kept - emitted per slot.
-  int *st_tab = nullptr, *st_state = nullptr, *st_plan = nullptr;
-  int st_slots = 0, st_cap = 0;
-  std::vector<int> st_absorbed, st_ready_ub;
+  // Voice prompts (ptts_dac_stream_open_voice): the slots' prefixes [slots][K][st_pre_ld]; a slot's fourth counter is its prefix length,
+  // negative when the prompt's frames are not emitted. Host side: the same per slot (st_voice, signed alike).
+  int *st_tab = nullptr, *st_state = nullptr, *st_plan = nullptr, *st_pre = nullptr;
+  int st_slots = 0, st_cap = 0, st_pre_ld = 0;
+  std::vector<int> st_absorbed, st_ready_ub, st_voice;
 
   template <typename T> int alloc(T** p, size_t n) {
     void* v = nullptr;
@@ -1032,7 +1036,7 @@ extern "C" void ptts_dac_destroy(ptts_dac* d) {
   PttsDeviceGuard _dg(d->cfg.device);
   hipDeviceSynchronize();
   for (void* p : d->allocs) hipFree(p);
-  for (void* p : {(void*)d->st_tab, (void*)d->st_state, (void*)d->st_plan}) if (p) hipFree(p);
+  for (void* p : {(void*)d->st_tab, (void*)d->st_state, (void*)d->st_plan, (void*)d->st_pre}) if (p) hipFree(p);
   if (d->own_stream) hipStreamDestroy(d->own_stream);
   delete d;
 }
@@ -1459,50 +1463,86 @@ struct StreamRowsArg {
   int r0, n;
   ptts_dac_stream_row row[STREAM_ROWS];
 };
+// the voice twin's own arguments (include/ptts_dac_stream_voice.h): the slots' prefixes [slots][K][pre_ld] and the cap of one pass's emit
+struct StreamVoiceArg {
+  const int* pre;
+  int pre_ld, max_emit;
+};
 // compact_codes_kernel's ballot scan with an append offset and the (col0, delay) indexing of the raw id buffer; lane 0 then plans the row.
+// VOICE (ptts_dac_stream_decode_capped, or a table opened with prefix storage): raw frame f of a slot whose fourth counter holds a prefix
+// length T (negative: the prompt is not emitted) comes from the prefix for f < T; the kept frames among those count as emitted at once when
+// the prompt is skipped; emit is capped and the window ends `halo` kept frames behind what is emitted. Compile-time: the plain instance keeps
+// its code.
+template <bool VOICE>
 __global__ void __launch_bounds__(256) stream_absorb_kernel(StreamRowsArg ra, const long long* __restrict__ ids, long long ids_ld, int col0, int delay,
                                                             int K, int ncodes, int* __restrict__ tab, int cap, int* __restrict__ state, int halo,
                                                             int hop, int Tmax, long long wave_ld, int* __restrict__ p_lens, int* __restrict__ p_start,
                                                             int* __restrict__ p_skip, int* __restrict__ p_tend, int* __restrict__ p_slot,
-                                                            int* __restrict__ out) {
+                                                            int* __restrict__ out, StreamVoiceArg va) {
   __shared__ int s_wsum[4];
   __shared__ int s_base;
+  __shared__ int s_psum[4];  // VOICE: kept prompt frames of the block, per wave
+  __shared__ int s_pbase;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const ptts_dac_stream_row row = ra.row[blockIdx.x];
   const int r = ra.r0 + blockIdx.x;
   int* st = state + (size_t)row.slot * 4;
-  const int absorbed = st[0], kept0 = st[1], emitted = st[2];
+  const int absorbed = st[0], kept0 = st[1];
+  int emitted = st[2];
   const long long* src = ids + (size_t)row.slot * K * ids_ld + col0;
   int* dst = tab + (size_t)row.slot * K * cap;
-  if (tid == 0) s_base = 0;
+  // VOICE: the slot's prefix; a request that brings none has Tp == 0 and reads the id buffer alone
+  const int Tp = VOICE ? abs(st[3]) : 0;
+  const bool skip_prompt = VOICE && st[3] < 0;
+  const int* pre = VOICE && va.pre ? va.pre + (size_t)row.slot * K * va.pre_ld : nullptr;
+  auto raw = [&](int k, int f) -> long long {
+    if constexpr (VOICE) { if (f < Tp) return pre[(size_t)k * va.pre_ld + f]; }
+    return src[(size_t)k * ids_ld + f + k * delay];
+  };
+  if (tid == 0) {
+    s_base = 0;
+    if constexpr (VOICE) s_pbase = 0;
+  }
   __syncthreads();
   for (int c0 = absorbed; c0 < row.complete; c0 += 256) {
     const int f = c0 + tid;
     int keep = 0;
     if (f < row.complete) {
       keep = 1;
-      for (int k = 0; k < K; ++k) { const long long v = src[(size_t)k * ids_ld + f + k * delay]; if (v < 0 || v >= ncodes) keep = 0; }
+      for (int k = 0; k < K; ++k) { const long long v = raw(k, f); if (v < 0 || v >= ncodes) keep = 0; }
     }
     const unsigned long long m = __ballot(keep);
     const int before = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) s_wsum[wave] = __popcll(m);
+    if constexpr (VOICE) {
+      const unsigned long long mp = __ballot(keep && f < Tp);
+      if (lane == 0) s_psum[wave] = __popcll(mp);
+    }
     __syncthreads();
     int off = kept0 + s_base;
     for (int w2 = 0; w2 < wave; ++w2) off += s_wsum[w2];
     if (keep && off + before < cap)
-      for (int k = 0; k < K; ++k) dst[(size_t)k * cap + off + before] = (int)src[(size_t)k * ids_ld + f + k * delay];
+      for (int k = 0; k < K; ++k) dst[(size_t)k * cap + off + before] = (int)raw(k, f);
     __syncthreads();
-    if (tid == 0) s_base += s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+    if (tid == 0) {
+      s_base += s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+      if constexpr (VOICE) s_pbase += s_psum[0] + s_psum[1] + s_psum[2] + s_psum[3];
+    }
     __syncthreads();
   }
   if (tid != 0) return;
   const int kept = min(kept0 + s_base, cap);
+  // a skipped prompt: its kept frames are the head of the table (the prompt is absorbed first) and leave as they come in, as left context only
+  if (skip_prompt) emitted = min(emitted + s_pbase, kept);
   const int ready = kept - emitted;
   int emit = row.final ? ready : (ready - halo >= max(row.min_emit, 1) ? ready - halo : 0);
+  if constexpr (VOICE) emit = min(emit, va.max_emit);
   const int w0 = max(0, emitted - halo);
+  // the window's end: a capped emit leaves kept frames behind it, of which `halo` are its right context (uncapped: this is `kept`)
+  const int w1 = VOICE ? (int)min((long long)kept, (long long)emitted + emit + halo) : kept;
   // the host sized the launch and the output rows from upper bounds of these: never true, and if it were, no store leaves its buffer
-  if (emit < 0 || kept - w0 > Tmax || (long long)emit * hop > wave_ld) emit = 0;
-  p_lens[r] = emit > 0 ? kept - w0 : 0;
+  if (emit < 0 || w1 - w0 > Tmax || (long long)emit * hop > wave_ld) emit = 0;
+  p_lens[r] = emit > 0 ? w1 - w0 : 0;
   p_start[r] = w0;
   p_skip[r] = (emitted - w0) * hop;
   p_tend[r] = (emitted - w0 + emit) * hop;
@@ -1512,6 +1552,18 @@ __global__ void __launch_bounds__(256) stream_absorb_kernel(StreamRowsArg ra, co
   st[0] = row.complete;
   st[1] = kept;
   st[2] = emitted + emit;
+}
+
+// ptts_dac_stream_reset_voice: the slot's prefix int64 [K][T] -> int [K][pre_ld] (an id outside int's range becomes -1: the filter drops its
+// frame either way), and the slot's fourth counter: T, negative when the prompt's frames are not to be emitted
+__global__ void __launch_bounds__(256) stream_prefix_kernel(const long long* __restrict__ codes, int K, int T, int* __restrict__ pre, int pre_ld,
+                                                            int* __restrict__ st, int emit_prompt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < K * T) {
+    const long long v = codes[i];
+    pre[(size_t)(i / T) * pre_ld + i % T] = (v < 0 || v > 0x7fffffffll) ? -1 : (int)v;
+  }
+  if (i == 0) st[3] = emit_prompt ? T : -T;
 }
 
 // samples [hop * emit, wave_ld) of every row are zero (emit = out[2r], written by the absorb kernel of the same pass)
@@ -1709,27 +1761,40 @@ extern "C" int ptts_dac_decode_chunk(ptts_dac* d, const int64_t* codes_dev, int6
 }
 
 // ---- streaming out of a continuous session: include/ptts.h "streaming out of a continuous session" ----
-extern "C" int ptts_dac_stream_open(ptts_dac* d, int32_t slots, int32_t cap_frames, void* stream) {
+// max_voice_frames > 0: + the slots' prefix storage (ptts_dac_stream_open_voice)
+static int dac_stream_open(ptts_dac* d, int32_t slots, int32_t cap_frames, int32_t max_voice_frames, void* stream) {
   PTTS_CHECK(d, PTTS_E_INVALID, "null argument");
   PTTS_CHECK(slots >= 1 && slots <= d->cfg.max_batch, PTTS_E_CAPACITY, "stream slots %d exceed dac max_batch %d", slots, d->cfg.max_batch);
   PTTS_CHECK(cap_frames >= 1, PTTS_E_INVALID, "bad stream capacity %d", cap_frames);
+  PTTS_CHECK(max_voice_frames >= 0, PTTS_E_INVALID, "bad max_voice_frames %d", max_voice_frames);
   PTTS_DEVICE(d->cfg.device);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (slots != d->st_slots || cap_frames != d->st_cap) {
+  if (slots != d->st_slots || cap_frames != d->st_cap || max_voice_frames != d->st_pre_ld) {
     PTTS_HIP(hipStreamSynchronize(st));  // a pass in flight still reads the old table
-    for (int** p : {&d->st_tab, &d->st_state, &d->st_plan}) { if (*p) hipFree(*p); *p = nullptr; }
-    d->st_slots = d->st_cap = 0;
+    for (int** p : {&d->st_tab, &d->st_state, &d->st_plan, &d->st_pre}) { if (*p) hipFree(*p); *p = nullptr; }
+    d->st_slots = d->st_cap = d->st_pre_ld = 0;
     PTTS_HIP(hipMalloc((void**)&d->st_tab, (size_t)slots * d->cfg.num_codebooks * cap_frames * sizeof(int)));
     PTTS_HIP(hipMalloc((void**)&d->st_state, (size_t)slots * 4 * sizeof(int)));
     PTTS_HIP(hipMalloc((void**)&d->st_plan, (size_t)slots * 5 * sizeof(int)));
+    if (max_voice_frames > 0) PTTS_HIP(hipMalloc((void**)&d->st_pre, (size_t)slots * d->cfg.num_codebooks * max_voice_frames * sizeof(int)));
     d->st_slots = slots;
     d->st_cap = cap_frames;
+    d->st_pre_ld = max_voice_frames;
   }
   PTTS_HIP(hipMemsetAsync(d->st_state, 0, (size_t)slots * 4 * sizeof(int), st));
   PTTS_HIP(hipMemsetAsync(d->st_plan, 0, (size_t)slots * 5 * sizeof(int), st));
   d->st_absorbed.assign(slots, 0);
   d->st_ready_ub.assign(slots, 0);
+  d->st_voice.assign(slots, 0);
   return PTTS_OK;
+}
+
+extern "C" int ptts_dac_stream_open(ptts_dac* d, int32_t slots, int32_t cap_frames, void* stream) {
+  return dac_stream_open(d, slots, cap_frames, 0, stream);
+}
+
+extern "C" int ptts_dac_stream_open_voice(ptts_dac* d, int32_t slots, int32_t cap_frames, int32_t max_voice_frames, void* stream) {
+  return dac_stream_open(d, slots, cap_frames, max_voice_frames, stream);
 }
 
 extern "C" int ptts_dac_stream_reset(ptts_dac* d, int32_t slot, void* stream) {
@@ -1738,15 +1803,37 @@ extern "C" int ptts_dac_stream_reset(ptts_dac* d, int32_t slot, void* stream) {
   PTTS_CHECK(slot >= 0 && slot < d->st_slots, PTTS_E_INVALID, "stream slot %d out of range [0, %d)", slot, d->st_slots);
   PTTS_DEVICE(d->cfg.device);
   PTTS_HIP(hipMemsetAsync(d->st_state + (size_t)slot * 4, 0, 4 * sizeof(int), reinterpret_cast<hipStream_t>(stream)));
-  d->st_absorbed[slot] = d->st_ready_ub[slot] = 0;
+  d->st_absorbed[slot] = d->st_ready_ub[slot] = d->st_voice[slot] = 0;
   return PTTS_OK;
 }
 
-extern "C" int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64_t ids_ld, int32_t col0, int32_t delay,
-                                      const ptts_dac_stream_row* rows_host, int32_t R, int32_t halo, float* wave_dev, int64_t wave_ld,
-                                      int32_t* out_dev, void* stream) {
+extern "C" int ptts_dac_stream_reset_voice(ptts_dac* d, int32_t slot, const int64_t* codes_dev, int32_t T, int32_t emit_prompt, void* stream) {
+  PTTS_CHECK(d, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(d->st_slots > 0, PTTS_E_INVALID, "no stream table: call ptts_dac_stream_open first");
+  PTTS_CHECK(slot >= 0 && slot < d->st_slots, PTTS_E_INVALID, "stream slot %d out of range [0, %d)", slot, d->st_slots);
+  PTTS_CHECK(T >= 0, PTTS_E_INVALID, "bad voice prompt: %d frames", T);
+  if (T == 0) return ptts_dac_stream_reset(d, slot, stream);
+  PTTS_CHECK(d->st_pre, PTTS_E_INVALID, "the stream table has no prefix storage: open it with ptts_dac_stream_open_voice");
+  PTTS_CHECK(T <= d->st_pre_ld, PTTS_E_INVALID, "voice prompt of %d frames, the stream table was opened for %d", T, d->st_pre_ld);
+  PTTS_CHECK(codes_dev, PTTS_E_INVALID, "null voice prompt codes with %d frames", T);
+  PTTS_TRY(ptts_dac_stream_reset(d, slot, stream));
+  const int K = d->cfg.num_codebooks;
+  PTTS_DEVICE(d->cfg.device);
+  hipLaunchKernelGGL(stream_prefix_kernel, dim3((unsigned)(((size_t)K * T + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     (const long long*)codes_dev, K, T, d->st_pre + (size_t)slot * K * d->st_pre_ld, d->st_pre_ld, d->st_state + (size_t)slot * 4,
+                     emit_prompt);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "stream prefix launch failed: %s", hipGetErrorString(e));
+  d->st_voice[slot] = emit_prompt ? T : -T;
+  return PTTS_OK;
+}
+
+// max_emit == INT_MAX: no cap (ptts_dac_stream_decode). The plain kernel instance runs iff there is neither a cap nor prefix storage.
+static int dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64_t ids_ld, int32_t col0, int32_t delay, const ptts_dac_stream_row* rows_host,
+                             int32_t R, int32_t halo, float* wave_dev, int64_t wave_ld, int32_t* out_dev, void* stream, int32_t max_emit) {
   PTTS_CHECK(d && ids_dev && rows_host && wave_dev && out_dev, PTTS_E_INVALID, "null argument");
   PTTS_CHECK(d->st_slots > 0, PTTS_E_INVALID, "no stream table: call ptts_dac_stream_open first");
+  PTTS_CHECK(max_emit >= 1, PTTS_E_INVALID, "bad stream pass: max_emit %d", max_emit);
   PTTS_TRY(ptts_dac_weights_ready(d));
   const ptts_dac_config& c = d->cfg;
   const int K = c.num_codebooks;
@@ -1757,6 +1844,11 @@ extern "C" int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64
   int T = 0;
   long long emit_ub_max = 0;
   std::vector<char> seen(d->st_slots, 0);
+  // the bound of ready once [absorbed, complete) is in: every raw frame may be kept, but those of a skipped prompt never become ready
+  auto ready_bound = [&](const ptts_dac_stream_row& w) {
+    const int v = d->st_voice[w.slot], a = d->st_absorbed[w.slot];
+    return d->st_ready_ub[w.slot] + (v < 0 ? std::max(w.complete, -v) - std::max(a, -v) : w.complete - a);
+  };
   for (int r = 0; r < R; ++r) {
     const ptts_dac_stream_row& w = rows_host[r];
     PTTS_CHECK(w.slot >= 0 && w.slot < d->st_slots, PTTS_E_INVALID, "bad stream row %d: slot %d out of range [0, %d)", r, w.slot, d->st_slots);
@@ -1767,10 +1859,11 @@ extern "C" int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64
     PTTS_CHECK(w.complete <= d->st_cap, PTTS_E_INVALID, "bad stream row %d: complete %d beyond the table's %d frames", r, w.complete, d->st_cap);
     PTTS_CHECK((long long)col0 + w.complete + (long long)(K - 1) * delay <= ids_ld || w.complete == d->st_absorbed[w.slot], PTTS_E_INVALID,
                "bad stream row %d: complete %d reads beyond ids_ld %lld (col0 %d, delay %d)", r, w.complete, (long long)ids_ld, col0, delay);
-    const int ready_ub = d->st_ready_ub[w.slot] + (w.complete - d->st_absorbed[w.slot]);
-    const int emit_ub = w.final ? ready_ub : (ready_ub - halo >= std::max(w.min_emit, 1) ? ready_ub - halo : 0);
+    const int ready_ub = ready_bound(w);
+    const int emit_ub = std::min(w.final ? ready_ub : (ready_ub - halo >= std::max(w.min_emit, 1) ? ready_ub - halo : 0), max_emit);
     if (emit_ub > 0) {
-      T = std::max(T, std::min(halo + ready_ub, w.complete));  // the window holds kept frames only: never more than the raw frames
+      // the window holds kept frames only: never more than the raw frames; a capped emit has `halo` frames on either side
+      T = std::max<long long>(T, std::min<long long>({(long long)halo + ready_ub, w.complete, 2ll * halo + max_emit}));
       emit_ub_max = std::max<long long>(emit_ub_max, emit_ub);
     }
   }
@@ -1787,13 +1880,20 @@ extern "C" int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64
     ra.n = std::min(STREAM_ROWS, R - r0);
     memset(ra.row, 0, sizeof ra.row);
     memcpy(ra.row, rows_host + r0, (size_t)ra.n * sizeof(ptts_dac_stream_row));
-    hipLaunchKernelGGL(stream_absorb_kernel, dim3(ra.n), dim3(256), 0, st, ra, (const long long*)ids_dev, (long long)ids_ld, col0, delay, K, c.codebook_size,
-                       d->st_tab, d->st_cap, d->st_state, halo, d->hop, T, (long long)wave_ld, pl, pl + S, pl + 2 * S, pl + 3 * S, pl + 4 * S, (int*)out_dev);
+    auto absorb = [&](auto voice) {
+      hipLaunchKernelGGL((stream_absorb_kernel<decltype(voice)::value>), dim3(ra.n), dim3(256), 0, st, ra, (const long long*)ids_dev, (long long)ids_ld,
+                         col0, delay, K, c.codebook_size, d->st_tab, d->st_cap, d->st_state, halo, d->hop, T, (long long)wave_ld, pl, pl + S, pl + 2 * S,
+                         pl + 3 * S, pl + 4 * S, (int*)out_dev, StreamVoiceArg{d->st_pre, d->st_pre_ld, max_emit});
+    };
+    if (d->st_pre || max_emit != INT_MAX) absorb(std::true_type{});
+    else absorb(std::false_type{});
   }
   for (int r = 0; r < R; ++r) {
     const ptts_dac_stream_row& w = rows_host[r];
-    int ub = d->st_ready_ub[w.slot] + (w.complete - d->st_absorbed[w.slot]);
-    ub = w.final ? 0 : std::min(ub, halo + std::max(w.min_emit, 1) - 1);  // emitted: `halo` frames are left; not emitted: fewer than halo + min_emit were ready
+    const int before = ready_bound(w);
+    // emitted: `halo` frames are left; not emitted: fewer than halo + min_emit were ready; flushed: none. A capped emit leaves ready - max_emit
+    // (max_emit == INT_MAX: never the larger one)
+    const int ub = std::max(w.final ? 0 : std::min(before, halo + std::max(w.min_emit, 1) - 1), before - max_emit);
     d->st_ready_ub[w.slot] = ub;
     d->st_absorbed[w.slot] = w.complete;
   }
@@ -1806,6 +1906,18 @@ extern "C" int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return ptts_fail(PTTS_E_HIP, "stream decode launch failed: %s", hipGetErrorString(e));
   return PTTS_OK;
+}
+
+extern "C" int ptts_dac_stream_decode(ptts_dac* d, const int64_t* ids_dev, int64_t ids_ld, int32_t col0, int32_t delay,
+                                      const ptts_dac_stream_row* rows_host, int32_t R, int32_t halo, float* wave_dev, int64_t wave_ld,
+                                      int32_t* out_dev, void* stream) {
+  return dac_stream_decode(d, ids_dev, ids_ld, col0, delay, rows_host, R, halo, wave_dev, wave_ld, out_dev, stream, INT_MAX);
+}
+
+extern "C" int ptts_dac_stream_decode_capped(ptts_dac* d, const int64_t* ids_dev, int64_t ids_ld, int32_t col0, int32_t delay,
+                                             const ptts_dac_stream_row* rows_host, int32_t R, int32_t halo, float* wave_dev, int64_t wave_ld,
+                                             int32_t* out_dev, void* stream, int32_t max_emit) {
+  return dac_stream_decode(d, ids_dev, ids_ld, col0, delay, rows_host, R, halo, wave_dev, wave_ld, out_dev, stream, max_emit);
 }
 
 // DACModel.encode (dac_wrapper/modeling_dac.py:33-104) for one chunk: wave_dev float32 [B][L] with L a multiple of the hop

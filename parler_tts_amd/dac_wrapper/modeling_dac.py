@@ -222,11 +222,20 @@ class DACModel(torch.nn.Module):
         return DACDecoderOutput(eng.decode_chunk(codes, first_frame, n_frames, halo, out=out, n_emit=n_emit))
 
     # -- streaming out of a continuous session (not in the reference wrapper) -----------------------------------------
-    def stream_open(self, slots: int, cap_frames: int, window_frames: int):
+    def stream_open(self, slots: int, cap_frames: int, window_frames: int, max_voice_frames: int = 0):
         """Opens the per-slot stream table (``ptts_dac_stream_open``) in a codec engine sized ONCE for ``slots`` rows of ``window_frames``
         frames. The table lives in that engine: if a later ``decode`` / ``encode`` call needs more capacity and ``_get_engine`` replaces the
         engine, the table and the requests in flight are lost, and ``stream_reset`` / ``stream_decode`` raise ``RuntimeError`` until
-        ``stream_open`` is called again (the streaming ``ContinuousBatcher`` does that and restarts nothing: it lets the error surface)."""
+        ``stream_open`` is called again (the streaming ``ContinuousBatcher`` does that and restarts nothing: it lets the error surface).
+        ``max_voice_frames > 0``: the table also holds a voice prompt of up to that many frames per slot (``ptts_dac_stream_open_voice``),
+        and if the checkpoint has an encoder the engine is built with it and for that many frames, so that ``encode`` of such a prompt
+        (``submit(input_values=)``) does not replace the engine under the table - ``slots`` rows of activation buffers that long."""
+        if max_voice_frames:
+            has_enc = any(k.startswith("model.encoder.") for k in self._weights)
+            eng = self._get_engine(slots, max(window_frames, max_voice_frames) if has_enc else window_frames, need_encoder=has_enc, whole_batch=True)
+            eng.stream_open(slots, cap_frames, max_voice_frames=max_voice_frames)
+            self._stream_engine = eng
+            return eng
         eng = self._get_engine(slots, window_frames, whole_batch=True)
         eng.stream_open(slots, cap_frames)
         self._stream_engine = eng
@@ -241,13 +250,19 @@ class DACModel(torch.nn.Module):
                                "lost; call stream_open again")
         return self._stream_engine
 
-    def stream_reset(self, slot: int):
-        self._stream().stream_reset(slot)
+    def stream_reset(self, slot: int, voice=None, emit_prompt: bool = True):
+        """``DacEngine.stream_reset``: a new request enters ``slot``; ``voice`` [K, T]: the voice prompt it continues, emitted or not."""
+        if voice is None:
+            self._stream().stream_reset(slot)
+        else:
+            self._stream().stream_reset(slot, voice=voice, emit_prompt=emit_prompt)
 
     @torch.no_grad()
-    def stream_decode(self, ids, ids_ld, rows, halo: int, col0: int = 0, delay: int = 0):
+    def stream_decode(self, ids, ids_ld, rows, halo: int, col0: int = 0, delay: int = 0, max_emit: Optional[int] = None):
         """``DacEngine.stream_decode`` on the engine that holds the table: (wave [R, ld], out [R, 2] = (emit, kept)) on the device."""
-        return self._stream().stream_decode(ids, ids_ld, rows, halo, col0=col0, delay=delay)
+        if max_emit is None:
+            return self._stream().stream_decode(ids, ids_ld, rows, halo, col0=col0, delay=delay)
+        return self._stream().stream_decode(ids, ids_ld, rows, halo, col0=col0, delay=delay, max_emit=max_emit)
 
     def forward(self, tensor):
         raise ValueError("`DACModel.forward` not implemented yet")  # modeling_dac.py:144-145

@@ -625,22 +625,42 @@ class DacEngine:
         return dst
 
     # -- streaming out of a continuous session (ptts_dac_stream_open / _reset / _decode) ---------------------------
-    def stream_open(self, slots: int, cap_frames: int):
-        """(Re)allocates and clears the per-slot stream table: kept codes [slots, K, cap_frames] and the counters, on the device."""
-        N.check(self.lib.ptts_dac_stream_open(self._h, int(slots), int(cap_frames), _stream_ptr(device=self.device)), "ptts_dac_stream_open")
+    def stream_open(self, slots: int, cap_frames: int, max_voice_frames: int = 0):
+        """(Re)allocates and clears the per-slot stream table: kept codes [slots, K, cap_frames] and the counters, on the device.
+        ``max_voice_frames > 0``: plus the slots' voice prompts [slots, K, max_voice_frames] (``ptts_dac_stream_open_voice``)."""
+        if int(max_voice_frames):
+            N.check(self.lib.ptts_dac_stream_open_voice(self._h, int(slots), int(cap_frames), int(max_voice_frames), _stream_ptr(device=self.device)),
+                    "ptts_dac_stream_open_voice")
+        else:
+            N.check(self.lib.ptts_dac_stream_open(self._h, int(slots), int(cap_frames), _stream_ptr(device=self.device)), "ptts_dac_stream_open")
         self.stream_slots, self.stream_cap = int(slots), int(cap_frames)
         self._st_absorbed, self._st_ready_ub = [0] * int(slots), [0] * int(slots)  # the library's host-side bounds, mirrored to size `wave`
+        self._st_voice = [0] * int(slots)  # prefix frames per slot, negative where the prompt is not emitted (the library's st_voice)
 
-    def stream_reset(self, slot: int):
-        """A new request enters ``slot``: its counters return to 0 (enqueued)."""
-        N.check(self.lib.ptts_dac_stream_reset(self._h, int(slot), _stream_ptr(device=self.device)), "ptts_dac_stream_reset")
+    def stream_reset(self, slot: int, voice: Optional[torch.Tensor] = None, emit_prompt: bool = True):
+        """A new request enters ``slot``: its counters return to 0 (enqueued). ``voice``: the un-delayed codes int64 [K, T] of the voice prompt
+        it continues (``ptts_dac_stream_reset_voice``); ``emit_prompt=False``: the prompt's frames are left context only."""
+        T = 0
+        if voice is None:
+            N.check(self.lib.ptts_dac_stream_reset(self._h, int(slot), _stream_ptr(device=self.device)), "ptts_dac_stream_reset")
+        else:
+            if voice.dim() != 2 or voice.shape[0] != self.K:
+                raise ValueError(f"voice must be [{self.K}, frames], got {tuple(voice.shape)}")
+            voice = voice.to(self.device, torch.int64).contiguous()
+            T = int(voice.shape[1])
+            N.check(self.lib.ptts_dac_stream_reset_voice(self._h, int(slot), C.c_void_p(voice.data_ptr() if T else None), T, int(bool(emit_prompt)),
+                                                         _stream_ptr(device=self.device)), "ptts_dac_stream_reset_voice")
+            self._keep = voice
         self._st_absorbed[int(slot)] = self._st_ready_ub[int(slot)] = 0
+        self._st_voice[int(slot)] = T if emit_prompt else -T
 
-    def stream_decode(self, ids, ids_ld: Optional[int], rows, halo: int, col0: int = 0, delay: int = 0):
+    def stream_decode(self, ids, ids_ld: Optional[int], rows, halo: int, col0: int = 0, delay: int = 0, max_emit: Optional[int] = None):
         """One windowed codec pass over the listed slots (``ptts_dac_stream_decode``). ``ids``: an int64 device tensor [slots, K, ld] of plain
         codes (``col0=0, delay=0``), or the pointer of ``DecoderEngine.ids_buffer()`` with its stride ``ids_ld`` (``col0=1, delay=1``), read in
         place. ``rows``: ``(slot, complete, final, min_emit)`` per listed slot. Returns ``(wave float32 [R, ld], out int32 [R, 2])`` on the
-        device: row r holds ``hop * out[r, 0]`` samples (zero beyond), ``out[r] = (emit, kept)``. Enqueued on the current stream; no sync."""
+        device: row r holds ``hop * out[r, 0]`` samples (zero beyond), ``out[r] = (emit, kept)``. Enqueued on the current stream; no sync.
+        ``max_emit``: no row emits more kept frames than this in one pass (``ptts_dac_stream_decode_capped``); a ``final`` row that had more
+        ready is listed again until its emits add up."""
         if not getattr(self, "stream_slots", 0):
             raise ValueError("no stream table: call stream_open first")
         if isinstance(ids, torch.Tensor):
@@ -657,15 +677,25 @@ class DacEngine:
         for slot, complete, final, min_emit in rows:
             ub = 0
             if 0 <= slot < self.stream_slots:  # a bad descriptor is refused by the library with its own message
-                ub = self._st_ready_ub[slot] + max(0, complete - self._st_absorbed[slot])
+                v, a = self._st_voice[slot], self._st_absorbed[slot]
+                # the frames of a prompt that is not emitted never become ready
+                ub = self._st_ready_ub[slot] + (max(0, max(complete, -v) - max(a, -v)) if v < 0 else max(0, complete - a))
                 emit_ub = max(emit_ub, ub if final else ub - int(halo))
             bounds.append(ub)
+        if max_emit is not None:
+            emit_ub = min(emit_ub, max(int(max_emit), 1))
         wave = torch.empty(max(R, 1), self.hop * emit_ub, dtype=torch.float32, device=self.device)
         out = torch.empty(max(R, 1), 2, dtype=torch.int32, device=self.device)
-        N.check(self.lib.ptts_dac_stream_decode(self._h, C.c_void_p(ptr), ids_ld, int(col0), int(delay), arr, R, int(halo), C.c_void_p(wave.data_ptr()),
-                                                int(wave.shape[1]), C.c_void_p(out.data_ptr()), _stream_ptr(device=self.device)), "ptts_dac_stream_decode")
+        if max_emit is None:
+            N.check(self.lib.ptts_dac_stream_decode(self._h, C.c_void_p(ptr), ids_ld, int(col0), int(delay), arr, R, int(halo), C.c_void_p(wave.data_ptr()),
+                                                    int(wave.shape[1]), C.c_void_p(out.data_ptr()), _stream_ptr(device=self.device)), "ptts_dac_stream_decode")
+        else:
+            N.check(self.lib.ptts_dac_stream_decode_capped(self._h, C.c_void_p(ptr), ids_ld, int(col0), int(delay), arr, R, int(halo),
+                                                           C.c_void_p(wave.data_ptr()), int(wave.shape[1]), C.c_void_p(out.data_ptr()),
+                                                           _stream_ptr(device=self.device), int(max_emit)), "ptts_dac_stream_decode_capped")
         for (slot, complete, final, min_emit), ub in zip(rows, bounds):
-            self._st_ready_ub[slot] = 0 if final else min(ub, int(halo) + max(min_emit, 1) - 1)
+            left = 0 if final else min(ub, int(halo) + max(min_emit, 1) - 1)
+            self._st_ready_ub[slot] = left if max_emit is None else max(left, ub - int(max_emit))  # a capped emit leaves ready - max_emit
             self._st_absorbed[slot] = complete
         return wave, out
 
