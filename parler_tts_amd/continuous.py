@@ -30,7 +30,8 @@ _VOICE_ARGUMENTS = ("input_values", "decoder_input_ids")
 
 
 class _Request:
-    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept")
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept",
+                 "cols", "absorbed", "kept", "emitted", "first_out")
 
     def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None):
         self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
@@ -38,10 +39,24 @@ class _Request:
         self.voice = voice  # un-delayed codes [K, T >= 1] of the voice prompt the request continues (admit_row's `voice`), or None
         # stream_voice_prompts="skip": prompt_kept[n] = frames the special-id filter keeps of the prompt's first n, n = 0..T (else None)
         self.prompt_kept = prompt_kept
+        # The request's progress in its slot (it occupies one slot, once). cols: columns the slot holds if it has not stopped on EOS, set at
+        # admission (BOS + the given columns + the first token), then one per step.
+        self.cols = 0
+        # Streaming: raw frames the stream table has absorbed, frames it kept of them and frames emitted; the first chunk is still outstanding
+        self.absorbed, self.kept, self.emitted, self.first_out = 0, 0, 0, True
 
     @property
     def T(self) -> int:
         return 0 if self.voice is None else int(self.voice.shape[1])
+
+    @property
+    def skipped(self) -> int:
+        """Frames of the prompt that are never emitted (stream_voice_prompts="skip"), else 0."""
+        return 0 if self.prompt_kept is None else self.T
+
+    def new_raw(self, complete: int) -> int:
+        """Raw frames of [absorbed, complete) that may become ready: all of them, less those of a prompt that is not emitted."""
+        return max(complete, self.skipped) - max(self.absorbed, self.skipped)
 
 
 class ContinuousBatcher:
@@ -140,22 +155,19 @@ class ContinuousBatcher:
         # admit_batch > 1: the engine carries `spare` arena rows behind the slots, where a group of requests is prefilled in one pass
         self.spare = self.spare_rows(self.slots, int(admit_batch))
         self.admissions, self.admission_groups = 0, []  # requests admitted; sizes of the groups that went through admit_rows
-        if self.max_voice_frames:  # the prefill of one slot runs P + 1 + T positions
-            self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length, self.max_voice_frames)
-        else:
-            self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length)
+        # An option that is off adds nothing to a call: no fifth argument here, no keyword below. With voice prompts the prefill of one slot
+        # runs P + 1 + T positions
+        voice_room = (self.max_voice_frames,) if self.max_voice_frames else ()
+        self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length, *voice_room)
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
-        if getattr(self.eng, "kv_fp8", False):  # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
-            self.eng.begin_session(self.slots, self.N, self.P, kv_fp8=True)
-        else:
-            self.eng.begin_session(self.slots, self.N, self.P)
+        # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
+        self.eng.begin_session(self.slots, self.N, self.P, **({"kv_fp8": True} if getattr(self.eng, "kv_fp8", False) else {}))
         # what a request's own record starts from (submit): the session's values as the caller gave them (top_k is not zeroed for a greedy session)
         self._gen = dict(min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0), top_k=int(gc.top_k or 0),
                          top_p=float(gc.top_p if gc.top_p is not None else 1.0))
         self._queue: Deque[_Request] = collections.deque()
         self._slot: List[Optional[_Request]] = [None] * self.slots
-        self._cols = [0] * self.slots  # columns a busy slot holds if it has not stopped on EOS: BOS + first token + one per step
         self._done: Deque[Tuple[int, torch.Tensor, int]] = collections.deque()
         self._next_ticket = 0
         self.chunk = None if stream_chunk_frames is None else int(stream_chunk_frames)
@@ -170,15 +182,11 @@ class ContinuousBatcher:
             # without reading the device (ptts.h), which after dropped frames is looser by up to another chunk + halo
             big = max(self.chunk, self.first_chunk)
             self.window_frames = min(3 * self.halo + 2 * big + self.poll_steps + 8, max(self.max_length, 1))
-            if self.stream_voice is None:
-                ae.stream_open(self.slots, self.max_length, self.window_frames)
-            else:
-                ae.stream_open(self.slots, self.max_length, self.window_frames, max_voice_frames=self.max_voice_frames)
+            ae.stream_open(self.slots, self.max_length, self.window_frames, **({} if self.stream_voice is None else {"max_voice_frames": self.max_voice_frames}))
+            if self.stream_voice is not None:
                 # a capped window = halo + max_emit + halo frames. A request without a prompt has fewer than chunk + poll_steps frames to emit
                 # at a poll, which is below this cap; a window as long as the longest request needs none
                 self.max_emit = self.window_frames - 2 * self.halo if self.window_frames < self.max_length else self.max_length
-            self._absorbed, self._kept, self._emitted = [0] * self.slots, [0] * self.slots, [0] * self.slots
-            self._first_out = [False] * self.slots  # the request's first chunk is still outstanding
             self._out: Deque[Tuple[int, torch.Tensor, bool]] = collections.deque()
             self.codec_passes, self.codec_rows, self.whole_requests = 0, 0, 0  # passes, listed rows, requests that ended below 2K - 1 columns
 
@@ -276,8 +284,7 @@ class ContinuousBatcher:
         self._next_ticket += 1
         prompt_kept = None
         if voice is not None and self.stream_voice == "skip":  # what the filter keeps of the prompt, known here: the codec's pairs do not say
-            cb = int(self.model.audio_encoder.config.codebook_size)
-            prompt_kept = [0] + ((voice >= 0) & (voice < cb)).all(dim=0).long().cumsum(0).tolist()
+            prompt_kept = [0] + self._valid_frames(voice).long().cumsum(0).tolist()
         self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept))
         return ticket
 
@@ -309,234 +316,196 @@ class ContinuousBatcher:
         """Requests queued or in a slot (finished ones waiting to be iterated are not counted)."""
         return len(self._queue) + sum(r is not None for r in self._slot)
 
-    def _admit_into(self, s: int, r: _Request):
-        """The one admission of both modes. A request without a record of its own goes through the same call as ever (no `gen` keyword)."""
-        kw = {} if r.gen is None else {"gen": dict(r.gen)}
-        if r.voice is not None:
-            kw["voice"] = r.voice
-        self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True, **kw)
-        self._slot[s], self._cols[s] = r, 2 + r.T  # BOS + the given columns + the first token
-        self.admissions += 1
-
-    def _admit_group(self, group):
-        """[(slot, request), ...] of 2 .. spare pairs through ONE prefill pass (``admit_rows``)."""
-        reqs = [r for _, r in group]
-        stack = lambda ts: None if ts[0] is None else torch.stack(list(ts))
-        gens = None if all(r.gen is None for r in reqs) else [None if r.gen is None else dict(r.gen) for r in reqs]
-        self.eng.admit_rows([s for s, _ in group], stack([r.enc for r in reqs]), stack([r.enc_mask for r in reqs]), stack([r.prompt for r in reqs]),
-                            stack([r.prompt_mask for r in reqs]), max_lengths=[r.max_length for r in reqs], sample=True, gens=gens)
-        for s, r in group:
-            self._slot[s], self._cols[s] = r, 2
-        self.admissions += len(group)
-        self.admission_groups.append(len(group))
-
-    def _admit_queued(self, admitted=None):
-        """Idle slots in ascending order take the queue in FIFO order; ``admitted(slot)`` runs behind each admission. Without spare rows
-        (``admit_batch=1``) every pair is one ``admit_row``; with them the pairs go in groups of at most ``spare`` through ``admit_rows``
-        (a group of one: ``admit_row``). A request with a voice prompt ends the group before it and goes alone (``admit_rows`` takes none);
-        which request meets which slot does not change."""
-        if not self.spare:
-            for s in range(self.slots):
-                if self._slot[s] is None and self._queue:
-                    self._admit_into(s, self._queue.popleft())
-                    if admitted is not None:
-                        admitted(s)
-            return
-        idle = [s for s in range(self.slots) if self._slot[s] is None][: len(self._queue)]
-        pairs = [(s, self._queue.popleft()) for s in idle]
-        groups = [[]]
-        for pair in pairs:
-            if pair[1].voice is not None:
-                groups += [[pair], []]
+    def _admit(self):
+        """The one admission path of both modes. Idle slots in ascending order meet the queue in FIFO order; the pairs are cut into groups of
+        at most ``max(spare, 1)``, a request with a voice prompt going alone (``admit_rows`` takes none). A group of one is one ``admit_row``, a
+        larger one ONE prefill pass (``admit_rows``); behind each group its slots' stream tables are reset (streaming mode). A request
+        leaves the queue immediately before the engine call that admits it: if that call raises, the requests behind it are still queued."""
+        groups = []
+        for s, r in zip((s for s in range(self.slots) if self._slot[s] is None), self._queue):
+            full = not groups or len(groups[-1]) == max(self.spare, 1)
+            if full or r.voice is not None or groups[-1][0][1].voice is not None:
+                groups.append([])
+            groups[-1].append((s, r))
+        for group in groups:
+            reqs = [self._queue.popleft() for _ in group]
+            if len(reqs) == 1:
+                (s, r), = group
+                # a request without a record or a prompt of its own goes through the same call as ever (no `gen`, no `voice` keyword)
+                kw = {} if r.gen is None else {"gen": dict(r.gen)}
+                if r.voice is not None:
+                    kw["voice"] = r.voice
+                self.eng.admit_row(s, r.enc, r.enc_mask, r.prompt, r.prompt_mask, max_length=r.max_length, sample=True, **kw)
             else:
-                if len(groups[-1]) == self.spare:
-                    groups.append([])
-                groups[-1].append(pair)
-        for group in [g for g in groups if g]:
-            if len(group) == 1:
-                self._admit_into(*group[0])
-            else:
-                self._admit_group(group)
-            if admitted is not None:
-                for s, _ in group:
-                    admitted(s)
+                stack = lambda ts: None if ts[0] is None else torch.stack(ts)
+                gens = None if all(r.gen is None for r in reqs) else [None if r.gen is None else dict(r.gen) for r in reqs]
+                self.eng.admit_rows([s for s, _ in group], stack([r.enc for r in reqs]), stack([r.enc_mask for r in reqs]), stack([r.prompt for r in reqs]),
+                                    stack([r.prompt_mask for r in reqs]), max_lengths=[r.max_length for r in reqs], sample=True, gens=gens)
+                self.admission_groups.append(len(group))
+            self.admissions += len(group)
+            for s, r in group:
+                self._slot[s], r.cols = r, 2 + r.T  # BOS + the given columns + the first token
+                if self.chunk is not None:  # a prompt comes only with stream_voice_prompts: submit refuses it otherwise
+                    voice = {} if r.voice is None else {"voice": r.voice, "emit_prompt": self.stream_voice == "emit"}
+                    self.model.audio_encoder.stream_reset(s, **voice)
+
+    def _retire(self, s: int):
+        self.eng.retire_row(s)
+        self._slot[s] = None
 
     def _poll(self):
-        """Admit FIFO into idle slots, run the live slots up to the next boundary, collect what finished."""
-        self._admit_queued()
-        busy = [s for s in range(self.slots) if self._slot[s] is not None]
+        """Admit, run the live slots up to the next boundary, hand out what is ready. The boundary: ``poll_steps``, or the nearest end by
+        max_length - the host knows it and meets it exactly, so that its slot is refilled at once; EOS ends show at a poll - or, streaming,
+        the nearest first chunk. Streaming then lists every slot that has a chunk ready or has finished for ONE codec pass."""
+        self._admit()
+        busy = [(s, r) for s, r in enumerate(self._slot) if r is not None]
         if not busy:
             return
-        # the nearest end by max_length is known to the host: meet it exactly, so that its slot is refilled at once; EOS ends show at a poll
-        n = max(0, min(min(self._slot[s].max_length - self._cols[s] for s in busy), self.poll_steps))
+        n = min(min(r.max_length - r.cols for _, r in busy), self.poll_steps)
+        if self.chunk is not None:
+            for _, r in busy:
+                f = self._first_chunk_steps(r)
+                if f is not None and f >= 1:
+                    n = min(n, f)
+                elif f is not None and r.voice is not None:
+                    n = 0  # the prompt alone holds the first chunk: the codec pass comes before any further step
         if n > 0:
             self.eng.decode_steps(n)
-            for s in busy:
-                self._cols[s] = min(self._cols[s] + n, self._slot[s].max_length)
+            for _, r in busy:
+                r.cols = min(r.cols + n, r.max_length)
         cur, live = self.eng.row_state()
-        finished = [s for s in busy if not live[s]]
-        if not finished:
-            return
-        group = [(self._slot[s], self.eng.row_ids(s, cur[s])) for s in finished]
-        for s in finished:
-            self.eng.retire_row(s)
-            self._slot[s] = None
-        self._decode_group(group)
+        if self.chunk is None:
+            whole = [(s, r) for s, r in busy if not live[s]]  # what finished at one poll is decoded whole, as one ragged batch
+        else:
+            rows, whole = self._stream_rows(busy, cur, live)
+            while rows:  # more than once only under stream_voice_prompts: a finished slot that had more than max_emit frames ready is drained here
+                rows = self._codec_pass(rows)
+        group = [(r, self.eng.row_ids(s, cur[s])) for s, r in whole]
+        for s, _ in busy:
+            if not live[s]:
+                self._retire(s)
+        if group:
+            self._decode_group(group)
+            if self.chunk is not None:
+                self._whole_to_chunks(group)
 
     # -- streaming ----------------------------------------------------------------------------------------------------------------
-    def _admit(self):
-        def fresh_stream(s):
-            r = self._slot[s]
-            if r.voice is None:
-                self.model.audio_encoder.stream_reset(s)
-            else:  # only with stream_voice_prompts: submit refuses the prompt otherwise
-                self.model.audio_encoder.stream_reset(s, voice=r.voice, emit_prompt=self.stream_voice == "emit")
-            self._absorbed[s] = self._kept[s] = self._emitted[s] = 0
-            self._first_out[s] = True
-
-        self._admit_queued(fresh_stream)
-
-    def _skipped(self, s: int) -> int:
-        """Frames of slot s's prompt that are never emitted (stream_voice_prompts="skip"), else 0."""
-        return 0 if self._slot[s].prompt_kept is None else self._slot[s].T
-
-    def _new_raw(self, s: int, complete: int) -> int:
-        """Raw frames of [absorbed, complete) that may become ready: all of them, less those of a prompt that is not emitted."""
-        T = self._skipped(s)
-        return max(complete, T) - max(self._absorbed[s], T)
-
-    def _streams(self, s: int, cur: int) -> bool:
-        """Whether slot s's frames can be named yet: below 2K - 1 columns build_delay_pattern_mask applies no pattern at all, and `cur` alone
+    def _streams(self, r: _Request, cur: int) -> bool:
+        """Whether r's frames can be named yet: below 2K - 1 columns build_delay_pattern_mask applies no pattern at all, and `cur` alone
         cannot tell which un-delay the finished request will get; a request whose max_length is below 2K - 1 never gets the pattern."""
-        return self._slot[s].max_length >= 2 * self.K - 1 and cur >= 2 * self.K - 1
+        return r.max_length >= 2 * self.K - 1 and cur >= 2 * self.K - 1
 
-    def _want(self, s: int) -> int:
-        return self.first_chunk if self._first_out[s] else self.chunk
+    def _want(self, r: _Request) -> int:
+        return self.first_chunk if r.first_out else self.chunk
 
-    def _first_chunk_steps(self, s: int) -> Optional[int]:
-        """Steps until slot s, whose first chunk is outstanding, can have it (no frame dropped from here on): kept + new raw frames - emitted
+    def _first_chunk_steps(self, r: _Request) -> Optional[int]:
+        """Steps until r, whose first chunk is outstanding, can have it (no frame dropped from here on): kept + new raw frames - emitted
         - halo >= first_chunk with complete = columns - K, i.e. first_chunk + halo + K columns on a clean request."""
-        if not self._first_out[s] or self._slot[s].max_length < 2 * self.K - 1:
+        if not r.first_out or r.max_length < 2 * self.K - 1:
             return None
-        need = self.first_chunk + self.halo - (self._kept[s] - self._emitted[s])  # raw frames still to absorb
+        need = self.first_chunk + self.halo - (r.kept - r.emitted)  # raw frames still to absorb
         # the frames of a prompt that is not emitted do not count. A prompt that is emitted may hold the first chunk at admission: <= 0 then
-        cols = max(2 * self.K - 1, max(self._absorbed[s], self._skipped(s)) + need + self.K)
-        return cols - self._cols[s]
+        cols = max(2 * self.K - 1, max(r.absorbed, r.skipped) + need + self.K)
+        return cols - r.cols
 
-    def _poll_stream(self):
-        """Admit, run to the next boundary (a poll, the nearest max_length end, or the nearest first chunk), then ONE codec pass over every
-        slot that has a chunk ready or has finished."""
-        self._admit()
-        busy = [s for s in range(self.slots) if self._slot[s] is not None]
-        if not busy:
-            return
-        n = min(min(self._slot[s].max_length - self._cols[s] for s in busy), self.poll_steps)
-        for s in busy:
-            f = self._first_chunk_steps(s)
-            if f is not None and f >= 1:
-                n = min(n, f)
-            elif f is not None and self._slot[s].voice is not None:
-                n = 0  # the prompt alone holds the first chunk: the codec pass comes before any further step
-        n = max(0, n)
-        if n > 0:
-            self.eng.decode_steps(n)
-            for s in busy:
-                self._cols[s] = min(self._cols[s] + n, self._slot[s].max_length)
-        cur, live = self.eng.row_state()
+    def _stream_rows(self, busy, cur, live):
+        """The rows ``(slot, complete, final, min_emit)`` of this poll's codec pass - a finished slot, and a live one that by the host's count
+        has a chunk ready - and the ``(slot, request)`` pairs that ended below 2K - 1 columns: those go the whole-utterance way."""
         rows, whole = [], []
-        for s in busy:
-            r, done = self._slot[s], not live[s]
-            if not self._streams(s, cur[s]):
+        for s, r in busy:
+            done = not live[s]
+            if not self._streams(r, cur[s]):
                 if done:
-                    whole.append(s)  # ended below 2K - 1 columns: today's un-delay + filtered decode, as one last chunk
+                    whole.append((s, r))
                 continue
             complete = min(cur[s], r.max_length) - self.K
             if done:
                 rows.append((s, complete, 1, 0))
-            elif self._kept[s] + self._new_raw(s, complete) - self._emitted[s] - self.halo >= self._want(s):
-                rows.append((s, complete, 0, self._want(s)))
-        while rows:  # more than once only under stream_voice_prompts: a finished slot that had more than max_emit frames ready is drained here
-            ptr, ld = self.eng.ids_buffer()
-            if self.stream_voice is None:
-                wave, out = self.model.audio_encoder.stream_decode(ptr, ld, rows, self.halo, col0=1, delay=1)
-            else:
-                wave, out = self.model.audio_encoder.stream_decode(ptr, ld, rows, self.halo, col0=1, delay=1, max_emit=self.max_emit)
-            self.codec_passes += 1
-            self.codec_rows += len(rows)
-            hop = self.model._codec_hop()
-            pairs = out.tolist()  # the pass's one host read: (emit, kept) per row
-            again = []
-            for i, (s, complete, final, _) in enumerate(rows):
-                emit, kept = int(pairs[i][0]), int(pairs[i][1])
-                pk = self._slot[s].prompt_kept
-                if pk is not None:  # the kept frames of a skipped prompt count as emitted when they are absorbed
-                    self._emitted[s] += pk[min(len(pk) - 1, complete)] - pk[min(len(pk) - 1, self._absorbed[s])]
-                self._absorbed[s], self._kept[s] = complete, kept
-                self._emitted[s] += emit
-                flushed = bool(final) and self._emitted[s] >= kept  # a capped final pass may leave frames behind
-                if final and not flushed:
-                    if emit == 0:
-                        raise RuntimeError(f"stream table of slot {s}: {kept - self._emitted[s]} frames left and none emitted")
-                    again.append(rows[i])
-                t = self._slot[s].ticket
-                if emit > 0:
-                    self._out.append((t, wave[i, : emit * hop].clone(), flushed))
-                    self._first_out[s] = False
-                elif final:  # nothing left to flush: the flag alone, or the reference's torch.zeros(1) for a request without any valid frame (:3641)
-                    self._out.append((t, torch.zeros(1 if self._emitted[s] == 0 else 0, device=wave.device), True))
-            rows = again
-        group = [(self._slot[s], self.eng.row_ids(s, cur[s])) for s in whole]
-        for s in busy:
-            if not live[s]:
-                self.eng.retire_row(s)
-                self._slot[s] = None
-        if group:
-            self.whole_requests += len(group)
-            done_before = len(self._done)
-            self._decode_group(group)
-            # stream_voice_prompts="skip": the samples of the prompt's kept frames are dropped here, on the host
-            drop = {r.ticket: self._whole_prompt_kept(r, ids) * self.model._codec_hop() for r, ids in group if r.prompt_kept is not None}
-            while len(self._done) > done_before:
-                t, w, _ = self._done.pop()
-                self._out.append((t, w[drop[t]:] if drop.get(t) else w, True))
+            elif r.kept + r.new_raw(complete) - r.emitted - self.halo >= self._want(r):
+                rows.append((s, complete, 0, self._want(r)))
+        return rows, whole
+
+    def _codec_pass(self, rows):
+        """ONE windowed codec pass over ``rows``: the requests' counts follow the pass's ``(emit, kept)`` pairs and the chunks go to ``_out``.
+        Returns the rows to list again: final ones that a capped pass has not flushed yet."""
+        ptr, ld = self.eng.ids_buffer()
+        cap = {} if self.stream_voice is None else {"max_emit": self.max_emit}
+        wave, out = self.model.audio_encoder.stream_decode(ptr, ld, rows, self.halo, col0=1, delay=1, **cap)
+        self.codec_passes += 1
+        self.codec_rows += len(rows)
+        hop = self.model._codec_hop()
+        pairs = out.tolist()  # the pass's one host read: (emit, kept) per row
+        again = []
+        for i, (s, complete, final, _) in enumerate(rows):
+            r, emit, kept = self._slot[s], int(pairs[i][0]), int(pairs[i][1])
+            pk = r.prompt_kept
+            if pk is not None:  # the kept frames of a skipped prompt count as emitted when they are absorbed
+                r.emitted += pk[min(len(pk) - 1, complete)] - pk[min(len(pk) - 1, r.absorbed)]
+            r.absorbed, r.kept = complete, kept
+            r.emitted += emit
+            flushed = bool(final) and r.emitted >= kept  # a capped final pass may leave frames behind
+            if final and not flushed:
+                if emit == 0:
+                    raise RuntimeError(f"stream table of slot {s}: {kept - r.emitted} frames left and none emitted")
+                again.append(rows[i])
+            if emit > 0:
+                self._out.append((r.ticket, wave[i, : emit * hop].clone(), flushed))
+                r.first_out = False
+            elif final:  # nothing left to flush: the flag alone, or the reference's torch.zeros(1) for a request without any valid frame (:3641)
+                self._out.append((r.ticket, torch.zeros(1 if r.emitted == 0 else 0, device=wave.device), True))
+        return again
+
+    def _whole_to_chunks(self, group):
+        """The requests that ended below 2K - 1 columns went through the un-delay + filtered decode of the other mode (``_decode_group``):
+        each waveform leaves as one last chunk."""
+        self.whole_requests += len(group)
+        # stream_voice_prompts="skip": the samples of the prompt's kept frames are dropped here, on the host
+        drop = {r.ticket: self._whole_prompt_kept(r, ids) * self.model._codec_hop() for r, ids in group if r.prompt_kept is not None}
+        while self._done:  # a streaming batcher keeps nothing else there
+            t, w, _ = self._done.pop()
+            self._out.append((t, w[drop[t]:] if drop.get(t) else w, True))
+
+    def _valid_frames(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes [K, frames] -> bool [frames]: the frames whose ids all lie in [0, codebook_size), the ones the special-id filter keeps."""
+        cb = int(self.model.audio_encoder.config.codebook_size)
+        return ((codes >= 0) & (codes < cb)).all(dim=0)
 
     def _whole_prompt_kept(self, r: _Request, ids: torch.Tensor) -> int:
         """Frames of r's prompt in the waveform of the whole-utterance path (a request that ended below 2K - 1 columns): there `_codes` strips
         nothing, a frame is a column, and the prompt's frames are columns 1 .. T (un-shifted where the request's max_length is below 2K - 1)."""
-        c = self._codes(ids, r.max_length, r.voice)[:, 1: 1 + r.T]
-        cb = int(self.model.audio_encoder.config.codebook_size)
-        return int(((c >= 0) & (c < cb)).all(dim=0).sum())
+        return int(self._valid_frames(self._codes(ids, r.max_length, r.voice)[:, 1: 1 + r.T]).sum())
+
+    def _drain(self, out: Deque):
+        """Hands out what is in ``out`` (``_done`` or ``_out``: where the mode's polls put their results) until nothing is queued or running."""
+        with torch.no_grad():
+            while out or self.pending():
+                if not out:
+                    self._poll()
+                while out:
+                    yield out.popleft()
 
     def chunks(self) -> Iterator[Tuple[int, torch.Tensor, bool]]:
         """Streaming mode: yields (ticket, chunk, last) in the order chunks become available, until nothing is queued or running. The chunks of
         a ticket concatenate to the waveform the non-streaming mode yields for the same request; ``last`` is True exactly once per ticket."""
         if self.chunk is None:
             raise RuntimeError("chunks() needs streaming mode: construct the batcher with `stream_chunk_frames`")
-        with torch.no_grad():
-            while self._out or self.pending():
-                if not self._out:
-                    self._poll_stream()
-                while self._out:
-                    yield self._out.popleft()
+        yield from self._drain(self._out)
 
     def cancel(self, ticket: int) -> bool:
         """Drops a request: a queued one leaves the queue, one in a slot is retired (``ptts_retire_row``: the slot is idle for the next
         admission), and nothing of it that is waiting to be handed out follows. False if the ticket is unknown or already finished."""
-        found = False
-        for r in list(self._queue):
-            if r.ticket == ticket:
-                self._queue.remove(r)
-                found = True
-        for s in range(self.slots):
-            if self._slot[s] is not None and self._slot[s].ticket == ticket:
-                self.eng.retire_row(s)
-                self._slot[s] = None
-                found = True
-        if found:
-            self._done = collections.deque(d for d in self._done if d[0] != ticket)
-            if self.chunk is not None:
-                self._out = collections.deque(c for c in self._out if c[0] != ticket)
-        return found
+        queued = [r for r in self._queue if r.ticket == ticket]
+        for r in queued:
+            self._queue.remove(r)
+        running = [s for s, r in enumerate(self._slot) if r is not None and r.ticket == ticket]
+        for s in running:
+            self._retire(s)
+        if queued or running:
+            out = self._done if self.chunk is None else self._out  # in place: a generator of _drain holds on to it
+            rest = [x for x in out if x[0] != ticket]
+            out.clear()
+            out.extend(rest)
+        return bool(queued or running)
 
     def _codes(self, ids: torch.Tensor, max_length: int, voice: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Raw ids [K, columns] of one request -> its un-delayed audio codes [K, frames] (generate()'s tail, modeling_parler_tts.py:3585-3600).
@@ -577,12 +546,7 @@ class ContinuousBatcher:
         """Yields (ticket, waveform, length) in the order requests finish, until nothing is queued or running."""
         if self.chunk is not None:
             raise RuntimeError("this batcher streams (`stream_chunk_frames`): iterate chunks() instead")
-        with torch.no_grad():
-            while self._done or self.pending():
-                if not self._done:
-                    self._poll()
-                while self._done:
-                    yield self._done.popleft()
+        yield from self._drain(self._done)
 
     def run(self, requests: Iterable[Dict]) -> List[Tuple[torch.Tensor, int]]:
         """``requests``: the keyword arguments of ``submit``, one dict per request. Returns (waveform, length) per request, in submission order."""
@@ -595,5 +559,4 @@ class ContinuousBatcher:
         self._queue.clear()
         for s in range(self.slots):
             if self._slot[s] is not None:
-                self.eng.retire_row(s)
-                self._slot[s] = None
+                self._retire(s)

@@ -139,6 +139,51 @@ def test_a_group_of_one_goes_through_admit_row():
     assert len(out) == 5 and eng.groups == [([0, 1, 2, 3], 0)] and eng.singles == [4]
 
 
+class RefusingEngine(GroupSessionEngine):
+    """Raises ``ValueError`` from the call that is handed the request whose encoded description is ``refuse``, before changing any state."""
+
+    refuse = None
+
+    def admit_row(self, row, enc, *a, **k):
+        if self.refuse is not None and not getattr(self, "_in_group", False) and torch.equal(enc, self.refuse):
+            raise ValueError("refused by the engine")
+        super().admit_row(row, enc, *a, **k)
+
+    def admit_rows(self, rows, enc, *a, **k):
+        if self.refuse is not None and any(torch.equal(e, self.refuse) for e in enc):
+            raise ValueError("refused by the engine")
+        super().admit_rows(rows, enc, *a, **k)
+
+
+@pytest.mark.parametrize("slots,admit_batch,bad,lost,queued", [(3, 1, 1, [1], [2, 3, 4, 5]), (9, 4, 2, [0, 1, 2, 3], [4, 5]), (9, 4, 5, [4, 5], [])])
+def test_an_admission_that_raises_loses_only_what_was_handed_to_the_failing_call(slots, admit_batch, bad, lost, queued):
+    """Six requests meet idle slots at the first poll and the engine refuses the call that carries ticket `bad`. A request leaves the queue
+    immediately before the call that admits it (alone, or with its group of up to 4): the request or group of the failing call is lost, the
+    admissions before it stand, the requests behind it are still queued, and iterating on finishes all of those as a clean run does."""
+    reqs = [dict(r, max_new_tokens=12) for r in TS._requests(6, seed=5)]
+
+    def batcher():
+        m, spec, sd, dac, _ = _model()
+        eng = RefusingEngine(spec, sd)
+        m._get_engine = lambda *a: eng
+        return P.ContinuousBatcher(m, slots=slots, admit_batch=admit_batch, **KW), eng
+
+    clean = batcher()[0].run(reqs)
+    cb, eng = batcher()
+    tickets = [cb.submit(**r) for r in reqs]
+    eng.refuse = cb._queue[bad].enc
+    with pytest.raises(ValueError, match="refused by the engine"):
+        next(iter(cb))
+    stand = [t for t in tickets if t not in lost + queued]
+    assert [r.ticket for r in cb._queue] == queued
+    assert [r.ticket for r in cb._slot if r is not None] == stand and [f is not None for f in eng.full] == [s < len(stand) for s in range(slots)]
+    assert cb.admissions == len(stand) and cb.pending() == 6 - len(lost) and eng.steps == 0
+    got = {t: (w, n) for t, w, n in cb}
+    assert sorted(got) == sorted(stand + queued) and cb.pending() == 0
+    for t, (w, n) in got.items():
+        assert n == clean[t][1] == w.shape[0] and torch.equal(w, clean[t][0]), t
+
+
 def test_header_and_ctypes_prototypes_of_ptts_admit_rows_agree(tmp_path):
     """The new entry point is additive: include/ptts.h keeps its declarations and ABI version 8 and includes include/ptts_session.h, which
     declares ptts_admit_rows; _native.SESSION_SYMBOLS binds it beside the SYMBOLS of ptts.h."""

@@ -95,7 +95,7 @@ def ttfc(frames_list, repeats):
                 first = None
                 with torch.no_grad():
                     for _ in range(8):  # the others have been decoding (and streaming) for 8 polls when the voice request arrives
-                        cb._poll_stream() if mode else cb._poll()
+                        cb._poll()
                     voice_ticket = cb.submit(desc[-1], prompt_input_ids=prompt[-1], max_new_tokens=voice_new, decoder_input_ids=codes)
                     for t, w, _ in (cb.chunks() if mode else iter(cb)):
                         if t == voice_ticket:
