@@ -36,6 +36,11 @@ class PttsGenParams(C.Structure):
     ]
 
 
+class PttsHistoryPenalty(C.Structure):
+    """ptts_history_penalty (include/ptts_penalty.h)."""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
+
+
 class PttsT5Config(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32), ("d_model", C.c_int32), ("d_kv", C.c_int32), ("d_ff", C.c_int32), ("num_layers", C.c_int32),
@@ -135,6 +140,12 @@ DAC_STREAM_VOICE_SYMBOLS = {
     "ptts_dac_stream_decode_capped": (C.c_int, [_VP, _VP, C.c_int64, _I32, _I32, C.POINTER(PttsDacStreamRow), _I32, _I32, _VP, C.c_int64, _VP, _VP, _I32]),
 }
 
+# include/ptts_penalty.h, additive likewise: repetition_penalty / no_repeat_ngram_size as a device node in front of the sampler tail
+PENALTY_SYMBOLS = {
+    "ptts_set_history_penalty": (C.c_int, [_VP, C.POINTER(PttsHistoryPenalty), _VP]),
+    "ptts_set_slot_history_penalty": (C.c_int, [_VP, _I32, C.POINTER(PttsHistoryPenalty), _VP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -157,7 +168,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 missing
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
     for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
-                              + list(SESSION_VOICE_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items())):
+                              + list(SESSION_VOICE_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -22,18 +22,21 @@ from typing import Deque, Dict, Iterable, Iterator, List, Optional, Tuple
 
 import torch
 
+from .engine import DecoderEngine
 from .generation_extras import active_extras, check_generation_mode
 from .modeling_parler_tts import apply_delay_pattern_mask, build_delay_pattern_mask
 
 _HOST_LOOP_ARGUMENTS = ("logits_processor", "stopping_criteria", "output_scores", "output_logits")
 _VOICE_ARGUMENTS = ("input_values", "decoder_input_ids")
+_DEVICE_PENALTIES = ("repetition_penalty", "no_repeat_ngram_size")
 
 
 class _Request:
-    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept",
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept", "pen",
                  "cols", "absorbed", "kept", "emitted", "first_out")
 
-    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None):
+    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None, pen=None):
+        self.pen = pen  # the request's own (repetition_penalty, no_repeat_ngram_size) (set_slot_history_penalty), or None: the session's
         self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
         self.gen = gen  # the request's own sampler record (DecoderEngine.admit_row's `gen`), or None: the session's
         self.voice = voice  # un-delayed codes [K, T >= 1] of the voice prompt the request continues (admit_row's `voice`), or None
@@ -133,6 +136,10 @@ class ContinuousBatcher:
             raise ValueError(f"The following arguments are not generation options: {sorted(unused)}")
         check_generation_mode(gc)
         extras = active_extras(gc)
+        # model.enable_device_penalties(): the two history penalties run as a device node of the session's step (ptts_penalty.h)
+        self.device_penalties = bool(getattr(model, "device_penalties", False))
+        if self.device_penalties:
+            extras = [x for x in extras if x not in _DEVICE_PENALTIES]
         if extras:
             raise NotImplementedError(f"generation options {extras} run on generate()'s host loop (generation_extras): not available in a continuous batch")
         if int(getattr(gc, "num_return_sequences", 1) or 1) != 1:
@@ -158,9 +165,17 @@ class ContinuousBatcher:
         # An option that is off adds nothing to a call: no fifth argument here, no keyword below. With voice prompts the prefill of one slot
         # runs P + 1 + T positions
         voice_room = (self.max_voice_frames,) if self.max_voice_frames else ()
+        # the session's own penalties (neutral where the caller gave none), checked before anything touches the engine
+        self._pen = self._penalty(gc.repetition_penalty, gc.no_repeat_ngram_size, (1.0, 0)) if self.device_penalties else None
         self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length, *voice_room)
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
+        # The penalty node is part of the session's step from its begin: on with the session's values (a request may bring its own), or off -
+        # also where an earlier call left it on. A model without the switch, on an engine that never had the node, makes no call here.
+        if self.device_penalties:
+            self.eng.set_history_penalty(*self._pen)
+        elif getattr(self.eng, "history_penalty", None) is not None:
+            self.eng.set_history_penalty(enabled=False)
         # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
         self.eng.begin_session(self.slots, self.N, self.P, **({"kv_fp8": True} if getattr(self.eng, "kv_fp8", False) else {}))
         # what a request's own record starts from (submit): the session's values as the caller gave them (top_k is not zeroed for a greedy session)
@@ -242,10 +257,19 @@ class ContinuousBatcher:
         gen["seed"] = None if seed is None else int(seed) & (2 ** 64 - 1)  # without effect on a greedy request
         return gen
 
+    @staticmethod
+    def _penalty(repetition_penalty, no_repeat_ngram_size, default) -> Tuple[float, int]:
+        """(repetition_penalty, no_repeat_ngram_size) with ``default``'s value for an option left ``None``; ``ValueError`` on a bad value."""
+        p = default[0] if repetition_penalty is None else repetition_penalty
+        n = default[1] if no_repeat_ngram_size is None else no_repeat_ngram_size
+        DecoderEngine._history_penalty(p, n)  # the engine wrapper's own checks, here so that a bad value never reaches the queue
+        return float(p), int(n)
+
     @torch.no_grad()
     def submit(self, input_ids, attention_mask=None, prompt_input_ids=None, prompt_attention_mask=None, max_new_tokens: Optional[int] = None,
                do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
-               min_new_tokens: Optional[int] = None, seed: Optional[int] = None, input_values=None, decoder_input_ids=None) -> int:
+               min_new_tokens: Optional[int] = None, seed: Optional[int] = None, input_values=None, decoder_input_ids=None,
+               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None) -> int:
         """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path).
         ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_new_tokens``: the request's own sampler settings; an option left ``None``
         takes the session's value. A request that sets any of them (or ``seed``) draws from its own stream ``(seed, column, codebook)``: with a
@@ -253,7 +277,16 @@ class ContinuousBatcher:
         (``torch.manual_seed`` governs the run). A request that sets none is admitted on the session's parameters and draw stream.
         ``input_values`` (a waveform [1, 1, samples], encoded on the model's own DAC encoder) or ``decoder_input_ids`` (codes [K, T], a leading
         BOS column is dropped): the voice prompt the request continues, as ``generate()`` takes it; needs ``max_voice_frames >= T``. The
-        request's waveform contains the prompt's frames, and ``max_new_tokens`` counts what follows them."""
+        request's waveform contains the prompt's frames, and ``max_new_tokens`` counts what follows them.
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` (a model with ``enable_device_penalties()``; ``NotImplementedError`` otherwise): the
+        request's own history penalties, an option left ``None`` taking the session's value. They are computed over the request's own
+        columns - BOS, the voice prompt's, what it generated - as ``generate()`` computes them for the same request alone."""
+        pen = None
+        if repetition_penalty is not None or no_repeat_ngram_size is not None:
+            if not self.device_penalties:
+                raise NotImplementedError("generation options ['repetition_penalty', 'no_repeat_ngram_size'] run on generate()'s host loop "
+                                          "(generation_extras): not available in a continuous batch without model.enable_device_penalties()")
+            pen = self._penalty(repetition_penalty, no_repeat_ngram_size, self._pen)
         voice = self._voice(input_values, decoder_input_ids)
         T = 0 if voice is None else int(voice.shape[1])
         if max_new_tokens is not None:
@@ -285,7 +318,7 @@ class ContinuousBatcher:
         prompt_kept = None
         if voice is not None and self.stream_voice == "skip":  # what the filter keeps of the prompt, known here: the codec's pairs do not say
             prompt_kept = [0] + self._valid_frames(voice).long().cumsum(0).tolist()
-        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept))
+        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept, *(() if pen is None else (pen,))))
         return ticket
 
     def _voice(self, input_values, decoder_input_ids) -> Optional[torch.Tensor]:
@@ -328,6 +361,9 @@ class ContinuousBatcher:
                 groups.append([])
             groups[-1].append((s, r))
         for group in groups:
+            for s, r in group:  # the record each slot's admission runs under, its first token included (retire_row put the session's back)
+                if r.pen is not None:
+                    self.eng.set_slot_history_penalty(s, *r.pen)
             reqs = [self._queue.popleft() for _ in group]
             if len(reqs) == 1:
                 (s, r), = group

@@ -11,11 +11,13 @@
 #include "ptts_common.h"
 #include "../../include/ptts_session_kv8.h"
 #include "../../include/ptts_session_voice.h"
+#include "../../include/ptts_penalty.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
 #include "ptts_strip_w8.h"
 #include "ptts_gemm_launch.h"
 #include "ptts_tail_launch.h"
+#include "ptts_penalty_launch.h"
 
 thread_local std::string g_ptts_err;
 int ptts_fail(int code, const char* fmt, ...) {
@@ -137,6 +139,10 @@ struct ptts_engine {
   AdmitScaleLayer* move_scales = nullptr; // [layers] kv_fp8 engines: scale arrays of admit_move_scales_kernel, written with h_adm_rows
   std::vector<char> slot_busy;           // host: admitted and not yet retired
   std::vector<int> slot_ub, slot_maxlen; // host: upper bound of the slot's self-KV positions (P + 1 + steps since admission), its max_length
+  // history penalties (ptts_penalty.h): one node in front of every sampler tail while pen_on
+  HistoryPenalty* pen = nullptr;         // [max_batch] device: the record of each utterance / slot; allocated at the first switch-on, the step graphs hold the pointer
+  bool pen_on = false;                   // the node is part of every tail (and of the step graph: its own key bit)
+  HistoryPenalty pen_default = {1.0f, 0}; // the values of ptts_set_history_penalty: every utterance of a static call, a slot without a request's own
 #ifdef PTTS_TIMING
   long long* dbg_stamps = nullptr;  // measurement build: [layers + 1][5 or 7 nodes][3 workgroups][16] wall-clock stamps of the decode step (ptts_debug_stamps)
 #endif
@@ -613,6 +619,12 @@ int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next
   t.logits = v.logits; t.ids = v.ids; t.ids_ld = e->ids_ld; t.cur_len = v.cur_len; t.unfinished = v.unfinished;
   t.has_eos = v.has_eos; t.first_unf = v.first_unf; t.gen = e->gen; t.sort_buf = e->sort_buf;
   t.B = v.B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
+  if (e->pen_on) {  // history penalties rewrite the logits the tail is about to read; the records are indexed like cur_len
+    PenaltyArgs p = {};
+    p.logits = v.logits; p.ids = v.ids; p.cur_len = v.cur_len; p.pen = e->pen + (v.cur_len - e->cur_len);
+    p.ids_ld = e->ids_ld; p.K = e->cfg.num_codebooks; p.V = e->cfg.vocab_size;
+    if (!penalty_launch(p, row < 0 ? 0 : row, row < 0 ? v.B : 1, st)) return ptts_fail(PTTS_E_UNSUPPORTED, "history penalty: no kernel for vocab_size %d", p.V);
+  }
   // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
   if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen, e->slot_T);
   else tail_launch(t, nullptr, 0, dim3(v.B), st);
@@ -1210,7 +1222,8 @@ static int get_graph(ptts_engine* e, int kv_bound, hipGraphExec_t* out) {
   // the node set of the step depends on the batch size and on the folded cross block; the attention fetch bound (a kernel argument)
   // on the 64-position bucket of the context this graph is captured for (`kv_bound`). (Several steps of one bucket per
   // graph launch - round 4's PTTS_GRAPH_STEPS - measured 0.3-0.7 %, profiles/r04_experiments.txt call 19: removed in round 6.)
-  const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (kv_bound / 64) + (e->session ? 1LL << 40 : 0);  // session steps end in their own tail
+  const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (kv_bound / 64) + (e->session ? 1LL << 40 : 0)  // session steps end in their own tail
+                        + (e->pen_on ? 1LL << 41 : 0);                                                                           // the history-penalty node is present
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) { if (out) *out = it->second; return PTTS_OK; }
   hipGraph_t g = nullptr;
@@ -1311,6 +1324,7 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
   launch_set_params(e, 0, st);
   hipLaunchKernelGGL(set_slot_gen_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->slot_gen, 0, c.max_batch, SlotGen{});  // no slot has a record of its own
   hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, e->slot_T, 0, (size_t)c.max_batch);  // ... nor a voice prompt
+  if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->pen, 0, c.max_batch, e->pen_default);  // ... nor penalties of its own
   // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);
@@ -1515,8 +1529,47 @@ extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
                      e->first_unf, e->row_maxlen, row, 1, e->cfg.num_codebooks, e->cfg.bos_token_id, 0, e->session_max_length);
   hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_gen, row, 1, SlotGen{});  // the next plain admission samples on the session's
   hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_T + row, 0, (size_t)1);  // ... and continues no voice prompt
+  if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->pen, row, 1, e->pen_default);  // ... under the session's penalties
   e->slot_busy[row] = 0; e->slot_ub[row] = e->P + 1;
   return PTTS_OK;
+}
+
+// ---- history penalties (ptts_penalty.h) --------------------------------------------------------------------------------------------------
+static int check_history_penalty(const ptts_history_penalty* hp) {
+  PTTS_CHECK(std::isfinite(hp->repetition_penalty) && hp->repetition_penalty > 0.0f, PTTS_E_INVALID, "repetition_penalty must be finite and > 0, got %g",
+             (double)hp->repetition_penalty);
+  PTTS_CHECK(hp->no_repeat_ngram_size >= 0, PTTS_E_INVALID, "no_repeat_ngram_size must be >= 0, got %d", hp->no_repeat_ngram_size);
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_history_penalty(ptts_engine* e, const ptts_history_penalty* hp, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  if (e->session)  // a session that holds a request is running: its node set was fixed at its begin
+    for (char busy : e->slot_busy) PTTS_CHECK(!busy, PTTS_E_INVALID, "ptts_set_history_penalty inside a running session (call it before ptts_session_begin)");
+  if (!hp) { e->pen_on = false; e->pen_default = HistoryPenalty{1.0f, 0}; return PTTS_OK; }
+  PTTS_TRY(check_history_penalty(hp));
+  const ptts_config& c = e->cfg;
+  PTTS_CHECK(c.vocab_size <= PTTS_PENALTY_MAX_V, PTTS_E_UNSUPPORTED, "history penalties serve vocabularies up to %d, this engine's is %d", PTTS_PENALTY_MAX_V, c.vocab_size);
+  PTTS_DEVICE(c.device);
+  if (!e->pen) PTTS_TRY(e->alloc(&e->pen, (size_t)c.max_batch));
+  e->pen_default = HistoryPenalty{hp->repetition_penalty, hp->no_repeat_ngram_size};
+  hipLaunchKernelGGL(set_penalty_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, pick_stream(e, stream), e->pen, 0, c.max_batch, e->pen_default);
+  PTTS_TRY(launch_status("set_penalty"));
+  e->pen_on = true;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_slot_history_penalty(ptts_engine* e, int32_t row, const ptts_history_penalty* hp, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_set_slot_history_penalty: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(e->pen_on, PTTS_E_INVALID, "ptts_set_slot_history_penalty: the session was begun without history penalties (ptts_set_history_penalty first)");
+  PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
+  PTTS_CHECK(!e->slot_busy[row], PTTS_E_INVALID, "slot %d still holds a request (ptts_retire_row first)", row);
+  if (hp) PTTS_TRY(check_history_penalty(hp));
+  PTTS_DEVICE(e->cfg.device);
+  const HistoryPenalty rec = hp ? HistoryPenalty{hp->repetition_penalty, hp->no_repeat_ngram_size} : e->pen_default;
+  hipLaunchKernelGGL(set_penalty_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->pen, row, 1, rec);
+  return launch_status("set_penalty");
 }
 
 extern "C" int ptts_row_state(ptts_engine* e, int32_t* cur_len_host, int32_t* live_host, void* stream) {

@@ -63,6 +63,7 @@ class DecoderEngine:
         self._h = C.c_void_p()
         N.check(self.lib.ptts_engine_create(C.byref(self.cfg), C.byref(self._h)), "ptts_engine_create")
         self.B = 0
+        self.history_penalty = None  # (repetition_penalty, no_repeat_ngram_size) while the device node is on (set_history_penalty)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -129,6 +130,39 @@ class DecoderEngine:
                              int(bool(use_eos_gate)), int(seed) & (2 ** 64 - 1))
         N.check(self.lib.ptts_set_gen_params(self._h, C.byref(gp)), "ptts_set_gen_params")
         self.max_length = int(max_length)
+
+    @staticmethod
+    def _history_penalty(repetition_penalty, no_repeat_ngram_size):
+        """The two options as a ``ptts_history_penalty`` (``None`` = the neutral value of that option); ``ValueError`` on values out of range."""
+        p = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        n = 0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size)
+        if not (math.isfinite(p) and p > 0.0):
+            raise ValueError(f"`repetition_penalty` must be a finite number > 0, got {repetition_penalty}")
+        if n < 0 or (no_repeat_ngram_size is not None and n != no_repeat_ngram_size):
+            raise ValueError(f"`no_repeat_ngram_size` must be an integer >= 0, got {no_repeat_ngram_size}")
+        return N.PttsHistoryPenalty(p, n)
+
+    def set_history_penalty(self, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, enabled: bool = True):
+        """transformers' ``repetition_penalty`` / ``no_repeat_ngram_size`` on the device (``ptts_set_history_penalty``): one kernel node in
+        front of every sampler tail from the next ``prefill`` / ``begin_session`` on, with these values for every utterance (a session: for
+        every request that brings none of its own). Neutral values (the defaults) keep the node and change no logit: how a session is
+        opened when only some requests will bring penalties. ``enabled=False`` switches the node off (the state of a new engine).
+        ``ValueError`` inside a session that holds a request."""
+        if not enabled:
+            N.check(self.lib.ptts_set_history_penalty(self._h, None, _stream_ptr(device=self.device)), "ptts_set_history_penalty")
+            self.history_penalty = None
+            return
+        hp = self._history_penalty(repetition_penalty, no_repeat_ngram_size)
+        N.check(self.lib.ptts_set_history_penalty(self._h, C.byref(hp), _stream_ptr(device=self.device)), "ptts_set_history_penalty")
+        self.history_penalty = (float(hp.repetition_penalty), int(hp.no_repeat_ngram_size))
+
+    def set_slot_history_penalty(self, slot: int, repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                                 default: bool = False):
+        """The record the next admission into the idle slot ``slot`` runs under (``ptts_set_slot_history_penalty``), its first token
+        included; ``default=True`` restores the session's values, as ``retire_row`` does. Only in a session begun with the node on."""
+        hp = None if default else self._history_penalty(repetition_penalty, no_repeat_ngram_size)
+        N.check(self.lib.ptts_set_slot_history_penalty(self._h, int(slot), None if hp is None else C.byref(hp), _stream_ptr(device=self.device)),
+                "ptts_set_slot_history_penalty")
 
     def prefill(self, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
                 prompt_mask: Optional[torch.Tensor], sample: bool = True):

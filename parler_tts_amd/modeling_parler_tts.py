@@ -592,6 +592,16 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         self._engine = None
         return self
 
+    def enable_device_penalties(self, enabled: bool = True):
+        """Opt-in: ``repetition_penalty`` and ``no_repeat_ngram_size`` run on the device, as one kernel node in front of the sampler tail
+        (``ptts_penalty.h``), bit for bit what transformers' two processors compute. ``generate()`` then stays on the captured step graph
+        when these are the only options beyond the device sampler's and the caller brings no processors, stopping criteria or score
+        outputs (any other combination runs the host loop as before), and ``ContinuousBatcher`` takes both options for a session and per
+        request. Off (the default): every call is routed exactly as without this switch."""
+        self.device_penalties = bool(enabled)
+        self._engine = None
+        return self
+
     def _get_engine(self, B: int, N: int, P: int, max_length: int, T: int = 0) -> DecoderEngine:
         """T = voice-prompt frames: the prefill runs the P prompt positions, the BOS column and the T given columns in one pass."""
         dev, dt = self.device, self.dtype
@@ -852,6 +862,11 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         # max_time ...): the reference honours them through transformers' _get_logits_processor (:3540-3552); here they run the host
         # loop with transformers' own processor objects (generation_extras.py). Nothing is silently ignored.
         extras = active_extras(gc)
+        # model.enable_device_penalties(): the two history penalties alone, with nothing that needs the host's view of a step, stay on the device
+        dev_pen = (bool(getattr(self, "device_penalties", False)) and bool(extras) and set(extras) <= {"repetition_penalty", "no_repeat_ngram_size"}
+                   and not manual and not (bool(getattr(gc, "return_dict_in_generate", False)) and (getattr(gc, "output_scores", False) or getattr(gc, "output_logits", False))))
+        if dev_pen:
+            extras = []
         manual = manual or bool(extras)
         # return_dict_in_generate + output_scores / output_logits: the reference returns `_sample`'s per-step tuples next to the waveform
         # (:3648-3651 keeps the ModelOutput); they exist on the host loop only
@@ -870,6 +885,10 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         #  profiles/r04_experiments.txt calls 20 / 26, profiles/r06_experiments.txt call 12; the split loop is gone since round 6)
         eng = self._get_engine(B, N, P, max_length, T0)
         eng.set_gen_params(seed=seed, **gen_kw)
+        if dev_pen:
+            eng.set_history_penalty(repetition_penalty=gc.repetition_penalty, no_repeat_ngram_size=gc.no_repeat_ngram_size)
+        elif getattr(eng, "history_penalty", None) is not None:  # the node of an earlier call: off, this call's graphs are the plain ones
+            eng.set_history_penalty(enabled=False)
         pad, eos = gc.pad_token_id if gc.pad_token_id is not None else d.pad_token_id, d.eos_token_id
         bos_col = torch.full((B * K, 1), bos, dtype=torch.long, device=dev)
         dec_ids = bos_col if prefix is None else torch.cat([bos_col, prefix], dim=-1)  # :3011-3018
