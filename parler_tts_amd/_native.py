@@ -41,6 +41,11 @@ class PttsHistoryPenalty(C.Structure):
     _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
 
 
+class PttsSampleWarp(C.Structure):
+    """ptts_sample_warp (include/ptts_warp.h)."""
+    _fields_ = [("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
+
+
 class PttsT5Config(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32), ("d_model", C.c_int32), ("d_kv", C.c_int32), ("d_ff", C.c_int32), ("num_layers", C.c_int32),
@@ -146,6 +151,12 @@ PENALTY_SYMBOLS = {
     "ptts_set_slot_history_penalty": (C.c_int, [_VP, _I32, C.POINTER(PttsHistoryPenalty), _VP]),
 }
 
+# include/ptts_warp.h, additive likewise: min_p / typical_p / epsilon_cutoff / eta_cutoff inside the sampler tail
+WARP_SYMBOLS = {
+    "ptts_set_sample_warp": (C.c_int, [_VP, C.POINTER(PttsSampleWarp), _VP]),
+    "ptts_set_slot_sample_warp": (C.c_int, [_VP, _I32, C.POINTER(PttsSampleWarp), _VP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -168,7 +179,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 missing
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
     for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
-                              + list(SESSION_VOICE_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())):
+                              + list(SESSION_VOICE_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())
+                              + list(WARP_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -29,13 +29,15 @@ from .modeling_parler_tts import apply_delay_pattern_mask, build_delay_pattern_m
 _HOST_LOOP_ARGUMENTS = ("logits_processor", "stopping_criteria", "output_scores", "output_logits")
 _VOICE_ARGUMENTS = ("input_values", "decoder_input_ids")
 _DEVICE_PENALTIES = ("repetition_penalty", "no_repeat_ngram_size")
+_DEVICE_WARPERS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
 
 
 class _Request:
-    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept", "pen",
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept", "pen", "warp",
                  "cols", "absorbed", "kept", "emitted", "first_out")
 
-    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None, pen=None):
+    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None, pen=None, warp=None):
+        self.warp = warp  # the request's own (min_p, typical_p, epsilon_cutoff, eta_cutoff) (set_slot_sample_warp), or None: the session's
         self.pen = pen  # the request's own (repetition_penalty, no_repeat_ngram_size) (set_slot_history_penalty), or None: the session's
         self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
         self.gen = gen  # the request's own sampler record (DecoderEngine.admit_row's `gen`), or None: the session's
@@ -140,6 +142,10 @@ class ContinuousBatcher:
         self.device_penalties = bool(getattr(model, "device_penalties", False))
         if self.device_penalties:
             extras = [x for x in extras if x not in _DEVICE_PENALTIES]
+        # model.enable_device_warpers(): min_p / typical_p / epsilon_cutoff / eta_cutoff inside the session's sampler tail (ptts_warp.h)
+        self.device_warpers = bool(getattr(model, "device_warpers", False))
+        if self.device_warpers:
+            extras = [x for x in extras if x not in _DEVICE_WARPERS]
         if extras:
             raise NotImplementedError(f"generation options {extras} run on generate()'s host loop (generation_extras): not available in a continuous batch")
         if int(getattr(gc, "num_return_sequences", 1) or 1) != 1:
@@ -167,6 +173,8 @@ class ContinuousBatcher:
         voice_room = (self.max_voice_frames,) if self.max_voice_frames else ()
         # the session's own penalties (neutral where the caller gave none), checked before anything touches the engine
         self._pen = self._penalty(gc.repetition_penalty, gc.no_repeat_ngram_size, (1.0, 0)) if self.device_penalties else None
+        self._warp = (self._warpers(gc.min_p, gc.typical_p, gc.epsilon_cutoff, gc.eta_cutoff, (0.0, 1.0, 0.0, 0.0))
+                      if self.device_warpers else None)
         self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length, *voice_room)
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
@@ -176,6 +184,11 @@ class ContinuousBatcher:
             self.eng.set_history_penalty(*self._pen)
         elif getattr(self.eng, "history_penalty", None) is not None:
             self.eng.set_history_penalty(enabled=False)
+        # The warpers likewise: the tail instance of the session is fixed at its begin
+        if self.device_warpers:
+            self.eng.set_sample_warp(*self._warp)
+        elif getattr(self.eng, "sample_warp", None) is not None:
+            self.eng.set_sample_warp(enabled=False)
         # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
         self.eng.begin_session(self.slots, self.N, self.P, **({"kv_fp8": True} if getattr(self.eng, "kv_fp8", False) else {}))
         # what a request's own record starts from (submit): the session's values as the caller gave them (top_k is not zeroed for a greedy session)
@@ -265,11 +278,19 @@ class ContinuousBatcher:
         DecoderEngine._history_penalty(p, n)  # the engine wrapper's own checks, here so that a bad value never reaches the queue
         return float(p), int(n)
 
+    @staticmethod
+    def _warpers(min_p, typical_p, epsilon_cutoff, eta_cutoff, default) -> Tuple[float, float, float, float]:
+        """(min_p, typical_p, epsilon_cutoff, eta_cutoff) with ``default``'s value for an option left ``None``; ``ValueError`` on a bad value."""
+        vals = tuple(d if v is None else v for v, d in zip((min_p, typical_p, epsilon_cutoff, eta_cutoff), default))
+        DecoderEngine._sample_warp(*vals)  # the engine wrapper's own checks, here so that a bad value never reaches the queue
+        return tuple(float(v) for v in vals)
+
     @torch.no_grad()
     def submit(self, input_ids, attention_mask=None, prompt_input_ids=None, prompt_attention_mask=None, max_new_tokens: Optional[int] = None,
                do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                min_new_tokens: Optional[int] = None, seed: Optional[int] = None, input_values=None, decoder_input_ids=None,
-               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None) -> int:
+               repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_p: Optional[float] = None,
+               typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None) -> int:
         """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path).
         ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_new_tokens``: the request's own sampler settings; an option left ``None``
         takes the session's value. A request that sets any of them (or ``seed``) draws from its own stream ``(seed, column, codebook)``: with a
@@ -280,7 +301,16 @@ class ContinuousBatcher:
         request's waveform contains the prompt's frames, and ``max_new_tokens`` counts what follows them.
         ``repetition_penalty`` / ``no_repeat_ngram_size`` (a model with ``enable_device_penalties()``; ``NotImplementedError`` otherwise): the
         request's own history penalties, an option left ``None`` taking the session's value. They are computed over the request's own
-        columns - BOS, the voice prompt's, what it generated - as ``generate()`` computes them for the same request alone."""
+        columns - BOS, the voice prompt's, what it generated - as ``generate()`` computes them for the same request alone.
+        ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` (a model with ``enable_device_warpers()``; ``NotImplementedError``
+        otherwise): the request's own warpers behind top-p, an option left ``None`` taking the session's value; without effect on a greedy
+        request."""
+        warp = None
+        if any(v is not None for v in (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
+            if not self.device_warpers:
+                raise NotImplementedError("generation options ['min_p', 'typical_p', 'epsilon_cutoff', 'eta_cutoff'] run on generate()'s host loop "
+                                          "(generation_extras): not available in a continuous batch without model.enable_device_warpers()")
+            warp = self._warpers(min_p, typical_p, epsilon_cutoff, eta_cutoff, self._warp)
         pen = None
         if repetition_penalty is not None or no_repeat_ngram_size is not None:
             if not self.device_penalties:
@@ -318,7 +348,8 @@ class ContinuousBatcher:
         prompt_kept = None
         if voice is not None and self.stream_voice == "skip":  # what the filter keeps of the prompt, known here: the codec's pairs do not say
             prompt_kept = [0] + self._valid_frames(voice).long().cumsum(0).tolist()
-        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept, *(() if pen is None else (pen,))))
+        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept, *(() if pen is None else (pen,)),
+                                    **({} if warp is None else {"warp": warp})))
         return ticket
 
     def _voice(self, input_values, decoder_input_ids) -> Optional[torch.Tensor]:
@@ -364,6 +395,8 @@ class ContinuousBatcher:
             for s, r in group:  # the record each slot's admission runs under, its first token included (retire_row put the session's back)
                 if r.pen is not None:
                     self.eng.set_slot_history_penalty(s, *r.pen)
+                if r.warp is not None:
+                    self.eng.set_slot_sample_warp(s, *r.warp)
             reqs = [self._queue.popleft() for _ in group]
             if len(reqs) == 1:
                 (s, r), = group

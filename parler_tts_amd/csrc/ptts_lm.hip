@@ -12,6 +12,7 @@
 #include "../../include/ptts_session_kv8.h"
 #include "../../include/ptts_session_voice.h"
 #include "../../include/ptts_penalty.h"
+#include "../../include/ptts_warp.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
 #include "ptts_strip_w8.h"
@@ -143,6 +144,10 @@ struct ptts_engine {
   HistoryPenalty* pen = nullptr;         // [max_batch] device: the record of each utterance / slot; allocated at the first switch-on, the step graphs hold the pointer
   bool pen_on = false;                   // the node is part of every tail (and of the step graph: its own key bit)
   HistoryPenalty pen_default = {1.0f, 0}; // the values of ptts_set_history_penalty: every utterance of a static call, a slot without a request's own
+  // sampling warpers (ptts_warp.h): every tail launch is the WARP instance while warp_on
+  DevWarp* warp = nullptr;               // [max_batch] device: the record of each utterance / slot; allocated at the first switch-on, the step graphs hold the pointer
+  bool warp_on = false;                  // the tail of every launch (and of the step graph: its own key bit) is tail_warp_kernel<NV, SESSION>
+  DevWarp warp_default = {0.f, 1.f, 0.f, 0.f};  // the values of ptts_set_sample_warp
 #ifdef PTTS_TIMING
   long long* dbg_stamps = nullptr;  // measurement build: [layers + 1][5 or 7 nodes][3 workgroups][16] wall-clock stamps of the decode step (ptts_debug_stamps)
 #endif
@@ -626,8 +631,10 @@ int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next
     if (!penalty_launch(p, row < 0 ? 0 : row, row < 0 ? v.B : 1, st)) return ptts_fail(PTTS_E_UNSUPPORTED, "history penalty: no kernel for vocab_size %d", p.V);
   }
   // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
-  if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen, e->slot_T);
-  else tail_launch(t, nullptr, 0, dim3(v.B), st);
+  // warpers on: the WARP instances, with the records indexed like cur_len (null picks the instances of an engine without the feature)
+  const DevWarp* warp = e->warp_on ? e->warp + (v.cur_len - e->cur_len) : nullptr;
+  if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen, e->slot_T, warp);
+  else tail_launch(t, nullptr, 0, dim3(v.B), st, nullptr, nullptr, warp);
   return launch_status("tail");
 }
 
@@ -1223,7 +1230,8 @@ static int get_graph(ptts_engine* e, int kv_bound, hipGraphExec_t* out) {
   // on the 64-position bucket of the context this graph is captured for (`kv_bound`). (Several steps of one bucket per
   // graph launch - round 4's PTTS_GRAPH_STEPS - measured 0.3-0.7 %, profiles/r04_experiments.txt call 19: removed in round 6.)
   const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (kv_bound / 64) + (e->session ? 1LL << 40 : 0)  // session steps end in their own tail
-                        + (e->pen_on ? 1LL << 41 : 0);                                                                           // the history-penalty node is present
+                        + (e->pen_on ? 1LL << 41 : 0)                                                                            // the history-penalty node is present
+                        + (e->warp_on ? 1LL << 42 : 0);                                                                          // the tail is the WARP instance
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) { if (out) *out = it->second; return PTTS_OK; }
   hipGraph_t g = nullptr;
@@ -1325,6 +1333,7 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
   hipLaunchKernelGGL(set_slot_gen_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->slot_gen, 0, c.max_batch, SlotGen{});  // no slot has a record of its own
   hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, e->slot_T, 0, (size_t)c.max_batch);  // ... nor a voice prompt
   if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->pen, 0, c.max_batch, e->pen_default);  // ... nor penalties of its own
+  if (e->warp_on) hipLaunchKernelGGL(set_warp_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->warp, 0, c.max_batch, e->warp_default);  // ... nor warpers
   // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);
@@ -1530,6 +1539,7 @@ extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
   hipLaunchKernelGGL(set_slot_gen_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_gen, row, 1, SlotGen{});  // the next plain admission samples on the session's
   hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_T + row, 0, (size_t)1);  // ... and continues no voice prompt
   if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->pen, row, 1, e->pen_default);  // ... under the session's penalties
+  if (e->warp_on) hipLaunchKernelGGL(set_warp_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->warp, row, 1, e->warp_default);  // ... and warpers
   e->slot_busy[row] = 0; e->slot_ub[row] = e->P + 1;
   return PTTS_OK;
 }
@@ -1570,6 +1580,46 @@ extern "C" int ptts_set_slot_history_penalty(ptts_engine* e, int32_t row, const 
   const HistoryPenalty rec = hp ? HistoryPenalty{hp->repetition_penalty, hp->no_repeat_ngram_size} : e->pen_default;
   hipLaunchKernelGGL(set_penalty_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->pen, row, 1, rec);
   return launch_status("set_penalty");
+}
+
+// ---- sampling warpers (ptts_warp.h) -------------------------------------------------------------------------------------------------------
+static int check_sample_warp(const ptts_sample_warp* w) {
+  PTTS_CHECK(std::isfinite(w->min_p) && w->min_p >= 0.0f && w->min_p <= 1.0f, PTTS_E_INVALID, "min_p must lie in [0, 1], got %g", (double)w->min_p);
+  PTTS_CHECK(std::isfinite(w->typical_p) && w->typical_p > 0.0f && w->typical_p <= 1.0f, PTTS_E_INVALID, "typical_p must lie in (0, 1], got %g", (double)w->typical_p);
+  PTTS_CHECK(std::isfinite(w->epsilon_cutoff) && w->epsilon_cutoff >= 0.0f && w->epsilon_cutoff < 1.0f, PTTS_E_INVALID,
+             "epsilon_cutoff must lie in [0, 1), got %g", (double)w->epsilon_cutoff);
+  PTTS_CHECK(std::isfinite(w->eta_cutoff) && w->eta_cutoff >= 0.0f && w->eta_cutoff < 1.0f, PTTS_E_INVALID, "eta_cutoff must lie in [0, 1), got %g",
+             (double)w->eta_cutoff);
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_sample_warp(ptts_engine* e, const ptts_sample_warp* w, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  if (e->session)  // a session that holds a request is running: its tail instance was fixed at its begin
+    for (char busy : e->slot_busy) PTTS_CHECK(!busy, PTTS_E_INVALID, "ptts_set_sample_warp inside a running session (call it before ptts_session_begin)");
+  if (!w) { e->warp_on = false; e->warp_default = DevWarp{0.f, 1.f, 0.f, 0.f}; return PTTS_OK; }
+  PTTS_TRY(check_sample_warp(w));
+  const ptts_config& c = e->cfg;
+  PTTS_DEVICE(c.device);
+  if (!e->warp) PTTS_TRY(e->alloc(&e->warp, (size_t)c.max_batch));
+  e->warp_default = DevWarp{w->min_p, w->typical_p, w->epsilon_cutoff, w->eta_cutoff};
+  hipLaunchKernelGGL(set_warp_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, pick_stream(e, stream), e->warp, 0, c.max_batch, e->warp_default);
+  PTTS_TRY(launch_status("set_warp"));
+  e->warp_on = true;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_slot_sample_warp(ptts_engine* e, int32_t row, const ptts_sample_warp* w, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_set_slot_sample_warp: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(e->warp_on, PTTS_E_INVALID, "ptts_set_slot_sample_warp: the session was begun without sampling warpers (ptts_set_sample_warp first)");
+  PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
+  PTTS_CHECK(!e->slot_busy[row], PTTS_E_INVALID, "slot %d still holds a request (ptts_retire_row first)", row);
+  if (w) PTTS_TRY(check_sample_warp(w));
+  PTTS_DEVICE(e->cfg.device);
+  const DevWarp rec = w ? DevWarp{w->min_p, w->typical_p, w->epsilon_cutoff, w->eta_cutoff} : e->warp_default;
+  hipLaunchKernelGGL(set_warp_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->warp, row, 1, rec);
+  return launch_status("set_warp");
 }
 
 extern "C" int ptts_row_state(ptts_engine* e, int32_t* cur_len_host, int32_t* live_host, void* stream) {

@@ -2563,6 +2563,12 @@ struct TailArgs {
   int H, bos, bf16_tables;
 };
 
+// The record of one utterance for the WARP instances of the tail (ptts_warp.h): min_p, typical_p, epsilon_cutoff, eta_cutoff of transformers'
+// sampling chain. {0, 1, 0, 0} is neutral: no stage runs. One record per utterance, [max_batch], indexed like cur_len.
+struct DevWarp {
+  float min_p, typical_p, epsilon_cutoff, eta_cutoff;
+};
+
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -2587,8 +2593,17 @@ __device__ __forceinline__ unsigned f32_key(float x) {
 //          the mass strictly above it is < top_p; the arg-max always stays)
 // The draw walks the kept entries in lane-major order (any fixed order gives the same distribution; torch.multinomial's
 // own stream cannot be matched, parity is statistical: tests/test_lm_gpu.py chi-square + support checks).
-template <int NV>
-__device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int lane, const DevGen& g, bool eos_blocked, int eos, float u01) {
+// WARP: the four threshold warpers that follow top-p in transformers' chain, on the same wave, each on the distribution renormalised over the
+// survivors of the stage before (p_i = e_i / tot, H = -sum p ln p). A stage at its neutral value is skipped; DESIGN.md 4.6.2 has the contract:
+//   min_p:          drop p_i < v * p_max; the arg-max has e = 1, so that is e_i < v
+//   typical_p:      s_i = |-ln p_i - H|; keep i iff mass{s_j < s_i} < v - the top-p radix search mirrored, on key = f32_key(s_i) (key[] is
+//                   free after top-p): the largest L with mass{key < L} < v. -ln p_i - H = (mx - x_i) - A, A = sum e_i (mx - x_i) / tot:
+//                   ln tot cancels, and x_i is recomputed from lg[i], so no new per-lane array is live
+//   epsilon_cutoff: drop p_i < v where x_i is below the maximum of the survivors
+//   eta_cutoff:     the same with eta = min(v, sqrt(v) exp(-H)), i.e. e_i < min(v tot, sqrt(v) exp(-A))
+template <int NV, bool WARP = false>
+__device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int lane, const DevGen& g, bool eos_blocked, int eos, float u01,
+                                               const DevWarp& wp = DevWarp{0.f, 1.f, 0.f, 0.f}) {
   const int nv = (V + 63) >> 6;
   float x[NV];
   unsigned key[NV];
@@ -2648,6 +2663,71 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
       ls += e[i];
     }
     tot = wave_sum(ls);
+  }
+  if constexpr (WARP) {
+    // the score of entry i as the first loop computed it (x[] holds the numerators by now); only read where e[i] > 0
+    auto score = [&](int i) { return (eos_blocked && lane + 64 * i == eos) ? -INFINITY : lg[i] / g.temperature; };
+    auto retotal = [&]() {
+      ls = 0.f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) ls += e[i];
+      tot = wave_sum(ls);
+    };
+    // A = sum e_i (mx - x_i) / tot over the survivors: H - ln tot
+    auto spread = [&]() {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        if (i < nv && e[i] > 0.f) a += e[i] * (mx - score(i));
+      return wave_sum(a) / tot;
+    };
+    // the largest surviving score: typical_p may have dropped the arg-max, and the cut-offs spare what is at the maximum of what is left
+    auto top = [&]() {
+      float m = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        if (i < nv && e[i] > 0.f) m = fmaxf(m, score(i));
+      return wave_max(m);
+    };
+    if (wp.min_p > 0.f) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        if (e[i] < wp.min_p) e[i] = 0.f;
+      retotal();
+    }
+    if (wp.typical_p < 1.0f) {
+      const float A = spread();
+#pragma unroll
+      for (int i = 0; i < NV; ++i) key[i] = (i < nv && e[i] > 0.f) ? f32_key(fabsf((mx - score(i)) - A)) : 0xffffffffu;
+      const float thr = wp.typical_p * tot;
+      unsigned L = 0u;
+      for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = L | (1u << bit);
+        float m = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+          if (i < nv) m += key[i] < cand ? e[i] : 0.f;
+        if (wave_sum(m) < thr) L = cand;
+      }
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        if (key[i] > L) e[i] = 0.f;
+      retotal();
+    }
+    if (wp.epsilon_cutoff > 0.f) {
+      const float thr = wp.epsilon_cutoff * tot, smx = top();
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        if (i < nv && e[i] > 0.f && e[i] < thr && score(i) < smx) e[i] = 0.f;
+      retotal();
+    }
+    if (wp.eta_cutoff > 0.f) {
+      const float thr = fminf(wp.eta_cutoff * tot, sqrtf(wp.eta_cutoff) * expf(-spread())), smx = top();
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        if (i < nv && e[i] > 0.f && e[i] < thr && score(i) < smx) e[i] = 0.f;
+      retotal();
+    }
   }
   // inverse CDF over the kept entries in lane-major order
   const float target = u01 * tot;
@@ -2743,139 +2823,34 @@ struct TailSessionArgs : TailArgs {
   const SlotGen* slot_gen = nullptr;  // [B] per-slot records, or null: every slot on *gen
   const int* slot_tprefix = nullptr;  // [B] voice-prompt frames of the request in each slot (ptts_admit_row_voice), or null: no slot has a prefix
 };
-template <bool SESSION> struct TailK { using T = TailArgs; };
-template <> struct TailK<true> { using T = TailSessionArgs; };
+// the WARP instances: the same arguments and, behind them, the per-utterance warper records
+struct TailWarpArgs : TailArgs {
+  const DevWarp* warp;  // [B]
+};
+struct TailSessionWarpArgs : TailSessionArgs {
+  const DevWarp* warp;  // [B], one per slot
+};
+template <bool SESSION, bool WARP = false> struct TailK { using T = TailArgs; };
+template <> struct TailK<true, false> { using T = TailSessionArgs; };
+template <> struct TailK<false, true> { using T = TailWarpArgs; };
+template <> struct TailK<true, true> { using T = TailSessionWarpArgs; };
 
 // NV = logits per lane: 8 (vocab <= 512), 18 (<= 1152: Mini / Large v1, vocab 1088) or 32 (<= 2048)
 // SESSION = the per-slot instance (TailSessionArgs); the body is written once, here, not in a shared device function: the static
 // instances are on the measured path and keep their instructions only this way (profiles/twin_kernels_isa_compare.txt)
+// WARP = min-p / typical-p / epsilon / eta cut-offs behind top-p (wave_sample_row<NV, true>), one DevWarp record per utterance: the instances
+// tail_warp_kernel<NV, SESSION>. The body is still written once - ptts_tail_body.inc, included into both kernels with WARP a constant of
+// each - and not in a shared device function, for the reason above: the instances without WARP keep their names AND their instructions
+// (profiles/device_warpers_isa_compare.txt; through a forced-inline device function they did not)
 template <int NV, bool SESSION>
 __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p) {
-  const TailArgs& a = p;
-  __shared__ int s_tok[32];
-  int b = blockIdx.x;
-  if constexpr (SESSION) b += p.row0;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // ---- t = 0: every load that does not depend on another load goes in flight together (the step's critical path ends
-  // here: lengths / flags / parameters / this wave's logits row are ONE round trip, the embedding rows a second one)
-  DevGen g = *a.gen;
-  int hrow0 = b * a.K;  // first row index of this utterance in the draw hash
-  const int t = a.cur_len[b];  // column the new token is written to; t-1 new tokens generated so far
-  // static: "has the reference loop already exited?" = every row finished BEFORE this step. Rows that finish during this very launch
-  // (other workgroups, stamp -(t + 1)) still count as active here, so the answer does not depend on workgroup timing.
-  // session: is this slot live (read by all before any wave of this workgroup writes a flag)
-  int any_local = 0;
-  if constexpr (SESSION) {
-    any_local = tid < a.K ? (a.unfinished[b * a.K + tid] > 0) : 0;
-  } else {
-    for (int i = tid; i < a.B * a.K; i += blockDim.x) {
-      const int v = a.unfinished[i];
-      any_local |= (v > 0) | (v <= -(t + 1));
-    }
-  }
-  const int fu0 = a.first_unf[b];
-  DevDims dd = *a.dims;  // the embedding of the next column needs P / max_length / the voice-prompt prefix: fetched now, not after the argmax
-  if constexpr (SESSION) {
-    dd.max_length = p.row_maxlen[b];  // the pad triangle (and whether there is a pattern at all) follows the request's own length
-  }
-  if constexpr (SESSION) {
-    // the slot's own record rides in the same batch of loads as *gen: both addresses come from kernel arguments alone (without records they
-    // fall back on *gen, read twice), and the choice between the two sets of values is made in registers - no flag is waited for first
-    // (written BEHIND the other loads of this prologue on purpose: in front of them the compiler ran out of SGPRs for the group and issued
-    // row_maxlen[b] behind a wait of its own, profiles/per_request_sampling_isa_compare.txt)
-    const bool recs = p.slot_gen != nullptr;
-    const DevGen* sgp = recs ? &p.slot_gen[b].g : a.gen;
-    const int* sfp = recs ? &p.slot_gen[b].own : &a.gen->max_length;  // {own, row_base}
-    const DevGen sg = *sgp;
-    const int sown = sfp[0], sbase = sfp[1];
-    const bool own = recs && sown != 0;
-    g.min_new_tokens = own ? sg.min_new_tokens : g.min_new_tokens; g.do_sample = own ? sg.do_sample : g.do_sample;
-    g.top_k = own ? sg.top_k : g.top_k; g.use_eos_gate = own ? sg.use_eos_gate : g.use_eos_gate;
-    g.temperature = own ? sg.temperature : g.temperature; g.top_p = own ? sg.top_p : g.top_p;
-    g.seed = own ? sg.seed : g.seed;
-    hrow0 = own ? sbase : hrow0;
-    // the slot's voice-prompt length, the same way: a load of this batch whose address needs the kernel arguments alone (without the array
-    // one more read of *gen), the zero of "no prefix" chosen in a register. What follows it: the min_new_tokens count and what the model is
-    // fed for the next column (s_tok below); the ids written stay the raw sampled tokens
-    const bool pres = p.slot_tprefix != nullptr;
-    const int* tpp = pres ? &p.slot_tprefix[b] : &a.gen->max_length;
-    const int stp = *tpp;
-    dd.T_prefix = pres ? stp : 0;
-  }
-  const int t_prefix = dd.T_prefix;
-  const int he = lane < a.K ? a.has_eos[b * a.K + lane] : 0;  // every wave: the K EOS flags of this utterance
-  float lg[NV];
-  const int k0 = w;  // greedy: wave w starts with codebook row w
-  if (k0 < a.K) {
-    const float* sc0 = a.logits + (size_t)(b * a.K + k0) * a.V;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) lg[i] = (lane + 64 * i < a.V) ? sc0[lane + 64 * i] : -INFINITY;
-  }
-  const int unf0 = k0 < a.K ? (a.unfinished[b * a.K + k0] > 0) : 0;
-  // static: every row of every utterance finished, the reference loop has exited (no-op step); session: idle or finished slot
-  if (!__syncthreads_or(any_local)) return;
-
-  int fu = fu0;
-  if (__shfl(he, fu0) > 0 && fu0 < a.K - 1) fu += 1;  // logits_processors.py:48 (advance <= 1 per step)
-  if (tid == 0) a.first_unf[b] = fu;
-  const bool block_eos_all = (t - 1 - t_prefix) < g.min_new_tokens;  // new tokens = columns after the (1 + T_prefix) given ones
-
-  // one wave per codebook row, no workgroup barrier until every row has its token. greedy: torch.argmax semantics (first
-  // index on ties); do_sample: the warpers + multinomial on the same wave (wave_sample_row)
-  for (int k = w; k < a.K; k += (int)(blockDim.x >> 6)) {
-    const int row = b * a.K + k;
-    if (k != k0) {
-      const float* sc = a.logits + (size_t)row * a.V;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) lg[i] = (lane + 64 * i < a.V) ? sc[lane + 64 * i] : -INFINITY;
-    }
-    const bool eos_blocked = block_eos_all || (g.use_eos_gate && k > fu);
-    int widx;
-    if (!g.do_sample) {
-      float best = -INFINITY;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int v = lane + 64 * i;
-        float x = lg[i];
-        if (eos_blocked && v == a.eos) x = -INFINITY;
-        if (v < a.V && (x > best || (x == best && v < bi))) { best = x; bi = v; }
-      }
-      const float wbest = wave_max(best);
-      const float cand = (best == wbest) ? (float)bi : 3.0e9f;  // vocabulary indices are exact in fp32
-      widx = (int)(-wave_max(-cand));
-    } else {
-      const int hrow = SESSION ? hrow0 + k : row;  // a slot with its own record: the codebook index inside the slot
-      const unsigned long long hsh = splitmix64(g.seed ^ splitmix64(((unsigned long long)t << 32) ^ (unsigned long long)hrow));
-      const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);  // [2^-25, 1], DESIGN.md 4.6
-      widx = wave_sample_row<NV>(lg, a.V, lane, g, eos_blocked, a.eos, u);
-    }
-    if (lane == 0) {
-      const int unf = k == k0 ? unf0 : (a.unfinished[row] > 0);
-      const int nxt = unf ? widx : a.pad;  // next_tokens * unfinished + pad * (1 - unfinished)
-      a.ids[(size_t)row * a.ids_ld + t] = nxt;
-      s_tok[k] = nxt;
-      if constexpr (SESSION) {
-        // behind a voice prompt the model is FED the shifted prompt code while the pattern holds one for this codebook (the first K - 1 steps of
-        // such a slot; BOS / PAD still win in tail_embed_rows); what is stored stays the raw token. Resolved here, by the one lane that owns the
-        // codebook and only for such a slot, so that the embedding below keeps its one batch of table-row loads (see there)
-        // (the pointer and the stride are read HERE, through volatile, not taken from the prologue's copy of *dims: kept live from there through
-        // the token loop they cost the prologue its load groups - profiles/session_voice_isa_compare.txt)
-        if (t - k - 1 < t_prefix && t > k && dd.max_length >= 2 * a.K - 1) {
-          const long long* pf = *reinterpret_cast<const long long* const volatile*>(&a.dims->prefix);
-          const int pld = *reinterpret_cast<const volatile int*>(&a.dims->prefix_ld);
-          s_tok[k] = (int)pf[(size_t)row * pld + (t - k - 1)];
-        }
-      }
-      if (nxt == a.eos) a.has_eos[row] = 1;
-      // EosTokenCriteria | MaxLengthCriteria (the slot's own length in a session)
-      if (unf && ((nxt == a.eos) || (t + 1 >= (SESSION ? dd.max_length : g.max_length)))) a.unfinished[row] = -(t + 1);
-    }
-  }
-  __syncthreads();
-  if (tid == 0) a.cur_len[b] = t + 1;
-  if constexpr (SESSION) dd.T_prefix = 0;  // s_tok already holds the prompt codes: no load of them between the table rows' loads
-  tail_embed_next(a, dd, b, t, s_tok, tid);
+  constexpr bool WARP = false;
+#include "ptts_tail_body.inc"
+}
+template <int NV, bool SESSION>
+__global__ void __launch_bounds__(1024) tail_warp_kernel(typename TailK<SESSION, true>::T p) {
+  constexpr bool WARP = true;
+#include "ptts_tail_body.inc"
 }
 
 // ptts_push_tokens inside a session: one workgroup per slot; only live slots take their K tokens and move their clock, and a slot
@@ -2978,6 +2953,11 @@ static __global__ void set_params_kernel(DevDims* dd, DevGen* dg, DevDims d, Dev
 // the sampler record of slots [row0, row0 + nrows): ptts_admit_row_gen writes one slot's (own = 1), session begin and ptts_retire_row clear
 // theirs (own = 0). The record travels by value as a kernel argument (no staging buffer, no copy to wait on)
 static __global__ void set_slot_gen_kernel(SlotGen* recs, int row0, int nrows, SlotGen rec) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nrows) recs[row0 + i] = rec;
+}
+// the warper records of utterances / slots [row0, row0 + nrows) (ptts_warp.h), the same way
+static __global__ void set_warp_kernel(DevWarp* recs, int row0, int nrows, DevWarp rec) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < nrows) recs[row0 + i] = rec;
 }

@@ -1,4 +1,4 @@
-// Host-side launch of the sampler tail (tail_kernel<NV, SESSION>, ptts_lm_kernels.h): the one place that picks the instance.
+// Host-side launch of the sampler tail (tail_kernel<NV, SESSION> / tail_warp_kernel<NV, SESSION>, ptts_lm_kernels.h): the one place that picks the instance.
 // Shared by the engine (launch_tail, ptts_lm.hip) and the test harness (tests/native/tail_harness.hip), so that a test of the
 // kernel runs the instance, the wave count and the argument struct the product would run for the same (V, K).
 #pragma once
@@ -13,15 +13,29 @@
 // slot_tprefix (session only): the per-slot voice-prompt lengths, or null: no slot has a prefix.
 // NV = logits per lane: 8 up to vocab 512, 18 up to 1152, 32 up to PTTS_SORT_N. One wave per codebook row (greedy arg-max or the
 // sort-free sampler), at least 4 waves for the embedding of the next column, at most 16 (more codebooks loop).
+// warp (null: off) picks the WARP instances (tail_warp_kernel): the per-utterance warper records (DevWarp, [B] indexed like cur_len) ride behind the arguments.
 static inline void tail_launch(const TailArgs& t, const int* row_maxlen, int row0, dim3 grid, hipStream_t st, const SlotGen* slot_gen = nullptr,
-                               const int* slot_tprefix = nullptr) {
+                               const int* slot_tprefix = nullptr, const DevWarp* warp = nullptr) {
   const int nw = std::min(std::max(t.K, 4), 16);
-  auto launch = [&](auto session, const auto& args) {  // one NV dispatch for both instances
-    constexpr bool S = decltype(session)::value;
-    if (t.V <= 512) hipLaunchKernelGGL((tail_kernel<8, S>), grid, dim3(nw * 64), 0, st, args);
-    else if (t.V <= 1152) hipLaunchKernelGGL((tail_kernel<18, S>), grid, dim3(nw * 64), 0, st, args);
-    else hipLaunchKernelGGL((tail_kernel<32, S>), grid, dim3(nw * 64), 0, st, args);
+  auto launch = [&](auto session, auto warped, const auto& args) {  // one NV dispatch for every instance
+    constexpr bool S = decltype(session)::value, W = decltype(warped)::value;
+    if constexpr (W) {
+      if (t.V <= 512) hipLaunchKernelGGL((tail_warp_kernel<8, S>), grid, dim3(nw * 64), 0, st, args);
+      else if (t.V <= 1152) hipLaunchKernelGGL((tail_warp_kernel<18, S>), grid, dim3(nw * 64), 0, st, args);
+      else hipLaunchKernelGGL((tail_warp_kernel<32, S>), grid, dim3(nw * 64), 0, st, args);
+    } else {
+      if (t.V <= 512) hipLaunchKernelGGL((tail_kernel<8, S>), grid, dim3(nw * 64), 0, st, args);
+      else if (t.V <= 1152) hipLaunchKernelGGL((tail_kernel<18, S>), grid, dim3(nw * 64), 0, st, args);
+      else hipLaunchKernelGGL((tail_kernel<32, S>), grid, dim3(nw * 64), 0, st, args);
+    }
   };
-  if (row_maxlen) launch(std::true_type{}, TailSessionArgs{t, row_maxlen, row0, slot_gen, slot_tprefix});  // per-slot clocks
-  else launch(std::false_type{}, t);
+  if (row_maxlen) {  // per-slot clocks
+    const TailSessionArgs s{t, row_maxlen, row0, slot_gen, slot_tprefix};
+    if (warp) launch(std::true_type{}, std::true_type{}, TailSessionWarpArgs{s, warp});
+    else launch(std::true_type{}, std::false_type{}, s);
+  } else if (warp) {
+    launch(std::false_type{}, std::true_type{}, TailWarpArgs{t, warp});
+  } else {
+    launch(std::false_type{}, std::false_type{}, t);
+  }
 }

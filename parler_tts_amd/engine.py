@@ -64,6 +64,7 @@ class DecoderEngine:
         N.check(self.lib.ptts_engine_create(C.byref(self.cfg), C.byref(self._h)), "ptts_engine_create")
         self.B = 0
         self.history_penalty = None  # (repetition_penalty, no_repeat_ngram_size) while the device node is on (set_history_penalty)
+        self.sample_warp = None  # (min_p, typical_p, epsilon_cutoff, eta_cutoff) while the tail's WARP instances are on (set_sample_warp)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -163,6 +164,53 @@ class DecoderEngine:
         hp = None if default else self._history_penalty(repetition_penalty, no_repeat_ngram_size)
         N.check(self.lib.ptts_set_slot_history_penalty(self._h, int(slot), None if hp is None else C.byref(hp), _stream_ptr(device=self.device)),
                 "ptts_set_slot_history_penalty")
+
+    @staticmethod
+    def _sample_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff):
+        """The four options as a ``ptts_sample_warp`` (``None`` = the neutral value of that option); ``ValueError`` on values out of range."""
+        def number(name, v, neutral):
+            if v is None:
+                return neutral
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"`{name}` must be a number, got {v!r}") from None
+            return f
+
+        m, t = number("min_p", min_p, 0.0), number("typical_p", typical_p, 1.0)
+        e, h = number("epsilon_cutoff", epsilon_cutoff, 0.0), number("eta_cutoff", eta_cutoff, 0.0)
+        if not (math.isfinite(m) and 0.0 <= m <= 1.0):
+            raise ValueError(f"`min_p` must lie in [0, 1], got {min_p}")
+        if not (math.isfinite(t) and 0.0 < t <= 1.0):
+            raise ValueError(f"`typical_p` must lie in (0, 1], got {typical_p}")
+        if not (math.isfinite(e) and 0.0 <= e < 1.0):
+            raise ValueError(f"`epsilon_cutoff` must lie in [0, 1), got {epsilon_cutoff}")
+        if not (math.isfinite(h) and 0.0 <= h < 1.0):
+            raise ValueError(f"`eta_cutoff` must lie in [0, 1), got {eta_cutoff}")
+        return N.PttsSampleWarp(m, t, e, h)
+
+    def set_sample_warp(self, min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                        eta_cutoff: Optional[float] = None, enabled: bool = True):
+        """transformers' ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` on the device (``ptts_set_sample_warp``): from the next
+        ``prefill`` / ``begin_session`` on every sampler tail is the instance that applies them behind top-p, with these values for every
+        utterance (a session: for every request that brings none of its own). Neutral values (the defaults) change no draw: how a session is
+        opened when only some requests will bring warpers. ``enabled=False`` switches the instances off (the state of a new engine).
+        ``ValueError`` inside a session that holds a request."""
+        if not enabled:
+            N.check(self.lib.ptts_set_sample_warp(self._h, None, _stream_ptr(device=self.device)), "ptts_set_sample_warp")
+            self.sample_warp = None
+            return
+        w = self._sample_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        N.check(self.lib.ptts_set_sample_warp(self._h, C.byref(w), _stream_ptr(device=self.device)), "ptts_set_sample_warp")
+        self.sample_warp = (float(w.min_p), float(w.typical_p), float(w.epsilon_cutoff), float(w.eta_cutoff))
+
+    def set_slot_sample_warp(self, slot: int, min_p: Optional[float] = None, typical_p: Optional[float] = None,
+                             epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, default: bool = False):
+        """The record the next admission into the idle slot ``slot`` runs under (``ptts_set_slot_sample_warp``), its first token included;
+        ``default=True`` restores the session's values, as ``retire_row`` does. Only in a session begun with the instances on."""
+        w = None if default else self._sample_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        N.check(self.lib.ptts_set_slot_sample_warp(self._h, int(slot), None if w is None else C.byref(w), _stream_ptr(device=self.device)),
+                "ptts_set_slot_sample_warp")
 
     def prefill(self, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
                 prompt_mask: Optional[torch.Tensor], sample: bool = True):

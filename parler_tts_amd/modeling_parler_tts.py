@@ -25,6 +25,10 @@ from .engine import DecoderEngine, T5Engine
 from .generation_extras import active_extras, build_processors, build_stopping_criteria, check_generation_mode, check_model_kwargs
 from .logits_processors import ParlerTTSLogitsProcessor
 
+# the generation options that have a device implementation behind a switch of the model (enable_device_penalties / enable_device_warpers)
+_DEVICE_PENALTIES = ("repetition_penalty", "no_repeat_ngram_size")
+_DEVICE_WARPERS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+
 
 # ------------------------------------------------------------------------------------------------------------
 # delay pattern (reference :205-276) — closed form instead of the reference's loop + triu/tril
@@ -602,6 +606,17 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         self._engine = None
         return self
 
+    def enable_device_warpers(self, enabled: bool = True):
+        """Opt-in: ``min_p``, ``typical_p``, ``epsilon_cutoff`` and ``eta_cutoff`` run on the device, inside the sampler tail behind top-p
+        (``ptts_warp.h``), in transformers' order and on its renormalised distributions. A sampling ``generate()`` then stays on the captured
+        step graph when these (and, with ``enable_device_penalties()``, the two history penalties) are the only options beyond the device
+        sampler's and the caller brings no processors, stopping criteria or score outputs (any other combination runs the host loop as
+        before), and ``ContinuousBatcher`` takes the four options for a session and per request. Off (the default): every call is routed
+        exactly as without this switch."""
+        self.device_warpers = bool(enabled)
+        self._engine = None
+        return self
+
     def _get_engine(self, B: int, N: int, P: int, max_length: int, T: int = 0) -> DecoderEngine:
         """T = voice-prompt frames: the prefill runs the P prompt positions, the BOS column and the T given columns in one pass."""
         dev, dt = self.device, self.dtype
@@ -863,9 +878,14 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         # loop with transformers' own processor objects (generation_extras.py). Nothing is silently ignored.
         extras = active_extras(gc)
         # model.enable_device_penalties(): the two history penalties alone, with nothing that needs the host's view of a step, stay on the device
-        dev_pen = (bool(getattr(self, "device_penalties", False)) and bool(extras) and set(extras) <= {"repetition_penalty", "no_repeat_ngram_size"}
-                   and not manual and not (bool(getattr(gc, "return_dict_in_generate", False)) and (getattr(gc, "output_scores", False) or getattr(gc, "output_logits", False))))
-        if dev_pen:
+        # model.enable_device_warpers(): likewise min_p / typical_p / epsilon_cutoff / eta_cutoff, which the sampler tail applies behind top-p
+        # (active only in a sampling call). With both switches a call may bring both kinds
+        on_device = (_DEVICE_PENALTIES if getattr(self, "device_penalties", False) else ()) + (_DEVICE_WARPERS if getattr(self, "device_warpers", False) else ())
+        stays = (bool(extras) and set(extras) <= set(on_device)
+                 and not manual and not (bool(getattr(gc, "return_dict_in_generate", False)) and (getattr(gc, "output_scores", False) or getattr(gc, "output_logits", False))))
+        dev_pen = stays and any(x in _DEVICE_PENALTIES for x in extras)
+        dev_warp = stays and any(x in _DEVICE_WARPERS for x in extras)
+        if stays:
             extras = []
         manual = manual or bool(extras)
         # return_dict_in_generate + output_scores / output_logits: the reference returns `_sample`'s per-step tuples next to the waveform
@@ -889,6 +909,10 @@ class ParlerTTSForConditionalGeneration(nn.Module):
             eng.set_history_penalty(repetition_penalty=gc.repetition_penalty, no_repeat_ngram_size=gc.no_repeat_ngram_size)
         elif getattr(eng, "history_penalty", None) is not None:  # the node of an earlier call: off, this call's graphs are the plain ones
             eng.set_history_penalty(enabled=False)
+        if dev_warp:
+            eng.set_sample_warp(min_p=gc.min_p, typical_p=gc.typical_p, epsilon_cutoff=gc.epsilon_cutoff, eta_cutoff=gc.eta_cutoff)
+        elif getattr(eng, "sample_warp", None) is not None:  # the instances of an earlier call: off, this call's graphs are the plain ones
+            eng.set_sample_warp(enabled=False)
         pad, eos = gc.pad_token_id if gc.pad_token_id is not None else d.pad_token_id, d.eos_token_id
         bos_col = torch.full((B * K, 1), bos, dtype=torch.long, device=dev)
         dec_ids = bos_col if prefix is None else torch.cat([bos_col, prefix], dim=-1)  # :3011-3018
