@@ -22,6 +22,13 @@
 #include "ptts_gemv.h"
 
 __device__ __forceinline__ float gv_gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+// The GELU behind GV_GELU_WT's engine-dtype output (gelu_erf_wt of ptts_lm_kernels.h: the strip kernels' EPI_GELU_WT). bf16 engine: gv_gelu_erf - its
+// fp32 error vanishes in the bf16 rounding. fp32 engine: 1 + erff cancels for x < 0, so gv_gelu_erf was up to 23 fp32 ulps of the (small) result
+// away on exact accumulators (tests/test_gemv_kernels_gpu.py); the output is held to ONE fp32 ulp, so it is 0.5 x erfc(-x / sqrt 2) in double,
+// rounded once. One evaluation per output row of the fp32 parity engine's fc1.
+template <typename WT> __device__ __forceinline__ float gv_gelu_erf_wt(float x);
+template <> __device__ __forceinline__ float gv_gelu_erf_wt<bf16_t>(float x) { return gv_gelu_erf(x); }
+template <> __device__ __forceinline__ float gv_gelu_erf_wt<float>(float x) { return (float)(0.5 * (double)x * erfc(-(double)x * 0.70710678118654752440)); }
 
 template <typename DT> __device__ __forceinline__ void gv_store(DT* p, float v);
 template <> __device__ __forceinline__ void gv_store<float>(float* p, float v) { *p = v; }
@@ -406,7 +413,7 @@ __global__ void __launch_bounds__((gv_prologue_waves<PRO, MB>(NCH * Elem<WT>::EP
     float* o = a.out + (size_t)em * a.out_ld + r0 + er;
     if (EPI == GV_STORE) *o = v;
     else if (EPI == GV_RESID) *o = res_pre + v;
-    else gv_store<WT>(reinterpret_cast<WT*>(a.out) + (size_t)em * a.out_ld + r0 + er, gv_gelu_erf(v));
+    else gv_store<WT>(reinterpret_cast<WT*>(a.out) + (size_t)em * a.out_ld + r0 + er, gv_gelu_erf_wt<WT>(v));
   }
   if (wave == NPW) GV_STAMP(a, 6);  // store issued
 }
