@@ -46,6 +46,11 @@ class PttsSampleWarp(C.Structure):
     _fields_ = [("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
 
 
+class PttsScoreIO(C.Structure):
+    """ptts_score_io (include/ptts_score.h): device pointers of one teacher-forced scoring call."""
+    _fields_ = [("input_ids", C.c_void_p), ("labels", C.c_void_p), ("nll", C.c_void_p), ("counted", C.c_void_p), ("logits", C.c_void_p)]
+
+
 class PttsT5Config(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32), ("d_model", C.c_int32), ("d_kv", C.c_int32), ("d_ff", C.c_int32), ("num_layers", C.c_int32),
@@ -157,6 +162,11 @@ WARP_SYMBOLS = {
     "ptts_set_slot_sample_warp": (C.c_int, [_VP, _I32, C.POINTER(PttsSampleWarp), _VP]),
 }
 
+# include/ptts_score.h, additive likewise: one teacher-forced forward ending in the fused LM-heads + cross-entropy kernel
+SCORE_SYMBOLS = {
+    "ptts_score": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(PttsScoreIO), _VP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -180,7 +190,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
     for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
                               + list(SESSION_VOICE_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())
-                              + list(WARP_SYMBOLS.items())):
+                              + list(WARP_SYMBOLS.items()) + list(SCORE_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

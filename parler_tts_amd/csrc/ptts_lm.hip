@@ -13,12 +13,14 @@
 #include "../../include/ptts_session_voice.h"
 #include "../../include/ptts_penalty.h"
 #include "../../include/ptts_warp.h"
+#include "../../include/ptts_score.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
 #include "ptts_strip_w8.h"
 #include "ptts_gemm_launch.h"
 #include "ptts_tail_launch.h"
 #include "ptts_penalty_launch.h"
+#include "ptts_score_launch.h"
 
 thread_local std::string g_ptts_err;
 int ptts_fail(int code, const char* fmt, ...) {
@@ -433,8 +435,9 @@ int gemv_step(const ptts_engine* e, FwdView v, hipStream_t st) {
 }
 
 // The MFMA strip path up to the logits: every prefill (Q positions per utterance), and the decode step above gemv_rows utterances
+// (heads = false: the layers only, the residual rows stay in v.h - ptts_score runs its own heads + loss kernel over them)
 template <typename WT>
-int strip_path(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStream_t st) {
+int strip_path(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStream_t st, bool heads = true) {
   const ptts_config& c = e->cfg;
   const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, B = v.B;
   const int nkv = e->nkv, nkc = e->nkc, Hkv = nkv * 64, QKV = H + 2 * Hkv;  // grouped-query attention: fewer K/V heads
@@ -594,7 +597,7 @@ int strip_path(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStream_t
   }
   // (the final LayerNorm + LM heads as one lnproj_fused_kernel node at 9..40 utterances measured neutral to +0.6 %: the 20 MB of head weights are
   //  re-read once per group of 8 utterances - profiles/r04_experiments.txt call 23; the rows_prep + strip GEMM pair stays)
-  {  // final LayerNorm + all K LM heads as one [K*V, H] projection, last position of each utterance only
+  if (heads) {  // final LayerNorm + all K LM heads as one [K*V, H] projection, last position of each utterance only
     GemmArgs g = {}; g.decode = dec;
     g.W = e->heads; g.W8 = e->heads_p8; g.wscale = e->heads_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = Q; g.x_row_off = Q - 1; g.gamma = e->lnf_g; g.beta = e->lnf_b;
     g.out = v.logits; g.out_ld = c.num_codebooks * c.vocab_size; g.M = B; g.N = c.num_codebooks * c.vocab_size; g.K = H;
@@ -1295,6 +1298,59 @@ extern "C" int ptts_decode_steps(ptts_engine* e, int32_t n_steps, void* stream) 
   }
   if (n_steps > 0) PTTS_TRY(precapture_graphs(e, 2));  // the current bucket and the next one, while the GPU works through what was just enqueued
   return PTTS_OK;
+}
+
+// ---- teacher-forced scoring (include/ptts_score.h) ------------------------------------------------------------------------------------
+template <typename WT>
+static int score_forward(const ptts_engine* e, FwdView v, int T, const ptts_score_io* io, hipStream_t st) {
+  const ptts_config& c = e->cfg;
+  const int Q = v.P + T;
+  PTTS_TRY(project_cross_kv<WT>(e, v, st));
+  EmbedRawArgs ea = {};
+  ea.tables = e->embed; ea.pos_table = c.rope ? nullptr : e->pos_table; ea.prompt = e->ffn; ea.ids = reinterpret_cast<const long long*>(io->input_ids); ea.h = v.h;
+  ea.H = c.hidden_size; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.P = v.P; ea.T = T;
+  hipLaunchKernelGGL((embed_raw_kernel<WT>), dim3(Q, v.B), dim3(256), 0, st, ea);
+  PTTS_TRY((strip_path<WT>(e, v, true, Q, st, false)));
+  ScoreArgs s = {};
+  s.x = v.h; s.x_ld = c.hidden_size; s.gamma = e->lnf_g; s.beta = e->lnf_b; s.W = e->heads;
+  s.ids = reinterpret_cast<const long long*>(io->input_ids); s.labels = reinterpret_cast<const long long*>(io->labels);
+  s.nll = io->nll; s.counted = io->counted; s.logits = io->logits;
+  s.H = c.hidden_size; s.K = c.num_codebooks; s.V = c.vocab_size; s.B = v.B; s.Q = Q; s.Qs = io->logits ? Q : T; s.T = T;
+  s.bos = c.bos_token_id; s.eos = c.eos_token_id;
+  return score_launch<WT>(s, st);
+}
+
+extern "C" int ptts_score(ptts_engine* e, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev, const int32_t* prompt_mask_dev,
+                          int32_t B, int32_t N, int32_t P, int32_t T, const ptts_score_io* io, void* stream) {
+  PTTS_CHECK(e && enc_dev && io, PTTS_E_INVALID, "null argument");
+  PTTS_TRY(ptts_weights_ready(e));
+  const ptts_config& c = e->cfg;
+  PTTS_CHECK(T >= 1, PTTS_E_INVALID, "T = %d: at least one decoder column", T);
+  PTTS_CHECK(io->input_ids && (io->labels || io->logits), PTTS_E_INVALID, "ptts_score_io: input_ids and at least one of labels / logits are required");
+  PTTS_CHECK(io->labels ? (io->nll && io->counted) : (!io->nll && !io->counted), PTTS_E_INVALID, "ptts_score_io: nll and counted are given exactly when labels is");
+  PTTS_CHECK(P >= 0 && (P == 0 || prompt_dev), PTTS_E_INVALID, "prompt length %d with prompt_dev %s", P, prompt_dev ? "given" : "null");
+  PTTS_CHECK(c.hidden_size <= LN_MAX_F4 * 256 && c.hidden_size % 32 == 0, PTTS_E_UNSUPPORTED, "ptts_score: hidden size %d outside the loss kernel's range", c.hidden_size);
+  PTTS_CHECK(!c.kv_fp8, PTTS_E_UNSUPPORTED, "ptts_score on a kv_fp8 engine: the loss of a checkpoint is not to depend on an opt-in cache format");
+  PTTS_CHECK(e->pending_T == 0, PTTS_E_UNSUPPORTED, "ptts_score with a pending voice prompt of %d frames (ptts_set_audio_prefix)", e->pending_T);
+  if (e->session)
+    for (int b = 0; b < e->B; ++b) PTTS_CHECK(!e->slot_busy[b], PTTS_E_INVALID, "ptts_score inside a session whose slot %d holds a request: the pass overwrites arena rows", b);
+  PTTS_CHECK(B >= 1 && B <= c.max_batch, PTTS_E_CAPACITY, "batch %d exceeds engine max_batch %d", B, c.max_batch);
+  PTTS_CHECK(N >= 1 && N <= c.max_enc, PTTS_E_CAPACITY, "encoder length %d exceeds engine max_enc %d", N, c.max_enc);
+  PTTS_CHECK((long long)P + T <= e->max_prompt, PTTS_E_CAPACITY, "P + T = %lld positions exceed the engine's prefill capacity %d (max_prompt)", (long long)P + T, e->max_prompt);
+  PTTS_CHECK(P + T <= c.max_ctx, PTTS_E_CAPACITY, "P + T = %d exceeds engine max_ctx %d", P + T, c.max_ctx);
+  PTTS_CHECK(P + T <= c.max_positions || c.rope, PTTS_E_CAPACITY, "P + T = %d exceeds max_position_embeddings %d", P + T, c.max_positions);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = pick_stream(e, stream);
+  e->B = B; e->N = N; e->P = P;
+  e->session = false;      // (an idle session ends here, as at ptts_prefill)
+  e->prefilled = false;    // the arena rows hold this pass, not a generation: ptts_decode_steps waits for the next prefill
+  e->h_ready = false; e->first_recorded = false;
+  e->xfold_valid = false;  // the un-folded cross block; nothing is folded for this call
+  e->kv_ub = 0; e->kv_bound = 0;
+  launch_set_params(e, 0, st);
+  PTTS_TRY(stage_inputs(e, 0, B, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
+  FwdView v = whole_view(e);
+  return c.dtype == PTTS_BF16 ? score_forward<bf16_t>(e, v, T, io, st) : score_forward<float>(e, v, T, io, st);
 }
 
 // ---- continuous session ---------------------------------------------------------------------------------------------------------------

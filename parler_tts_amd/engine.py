@@ -236,6 +236,57 @@ class DecoderEngine:
         self.B, self.P = B, P
         self._keep = keep  # inputs are consumed asynchronously by the enqueued kernels
 
+    def score(self, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor], prompt_mask: Optional[torch.Tensor],
+              input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None, return_logits: bool = False):
+        """One teacher-forced forward over the given decoder columns (``ptts_score``): ``input_ids`` int64 [B*K, T] (or [B, K, T]) exactly as the
+        model is to see them, ``labels`` int64 [B, T, K] or None. Returns ``(nll, counted, logits)`` on the device: per-token negative
+        log-likelihoods fp32 [B, T, K] (0 where a position does not count), int32 [B, T, K], and fp32 logits [B*K, P + T, V] - each None when not
+        asked for. Without ``return_logits`` the logits are never materialised. The engine is left un-prefilled."""
+        enc = enc.to(self.device, torch.float32).contiguous()
+        B, Nn, H = enc.shape
+        if H != self.H:
+            raise ValueError(f"encoder_hidden_states width {H} != decoder hidden_size {self.H}")
+        if labels is None and not return_logits:
+            raise ValueError("score needs labels, return_logits=True, or both")
+        ids = input_ids.to(self.device, torch.int64)
+        if ids.dim() == 3:
+            ids = ids.reshape(-1, ids.shape[-1])
+        if ids.dim() != 2 or ids.shape[0] != B * self.K or ids.shape[1] < 1:
+            raise ValueError(f"input_ids must be [B*K, T] or [B, K, T] with B = {B}, K = {self.K}, T >= 1; got {tuple(input_ids.shape)}")
+        ids = ids.contiguous()
+        T = ids.shape[1]
+        if bool(((ids < 0) | (ids > self.V)).any()):
+            raise ValueError(f"input_ids outside the embedding tables [0, {self.V}]")
+        P = 0
+        pm = em = pr = lab = nll = counted = logits = None
+        if prompt is not None and prompt.shape[1] > 0:
+            pr = prompt.to(self.device, torch.float32).contiguous()
+            P = pr.shape[1]
+            if pr.shape[0] != B or pr.shape[2] != H:
+                raise ValueError(f"prompt must be [{B}, P, {H}], got {tuple(pr.shape)}")
+        if enc_mask is not None:
+            em = enc_mask.to(self.device, torch.int32).contiguous()
+        if prompt_mask is not None and P > 0:
+            pm = prompt_mask.to(self.device, torch.int32).contiguous()
+        if labels is not None:
+            lab = labels.to(self.device, torch.int64).contiguous()
+            if tuple(lab.shape) != (B, T, self.K):
+                raise ValueError(f"labels must be [B, T, K] = [{B}, {T}, {self.K}], got {tuple(lab.shape)}")
+            # what torch's CrossEntropyLoss refuses: a target that takes part in the loss and is no class
+            takes_part = (lab != -100) & (lab != int(self.cfg.bos_token_id)) & (ids.view(B, self.K, T).transpose(1, 2) != int(self.cfg.eos_token_id))
+            if bool((takes_part & ((lab < 0) | (lab >= self.V))).any()):
+                raise ValueError(f"labels outside [0, {self.V}) at positions that count towards the loss")
+            nll = torch.empty(B, T, self.K, dtype=torch.float32, device=self.device)
+            counted = torch.empty(B, T, self.K, dtype=torch.int32, device=self.device)
+        if return_logits:
+            logits = torch.empty(B * self.K, P + T, self.V, dtype=torch.float32, device=self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+        io = N.PttsScoreIO(ptr(ids), ptr(lab), ptr(nll), ptr(counted), ptr(logits))
+        N.check(self.lib.ptts_score(self._h, ptr(enc), ptr(em), ptr(pr), ptr(pm), B, Nn, P, T, C.byref(io), _stream_ptr(device=self.device)), "ptts_score")
+        self.B, self.P = B, P
+        self._keep = [enc, pr, em, pm, ids, lab]  # inputs are consumed asynchronously by the enqueued kernels
+        return nll, counted, logits
+
     def first_token_sync(self):
         """Blocks until the first token of the last sampling ``prefill`` exists on the device (``ptts_first_token_sync``): the end of
         time-to-first-token; work the prefill enqueued behind the sampler tail (cross-attention fold) is not waited for."""

@@ -14,6 +14,7 @@ import copy
 import json
 import math
 import os
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -201,6 +202,34 @@ class ParlerTTSForCausalLM(nn.Module):
         signature at :2041-2043) and raises TypeError. Generation goes through the composite model."""
         raise NotImplementedError("decoder-only generate() is dead code in the reference (TypeError at modeling_parler_tts.py:2189); "
                                   "call ParlerTTSForConditionalGeneration.generate()")
+
+
+@dataclass
+class ParlerTTSSeq2SeqLMOutput:
+    """What ``ParlerTTSForConditionalGeneration.forward`` returns: the reference's fields (:147-160); those the HIP engine does not
+    materialise stay None."""
+    loss: Optional[torch.Tensor] = None
+    logits: Optional[torch.Tensor] = None
+    past_key_values: Optional[tuple] = None
+    decoder_hidden_states: Optional[tuple] = None
+    decoder_attentions: Optional[tuple] = None
+    cross_attentions: Optional[tuple] = None
+    encoder_last_hidden_state: Optional[torch.Tensor] = None
+    encoder_hidden_states: Optional[tuple] = None
+    encoder_attentions: Optional[tuple] = None
+    per_codebook_losses: Optional[List[torch.Tensor]] = None
+
+
+@dataclass
+class ParlerTTSCausalLMOutputWithCrossAttentions:
+    """The decoder-only output class of the reference (:162-204), by field name."""
+    loss: Optional[torch.Tensor] = None
+    logits: Optional[torch.Tensor] = None
+    past_key_values: Optional[tuple] = None
+    hidden_states: Optional[tuple] = None
+    attentions: Optional[tuple] = None
+    cross_attentions: Optional[tuple] = None
+    per_codebook_losses: Optional[List[torch.Tensor]] = None
 
 
 class GenerateOutput(dict):
@@ -417,8 +446,90 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         self.decoder.lm_heads = new_embeddings
         self._engine = None
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError("the training forward (:2695-2880) is outside this inference implementation; call .generate()")
+    @torch.no_grad()
+    def forward(self, input_ids=None, attention_mask=None, input_values=None, padding_mask=None, decoder_input_ids=None,
+                decoder_attention_mask=None, encoder_outputs=None, past_key_values=None, inputs_embeds=None, decoder_inputs_embeds=None,
+                prompt_input_ids=None, prompt_attention_mask=None, prompt_hidden_states=None, decoder_position_ids=None, labels=None,
+                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, cache_position=None,
+                loss_reduction: str = "mean", output_logits: bool = True, **kwargs):
+        """The teacher-forced forward of the reference (:2695-2880, loss :1924-1957) without gradients: one pass of the HIP engine over the given
+        decoder columns (``ptts_score``) that yields per-token negative log-likelihoods from a fused LM-heads + cross-entropy kernel; the
+        reductions run in torch on those. Decoder columns come from ``decoder_input_ids`` ([B*K, T] or [B, K, T]), else from ``labels``
+        ([B, T, K], shifted right), else from ``input_values`` through the model's codec encoder. ``output_logits=False`` (not in the
+        reference) leaves ``logits`` None and never materialises them: what an evaluation loop wants. ``use_cache`` is ignored. Batches above
+        8 utterances on a model with ``enable_fp8_kv_cache()`` run in groups of at most 8 (the loss does not depend on the opt-in cache
+        format; rows are independent); no other split is made. Memory: the pass runs on the cached engine of the batch-size class, whose row
+        capacity grows to ``P + T`` and stays there (capacities are grow-only): its activation scratch is ``max_batch * (P + T) * ffn_dim`` floats
+        (0.34 GB for 8 utterances of 2580 columns at Mini-v1) and remains allocated for later ``generate()`` calls until the engines are dropped
+        (``model._engine = None``, or a move / dtype change)."""
+        if labels is None and decoder_input_ids is None and input_values is None:
+            raise NotImplementedError("forward() needs `labels`, `decoder_input_ids` or `input_values` (the teacher-forced pass, :2695-2880); "
+                                      "to synthesise, call .generate()")
+        refused = dict(decoder_attention_mask=decoder_attention_mask, decoder_position_ids=decoder_position_ids, decoder_inputs_embeds=decoder_inputs_embeds,
+                       inputs_embeds=inputs_embeds, past_key_values=past_key_values, **{k: v for k, v in kwargs.items() if k.endswith("head_mask")})
+        for name, value in refused.items():
+            if value is not None:
+                raise NotImplementedError(f"forward(): `{name}` is not implemented by the HIP engine")
+        unknown = [k for k in kwargs if not k.endswith("head_mask")]
+        if unknown:
+            raise TypeError(f"forward() got unexpected keyword arguments {sorted(unknown)}")
+        if return_dict is False:
+            raise NotImplementedError("forward(): return_dict=False is not implemented; the result is a ParlerTTSSeq2SeqLMOutput")
+        if output_attentions or output_hidden_states:
+            raise NotImplementedError("output_attentions / output_hidden_states: the HIP decoder does not materialise attention maps or per-layer states")
+        if loss_reduction not in ("mean", "sum"):
+            raise ValueError(f"loss_reduction must be 'mean' or 'sum', got {loss_reduction!r}")
+        d = self.config.decoder
+        K, dev = d.num_codebooks, self.device
+        enc, enc_mask, prompt, prompt_mask = self._conditioning(input_ids, attention_mask, encoder_outputs, prompt_input_ids, prompt_hidden_states,
+                                                                prompt_attention_mask)
+        B, N = enc.shape[0], enc.shape[1]
+        P = prompt.shape[1] if prompt is not None else 0
+        if labels is not None:
+            labels = labels.to(dev).long()
+            if labels.dim() != 3 or labels.shape[0] != B or labels.shape[2] != K:
+                raise ValueError(f"labels must be [batch, seq_len, num_codebooks] = [{B}, T, {K}], got {tuple(labels.shape)}")
+        if decoder_input_ids is not None:
+            cols = decoder_input_ids.to(dev).long()
+            cols = cols.reshape(-1, cols.shape[-1])
+        elif labels is not None:  # :2820-2823
+            cols = self.prepare_decoder_input_ids_from_labels(labels).reshape(B * K, -1)
+        else:  # :2825-2843
+            cols = self._voice_prompt_codes(input_values).long()
+        if cols.shape[0] != B * K or cols.shape[1] < 1:
+            raise ValueError(f"decoder_input_ids must hold [{B} * {K}, T >= 1] columns, got {tuple(cols.shape)}")
+        T = cols.shape[1]
+        if labels is not None and labels.shape[1] != T:
+            raise ValueError(f"labels cover {labels.shape[1]} positions, decoder_input_ids {T}")
+        group = 8 if (getattr(self, "decoder_kv_fp8", False) and B > 8) else B
+        nll, counted, logits = [], [], []
+        for b0 in range(0, B, group):
+            sl = slice(b0, min(B, b0 + group))
+            n = sl.stop - sl.start
+            eng = self._get_engine(n, N, P, T, T - 1)  # (max_length = T, T - 1 given columns): its capacity rule then holds P + T rows
+            part = eng.score(enc[sl], enc_mask[sl] if enc_mask is not None else None, prompt[sl] if prompt is not None else None,
+                             prompt_mask[sl] if prompt_mask is not None else None, cols[sl.start * K:sl.stop * K],
+                             labels[sl] if labels is not None else None, return_logits=bool(output_logits) or labels is None)
+            nll.append(part[0]); counted.append(part[1]); logits.append(part[2])
+        loss = per_codebook = None
+        if labels is not None:
+            loss, per_codebook = self._loss_from_nll(torch.cat(nll), torch.cat(counted), loss_reduction)
+        return ParlerTTSSeq2SeqLMOutput(loss=loss, logits=torch.cat(logits) if (output_logits or labels is None) else None,
+                                        per_codebook_losses=per_codebook, encoder_last_hidden_state=enc)
+
+    def _loss_from_nll(self, nll: torch.Tensor, counted: torch.Tensor, loss_reduction: str):
+        """:1940-1957 on the engine's per-token values: per codebook CrossEntropyLoss(reduction) over the counted positions (mean of nothing is nan,
+        sum of nothing 0, as torch gives), then the codebook weights, or / num_codebooks without them."""
+        c = counted.to(nll.dtype)
+        s = (nll * c).sum(dim=(0, 1))
+        per = s / c.sum(dim=(0, 1)) if loss_reduction == "mean" else s
+        w = getattr(self.config.decoder, "codebook_weights", None)
+        if w is not None:
+            wt = torch.tensor(list(w), dtype=nll.dtype, device=nll.device)
+            loss = (per * wt).sum() / wt.sum()
+        else:
+            loss = per.sum() / per.shape[0]
+        return loss, list(per.unbind(0))
 
     def prepare_decoder_input_ids_from_labels(self, labels: torch.Tensor):
         """shift_tokens_right over [bsz, seq, codebooks] labels, transposed to [bsz, codebooks, seq] (:3196-3199, :187-202)."""
@@ -773,6 +884,39 @@ class ParlerTTSForConditionalGeneration(nn.Module):
             decoder_input_ids = decoder_input_ids[:, 1:]
         return decoder_input_ids
 
+    def _conditioning(self, input_ids, attention_mask, encoder_outputs, prompt_input_ids, prompt_hidden_states, prompt_attention_mask):
+        """What the decoder is conditioned on, shared by generate() and forward(): ``(enc, enc_mask, prompt, prompt_mask)`` on the model's device -
+        the description states (fp32, masked positions zeroed), their mask, and the prompt embeddings that are prepended to the decoder input with
+        their mask; a ``prompt_cross_attention`` model joins the prompt to the cross-attention context instead (:3102-3128, :2791-2811)."""
+        dev = self.device
+        if encoder_outputs is not None:
+            enc = encoder_outputs[0] if isinstance(encoder_outputs, (tuple, list)) else encoder_outputs.last_hidden_state
+        else:
+            if input_ids is None:
+                raise ValueError("`input_ids` (the tokenized description) or `encoder_outputs` must be given")
+            input_ids = input_ids.to(dev)
+            enc = self._encode_description(input_ids, attention_mask.to(dev) if attention_mask is not None else None)
+        enc = enc.to(dev).float()
+        enc_mask = attention_mask.to(dev) if attention_mask is not None else None
+        prompt, prompt_mask = None, None
+        if prompt_hidden_states is None and prompt_input_ids is not None:
+            prompt_hidden_states = self.embed_prompts(prompt_input_ids.to(dev))  # :3100
+        if prompt_hidden_states is not None:
+            ph = prompt_hidden_states.to(dev).float()
+            pm = prompt_attention_mask.to(dev) if prompt_attention_mask is not None else None
+            if self.prompt_cross_attention:  # :3102-3128: prompt joins the cross-attention context
+                ph = ph + self.embed_positions.weights[: ph.shape[1]].float()[None]
+                if pm is not None and enc_mask is None:
+                    enc_mask = torch.ones(enc.shape[:2], device=dev, dtype=pm.dtype)
+                elif enc_mask is not None and pm is None:
+                    pm = torch.ones(ph.shape[:2], device=dev, dtype=enc_mask.dtype)
+                enc = torch.cat([enc, ph], dim=1)
+                if pm is not None:
+                    enc_mask = torch.cat([enc_mask, pm], dim=1)
+            else:
+                prompt, prompt_mask = ph, pm
+        return enc, enc_mask, prompt, prompt_mask
+
     @torch.no_grad()
     def generate(self, inputs: Optional[torch.Tensor] = None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  synced_gpus: Optional[bool] = None, streamer=None, **kwargs):
@@ -806,35 +950,11 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         d = self.config.decoder
         K = d.num_codebooks
         # --- description / prompt conditioning ---------------------------------------------------------------------
-        if encoder_outputs is not None:
-            enc = encoder_outputs[0] if isinstance(encoder_outputs, (tuple, list)) else encoder_outputs.last_hidden_state
-        else:
-            if input_ids is None:
-                raise ValueError("`input_ids` (the tokenized description) or `encoder_outputs` must be given")
-            input_ids = input_ids.to(dev)
-            enc = self._encode_description(input_ids, attention_mask.to(dev) if attention_mask is not None else None)
+        enc, enc_mask, prompt, prompt_mask = self._conditioning(input_ids, attention_mask, encoder_outputs, prompt_input_ids, prompt_hidden_states,
+                                                                prompt_attention_mask)
         B = enc.shape[0]
         if streamer is not None and B > 1:
             raise ValueError("ParlerTTSStreamer only supports batch size 1")
-        enc = enc.to(dev).float()
-        enc_mask = attention_mask.to(dev) if attention_mask is not None else None
-        prompt, prompt_mask = None, None
-        if prompt_hidden_states is None and prompt_input_ids is not None:
-            prompt_hidden_states = self.embed_prompts(prompt_input_ids.to(dev))  # :3100
-        if prompt_hidden_states is not None:
-            ph = prompt_hidden_states.to(dev).float()
-            pm = prompt_attention_mask.to(dev) if prompt_attention_mask is not None else None
-            if self.prompt_cross_attention:  # :3102-3128: prompt joins the cross-attention context
-                ph = ph + self.embed_positions.weights[: ph.shape[1]].float()[None]
-                if pm is not None and enc_mask is None:
-                    enc_mask = torch.ones(enc.shape[:2], device=dev, dtype=pm.dtype)
-                elif enc_mask is not None and pm is None:
-                    pm = torch.ones(ph.shape[:2], device=dev, dtype=enc_mask.dtype)
-                enc = torch.cat([enc, ph], dim=1)
-                if pm is not None:
-                    enc_mask = torch.cat([enc_mask, pm], dim=1)
-            else:
-                prompt, prompt_mask = ph, pm
         num_return = int(getattr(gc, "num_return_sequences", 1) or 1)
         if num_return > 1:  # _expand_inputs_for_generation (:3556-3561)
             enc = enc.repeat_interleave(num_return, 0)
