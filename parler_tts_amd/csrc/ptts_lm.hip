@@ -16,6 +16,7 @@
 #include "../../include/ptts_score.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
+#include "ptts_step_plan.h"
 #include "ptts_strip_w8.h"
 #include "ptts_gemm_launch.h"
 #include "ptts_tail_launch.h"
@@ -72,28 +73,21 @@ struct ptts_engine {
   void* heads = nullptr;  // [K*V][H] packed
   void* heads_rm = nullptr;  // [K*V][H] row-major (GEMV step)
   void* heads_p8 = nullptr;  // [K*V][H] e4m3 strips (weights_fp8, MFMA decode)
-  bool w8_strips = false;    // weights_fp8 engine whose decode step runs on the MFMA strips: e4m3 strip copies are allocated
   float* heads_sc = nullptr;
-  bool use_gemv = false;     // decode step at batch <= gemv_rows on the row-per-wave GEMV kernels
-  int gemv_rows = 1;         // 1 (fp32 parity engine) or GV_MAX_ROWS
-  int xfold_ne = 0;          // > 0: static cross-attention folding available (positions per head in the folded layout)
+  StepSwitches sw;           // the environment switches, read once at create (read_env_switches)
+  StepConfig sc = {};        // what create derives once from cfg (step_config): which step kernels this engine runs, split factors, K/V heads
   KvLayer* kv_layers = nullptr;      // [layers] operands of the batched cross K/V projection (device memory, written once at create)
   FoldLayer* fold_layers = nullptr;  // [layers] operand pointers of the fold kernels (device memory, written once at create)
   bool xfold_valid = false;  // the folded matrices of the CURRENT call are in place (single utterance)
-  bool w8 = false;           // cfg.weights_fp8: e4m3 row-major weights for the GEMV step (the MFMA paths use the exact bf16 dequantisation)
   std::set<std::string> loaded_fp8, required_fp8;
   std::set<std::string> loaded, required;
   // scratch
   float *h = nullptr, *qkv = nullptr, *qc = nullptr, *part = nullptr, *stats = nullptr, *ffn = nullptr, *logits = nullptr;
   float* sort_buf = nullptr;
   void *xw = nullptr, *xw2 = nullptr;  // engine-dtype activation rows for the M > 8 path: [rows][H], [rows][F]
-  int nkv = 0, nkc = 0;                // self / cross K/V heads (== num_heads unless grouped-query attention)
   long long* prefix = nullptr;         // voice-prompt codes [max_batch*K][max_ctx], valid for the next prefill when pending_T > 0
   int pending_T = 0;
   float* lnstat = nullptr;             // strip statistics of the residual rows (EPI_RESID -> PRO_LNS), [max_batch][H/16][2]
-  bool use_lns = true;                 // 8 < batch <= 32 decode: LayerNorm fused into the consumer GEMM (no rows_prep node)
-  int S_self = 4;
-  int cross_waves = 4; // waves per cross-attention workgroup on the GEMV step: one 8-deep batch of row groups per wave covers max_enc
   // state
   long long* ids = nullptr;
   int ids_ld = 0;
@@ -106,27 +100,12 @@ struct ptts_engine {
   int B = 0, N = 0, P = 0;
   bool prefilled = false;
   bool h_ready = false;  // residual-stream input of the next decode step already embedded by the last tail
-  int lnproj = -1;            // -1 = on (3) at every batch size above 8: 8 utterances per workgroup up to 40 (round 4: -5.3 % at 32, -3.2 % at 12; neutral at 64, +12 % at 128
-                              // with 8 per workgroup), 16 per workgroup above (round 5, profiles/r05_experiments.txt call 2: 48 / 64 / 96 / 128 utterances -9.7 / -6.6 / -2.3 / -5.1 % per step). Decode at batch > 8: LayerNorm + projection as ONE node tiled over 64 weight rows x lnproj_g utterances instead of rows_prep + strip GEMM
-                              // (PTTS_LNPROJ: 0 off, 1 = LN1 + QKV, 2 = + LN3 + fc1 above 32 utterances, 3 = + LN3 + fc1 at 9..32 too instead of the producer-statistics prologue)
-  int fuse_qa_max = 3;        // largest batch that runs it (PTTS_FUSE_QA_MAX = 1..8)
   int last_graph_nodes = 0;   // kernel nodes of the step graph captured last (ptts_debug_graph_nodes)
-  bool fuse_qa = true;        // single-utterance GEMV step: LN1 + QKV rows + self-attention + append as one node (qkv_attn_kernel), PTTS_NO_FUSE_QA=1 = two nodes
-  int fuse_x = -1;            // single-utterance GEMV step, folded cross block: LN2 + scores + softmax + U p as one node of per-head partial rows (xfold_attn_kernel),
-                              // summed by the LN3 + fc1 node's prologue (GV_LNP). -1 = by width: on up to hidden 1024 (Mini-v1 -1 %: 566 -> 561 us per step), off
-                              // above (Large-v1 +8..17 %: every fc1 workgroup pulls 24 x 6 KB of partial rows through the L2; profiles/r04_experiments.txt
-                              // call 16); PTTS_FUSE_X=0 / 1 forces it
-  int fuse_x_nur = 2;         // rounds of output rows per workgroup of that node (PTTS_FUSE_X_NUR = 2 / 4: nheads x 8 / nheads x 4 workgroups at Mini-v1)
   float* xpart = nullptr;     // [nheads][H] per-head partial rows of the fused cross block
   float* h2 = nullptr;        // [H] residual row after the cross block (x + partial rows), written by the LN3 + fc1 node
-  bool fuse_xq = true;        // GEMV step, un-folded cross block: LN2 + cross-q rows + cross-attention as one node (xq_attn_kernel), PTTS_NO_FUSE_XQ=1 = two nodes
-  int lnproj_g = 0;           // utterances per workgroup of that node: 0 = by batch size (8 up to 40 utterances, 16 above), PTTS_LNPROJ_G = 4 / 8 / 16 forces one
-  int xattn_g = 0;            // utterances per workgroup of the fused cross block above 8 utterances: 0 = by batch size (2 up to 32, 4 up to 64, 8 above), PTTS_XATTN_G = 8 / 4 / 2 forces one
-  bool xattn_g_ok = false;    // the g < 8 instances exist for this width (Mini-v1, Large-v1)
-  bool xattn_groups = true;   // the fused LN2 + cross-q + cross-attention kernel also at batch 9..32, in groups of 8 utterances (PTTS_NO_XATTN_GROUPS=1: two nodes)
   int kv_ub = 0;         // host-side upper bound of the self-KV positions written so far (prefill + one per decode forward)
   int kv_bound = 0;      // attention fetch bound of the next decode forward: kv_ub + 1 rounded up to 64, <= max_ctx
-  std::map<long long, hipGraphExec_t> graphs;  // key: 2 * batch size + folded-cross-block flag + context bucket + steps per launch (get_graph)
+  std::map<long long, hipGraphExec_t> graphs;  // key: 2 * batch size + folded-cross-block flag + context bucket + session / penalty / warper bits (get_graph)
   int* host_pinned = nullptr;
   // continuous session (ptts_session_begin): every slot of the batch has its own clock, end and fetch bound
   bool session = false;
@@ -208,8 +187,8 @@ FwdView rows_view(const ptts_engine* e, int row, int n, float* h) {
   v.ids += r * K * e->ids_ld; v.cur_len += r; v.first_unf += r; v.unfinished += r * K; v.has_eos += r * K;
   v.logits += r * K * c.vocab_size; v.enc_mask += r * c.max_enc; v.prompt_mask += r * e->max_prompt;
   // an e4m3 self row is 64 bytes with one scale beside it; the cross arena stays in the engine dtype
-  v.self_off = r * e->nkv * c.max_ctx * 64 * (c.kv_fp8 ? 1 : e->esize); v.cross_off = r * e->nkc * c.max_enc * 64 * e->esize;
-  v.scale_off = r * e->nkv * c.max_ctx;
+  v.self_off = r * e->sc.nkv * c.max_ctx * 64 * (c.kv_fp8 ? 1 : e->esize); v.cross_off = r * e->sc.nkc * c.max_enc * 64 * e->esize;
+  v.scale_off = r * e->sc.nkv * c.max_ctx;
   return v;
 }
 
@@ -224,16 +203,9 @@ inline float* scale_at(float* p, size_t off) { return p ? p + off : nullptr; }  
 
 // (launch_status, launch_lnproj and launch_xattn_fused: ptts_gemm_launch.h, shared with tests/native/step_harness.hip)
 
-// LN -> GEMM and split-KV-combine -> GEMM: fused prologue at M <= 8 rows, prep kernel + copy staging above (the
-// redundant per-workgroup prologue is 88 % of the GEMM at M = 32: tools/phase_probe, profiles/).
+// rows_prep node (LayerNorm, or the split-KV combine) into e->xw, then the GEMM with copy staging
 template <typename WT, int PRO, int EPI>
-int gemm_with_prologue(const ptts_engine* e, GemmArgs g, hipStream_t st) {
-  if (g.M <= 8) return launch_gemm<WT, PRO, EPI>(g, st);
-  if constexpr (PRO == PRO_LN) {
-    // statistics came with the residual rows and all M normalised rows fit in LDS beside the reduction buffer
-    if (g.lnstat && g.M <= 32 && (size_t)g.M * ((size_t)g.K * sizeof(WT) + 16) + 16 * 1024 <= 159 * 1024 && (g.K == 1024 || g.K == 1536))
-      return launch_gemm<WT, PRO_LNS, EPI>(g, st);
-  }
+int prep_copy_gemm(const ptts_engine* e, GemmArgs g, hipStream_t st) {
   GemmArgs gp = g;
   gp.out_fo = g.x_fo;  // the prep kernel writes the rows in the order the consumer reads them (x_fo set by the caller: decode, batch > 8)
   PTTS_TRY((launch_prep<WT, PRO>(gp, e->xw, st)));
@@ -242,11 +214,21 @@ int gemm_with_prologue(const ptts_engine* e, GemmArgs g, hipStream_t st) {
   return launch_gemm<WT, PRO_COPY, EPI>(g, st);
 }
 
+// LayerNorm -> GEMM as the plan chose it (ptts_step_plan.h: pro_gemm)
+template <typename WT, int EPI>
+int ln_gemm(const ptts_engine* e, const GemmArgs& g, int how, hipStream_t st) {
+  switch (how) {
+    case PG_FUSED: return launch_gemm<WT, PRO_LN, EPI>(g, st);
+    case PG_LNS: return launch_gemm<WT, PRO_LNS, EPI>(g, st);
+    default: return prep_copy_gemm<WT, PRO_LN, EPI>(e, g, st);
+  }
+}
+
 // Causal self-attention of layer `w` over the view's rows of the KV arena, Q positions per utterance from the QKV rows in e->qkv, RoPE fused: a
-// decode pass appends the new position and splits the context S_self ways; a prefill reads the rows written before it and never splits (strip_path)
-AttnArgs self_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w, int Q, bool prefill, int fo) {
+// decode pass appends the new position and splits the context S_self ways; a prefill reads the rows written before it and never splits (S: the plan's)
+AttnArgs self_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w, int Q, bool prefill, int fo, int S) {
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, nh = c.num_heads, nkv = e->nkv, Hkv = nkv * 64, QKV = H + 2 * Hkv, S = prefill ? 1 : e->S_self;
+  const int H = c.hidden_size, nh = c.num_heads, nkv = e->sc.nkv, Hkv = nkv * 64, QKV = H + 2 * Hkv;
   AttnArgs a = {};
   a.q = e->qkv; a.q_ld = QKV; a.knew = e->qkv + H; a.vnew = e->qkv + H + Hkv; a.kv_ld = QKV; a.kv_heads = nkv; a.n_rep = nh / nkv;
   a.kcache = at(w.k_self, v.self_off); a.vcache = at(w.v_self, v.self_off); a.cap = c.max_ctx; a.kv_bound = prefill ? c.max_ctx : v.kv_bound;
@@ -263,7 +245,7 @@ AttnArgs self_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w,
 // in the attention kernel.
 AttnArgs cross_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w, int Q, bool prefill, int fo) {
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, nh = c.num_heads, nkc = e->nkc;
+  const int H = c.hidden_size, nh = c.num_heads, nkc = e->sc.nkc;
   AttnArgs a = {};
   a.q = e->qc; a.q_ld = H; a.kcache = at(w.k_cross, v.cross_off); a.vcache = at(w.v_cross, v.cross_off); a.cap = c.max_enc; a.kv_bound = c.max_enc;
   a.cur_len = prefill ? nullptr : v.cur_len; a.dims = e->dims; a.mask = v.enc_mask; a.mask_ld = c.max_enc;
@@ -277,7 +259,7 @@ AttnArgs cross_attn_args(const ptts_engine* e, const FwdView& v, const LayerW& w
 template <typename WT>
 int project_cross_kv(const ptts_engine* e, FwdView v, hipStream_t st) {
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, nkc = e->nkc, B = v.B;
+  const int H = c.hidden_size, nkc = e->sc.nkc, B = v.B;
   // encoder states were staged into qc by stage_inputs (fp32 row-major [B*N][H]); convert once to the engine dtype
   const size_t n = (size_t)B * v.N * H;
   hipLaunchKernelGGL((convert_kernel<WT, float>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, e->qc,
@@ -311,31 +293,17 @@ void launch_embed(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStrea
     hipLaunchKernelGGL((embed_kernel<WT, false>), dim3(Q, v.B), dim3(256), 0, st, ea);
 }
 
-// Decode step of 1..gemv_rows utterances up to the logits: 8 row-per-wave GEMV / attention nodes per layer, every weight matrix spread over all
-// CUs and read once
+// Decode step of 1..gemv_rows utterances up to the logits: row-per-wave GEMV / attention nodes, every weight matrix spread over all CUs and read
+// once. Which nodes: the plan (ptts_step_plan.h: gemv_plan); this walker fills their arguments and launches them.
 template <typename WT>
-int gemv_step(const ptts_engine* e, FwdView v, hipStream_t st) {
+int gemv_step(const ptts_engine* e, FwdView v, const GemvPlan& p, hipStream_t st) {
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, M = v.B;
-  const int nkv = e->nkv, nkc = e->nkc, QKV = H + 2 * nkv * 64;  // grouped-query attention: fewer K/V heads
+  const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, M = p.M;
+  const int nkv = e->sc.nkv, nkc = e->sc.nkc, QKV = H + 2 * nkv * 64;  // grouped-query attention: fewer K/V heads
   const float scale = 1.0f / sqrtf((float)(H / nh));
-  const int mode = c.dtype == PTTS_F32 ? GV_F32 : (e->w8 ? GV_BF16_W8 : GV_BF16);
-  // single utterance, sinusoidal positions: the two nodes of the self-attention block's first half as one (PTTS_NO_FUSE_QA=1: two nodes)
-  // (round 5: 2..8 utterances too - one grid slice per utterance, the slices of a head share its weight rows in the L2; PTTS_FUSE_QA_MAX=1: one only)
-  // measured, Mini-v1 us per step at contexts ~210 / ~460 / ~710, fused | two nodes (profiles/r05_experiments.txt call 2): 2 utterances 720 / 756 / 791 |
-  // 769 / 777 / 791; 3: 741 / 788 / 862 | 780 / 796 / 821; 4: 777 / 864 / 923 | 803 / 832 / 862; 8: 966 / 1010 / 1068 | 907 / 965 / 1023 (the slices of
-  // a head re-read its q / k / v rows from the L2 once per utterance and split): on up to fuse_qa_max utterances (3), PTTS_FUSE_QA_MAX forces a bound
-  const bool fuse_qa = e->fuse_qa && (M == 1 || (M <= e->fuse_qa_max && mode != GV_F32)) && !c.rope && ptts_qkvattn_ok(H, mode);
-  // KV splits of the fused node: the smallest count whose FIRST batch of row groups (8 waves x 4 groups x 8 bf16 / 4 fp32 rows per split,
-  // requested before q exists) covers the context bucket this graph is captured for - fewer workgroups recompute the head's q rows, and no
-  // split needs a second, dependent K/V batch (context ~210 / ~460 / ~710: 2 splits 554 / 562 / 586 us per step, 4 splits 575 / 577 / 579,
-  // 8 splits 645 / 646 / 648; profiles/r04_experiments.txt call 15)
-  int S_f = 1;
-  const int S_cap = M == 1 ? 8 : (M <= 4 ? 4 : 2);  // the combine prologue of the out_proj node holds S + 1 slots per lane: 12-wave workgroups (5..8 utterances) fit 2 splits
-  while (S_f < S_cap && S_f * ptts_qkvattn_rows_per_split(mode) < v.kv_bound) S_f *= 2;
-  auto gv = [&](int pro, int epi, int S, GemvArgs g, const char* what) -> int {
-    g.M = M;
-    const int rc_ = ptts_gemv_launch(mode, pro, epi, S, g, st);
+  auto gv = [&](const GemvNode& n, GemvArgs g, const char* what) -> int {
+    g.M = M; g.N = n.N; g.K = n.K;
+    const int rc_ = ptts_gemv_launch(n.mode, n.pro, n.epi, n.S, g, st);
     if (rc_ == -1) return ptts_fail(PTTS_E_UNSUPPORTED, "gemv: no instance for %s (N=%d K=%d M=%d)", what, g.N, g.K, M);
     if (rc_ != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (%s)", what);
     return PTTS_OK;
@@ -343,278 +311,244 @@ int gemv_step(const ptts_engine* e, FwdView v, hipStream_t st) {
 #define PTTS_DBG_NODE(args, l_, k_) PTTS_DBG_STAMP(args, M == 1, (size_t)(l_) * 5 + (k_))
   for (int l = 0; l < c.num_layers; ++l) {
     const LayerW& w = e->L[l];
-    if (fuse_qa) {  // LN1 + the head's q / k / v rows + split-KV self-attention + append in ONE node (qkv_attn_kernel), then combine + out_proj
+    if (p.fuse_qa) {  // LN1 + the head's q / k / v rows + split-KV self-attention + append in ONE node (qkv_attn_kernel), then combine + out_proj
       QkvAttnArgs q = {};
       q.W = w.qkv_rm; q.wscale = w.qkv_sc; q.x = v.h; q.gamma = w.ln1_g; q.beta = w.ln1_b;
       q.kcache = at(w.k_self, v.self_off); q.vcache = at(w.v_self, v.self_off); q.cur_len = v.cur_len; q.P = &e->dims->P; q.mask = v.prompt_mask;
       q.part = e->part; q.stats = e->stats; q.cap = c.max_ctx; q.kv_bound = v.kv_bound; q.mask_ld = e->max_prompt;
-      q.S = S_f; q.nheads = nh; q.H = H; q.kv_heads = nkv; q.scale = scale; q.M = M; q.x_ld = H;
+      q.S = p.S_f; q.nheads = nh; q.H = H; q.kv_heads = nkv; q.scale = scale; q.M = M; q.x_ld = H;
       PTTS_DBG_NODE(q, l, 0);
-      if (ptts_qkvattn_launch(mode, q, st) != 0) return ptts_fail(PTTS_E_HIP, "qkv_attn launch failed");
+      if (ptts_qkvattn_launch(p.mode, q, st) != 0) return ptts_fail(PTTS_E_HIP, "qkv_attn launch failed");
+    } else {
+      GemvArgs g = {};  // LN1 + fused QKV projection (:1020-1021, :848-850)
+      g.W = w.qkv_rm; g.wscale = w.qkv_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln1_g; g.beta = w.ln1_b; g.out = e->qkv; g.out_ld = QKV;
+      PTTS_TRY(gv(p.qkv, g, "LN1+QKV"));
+      // causal self-attention over the KV arena, fused RoPE + append
+      PTTS_TRY((launch_attn<WT>(self_attn_args(e, v, w, 1, false, 0, p.S_self), M, st)));
+    }
+    {  // [combine splits] + out_proj + residual (:1034): the activation rows of an unsplit attention, or the partials of the node before
       GemvArgs g = {};
-      g.W = w.o_rm; g.wscale = w.o_sc; g.out = v.h; g.out_ld = H; g.N = H; g.K = H; g.part = e->part; g.stats = e->stats; g.nheads = nh;
+      g.W = w.o_rm; g.wscale = w.o_sc; g.out = v.h; g.out_ld = H;
+      if (p.out_proj.pro == GV_COPY) { g.xw = e->xw; g.xw_ld = H; }
+      else { g.part = e->part; g.stats = e->stats; g.nheads = nh; }
       PTTS_DBG_NODE(g, l, 1);
-      PTTS_TRY(gv(GV_ATTN2, GV_RESID, S_f, g, "combine+out_proj"));
-    } else {
-    {  // LN1 + fused QKV projection (:1020-1021, :848-850)
+      PTTS_TRY(gv(p.out_proj, g, "[combine+]out_proj"));
+    }
+    switch (p.cross) {
+      case XFOLD_ONE_NODE: {  // folded cross block as ONE node: LN2 + the head's rows of M + softmax + the head's columns of U -> xpart[h][:]
+        XfoldAttnArgs x = {};
+        x.Mw = w.xM; x.Uw = w.xU; x.x = v.h; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.mask = v.enc_mask; x.n_valid = &e->dims->N;
+        x.xpart = e->xpart; x.nheads = nh; x.H = H; x.nur = p.fuse_x_nur;
+        PTTS_DBG_NODE(x, l, 2);
+        if (ptts_xfoldattn_launch(p.fold_mode, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xfold_attn launch failed");
+        break;
+      }
+      case XFOLD_TWO_NODES: {  // folded cross block (xfold_*_kernel at prefill): LN2 + (K Wq) x -> base-2 scores; per-head softmax + (Wo V^T) p + residual
+        GemvArgs g = {};
+        g.W = w.xM; g.x = v.h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = p.xscores.N;
+        PTTS_TRY(gv(p.xscores, g, "LN2 + folded scores"));
+        GemvArgs g2 = {};
+        g2.W = w.xU; g2.x = e->qc; g2.mask = v.enc_mask; g2.n_valid = &e->dims->N; g2.ne = p.xfold_ne; g2.out = v.h; g2.out_ld = H;
+        PTTS_TRY(gv(p.xsoftmax, g2, "softmax + folded out_proj"));
+        break;
+      }
+      case XQ_FUSED: {  // LN2 + the head's cross-q rows + cross-attention of one (head, utterance) as ONE node (xq_attn_kernel): no static fold
+        XqAttnArgs x = {};
+        x.W = w.cq_rm; x.wscale = w.cq_sc; x.x = v.h; x.x_ld = H; x.gamma = w.ln2_g; x.beta = w.ln2_b;
+        x.kcache = at(w.k_cross, v.cross_off); x.vcache = at(w.v_cross, v.cross_off); x.mask = v.enc_mask; x.mask_ld = c.max_enc; x.cap = c.max_enc; x.n_valid = &e->dims->N;
+        x.out = e->xw; x.out_ld = H; x.nheads = nh; x.H = H; x.kv_heads = nkc; x.M = M; x.scale = scale;
+        if (ptts_xqattn_launch(p.mode, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xq_attn launch failed");
+        break;
+      }
+      default: {  // PLAIN: LN2 + cross q projection (:1040, :855), then cross-attention against the static description K/V, softmax finished in the kernel
+        GemvArgs g = {};
+        g.W = w.cq_rm; g.wscale = w.cq_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = H;
+        PTTS_TRY(gv(p.cq, g, "LN2+cross q"));
+        PTTS_TRY((launch_attn<WT>(cross_attn_args(e, v, w, 1, false, 0), M, st, p.cross_waves)));
+      }
+    }
+    if (p.co.on) {  // cross out_proj + residual (:1052)
       GemvArgs g = {};
-      g.W = w.qkv_rm; g.wscale = w.qkv_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln1_g; g.beta = w.ln1_b; g.out = e->qkv; g.out_ld = QKV; g.N = QKV; g.K = H;
-      PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "LN1+QKV"));
-    }
-    // causal self-attention over the KV arena, fused RoPE + append
-    PTTS_TRY((launch_attn<WT>(self_attn_args(e, v, w, 1, false, 0), M, st)));
-    {  // [combine splits] + out_proj + residual (:1034)
-      GemvArgs g = {};
-      g.W = w.o_rm; g.wscale = w.o_sc; g.out = v.h; g.out_ld = H; g.N = H; g.K = H;
-      if (e->S_self == 1) { g.xw = e->xw; g.xw_ld = H; PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g, "out_proj")); }
-      else { g.part = e->part; g.stats = e->stats; g.nheads = nh; PTTS_TRY(gv(GV_ATTN, GV_RESID, e->S_self, g, "combine+out_proj")); }
-    }
-    }
-    bool x_fused = false;  // the cross block left its output as per-head partial rows (summed by the LN3 + fc1 node)
-    if (v.xfold_valid && M == 1 && (e->fuse_x < 0 ? H <= 1024 : e->fuse_x != 0) && e->xfold_ne == 64 && ptts_xfoldattn_ok(H, nh, c.dtype == PTTS_F32 ? GV_F32 : GV_BF16)) {
-      // folded cross block as ONE node: LN2 + the head's rows of M + softmax + the head's columns of U -> xpart[h][:]
-      XfoldAttnArgs x = {};
-      x.Mw = w.xM; x.Uw = w.xU; x.x = v.h; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.mask = v.enc_mask; x.n_valid = &e->dims->N;
-      x.xpart = e->xpart; x.nheads = nh; x.H = H; x.nur = e->fuse_x_nur;
-      PTTS_DBG_NODE(x, l, 2);
-      if (ptts_xfoldattn_launch(c.dtype == PTTS_F32 ? GV_F32 : GV_BF16, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xfold_attn launch failed");
-      x_fused = true;
-    } else if (v.xfold_valid && M == 1) {
-      // folded cross block (xfold_*_kernel at prefill): LN2 + (K Wq) x -> base-2 scores; per-head softmax + (Wo V^T) p + residual
-      const int K2 = nh * e->xfold_ne, gm = c.dtype == PTTS_F32 ? GV_F32 : GV_BF16;  // M / U are in the engine dtype, never e4m3
-      GemvArgs g = {};
-      g.W = w.xM; g.x = v.h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = K2; g.N = K2; g.K = H; g.M = 1;
-      if (ptts_gemv_launch(gm, GV_LN, GV_STORE, 1, g, st) != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (LN2 + folded scores)");
-      GemvArgs g2 = {};
-      g2.W = w.xU; g2.x = e->qc; g2.mask = v.enc_mask; g2.n_valid = &e->dims->N; g2.ne = e->xfold_ne;
-      g2.out = v.h; g2.out_ld = H; g2.N = H; g2.K = K2; g2.M = 1;
-      if (ptts_gemv_launch(gm, GV_SOFTMAX, GV_RESID, 1, g2, st) != 0) return ptts_fail(PTTS_E_HIP, "gemv launch failed (softmax + folded out_proj)");
-    } else {
-    if (e->fuse_xq && !c.rope && ptts_xqattn_ok(H, mode)) {
-      // LN2 + the head's cross-q rows + cross-attention of one (head, utterance) as ONE node (xq_attn_kernel): 1..8 utterances without the static fold
-      XqAttnArgs x = {};
-      x.W = w.cq_rm; x.wscale = w.cq_sc; x.x = v.h; x.x_ld = H; x.gamma = w.ln2_g; x.beta = w.ln2_b;
-      x.kcache = at(w.k_cross, v.cross_off); x.vcache = at(w.v_cross, v.cross_off); x.mask = v.enc_mask; x.mask_ld = c.max_enc; x.cap = c.max_enc; x.n_valid = &e->dims->N;
-      x.out = e->xw; x.out_ld = H; x.nheads = nh; x.H = H; x.kv_heads = nkc; x.M = M; x.scale = scale;
-      if (ptts_xqattn_launch(mode, x, st) != 0) return ptts_fail(PTTS_E_HIP, "xq_attn launch failed");
-    } else {
-    {  // LN2 + cross q projection (:1040, :855)
-      GemvArgs g = {};
-      g.W = w.cq_rm; g.wscale = w.cq_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln2_g; g.beta = w.ln2_b; g.out = e->qc; g.out_ld = H; g.N = H; g.K = H;
-      PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "LN2+cross q"));
-    }
-    // cross-attention against the static description K/V: one workgroup per head, softmax finished in the kernel
-    PTTS_TRY((launch_attn<WT>(cross_attn_args(e, v, w, 1, false, 0), M, st, e->cross_waves)));
-    }
-    {  // cross out_proj + residual (:1052)
-      GemvArgs g = {};
-      g.W = w.co_rm; g.wscale = w.co_sc; g.xw = e->xw; g.xw_ld = H; g.out = v.h; g.out_ld = H; g.N = H; g.K = H;
-      PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g, "cross out_proj"));
-    }
+      g.W = w.co_rm; g.wscale = w.co_sc; g.xw = e->xw; g.xw_ld = H; g.out = v.h; g.out_ld = H;
+      PTTS_TRY(gv(p.co, g, "cross out_proj"));
     }
     {  // LN3 + fc1 + GELU (engine dtype), fc2 + residual (:1059-1064)
       GemvArgs g = {};
       g.W = w.fc1_rm; g.wscale = w.fc1_sc; g.x = v.h; g.x_ld = H; g.gamma = w.ln3_g; g.beta = w.ln3_b;
-      g.out = reinterpret_cast<float*>(e->xw2); g.out_ld = F; g.N = F; g.K = H;
+      g.out = reinterpret_cast<float*>(e->xw2); g.out_ld = F;
+      if (p.x_fused) { g.part = e->xpart; g.npart = nh; g.hsum = e->h2; }  // GV_LNP sums the cross block's partial rows
       PTTS_DBG_NODE(g, l, 3);
-      if (x_fused) { g.part = e->xpart; g.npart = nh; g.hsum = e->h2; PTTS_TRY(gv(GV_LNP, GV_GELU_WT, 1, g, "partial rows+LN3+fc1")); }
-      else PTTS_TRY(gv(GV_LN, GV_GELU_WT, 1, g, "LN3+fc1"));
+      PTTS_TRY(gv(p.fc1, g, "[partial rows+]LN3+fc1"));
       GemvArgs g2 = {};
-      g2.W = w.fc2_rm; g2.wscale = w.fc2_sc; g2.xw = e->xw2; g2.xw_ld = F; g2.out = v.h; g2.out_ld = H; g2.N = H; g2.K = F;
-      if (x_fused) g2.resid = e->h2;  // h = (x + partial rows) + fc2(...)
+      g2.W = w.fc2_rm; g2.wscale = w.fc2_sc; g2.xw = e->xw2; g2.xw_ld = F; g2.out = v.h; g2.out_ld = H;
+      if (p.x_fused) g2.resid = e->h2;  // h = (x + partial rows) + fc2(...)
       PTTS_DBG_NODE(g2, l, 4);
-      PTTS_TRY(gv(GV_COPY, GV_RESID, 1, g2, "fc2"));
+      PTTS_TRY(gv(p.fc2, g2, "fc2"));
     }
   }
   GemvArgs g = {};  // final LayerNorm + all K LM heads (:1632, :1917-1960)
-  g.W = e->heads_rm; g.wscale = e->heads_sc; g.x = v.h; g.x_ld = H; g.gamma = e->lnf_g; g.beta = e->lnf_b; g.out = v.logits;
-  g.out_ld = c.num_codebooks * c.vocab_size; g.N = c.num_codebooks * c.vocab_size; g.K = H;
+  g.W = e->heads_rm; g.wscale = e->heads_sc; g.x = v.h; g.x_ld = H; g.gamma = e->lnf_g; g.beta = e->lnf_b; g.out = v.logits; g.out_ld = p.heads.N;
   PTTS_DBG_NODE(g, c.num_layers, 0);
-  PTTS_TRY(gv(GV_LN, GV_STORE, 1, g, "final LN + LM heads"));
+  PTTS_TRY(gv(p.heads, g, "final LN + LM heads"));
   return launch_status("forward");
 }
 
 // The MFMA strip path up to the logits: every prefill (Q positions per utterance), and the decode step above gemv_rows utterances
-// (heads = false: the layers only, the residual rows stay in v.h - ptts_score runs its own heads + loss kernel over them)
+// (heads = false: the layers only, the residual rows stay in v.h - ptts_score runs its own heads + loss kernel over them).
+// Which nodes: the plan (ptts_step_plan.h: strip_plan); this walker fills their arguments and launches them.
 template <typename WT>
-int strip_path(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStream_t st, bool heads = true) {
+int strip_path(const ptts_engine* e, FwdView v, const StripPlan& p, hipStream_t st, bool heads = true) {
+  static_assert(Elem<WT>::KT == step_kt(sizeof(WT) == 2), "ptts_step_plan.h: step_kt");
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, B = v.B;
-  const int nkv = e->nkv, nkc = e->nkc, Hkv = nkv * 64, QKV = H + 2 * Hkv;  // grouped-query attention: fewer K/V heads
-  const int M = B * Q;
-  const bool big = M > 8;
-  const int dec = prefill ? 0 : 1;  // GemmArgs::decode: rows per M pass of the strip GEMMs (msplit_rows)
+  const int H = c.hidden_size, F = c.ffn_dim, nh = c.num_heads, B = p.B, Q = p.Q, M = p.M, fo = p.fo;
+  const bool prefill = p.prefill != 0;
+  const int nkv = e->sc.nkv, nkc = e->sc.nkc, Hkv = nkv * 64, QKV = H + 2 * Hkv;  // grouped-query attention: fewer K/V heads
   const float scale = 1.0f / sqrtf((float)(H / nh));
-  // KV splits of the self-attention: the engine's split factor at decode (long context, few rows); ONE at prefill - the context is the
-  // prompt (tens of positions) and there is one workgroup per (head, position) anyway: splitting 4 ways + a combine kernel cost
-  // 15 + 9 us per layer on the time-to-first-token path against ~7 us unsplit (profiles/r03_prefill_kernels.txt)
-  const int S_used = prefill ? 1 : e->S_self;
-  const bool lns = e->use_lns && !prefill && M > 8 && M <= 32;  // LayerNorm statistics carried by the producer GEMM (PRO_LNS)
-  // decode at batch > 8: engine-dtype activations travel between kernels in MFMA B-fragment order (ptts_lm_kernels.h: fo_vec_index)
-  // (and the prefill while its rows stay on the strip kernels, M <= 256: a single utterance's 33-position prefill is 240 latency-bound
-  // launches on the time-to-first-token path)
-  const int fo = (M > 8 && (!prefill || M <= 256)) ? 1 : 0;
-  // LayerNorm + projection as one node (lnproj_fused_kernel): decode, batch > 8, Mini / Large widths, weights in the engine dtype (e4m3 strips keep
-  // streaming bytes through the strip GEMMs)
-  const int KT = Elem<WT>::KT;
-  const int lnproj = e->lnproj >= 0 ? e->lnproj : 3;
-  // utterances per workgroup of that node: 8 (one row per wave) up to 40, 16 (two rows per wave, the whole MFMA tile, half the weight re-reads) above
-  const int lnproj_g = e->lnproj_g > 0 ? e->lnproj_g : (M <= 40 ? 8 : 16);
-  // (round 5: the prefill rows of a short prompt, 8 < M <= 40, run the same fused nodes - three rows_prep nodes less per layer on the
-  //  time-to-first-token path: prefill 1.41 -> 1.29 ms, first token 2.41 -> 2.28 ms at 33 rows, profiles/r05_experiments.txt call 2)
-  const bool lnproj_ok = lnproj > 0 && (!prefill || M <= 40) && M > 8 && !e->w8_strips && (H == 1024 || H == 1536) && ((H / KT) / 2) % 8 == 0 && QKV % 64 == 0 && F % 64 == 0;
-  // prefill attention on the tiled kernel (8 query rows per workgroup share the K / V tile; PTTS_PREFILL_ATTN=0: one workgroup per query row, attn_kernel)
-  const int prefill_attn_mode = getenv("PTTS_PREFILL_ATTN") ? atoi(getenv("PTTS_PREFILL_ATTN")) : 3;  // 0: one workgroup per query row, 1: tiled VALU kernel, 2: f32-MFMA kernel, 3: by batch
-  const bool prefill_attn = prefill_attn_mode != 0;
-  // prefill rows on the fused LN1 + QKV node, sinusoidal positions, engine-dtype cache: the node's epilogue writes the cache rows itself (no
-  // kv_append node: 24 launches of ~4 us + their boundaries off the time-to-first-token path)
-  const bool kv_in_qkv = prefill && lnproj_ok && !c.rope && !e->L[0].ks_self;
-  // ... and above 256 rows (a batch's prompts on the > 256-row GEMMs; round 6): the QKV projection's tile epilogue writes them (GemmArgs::kv_col0) -
-  // 24 kv_append launches of ~6 us + their boundaries off the time-to-first-token path of a batch. Between 41 and 256 rows the kv_append node stays
-  // (fragment-order rows_prep + strips: measured path of round 5).
-  const bool kv_in_gemm = prefill && !kv_in_qkv && !lnproj_ok && M > 256 && !c.rope && !e->L[0].ks_self;
+  auto attn = [&](AttnArgs a, int waves) -> int {  // self- or cross-attention node
+    a.hostP = v.P; a.hostN = v.N;  // the prefill kernels' preloaded head (PrefillAttnHead::pack)
+    return p.attn == ATTN_PREFILL ? launch_prefill_attn<WT>(a, B, st, p.prefill_attn_mode) : launch_attn<WT>(a, B, st, waves);
+  };
 #define PTTS_DBG_BIG(args, l_, k_) PTTS_DBG_STAMP(args, !prefill && M > 8, (size_t)(l_) * 7 + (k_))
   for (int l = 0; l < c.num_layers; ++l) {
     const LayerW& w = e->L[l];
     void *const k_self = at(w.k_self, v.self_off), *const v_self = at(w.v_self, v.self_off);
-    if (lnproj_ok) {  // LN1 + fused QKV projection in one node
-      LnProjArgs p = {};
-      PTTS_DBG_BIG(p, l, 0);
-      p.W = w.qkv; p.x = v.h; p.x_ld = H; p.gamma = w.ln1_g; p.beta = w.ln1_b; p.K = H; p.out = e->qkv; p.out_ld = QKV; p.M = M; p.N = QKV;
-      if (kv_in_qkv) { p.kcache = k_self; p.vcache = v_self; p.kv_Q = Q; p.kv_cap = c.max_ctx; p.kv_heads = nkv; p.kv_H = H; }
-      PTTS_TRY((launch_lnproj<WT, EPI_STORE>(e, p, st, lnproj_g)));
-    } else {  // LN1 + fused QKV projection
-      GemmArgs g = {}; g.decode = dec;
-      g.W = w.qkv; g.W8 = w.qkv_p8; g.wscale = w.qkv_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln1_g; g.beta = w.ln1_b;
-      g.out = e->qkv; g.out_ld = QKV; g.M = M; g.N = QKV; g.K = H; g.x_fo = fo;
-      if (kv_in_gemm) { g.kcache = k_self; g.vcache = v_self; g.kv_rows_per_b = Q; g.kv_cap = c.max_ctx; g.nheads = nkv; g.kv_col0 = H; }
-      PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_STORE>(e, g, st)));
-    }
-    if (prefill && !kv_in_qkv && !kv_in_gemm) {
-      bool done8 = false;
-      if constexpr (sizeof(WT) == 2) {
-        if (w.ks_self) {
-          hipLaunchKernelGGL((kv_append_kernel<WT, true>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, k_self, v_self, c.max_ctx,
-                             Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr, scale_at(w.ks_self, v.scale_off), scale_at(w.vs_self, v.scale_off));
-          done8 = true;
-        }
+    switch (p.qkv) {
+      case QKV_LNPROJ: case QKV_LNPROJ_KV: {  // LN1 + fused QKV projection in one node
+        LnProjArgs a = {};
+        PTTS_DBG_BIG(a, l, 0);
+        a.W = w.qkv; a.x = v.h; a.x_ld = H; a.gamma = w.ln1_g; a.beta = w.ln1_b; a.K = H; a.out = e->qkv; a.out_ld = QKV; a.M = M; a.N = QKV;
+        if (p.qkv == QKV_LNPROJ_KV) { a.kcache = k_self; a.vcache = v_self; a.kv_Q = Q; a.kv_cap = c.max_ctx; a.kv_heads = nkv; a.kv_H = H; }
+        PTTS_TRY((launch_lnproj<WT, EPI_STORE>(e, a, st, p.lnproj_g)));
+        break;
       }
-      if (!done8)
+      default: {  // QKV_GEMM, QKV_GEMM_KV: LN1 + fused QKV projection
+        GemmArgs g = {}; g.decode = p.dec;
+        g.W = w.qkv; g.W8 = w.qkv_p8; g.wscale = w.qkv_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln1_g; g.beta = w.ln1_b;
+        g.out = e->qkv; g.out_ld = QKV; g.M = M; g.N = QKV; g.K = H; g.x_fo = fo;
+        if (p.qkv == QKV_GEMM_KV) { g.kcache = k_self; g.vcache = v_self; g.kv_rows_per_b = Q; g.kv_cap = c.max_ctx; g.nheads = nkv; g.kv_col0 = H; }
+        PTTS_TRY((ln_gemm<WT, EPI_STORE>(e, g, p.qkv_how, st)));
+      }
+    }
+    if (p.kv_append == KVA_E4M3) {
+      if constexpr (sizeof(WT) == 2)
+        hipLaunchKernelGGL((kv_append_kernel<WT, true>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, k_self, v_self, c.max_ctx,
+                           Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr, scale_at(w.ks_self, v.scale_off), scale_at(w.vs_self, v.scale_off));
+    } else if (p.kv_append == KVA_ENGINE) {
       hipLaunchKernelGGL((kv_append_kernel<WT>), dim3(Q, nkv, B), dim3(64), 0, st, e->qkv + H, e->qkv + H + Hkv, QKV, k_self,
                          v_self, c.max_ctx, Q, nkv, c.rope ? e->rope_cos : nullptr, c.rope ? e->rope_sin : nullptr);
     }
     {  // causal self-attention over the KV arena
-      AttnArgs a = self_attn_args(e, v, w, Q, prefill, fo);
-      a.hostP = v.P; a.hostN = v.N;  // the prefill kernels' preloaded head (PrefillAttnHead::pack)
+      AttnArgs a = self_attn_args(e, v, w, Q, prefill, fo, p.S_used);
       PTTS_DBG_BIG(a, l, 1);
-      if (prefill && prefill_attn) PTTS_TRY((launch_prefill_attn<WT>(a, B, st, prefill_attn_mode)));
-      else PTTS_TRY((launch_attn<WT>(a, B, st)));
+      PTTS_TRY(attn(a, 4));
     }
     {  // [combine splits] + out_proj + residual
-      GemmArgs g = {}; g.decode = dec;
-      g.W = w.o; g.W8 = w.o_p8; g.wscale = w.o_sc; g.part = e->part; g.stats = e->stats; g.S = S_used; g.nheads = nh;
+      GemmArgs g = {}; g.decode = p.dec;
+      g.W = w.o; g.W8 = w.o_p8; g.wscale = w.o_sc; g.part = e->part; g.stats = e->stats; g.S = p.S_used; g.nheads = nh;
       g.out = v.h; g.out_ld = H; g.M = M; g.N = H; g.K = H; g.x_fo = fo;
-      if (lns) g.stats_out = e->lnstat;  // strip statistics of the new residual rows for LN2 (PRO_LNS)
+      if (p.lns) g.stats_out = e->lnstat;  // strip statistics of the new residual rows for LN2 (PRO_LNS)
       PTTS_DBG_BIG(g, l, 2);
-      if (S_used == 1) {
-        g.x = reinterpret_cast<const float*>(e->xw); g.x_ld = H; g.x_row_mul = 1;
-        PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_RESID>(g, st)));
-      } else {
-        PTTS_TRY((gemm_with_prologue<WT, PRO_ATTN, EPI_RESID>(e, g, st)));
+      switch (p.out_proj) {
+        case OUT_COPY:
+          g.x = reinterpret_cast<const float*>(e->xw); g.x_ld = H; g.x_row_mul = 1;
+          PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_RESID>(g, st)));
+          break;
+        case OUT_COMBINE_FUSED: PTTS_TRY((launch_gemm<WT, PRO_ATTN, EPI_RESID>(g, st))); break;
+        default: PTTS_TRY((prep_copy_gemm<WT, PRO_ATTN, EPI_RESID>(e, g, st)));
       }
     }
-    if (!prefill && (M <= 8 || (e->xattn_groups && M <= 256)) && (H / KT) % 16 == 0 && (H == 512 || H == 1024 || H == 1536)) {
-      // decode, small batch: LN2 + cross q projection + cross-attention fused, one workgroup per head
-      XAttnArgs x = {};
-      x.W = w.cq; x.x = v.h; x.x_ld = H; x.x_row_mul = 1; x.x_row_off = 0; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.K = H;
-      x.invK = 1.0f / (float)H; x.kcache = at(w.k_cross, v.cross_off); x.vcache = at(w.v_cross, v.cross_off); x.cap = c.max_enc; x.cur_len = v.cur_len; x.dims = e->dims;
-      x.mask = v.enc_mask; x.mask_ld = c.max_enc; x.cos = c.rope ? e->rope_cos : nullptr; x.sin = c.rope ? e->rope_sin : nullptr;
-      x.out = e->xw; x.B = M; x.nheads = nh; x.kv_heads = nkc; x.n_rep = nh / nkc; x.scale = scale; x.out_fo = fo;
-      PTTS_DBG_BIG(x, l, 3);
-      // utterances per workgroup: 8 (one per wave) up to 8 utterances; above, e->xattn_g (8 / 4 / 2: heads x ceil(M / g) workgroups, the 8 / g
-      // waves of an utterance split the description's row groups)
-      // measured (profiles/r04_experiments.txt, us per step at mid context, g = 8 / 4 / 2): batch 32 1432 / 1381 / 1360, batch 128 2596 / 2682 / 2860
-      const int gsz = M <= 8 ? 8 : (e->xattn_g ? e->xattn_g : (e->xattn_g_ok ? (M <= 32 ? 2 : (M <= 64 ? 4 : 8)) : 8));
-      launch_xattn_fused<WT>(x, gsz, st);
-    } else {
-    if (prefill && lnproj_ok) {  // LN2 + cross q projection as one node
-      LnProjArgs p = {};
-      p.W = w.cq; p.x = v.h; p.x_ld = H; p.gamma = w.ln2_g; p.beta = w.ln2_b; p.K = H; p.out = e->qc; p.out_ld = H; p.M = M; p.N = H;
-      PTTS_TRY((launch_lnproj<WT, EPI_STORE>(e, p, st, lnproj_g)));
-    } else
-    {  // LN2 + cross q projection
-      GemmArgs g = {}; g.decode = dec;
-      g.W = w.cq; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln2_g; g.beta = w.ln2_b;
-      g.out = e->qc; g.out_ld = H; g.M = M; g.N = H; g.K = H; g.x_fo = fo;
-      if (lns) g.lnstat = e->lnstat;
-      PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_STORE>(e, g, st)));
-    }
-    {  // cross-attention against the static description K/V
-      AttnArgs a = cross_attn_args(e, v, w, Q, prefill, fo);
-      a.hostP = v.P; a.hostN = v.N;
-      if (prefill && prefill_attn) PTTS_TRY((launch_prefill_attn<WT>(a, B, st, prefill_attn_mode)));
-      else PTTS_TRY((launch_attn<WT>(a, B, st, prefill ? 4 : e->cross_waves)));  // decode: as few waves as cover the description (no LDS combine at 1)
-    }
+    switch (p.cross) {
+      case CROSS_XATTN_FUSED: {  // decode: LN2 + cross q projection + cross-attention fused, one workgroup per (head, p.xattn_g utterances)
+        XAttnArgs x = {};
+        x.W = w.cq; x.x = v.h; x.x_ld = H; x.x_row_mul = 1; x.x_row_off = 0; x.gamma = w.ln2_g; x.beta = w.ln2_b; x.K = H;
+        x.invK = 1.0f / (float)H; x.kcache = at(w.k_cross, v.cross_off); x.vcache = at(w.v_cross, v.cross_off); x.cap = c.max_enc; x.cur_len = v.cur_len; x.dims = e->dims;
+        x.mask = v.enc_mask; x.mask_ld = c.max_enc; x.cos = c.rope ? e->rope_cos : nullptr; x.sin = c.rope ? e->rope_sin : nullptr;
+        x.out = e->xw; x.B = M; x.nheads = nh; x.kv_heads = nkc; x.n_rep = nh / nkc; x.scale = scale; x.out_fo = fo;
+        PTTS_DBG_BIG(x, l, 3);
+        launch_xattn_fused<WT>(x, p.xattn_g, st);
+        break;
+      }
+      case CROSS_LNPROJ_ATTN: {  // LN2 + cross q projection as one node, then cross-attention against the static description K/V
+        LnProjArgs a = {};
+        a.W = w.cq; a.x = v.h; a.x_ld = H; a.gamma = w.ln2_g; a.beta = w.ln2_b; a.K = H; a.out = e->qc; a.out_ld = H; a.M = M; a.N = H;
+        PTTS_TRY((launch_lnproj<WT, EPI_STORE>(e, a, st, p.lnproj_g)));
+        PTTS_TRY(attn(cross_attn_args(e, v, w, Q, prefill, fo), p.cross_waves));
+        break;
+      }
+      default: {  // CROSS_GEMM_ATTN: LN2 + cross q projection, then cross-attention
+        GemmArgs g = {}; g.decode = p.dec;
+        g.W = w.cq; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln2_g; g.beta = w.ln2_b;
+        g.out = e->qc; g.out_ld = H; g.M = M; g.N = H; g.K = H; g.x_fo = fo;
+        if (p.lns) g.lnstat = e->lnstat;
+        PTTS_TRY((ln_gemm<WT, EPI_STORE>(e, g, p.cq_how, st)));
+        PTTS_TRY(attn(cross_attn_args(e, v, w, Q, prefill, fo), p.cross_waves));
+      }
     }
     {  // cross out_proj + residual, activations read straight from the attention output
-      GemmArgs g = {}; g.decode = dec;
+      GemmArgs g = {}; g.decode = p.dec;
       g.W = w.co; g.W8 = w.co_p8; g.wscale = w.co_sc; g.x = reinterpret_cast<const float*>(e->xw); g.x_ld = H; g.x_row_mul = 1; g.x_fo = fo;
       g.out = v.h; g.out_ld = H; g.M = M; g.N = H; g.K = H;
-      if (lns) g.stats_out = e->lnstat;  // for LN3
+      if (p.lns) g.stats_out = e->lnstat;  // for LN3
       PTTS_DBG_BIG(g, l, 4);
       PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_RESID>(g, st)));
     }
     {  // LN3 + fc1 + GELU, then fc2 + residual. Above 8 rows the GELU output is written in the engine dtype so fc2
        // stages it with plain copies too.
-      GemmArgs g = {}; g.decode = dec;
+      GemmArgs g = {}; g.decode = p.dec;
       g.W = w.fc1; g.W8 = w.fc1_p8; g.wscale = w.fc1_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = 1; g.gamma = w.ln3_g; g.beta = w.ln3_b;
       g.out_ld = F; g.M = M; g.N = F; g.K = H;
-      GemmArgs g2 = {}; g2.decode = dec;
+      GemmArgs g2 = {}; g2.decode = p.dec;
       g2.W = w.fc2; g2.W8 = w.fc2_p8; g2.wscale = w.fc2_sc; g2.x_ld = F; g2.x_row_mul = 1; g2.out = v.h; g2.out_ld = H; g2.M = M; g2.N = H; g2.K = F;
-      if (big) {
-        g.out = reinterpret_cast<float*>(e->xw2); g.x_fo = fo; g.out_fo = fo;
-        if (lns) g.lnstat = e->lnstat;
-        if (lnproj_ok && (lnproj >= 3 || (lnproj == 2 && M > 32))) {  // LN3 + fc1 + GELU in one node
-          LnProjArgs p = {};
-          p.W = w.fc1; p.x = v.h; p.x_ld = H; p.gamma = w.ln3_g; p.beta = w.ln3_b; p.K = H; p.out = e->xw2; p.out_ld = F; p.out_fo = fo; p.M = M; p.N = F;
-          PTTS_DBG_BIG(p, l, 5);
-          PTTS_TRY((launch_lnproj<WT, EPI_GELU_WT>(e, p, st, lnproj_g)));
-        } else
-        PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_GELU_WT>(e, g, st)));
+      if (p.fc == FC_SMALL) {
+        g.out = e->ffn;
+        PTTS_TRY((launch_gemm<WT, PRO_LN, EPI_GELU>(g, st)));
+        g2.x = e->ffn;
+        PTTS_TRY((launch_gemm<WT, PRO_PLAIN, EPI_RESID>(g2, st)));
+      } else {
+        if (p.fc == FC_LNPROJ) {  // LN3 + fc1 + GELU in one node
+          LnProjArgs a = {};
+          a.W = w.fc1; a.x = v.h; a.x_ld = H; a.gamma = w.ln3_g; a.beta = w.ln3_b; a.K = H; a.out = e->xw2; a.out_ld = F; a.out_fo = fo; a.M = M; a.N = F;
+          PTTS_DBG_BIG(a, l, 5);
+          PTTS_TRY((launch_lnproj<WT, EPI_GELU_WT>(e, a, st, p.lnproj_g)));
+        } else {
+          g.out = reinterpret_cast<float*>(e->xw2); g.x_fo = fo; g.out_fo = fo;
+          if (p.lns) g.lnstat = e->lnstat;
+          PTTS_TRY((ln_gemm<WT, EPI_GELU_WT>(e, g, p.fc1_how, st)));
+        }
         g2.x = reinterpret_cast<const float*>(e->xw2); g2.x_fo = fo;
         PTTS_DBG_BIG(g2, l, 6);
         // fc2 runs un-split at every batch size (round 6, profiles/r06_experiments.txt calls 15-16: the split-K partials of round 2 cost the next LN1 node
         // +1.0 us and the out_proj epilogue +1.2 us per layer - un-split: -2 % at 32, -3.3 % at 40, -7 % at Large-v1 x 32, equal at 12..16; only the
         // e4m3-weight Mini engine loses 1.4-3 %; the split path and its folds are gone)
         PTTS_TRY((launch_gemm<WT, PRO_COPY, EPI_RESID>(g2, st)));
-      } else {
-        g.out = e->ffn;
-        PTTS_TRY((launch_gemm<WT, PRO_LN, EPI_GELU>(g, st)));
-        g2.x = e->ffn;
-        PTTS_TRY((launch_gemm<WT, PRO_PLAIN, EPI_RESID>(g2, st)));
       }
     }
   }
-  // (the final LayerNorm + LM heads as one lnproj_fused_kernel node at 9..40 utterances measured neutral to +0.6 %: the 20 MB of head weights are
-  //  re-read once per group of 8 utterances - profiles/r04_experiments.txt call 23; the rows_prep + strip GEMM pair stays)
   if (heads) {  // final LayerNorm + all K LM heads as one [K*V, H] projection, last position of each utterance only
-    GemmArgs g = {}; g.decode = dec;
+    GemmArgs g = {}; g.decode = p.dec;
     g.W = e->heads; g.W8 = e->heads_p8; g.wscale = e->heads_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = Q; g.x_row_off = Q - 1; g.gamma = e->lnf_g; g.beta = e->lnf_b;
     g.out = v.logits; g.out_ld = c.num_codebooks * c.vocab_size; g.M = B; g.N = c.num_codebooks * c.vocab_size; g.K = H;
-    g.x_fo = (B > 8 && (!prefill || B <= 256)) ? 1 : 0;
-    PTTS_TRY((gemm_with_prologue<WT, PRO_LN, EPI_STORE>(e, g, st)));
+    g.x_fo = p.heads_x_fo;
+    PTTS_TRY((ln_gemm<WT, EPI_STORE>(e, g, p.heads_how, st)));
   }
   return launch_status("forward");
 }
 
-// One decoder forward over Q positions per utterance (Q = P+1 at prefill, 1 at decode) up to the logits.
+// The plan of a strip-path forward. PTTS_PREFILL_ATTN is the one switch read per forward, not at create: 0: one workgroup per
+// query row, 1: tiled VALU kernel, 2: f32-MFMA kernel, 3 (default): by batch
+StripPlan strip_plan_now(const ptts_engine* e, const FwdView& v, bool prefill, int Q) {
+  const int prefill_attn_mode = getenv("PTTS_PREFILL_ATTN") ? atoi(getenv("PTTS_PREFILL_ATTN")) : 3;
+  return strip_plan(e->sc, e->cfg, e->sw, prefill, v.B, Q, prefill_attn_mode);
+}
+
+// One decoder forward over Q positions per utterance (Q = P+1 at prefill, 1 at decode) up to the logits: one plan, then its walker.
 template <typename WT>
 int forward(const ptts_engine* e, FwdView v, bool prefill, hipStream_t st, bool with_embed = true) {
   const int Q = prefill ? v.P + 1 + v.T : 1;  // prompt positions + BOS column [+ the voice-prompt columns, run in the same pass]
   if (prefill) PTTS_TRY(project_cross_kv<WT>(e, v, st));
   if (with_embed) launch_embed<WT>(e, v, prefill, Q, st);
-  if (e->use_gemv && !prefill && v.B <= e->gemv_rows) return gemv_step<WT>(e, v, st);  // batch 1..4 (fp32: 1)
-  return strip_path<WT>(e, v, prefill, Q, st);
+  if (step_on_gemv(e->sc, prefill, v.B)) return gemv_step<WT>(e, v, gemv_plan(e->sc, e->cfg, e->sw, v.B, v.kv_bound, v.xfold_valid), st);  // batch 1..8 (fp32: 1)
+  return strip_path<WT>(e, v, strip_plan_now(e, v, prefill, Q), st);
 }
 
 // the sampler tail over the view's utterances; row >= 0 (sessions only): the tail of that one slot (ptts_admit_row)
@@ -645,7 +579,7 @@ int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next
 template <typename WT, bool W8>
 int fold_cross(ptts_engine* e, hipStream_t st) {
   const ptts_config& c = e->cfg;
-  const int H = c.hidden_size, nh = c.num_heads, NE = e->xfold_ne, n_rep = nh / e->nkc, L = c.num_layers;
+  const int H = c.hidden_size, nh = c.num_heads, NE = e->sc.xfold_ne, n_rep = nh / e->sc.nkc, L = c.num_layers;
   const float qscale = 1.44269504088896340736f / sqrtf((float)(H / nh));
   // tiled kernels (round 5; bit-identical to the row kernels, which serve the widths the tiles do not)
   if (H % 64 == 0 && NE <= 64) {
@@ -720,7 +654,7 @@ int rowmajor_dispatch(ptts_engine* e, void* dst, const void* src, int src_dtype,
 // (GEMV step), of the e4m3 strip copy and of the row scales (weights_fp8) - null where this engine holds none; K = -1: an fp32 vector of N
 struct LayerTensor { const char* name; void *dst, *rm, *p8; float* sc; int N, K, row0; };
 std::array<LayerTensor, 16> layer_tensors(const ptts_engine* e, const LayerW& w) {
-  const int H = e->cfg.hidden_size, F = e->cfg.ffn_dim, kv = e->nkv * 64, kc = e->nkc * 64;
+  const int H = e->cfg.hidden_size, F = e->cfg.ffn_dim, kv = e->sc.nkv * 64, kc = e->sc.nkc * 64;
   return {{{"self_attn.q_proj.weight", w.qkv, w.qkv_rm, w.qkv_p8, w.qkv_sc, H, H, 0},
            {"self_attn.k_proj.weight", w.qkv, w.qkv_rm, w.qkv_p8, w.qkv_sc, kv, H, H},
            {"self_attn.v_proj.weight", w.qkv, w.qkv_rm, w.qkv_p8, w.qkv_sc, kv, H, H + kv},
@@ -736,17 +670,17 @@ std::array<LayerTensor, 16> layer_tensors(const ptts_engine* e, const LayerW& w)
            {"final_layer_norm.weight", w.ln3_g, nullptr, nullptr, nullptr, H, -1, 0}, {"final_layer_norm.bias", w.ln3_b, nullptr, nullptr, nullptr, H, -1, 0}}};
 }
 
-// The engine's environment switches, read once when it is created. PTTS_PREFILL_ATTN alone is read per forward (strip_path).
-void read_env_switches(ptts_engine* e) {
-  if (const char* ev = getenv("PTTS_FUSE_X")) e->fuse_x = atoi(ev) ? 1 : 0;
-  if (const char* ev = getenv("PTTS_FUSE_X_NUR")) { const int v = atoi(ev); if (v == 2 || v == 4) e->fuse_x_nur = v; }
-  e->fuse_qa = !(getenv("PTTS_NO_FUSE_QA") && atoi(getenv("PTTS_NO_FUSE_QA")));
-  if (const char* ev = getenv("PTTS_FUSE_QA_MAX")) e->fuse_qa_max = std::max(1, std::min(GV_MAX_ROWS, atoi(ev)));
-  e->fuse_xq = !(getenv("PTTS_NO_FUSE_XQ") && atoi(getenv("PTTS_NO_FUSE_XQ")));
-  if (const char* ev = getenv("PTTS_LNPROJ")) e->lnproj = std::max(0, std::min(3, atoi(ev)));
-  if (const char* ev = getenv("PTTS_LNPROJ_G")) e->lnproj_g = atoi(ev) == 4 ? 4 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 8 ? 8 : 0));
-  if (const char* ev = getenv("PTTS_XATTN_G")) { const int g = atoi(ev); if (g == 2 || g == 4 || g == 8) e->xattn_g = e->xattn_g_ok ? g : 8; }  // after xattn_g_ok
-  e->xattn_groups = !(getenv("PTTS_NO_XATTN_GROUPS") && atoi(getenv("PTTS_NO_XATTN_GROUPS")));  // measured: 1386 -> 1360 us per batch-32 step (profiles/r03_experiments.txt)
+// The engine's environment switches, read once when it is created. PTTS_PREFILL_ATTN alone is read per forward (strip_plan_now).
+void read_env_switches(StepSwitches* sw) {
+  if (const char* ev = getenv("PTTS_FUSE_X")) sw->fuse_x = atoi(ev) ? 1 : 0;
+  if (const char* ev = getenv("PTTS_FUSE_X_NUR")) { const int v = atoi(ev); if (v == 2 || v == 4) sw->fuse_x_nur = v; }
+  sw->fuse_qa = !(getenv("PTTS_NO_FUSE_QA") && atoi(getenv("PTTS_NO_FUSE_QA")));
+  if (const char* ev = getenv("PTTS_FUSE_QA_MAX")) sw->fuse_qa_max = std::max(1, std::min(GV_MAX_ROWS, atoi(ev)));
+  sw->fuse_xq = !(getenv("PTTS_NO_FUSE_XQ") && atoi(getenv("PTTS_NO_FUSE_XQ")));
+  if (const char* ev = getenv("PTTS_LNPROJ")) sw->lnproj = std::max(0, std::min(3, atoi(ev)));
+  if (const char* ev = getenv("PTTS_LNPROJ_G")) sw->lnproj_g = atoi(ev) == 4 ? 4 : (atoi(ev) == 16 ? 16 : (atoi(ev) == 8 ? 8 : 0));
+  if (const char* ev = getenv("PTTS_XATTN_G")) { const int g = atoi(ev); if (g == 2 || g == 4 || g == 8) sw->xattn_g = g; }  // (a width without the g < 8 instances runs 8: xattn_group_size)
+  sw->xattn_groups = !(getenv("PTTS_NO_XATTN_GROUPS") && atoi(getenv("PTTS_NO_XATTN_GROUPS")));
 }
 
 // NULL is the legacy default stream (what torch.cuda.current_stream() is on ROCm unless the caller switched): pass through.
@@ -766,7 +700,8 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   PTTS_CHECK(c.num_codebooks >= 1 && c.num_codebooks <= 32, PTTS_E_INVALID, "num_codebooks out of range");
   PTTS_CHECK(c.vocab_size <= PTTS_SORT_N, PTTS_E_UNSUPPORTED, "vocab_size > %d unsupported by the sampler", PTTS_SORT_N);
   PTTS_CHECK(c.max_batch >= 1 && c.max_ctx >= 2 && c.max_enc >= 1 && c.max_prompt >= 1 && c.max_prompt <= c.max_ctx, PTTS_E_INVALID, "bad capacities");
-  const int nkv_ = c.num_kv_heads > 0 ? c.num_kv_heads : c.num_heads, nkc_ = c.num_cross_kv_heads > 0 ? c.num_cross_kv_heads : nkv_;
+  const StepConfig sc = step_config(c);  // which step kernels this engine runs: it sizes the weight copies and the scratch below
+  const int nkv_ = sc.nkv, nkc_ = sc.nkc;
   PTTS_CHECK(c.num_heads % nkv_ == 0 && c.num_heads % nkc_ == 0, PTTS_E_INVALID, "num_heads %d not divisible by the K/V head counts %d / %d", c.num_heads, nkv_, nkc_);
   // the bit-packed fields of the preloaded kernel heads: P and the prompt / description mask strides (PrefillAttnHead), the LM heads' row selection
   // Q, Q - 1 (RowsPrepHead) in 16 bits; the prefill GEMMs' tile grid over B x max_prompt rows and B x max_enc description rows (GemmGldsHead)
@@ -780,7 +715,8 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   PTTS_DEVICE(c.device);
   ptts_engine* e = new ptts_engine();
   e->cfg = c;
-  e->nkv = nkv_; e->nkc = nkc_;
+  e->sc = sc;
+  read_env_switches(&e->sw);
   e->esize = c.dtype == PTTS_BF16 ? 2 : 4;
   e->max_prompt = c.max_prompt;
   int rc = PTTS_OK;
@@ -791,55 +727,43 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   const int H = c.hidden_size, F = c.ffn_dim, K = c.num_codebooks, V = c.vocab_size, nh = c.num_heads;
   const size_t es = e->esize;
   e->L.resize(c.num_layers);
-  // single-utterance decode step on the row-per-wave GEMV kernels: shapes whose rows are whole 1 KiB chunks
-  const int gmode = c.dtype == PTTS_F32 ? GV_F32 : GV_BF16;
-  // (an engine created for more than GV_MAX_ROWS utterances never takes the GEMV step: it does not hold the row-major copies either -
-  // the model-level cache keeps one engine per batch-size class, each with the weight copies its own decode step streams)
-  e->use_gemv = ptts_gemv_k_ok(H, gmode) && ptts_gemv_k_ok(F, gmode) && H <= 2048 && c.max_batch <= GV_MAX_ROWS;
-  e->gemv_rows = c.dtype == PTTS_F32 ? 1 : GV_MAX_ROWS;
-  e->w8 = c.weights_fp8 != 0;
-  // static cross-attention folding: single utterance, sinusoidal positions (RoPE rotates the cross query by position), <= 64
-  // description tokens, full cross K/V heads not required (n_rep handled), folded widths must be GEMV shapes
-  if (e->use_gemv && !c.rope && c.max_enc <= 64 && ptts_gemv_k_ok(nh * 64, gmode))
-    e->xfold_ne = 64;
-  e->w8_strips = e->w8 && !e->use_gemv;
   if (c.kv_fp8 && (c.dtype != PTTS_BF16 || c.max_batch <= GV_MAX_ROWS))  // by capacity, not by path (a width without GEMV instances runs strips at 1..8 too)
     return fail(ptts_fail(PTTS_E_UNSUPPORTED, "kv_fp8 (e4m3 self-attention cache) needs the bf16 engine created for more than %d utterances (the MFMA strip step)", GV_MAX_ROWS));
-  if (e->w8 && (c.dtype != PTTS_BF16 || H % 512 || F % 512 || H > 2048))
+  if (e->sc.w8 && (c.dtype != PTTS_BF16 || H % 512 || F % 512 || H > 2048))
     return fail(ptts_fail(PTTS_E_UNSUPPORTED, "weights_fp8 needs the bf16 engine and hidden / ffn sizes that are multiples of 512 (hidden <= 2048)"));
 #define A(expr) if ((rc = (expr)) != PTTS_OK) return fail(rc)
   for (int l = 0; l < c.num_layers; ++l) {
     LayerW& w = e->L[l];
-    const int nq = H + 2 * e->nkv * 64;
+    const int nq = H + 2 * e->sc.nkv * 64;
     A(e->alloc_bytes(&w.qkv, (size_t)nq * H * es));
     A(e->alloc_bytes(&w.o, (size_t)H * H * es));
     A(e->alloc_bytes(&w.cq, (size_t)H * H * es));
-    A(e->alloc_bytes(&w.ckv, (size_t)2 * e->nkc * 64 * H * es));
+    A(e->alloc_bytes(&w.ckv, (size_t)2 * e->sc.nkc * 64 * H * es));
     A(e->alloc_bytes(&w.co, (size_t)H * H * es));
     A(e->alloc_bytes(&w.fc1, (size_t)F * H * es));
     A(e->alloc_bytes(&w.fc2, (size_t)F * H * es));
-    if (e->use_gemv) {
-      const size_t res = e->w8 ? 1 : es;  // row-major element size: e4m3 bytes or the engine dtype
+    if (e->sc.use_gemv) {
+      const size_t res = e->sc.w8 ? 1 : es;  // row-major element size: e4m3 bytes or the engine dtype
       A(e->alloc_bytes(&w.qkv_rm, (size_t)nq * H * res)); A(e->alloc_bytes(&w.o_rm, (size_t)H * H * res));
       A(e->alloc_bytes(&w.cq_rm, (size_t)H * H * res)); A(e->alloc_bytes(&w.co_rm, (size_t)H * H * res));
       A(e->alloc_bytes(&w.fc1_rm, (size_t)F * H * res)); A(e->alloc_bytes(&w.fc2_rm, (size_t)F * H * res));
-      if (e->xfold_ne) {
-        A(e->alloc_bytes(&w.xM, (size_t)nh * e->xfold_ne * H * es)); A(e->alloc_bytes(&w.xU, (size_t)nh * e->xfold_ne * H * es));
+      if (e->sc.xfold_ne) {
+        A(e->alloc_bytes(&w.xM, (size_t)nh * e->sc.xfold_ne * H * es)); A(e->alloc_bytes(&w.xU, (size_t)nh * e->sc.xfold_ne * H * es));
       }
     }
-    if (e->w8) {  // row scales serve both e4m3 layouts (row-major for the GEMV step, strips for the MFMA step)
+    if (e->sc.w8) {  // row scales serve both e4m3 layouts (row-major for the GEMV step, strips for the MFMA step)
       A(e->alloc(&w.qkv_sc, nq)); A(e->alloc(&w.o_sc, H)); A(e->alloc(&w.cq_sc, H)); A(e->alloc(&w.co_sc, H));
       A(e->alloc(&w.fc1_sc, F)); A(e->alloc(&w.fc2_sc, H));
-      if (e->w8_strips) {
+      if (e->sc.w8_strips) {
         A(e->alloc_bytes(&w.qkv_p8, (size_t)nq * H)); A(e->alloc_bytes(&w.o_p8, (size_t)H * H)); A(e->alloc_bytes(&w.co_p8, (size_t)H * H));
         A(e->alloc_bytes(&w.fc1_p8, (size_t)F * H)); A(e->alloc_bytes(&w.fc2_p8, (size_t)F * H));
       }
     }
     A(e->alloc(&w.ln1_g, H)); A(e->alloc(&w.ln1_b, H)); A(e->alloc(&w.ln2_g, H)); A(e->alloc(&w.ln2_b, H));
     A(e->alloc(&w.ln3_g, H)); A(e->alloc(&w.ln3_b, H));
-    const size_t kvs = (size_t)c.max_batch * e->nkv * c.max_ctx * 64 * (c.kv_fp8 ? 1 : es), kvc = (size_t)c.max_batch * e->nkc * c.max_enc * 64 * es;
+    const size_t kvs = (size_t)c.max_batch * e->sc.nkv * c.max_ctx * 64 * (c.kv_fp8 ? 1 : es), kvc = (size_t)c.max_batch * e->sc.nkc * c.max_enc * 64 * es;
     A(e->alloc_bytes(&w.k_self, kvs)); A(e->alloc_bytes(&w.v_self, kvs));
-    if (c.kv_fp8) { A(e->alloc(&w.ks_self, (size_t)c.max_batch * e->nkv * c.max_ctx)); A(e->alloc(&w.vs_self, (size_t)c.max_batch * e->nkv * c.max_ctx)); }
+    if (c.kv_fp8) { A(e->alloc(&w.ks_self, (size_t)c.max_batch * e->sc.nkv * c.max_ctx)); A(e->alloc(&w.vs_self, (size_t)c.max_batch * e->sc.nkv * c.max_ctx)); }
     A(e->alloc_bytes(&w.k_cross, kvc)); A(e->alloc_bytes(&w.v_cross, kvc));
     char nm[160];
     for (const LayerTensor& m : layer_tensors(e, w)) {
@@ -854,7 +778,7 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
     if (hipMemcpy(e->kv_layers, kl.data(), kl.size() * sizeof(KvLayer), hipMemcpyHostToDevice) != hipSuccess)
       return fail(ptts_fail(PTTS_E_HIP, "hipMemcpy(cross K/V operand table) failed"));
   }
-  if (e->xfold_ne) {
+  if (e->sc.xfold_ne) {
     std::vector<FoldLayer> fl(c.num_layers);
     for (int l = 0; l < c.num_layers; ++l) {
       const LayerW& w = e->L[l];
@@ -866,9 +790,9 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   }
   A(e->alloc_bytes(&e->embed, (size_t)K * (V + 1) * H * es));
   A(e->alloc_bytes(&e->heads, (size_t)K * V * H * es));
-  if (e->use_gemv) A(e->alloc_bytes(&e->heads_rm, (size_t)K * V * H * (e->w8 ? 1 : es)));
-  if (e->w8_strips) A(e->alloc_bytes(&e->heads_p8, (size_t)K * V * H));
-  if (e->w8) {
+  if (e->sc.use_gemv) A(e->alloc_bytes(&e->heads_rm, (size_t)K * V * H * (e->sc.w8 ? 1 : es)));
+  if (e->sc.w8_strips) A(e->alloc_bytes(&e->heads_p8, (size_t)K * V * H));
+  if (e->sc.w8) {
     A(e->alloc(&e->heads_sc, (size_t)K * V));
     for (int k = 0; k < K; ++k) { char nm[96]; snprintf(nm, sizeof nm, "lm_heads.%d.weight", k); e->required_fp8.insert(nm); }
   }
@@ -889,25 +813,13 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
     A(e->alloc(&e->pos_table, (size_t)c.max_positions * H));
     e->required.insert("model.decoder.embed_positions.weights");
   }
-  // split-KV factor: enough workgroups to cover the chip at small batch, none needed at large batch
-  {
-    int s = 256 / (c.max_batch * nh);
-    if (s < 1) s = 1;
-    if (s > 8) s = 8;
-    while (s > 1 && (s - 1) * 4 * 8 * 8 >= c.max_ctx) --s;  // do not split below one 8-deep batch of row groups per wave
-    e->S_self = s;
-    const int rows_per_wave = (c.dtype == PTTS_BF16 ? 8 : 4) * 8;  // RPI row groups x 8 loads in flight
-    const int need = (c.max_enc + rows_per_wave - 1) / rows_per_wave;
-    e->cross_waves = need <= 1 ? 1 : (need <= 2 ? 2 : 4);
-    if (e->use_gemv) while (e->S_self & (e->S_self - 1)) --e->S_self;  // the GEMV combine prologue is instantiated for 2 / 4 / 8 splits
-  }
   const size_t rows = (size_t)c.max_batch * e->max_prompt;
   const size_t enc_rows = (size_t)c.max_batch * c.max_enc;
   A(e->alloc(&e->h, rows * H));
   A(e->alloc(&e->qkv, rows * 3 * H));
   A(e->alloc(&e->qc, std::max(rows, enc_rows) * H));
   // qkv_attn_kernel: up to 8 splits + the new position's own slot for one utterance, up to 4 + 1 for each of 2..8
-  const size_t part_rows = std::max(rows * (size_t)e->S_self, (size_t)c.max_batch * 5) + 9;
+  const size_t part_rows = std::max(rows * (size_t)e->sc.S_self, (size_t)c.max_batch * 5) + 9;
   A(e->alloc(&e->part, part_rows * H));
   A(e->alloc(&e->stats, part_rows * nh * 2));
   A(e->alloc(&e->xpart, (size_t)nh * H));
@@ -918,9 +830,6 @@ extern "C" int ptts_engine_create(const ptts_config* cfg, ptts_engine** out) {
   A(e->alloc_bytes(&e->xw, (rows + 16) * H * es));  // + 16 rows: fragment order addresses whole 16-row tiles
   A(e->alloc_bytes(&e->xw2, std::max((rows + 16) * F, enc_rows * (size_t)H) * es));
   A(e->alloc(&e->lnstat, (size_t)c.max_batch * (H / 16) * 2 + 16));
-  e->use_lns = H == 1024 || H == 1536;
-  e->xattn_g_ok = (H == 1024 && ((H / (c.dtype == PTTS_BF16 ? 32 : 16)) / 2) % 16 == 0) || H == 1536;
-  read_env_switches(e);
   A(e->alloc(&e->prefix, (size_t)c.max_batch * K * c.max_ctx));
   e->ids_ld = c.max_ctx + 8;
   A(e->alloc(&e->ids, (size_t)c.max_batch * K * e->ids_ld));
@@ -984,7 +893,7 @@ extern "C" int ptts_load_weight(ptts_engine* e, const char* name_c, const void* 
         PTTS_TRY(want(m.N, m.K));
         if (m.K < 0) PTTS_TRY(convert_into<float>((float*)m.dst, dev_ptr, src_dtype, m.N, st));
         else PTTS_TRY(pack_dispatch(e, m.dst, dev_ptr, src_dtype, m.N, m.K, m.row0, st));
-        if (m.rm && !e->w8) PTTS_TRY(rowmajor_dispatch(e, m.rm, dev_ptr, src_dtype, m.N, m.K, m.row0, st));
+        if (m.rm && !e->sc.w8) PTTS_TRY(rowmajor_dispatch(e, m.rm, dev_ptr, src_dtype, m.N, m.K, m.row0, st));
         e->loaded.insert(name);
         return PTTS_OK;
       }
@@ -1003,14 +912,14 @@ extern "C" int ptts_load_weight(ptts_engine* e, const char* name_c, const void* 
     PTTS_CHECK(k >= 0 && k < K, PTTS_E_INVALID, "%s: codebook index out of range", name_c);
     PTTS_TRY(want(V, H));
     PTTS_TRY(pack_dispatch(e, e->heads, dev_ptr, src_dtype, V, H, k * V, st));
-    if (e->heads_rm && !e->w8) PTTS_TRY(rowmajor_dispatch(e, e->heads_rm, dev_ptr, src_dtype, V, H, k * V, st));
+    if (e->heads_rm && !e->sc.w8) PTTS_TRY(rowmajor_dispatch(e, e->heads_rm, dev_ptr, src_dtype, V, H, k * V, st));
     e->loaded.insert(name);
     return PTTS_OK;
   }
   if (name == "lm_heads.weight") {  // use_fused_lm_heads :1834-1840
     PTTS_TRY(want((int64_t)K * V, H));
     PTTS_TRY(pack_dispatch(e, e->heads, dev_ptr, src_dtype, K * V, H, 0, st));
-    if (e->heads_rm && !e->w8) PTTS_TRY(rowmajor_dispatch(e, e->heads_rm, dev_ptr, src_dtype, K * V, H, 0, st));
+    if (e->heads_rm && !e->sc.w8) PTTS_TRY(rowmajor_dispatch(e, e->heads_rm, dev_ptr, src_dtype, K * V, H, 0, st));
     for (int i = 0; i < K; ++i) { char nm[64]; snprintf(nm, sizeof nm, "lm_heads.%d.weight", i); e->loaded.insert(nm); }
     return PTTS_OK;
   }
@@ -1056,7 +965,7 @@ extern "C" int ptts_weights_ready(ptts_engine* e) {
 extern "C" int ptts_load_weight_fp8(ptts_engine* e, const char* name_c, const uint8_t* q_dev, const float* scale_dev, const int64_t* shape,
                                     int32_t ndim, void* stream) {
   PTTS_CHECK(e && name_c && q_dev && scale_dev && shape, PTTS_E_INVALID, "null argument");
-  PTTS_CHECK(e->w8, PTTS_E_INVALID, "ptts_load_weight_fp8 on an engine created without weights_fp8");
+  PTTS_CHECK(e->sc.w8, PTTS_E_INVALID, "ptts_load_weight_fp8 on an engine created without weights_fp8");
   PTTS_CHECK(ndim == 2, PTTS_E_INVALID, "%s: expected a matrix", name_c);
   PTTS_DEVICE(e->cfg.device);
   hipStream_t st = pick_stream(e, stream);
@@ -1209,14 +1118,14 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
   if (sample) { PTTS_HIP(hipEventRecord(e->ev_tail0, st)); PTTS_TRY(launch_tail(e, whole_view(e), st, true)); }  // also embeds the sampled column for the first decode step
   e->first_recorded = false;
   if (sample) { PTTS_HIP(hipEventRecord(e->ev_first, st)); e->first_recorded = true; }
-  if (e->xfold_ne && B == 1) {
+  if (e->sc.xfold_ne && B == 1) {
     // The fold only needs the cross K/V cache. It is enqueued AFTER the sampler tail, so the first token is materialised before the
     // fold's two launches run (time-to-first-token does not pay for it); every decode step that follows on `st` sees the folded
     // matrices by stream order. (Round 2 ran 48 per-layer launches BEFORE the tail: +0.8 ms of time-to-first-token. Running it on a
     // second stream beside the prefill was measured and lost: 8.98 vs 8.44 ms to the first token, and the first streamed chunk 23 ms
     // later, the decode steps waiting on the second hardware queue.)
     if (c.dtype == PTTS_F32) PTTS_TRY((fold_cross<float, false>(e, st)));
-    else if (e->w8) PTTS_TRY((fold_cross<bf16_t, true>(e, st)));
+    else if (e->sc.w8) PTTS_TRY((fold_cross<bf16_t, true>(e, st)));
     else PTTS_TRY((fold_cross<bf16_t, false>(e, st)));
     e->xfold_valid = true;
   }
@@ -1229,8 +1138,9 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
 // The decode step (170 kernel nodes for Mini-v1 at batch <= 8) is captured ONCE per batch size on the engine's private stream
 // (capture records, it does not execute; the legacy NULL stream cannot be captured) and replayed into the caller's.
 static int get_graph(ptts_engine* e, int kv_bound, hipGraphExec_t* out) {
-  // the node set of the step depends on the batch size and on the folded cross block; the attention fetch bound (a kernel argument)
-  // on the 64-position bucket of the context this graph is captured for (`kv_bound`). (Several steps of one bucket per
+  // The node set of the step is its plan (ptts_step_plan.h), and gemv_plan / strip_plan take no engine: beside the engine's fixed cfg, sc and sw they
+  // see the batch size, the folded-cross-block flag and the 64-position bucket `kv_bound` (also a kernel argument: the attention fetch bound) -
+  // all three in the key. The tail adds session, pen_on and warp_on: the key's upper bits. (Several steps of one bucket per
   // graph launch - round 4's PTTS_GRAPH_STEPS - measured 0.3-0.7 %, profiles/r04_experiments.txt call 19: removed in round 6.)
   const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (kv_bound / 64) + (e->session ? 1LL << 40 : 0)  // session steps end in their own tail
                         + (e->pen_on ? 1LL << 41 : 0)                                                                            // the history-penalty node is present
@@ -1310,7 +1220,7 @@ static int score_forward(const ptts_engine* e, FwdView v, int T, const ptts_scor
   ea.tables = e->embed; ea.pos_table = c.rope ? nullptr : e->pos_table; ea.prompt = e->ffn; ea.ids = reinterpret_cast<const long long*>(io->input_ids); ea.h = v.h;
   ea.H = c.hidden_size; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.P = v.P; ea.T = T;
   hipLaunchKernelGGL((embed_raw_kernel<WT>), dim3(Q, v.B), dim3(256), 0, st, ea);
-  PTTS_TRY((strip_path<WT>(e, v, true, Q, st, false)));
+  PTTS_TRY((strip_path<WT>(e, v, strip_plan_now(e, v, true, Q), st, false)));
   ScoreArgs s = {};
   s.x = v.h; s.x_ld = c.hidden_size; s.gamma = e->lnf_g; s.beta = e->lnf_b; s.W = e->heads;
   s.ids = reinterpret_cast<const long long*>(io->input_ids); s.labels = reinterpret_cast<const long long*>(io->labels);
@@ -1374,7 +1284,7 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
     PTTS_TRY(e->alloc(&e->h_adm, (size_t)e->max_prompt * H));
     PTTS_TRY(e->alloc(&e->kv_layers_rows, (size_t)c.max_batch * c.num_layers));  // rows_view points into it
     std::vector<KvLayer> kl((size_t)c.max_batch * c.num_layers);
-    const size_t kvc = (size_t)e->nkc * c.max_enc * 64 * e->esize;  // one slot's cross K (or V) rows of a layer
+    const size_t kvc = (size_t)e->sc.nkc * c.max_enc * 64 * e->esize;  // one slot's cross K (or V) rows of a layer
     for (int b = 0; b < c.max_batch; ++b)
       for (int l = 0; l < c.num_layers; ++l)
         kl[(size_t)b * c.num_layers + l] = KvLayer{e->L[l].ckv, (char*)e->L[l].k_cross + b * kvc, (char*)e->L[l].v_cross + b * kvc};
@@ -1402,8 +1312,8 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
     // cross rows [0, N) (engine dtype; what a recycled allocation holds may read as NaN). The fused append of an idle or finished slot keeps
     // rewriting its own row (position P, or where the request ended) every step: harmless, an admission rewrites rows [0, P + 1)
     for (const LayerW& w : e->L) {
-      hipLaunchKernelGGL(kv8_zero_rows_kernel, dim3(B * e->nkv), dim3(256), 0, st, w.k_self, w.v_self, w.ks_self, w.vs_self, c.max_ctx, P + 1, 4);
-      hipLaunchKernelGGL(kv8_zero_rows_kernel, dim3(B * e->nkc), dim3(256), 0, st, w.k_cross, w.v_cross, (float*)nullptr, (float*)nullptr, c.max_enc, N,
+      hipLaunchKernelGGL(kv8_zero_rows_kernel, dim3(B * e->sc.nkv), dim3(256), 0, st, w.k_self, w.v_self, w.ks_self, w.vs_self, c.max_ctx, P + 1, 4);
+      hipLaunchKernelGGL(kv8_zero_rows_kernel, dim3(B * e->sc.nkc), dim3(256), 0, st, w.k_cross, w.v_cross, (float*)nullptr, (float*)nullptr, c.max_enc, N,
                          (int)(64 * e->esize / 16));
     }
     PTTS_TRY(launch_status("kv8_zero_rows"));
@@ -1561,17 +1471,17 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
     const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
     AdmitMoveArgs a = {};
     a.layers = e->move_layers; a.logits = e->logits; a.enc_mask = e->enc_mask; a.prompt_mask = e->prompt_mask;
-    a.src0 = B + j0; a.nlayers = c.num_layers; a.nkv = e->nkv; a.nkc = e->nkc;
+    a.src0 = B + j0; a.nlayers = c.num_layers; a.nkv = e->sc.nkv; a.nkc = e->sc.nkc;
     a.self_u = (P + 1) * sru; a.self_cap_u = c.max_ctx * sru; a.cross_u = N * ru; a.cross_cap_u = c.max_enc * ru;
     a.logit_u = K * c.vocab_size / 4;
     a.enc_n = enc_mask_dev ? N : c.max_enc; a.enc_ld = c.max_enc;  // what ptts_admit_row writes of each mask row
     a.prompt_n = (prompt_mask_dev && P > 0) ? P : e->max_prompt; a.prompt_ld = e->max_prompt;
     for (int j = 0; j < nj; ++j) a.rows[j] = rows[j0 + j];
-    const int units = 2 * (e->nkv * a.self_u + e->nkc * a.cross_u);
+    const int units = 2 * (e->sc.nkv * a.self_u + e->sc.nkc * a.cross_u);
     hipLaunchKernelGGL(admit_move_rows_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, a);
     if (c.kv_fp8) {  // the rows' scales travel with them
       AdmitScaleArgs sa = {};
-      sa.layers = e->move_scales; sa.src0 = B + j0; sa.nkv = e->nkv; sa.n = P + 1; sa.cap = c.max_ctx;
+      sa.layers = e->move_scales; sa.src0 = B + j0; sa.nkv = e->sc.nkv; sa.n = P + 1; sa.cap = c.max_ctx;
       for (int j = 0; j < nj; ++j) sa.rows[j] = rows[j0 + j];
       hipLaunchKernelGGL(admit_move_scales_kernel, dim3(1, c.num_layers, nj), dim3(256), 0, st, sa);
     }
@@ -1795,7 +1705,7 @@ extern "C" int ptts_debug_self_kv(ptts_engine* e, int32_t layer, void** k_dev, v
   PTTS_CHECK(layer >= 0 && layer < e->cfg.num_layers, PTTS_E_INVALID, "layer %d outside the engine's %d layers", layer, e->cfg.num_layers);
   const LayerW& w = e->L[layer];
   *k_dev = w.k_self; *v_dev = w.v_self; *kscale_dev = w.ks_self; *vscale_dev = w.vs_self;
-  *row_bytes = (int32_t)(64 * (e->cfg.kv_fp8 ? 1 : e->esize)); *kv_heads = e->nkv; *cap = e->cfg.max_ctx;
+  *row_bytes = (int32_t)(64 * (e->cfg.kv_fp8 ? 1 : e->esize)); *kv_heads = e->sc.nkv; *cap = e->cfg.max_ctx;
   return PTTS_OK;
 }
 

@@ -1,7 +1,9 @@
 """Shapes, instance selection and input constructions of the GEMV decode-step tests (tests/test_gemv_kernels_gpu.py, tests/test_gemv_harness_cpu.py).
 Everything is generated on the CPU from a seed.
 
-nodes() restates which gemv_kernel launches ptts_lm.hip::gemv_step issues for the widths the product is built for; instance_of() restates
+nodes() is the table of gemv_kernel launches the case lists are built from, for the widths the product is built for. It is tied to the product by
+the product's own plan (ptts_step_plan.h: gemv_plan, read through the harness): tests/test_gemv_harness_cpu.py sweeps the plan over these widths,
+batch sizes, contexts and switches and requires the launches it lists to be exactly nodes() minus UNREACHED_NODES. instance_of() restates
 ptts_gemv_launch.inc's selection (pick_rows, the MB / STG choice), naming the gemv_kernel template instance a launch lands on; gemv_cases() is the
 table of test shapes: one per reached instance at the smallest N that selects it and exercises the row clamp, plus the product's own widths named
 by the issue (the LM heads' 9 * 1088 rows, a grouped-query QKV width)."""
@@ -45,7 +47,7 @@ def rows_per_split(mode):
 # ---- the nodes gemv_step issues ---------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def nodes():
-    """{(pro, epi, S, M, N, K, mode)}: every ptts_gemv_launch call of gemv_step over WIDTHS x {all K/V heads, half} x M = 1..8 x the three modes,
+    """{(pro, epi, S, M, N, K, mode)}: the ptts_gemv_launch calls of gemv_step over WIDTHS x {all K/V heads, half} x M = 1..8 x the three modes,
     with both sides of each of its switches (fused / two-node self-attention, folded / fused / plain cross block, every split count it can pick)."""
     out = set()
     for H, nh, F in WIDTHS:
@@ -74,6 +76,13 @@ def nodes():
                     add(GV_COPY, GV_RESID, 1, H, F)                      # fc2
                     add(GV_LN, GV_STORE, 1, LM_HEAD_ROWS, H)             # final LayerNorm + LM heads
     return frozenset(out)
+
+
+# the nodes of the table that no engine's plan issues: a two-node self-attention runs on S_self = 256 / (max_batch * heads) splits (a power of two), so a
+# GV_ATTN combine of S splits needs S * M * heads <= 256 - eight utterances of 24 heads never split, one utterance of 8 heads reaches every count
+UNREACHED_NODES = frozenset((GV_ATTN, GV_RESID, S, M, H, H, mode) for H, nh, _ in WIDTHS for mode in GH.MODES for S in (2, 4, 8)
+                            for M in range(1, (1 if mode == GV_F32 else GV_MAX_ROWS) + 1) if S * M * nh > 256)
+assert len(UNREACHED_NODES) == 60 and UNREACHED_NODES < nodes()
 
 
 # ---- ptts_gemv_launch.inc restated ------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
+import step_plan as SP
 from gemm_harness import CSRC, HIPCC_FLAGS, ROOT
 
 SRC = os.path.join(ROOT, "tests", "native", "gemv_harness.hip")
@@ -21,7 +22,8 @@ PRO_NAMES = {GV_LN: "LN", GV_ATTN: "ATTN", GV_COPY: "COPY", GV_SOFTMAX: "SOFTMAX
 EPI_NAMES = {GV_STORE: "STORE", GV_RESID: "RESID", GV_GELU_WT: "GELU_WT"}
 MODE_NAMES = {GV_F32: "fp32", GV_BF16: "bf16", GV_BF16_W8: "w8"}
 ENTRY_POINTS = ("gvh_last_error", "gvh_args_size", "gvh_const", "gvh_gemv_k_ok", "gvh_qkvattn_ok", "gvh_xfoldattn_ok", "gvh_xqattn_ok",
-                "gvh_qkvattn_rows_per_split", "gvh_gemv", "gvh_qkvattn", "gvh_xfoldattn", "gvh_xqattn")
+                "gvh_qkvattn_rows_per_split", "gvh_gemv", "gvh_qkvattn", "gvh_xfoldattn", "gvh_xqattn",
+                "gvh_step_config", "gvh_default_switches", "gvh_step_config_size", "gvh_gemv_plan")  # the last four: host only, the product's plan
 
 
 def _headers():
@@ -126,6 +128,12 @@ class Harness:
         for n, st in (("gvh_gemv", GvhGemv), ("gvh_qkvattn", GvhQkvAttn), ("gvh_xfoldattn", GvhXfold), ("gvh_xqattn", GvhXq)):
             getattr(L, n).argtypes = [C.POINTER(st), C.c_void_p]
         self.PMAX, self.MAX_ROWS = L.gvh_const(0), L.gvh_const(1)
+        L.gvh_default_switches.argtypes = [C.POINTER(SP.StepSwitches)]
+        sw = SP.StepSwitches(**{n: -99 for n in SP.StepSwitches.DEFAULTS})
+        assert L.gvh_default_switches(C.byref(sw)) == C.sizeof(SP.StepSwitches) and L.gvh_step_config_size() == C.sizeof(SP.StepConfig), "ptts_step_plan.h / tests/step_plan.py"
+        assert {n: getattr(sw, n) for n in SP.StepSwitches.DEFAULTS} == SP.StepSwitches.DEFAULTS, "StepSwitches defaults differ between ptts_step_plan.h and tests/step_plan.py"
+        L.gvh_step_config.argtypes = [C.c_void_p, C.POINTER(SP.StepConfig)]
+        L.gvh_gemv_plan.argtypes = [C.c_void_p, C.POINTER(SP.StepSwitches), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
 
     def error(self):
         return self.lib.gvh_last_error().decode()
@@ -157,3 +165,20 @@ class Harness:
 
     def rows_per_split(self, mode):
         return self.lib.gvh_qkvattn_rows_per_split(mode)
+
+    # ---- the product's plan (ptts_step_plan.h), host only ----
+    def step_config(self, cfg):
+        """StepConfig of a ptts_config (step_plan.config), or None where the harness declines the config."""
+        out = SP.StepConfig()
+        return out if self.lib.gvh_step_config(C.addressof(cfg), C.byref(out)) == PTTS_OK else None
+
+    def gemv_plan(self, cfg, sw, M, kv_bound, xfold_valid):
+        """(launches, per_layer, head, cross, fuse_qa, S_f) of one gemv_step: launches = [(pro, epi, S, M, N, K, mode)] in launch order, per_layer / head =
+        kernel launches of one layer / of the head projection. None where M utterances of this engine do not run the GEMV step."""
+        cap = 8 * cfg.num_layers + 1
+        buf, counts = (C.c_int * (7 * cap))(), (C.c_int * 5)()
+        n = self.lib.gvh_gemv_plan(C.addressof(cfg), C.byref(sw), M, kv_bound, int(xfold_valid), buf, cap, counts)
+        if n < 0:
+            return None
+        assert n <= cap
+        return ([tuple(buf[7 * i:7 * i + 7]) for i in range(n)],) + tuple(counts)

@@ -7,14 +7,16 @@
 // (tests/gemv_harness.py). A linker version script keeps everything but the gvh_* entry points local to the library.
 //
 // The caller describes every buffer by its size in elements (the n_* fields). A launch whose arguments let a kernel form an index outside a buffer
-// so described, or a shape / batch / split combination gemv_step's dispatch does not have, is PTTS_E_INVALID with a message in gvh_last_error() and
-// never reaches the device. The bounds are read off the kernels (ptts_gemv_kernels.h); each check names the access it covers.
+// so described, or a shape / batch / split combination the step does not have (the split cap is the product's: ptts_step_plan.h), is PTTS_E_INVALID
+// with a message in gvh_last_error() and never reaches the device. The gvh_step_config / gvh_gemv_plan entry points launch nothing: they hand the
+// product's own plan of a step (ptts_step_plan.h) to the tests. The bounds are read off the kernels (ptts_gemv_kernels.h); each check names the access it covers.
 #include <stdarg.h>
 #include <stdio.h>
 
 #include <string>
 
 #include "ptts_gemv.h"
+#include "ptts_step_plan.h"
 
 #define GVH_API extern "C" __attribute__((visibility("default")))
 #define GVH_E_HIP PTTS_E_HIP                  // the launch function reported -2, or a device-to-host read of a length failed
@@ -122,6 +124,46 @@ GVH_API int gvh_xfoldattn_ok(int H, int nheads, int mode) { return mode_ok(mode)
 GVH_API int gvh_xqattn_ok(int H, int mode) { return mode_ok(mode) && ptts_xqattn_ok(H, mode) ? 1 : 0; }
 GVH_API int gvh_qkvattn_rows_per_split(int mode) { return mode_ok(mode) ? ptts_qkvattn_rows_per_split(mode) : -1; }
 
+// ---- the product's plan of a GEMV step (ptts_step_plan.h), host only: nothing is launched and no device is touched -------------------------------------
+// what ptts_engine_create checks before it derives anything from a config
+static bool config_ok(const ptts_config* c) {
+  return c && c->hidden_size > 0 && c->num_heads > 0 && c->hidden_size == 64 * c->num_heads && (c->dtype == PTTS_F32 || c->dtype == PTTS_BF16) && c->ffn_dim > 0 &&
+         c->num_layers >= 1 && c->num_codebooks >= 1 && c->vocab_size > 0 && c->max_batch >= 1 && c->max_ctx >= 2 && c->max_enc >= 1 && c->num_kv_heads >= 0 &&
+         c->num_cross_kv_heads >= 0;
+}
+GVH_API int gvh_step_config(const ptts_config* c, StepConfig* out) {
+  if (!config_ok(c) || !out) return gvh_fail(PTTS_E_INVALID, "gvh_step_config: null or invalid config");
+  *out = step_config(*c);
+  return PTTS_OK;
+}
+// the switches as an engine holds them with nothing set in the environment; returns sizeof(StepSwitches)
+GVH_API int gvh_default_switches(StepSwitches* out) {
+  if (out) *out = StepSwitches();
+  return (int)sizeof(StepSwitches);
+}
+GVH_API int gvh_step_config_size(void) { return (int)sizeof(StepConfig); }
+// gemv_plan for M utterances: the ptts_gemv_launch calls of one gemv_step in launch order, seven ints each (pro, epi, S, M, N, K, mode), into
+// out[cap] (counted past cap); counts[0] = kernel launches of one layer, counts[1] = of the head projection, counts[2] = GemvCross, counts[3] = fuse_qa,
+// counts[4] = S_f. Returns the number of ptts_gemv_launch calls, or PTTS_E_INVALID where the engine would not take the GEMV step
+GVH_API int gvh_gemv_plan(const ptts_config* c, const StepSwitches* sw, int M, int kv_bound, int xfold_valid, int* out, int cap, int* counts) {
+  if (!config_ok(c) || !sw || !counts || M < 1 || M > c->max_batch || kv_bound < 1 || kv_bound > c->max_ctx)
+    return gvh_fail(PTTS_E_INVALID, "gvh_gemv_plan: config / M=%d / kv_bound=%d", M, kv_bound);
+  const StepConfig sc = step_config(*c);
+  if (!step_on_gemv(sc, false, M)) return gvh_fail(PTTS_E_INVALID, "gvh_gemv_plan: %d utterances of this engine do not run the GEMV step", M);
+  const GemvPlan p = gemv_plan(sc, *c, *sw, M, kv_bound, xfold_valid != 0);
+  int n = 0;
+  auto put = [&](const GemvNode& g) {
+    if (!g.on) return;
+    if (n < cap) { int* o = out + 7 * n; o[0] = g.pro; o[1] = g.epi; o[2] = g.S; o[3] = p.M; o[4] = g.N; o[5] = g.K; o[6] = g.mode; }
+    ++n;
+  };
+  for (int l = 0; l < c->num_layers; ++l)
+    for (int i = 0; p.layer_nodes(i); ++i) put(*p.layer_nodes(i));
+  put(p.heads);
+  counts[0] = p.launches(); counts[1] = p.head_launches(); counts[2] = p.cross; counts[3] = p.fuse_qa; counts[4] = p.S_f;
+  return n;
+}
+
 // the (prologue, epilogue, S, M) combinations of ptts_gemv_launch's dispatch (GV_FN in ptts_gemv_launch.inc); fp32 instances serve one utterance
 static bool gemv_combo_ok(int mode, int pro, int epi, int S, int M) {
   if (M < 1 || M > GV_MAX_ROWS || (mode == GV_F32 && M != 1)) return false;
@@ -130,7 +172,7 @@ static bool gemv_combo_ok(int mode, int pro, int epi, int S, int M) {
   if (pro == GV_SOFTMAX) return epi == GV_RESID && S == 1 && M == 1 && mode != GV_BF16_W8;  // the folded matrices are never e4m3
   if (pro == GV_ATTN) return epi == GV_RESID && (S == 2 || S == 4 || S == 8);
   if (pro == GV_LNP) return epi == GV_GELU_WT && S == 1 && M == 1;
-  if (pro == GV_ATTN2) return epi == GV_RESID && (S == 1 || S == 2 || (S == 4 && M <= 4) || (S == 8 && M == 1));
+  if (pro == GV_ATTN2) return epi == GV_RESID && (S == 1 || S == 2 || S == 4 || S == 8) && S <= qkvattn_split_cap(M);
   return false;
 }
 
@@ -189,9 +231,9 @@ GVH_API int gvh_gemv(const GvhGemv* g, void* stream) {
 GVH_API int gvh_qkvattn(const GvhQkvAttn* g, void* stream) {
   if (!g) return gvh_fail(PTTS_E_INVALID, "gvh_qkvattn: null arguments");
   const int M = g->M, S = g->S, H = g->H, nh = g->nheads, nkv = g->kv_heads, mode = g->mode;
-  // gemv_step: 1, 2, 4 or 8 splits at one utterance, up to 4 at 2..4, up to 2 at 5..8; the fp32 engine serves one utterance
+  // a power of two up to the product's cap for M utterances (ptts_step_plan.h: qkvattn_split_cap); the fp32 engine serves one utterance
   if (!mode_ok(mode) || !ptts_qkvattn_ok(H, mode) || M < 1 || M > GV_MAX_ROWS || (mode == GV_F32 && M != 1) || (S != 1 && S != 2 && S != 4 && S != 8) ||
-      S > (M == 1 ? 8 : (M <= 4 ? 4 : 2)))
+      S > qkvattn_split_cap(M))
     return gvh_fail(PTTS_E_INVALID, "gvh_qkvattn: mode=%d H=%d S=%d M=%d", mode, H, S, M);
   if (nh <= 0 || nh * 64 != H || nkv <= 0 || nh % nkv) return gvh_fail(PTTS_E_INVALID, "gvh_qkvattn: heads=%d kv_heads=%d H=%d", nh, nkv, H);
   const long long rows = (long long)H + 2 * nkv * 64;

@@ -1,6 +1,6 @@
 // Test-only harness of the teacher-forced scoring kernel (tests/test_score_kernel_gpu.py, tools/score_probe.py). It includes the product headers and
 // launches the product's own templates on device pointers the test allocates with torch: pack_weight_kernel, score_launch (the function the engine
-// calls, ptts_score_launch.h) and - as the comparison - the existing final-LayerNorm + heads projection the way gemm_with_prologue<WT, PRO_LN,
+// calls, ptts_score_launch.h) and - as the comparison - the existing final-LayerNorm + heads projection the way ln_gemm<WT,
 // EPI_STORE> (ptts_lm.hip) runs it: the fused prologue up to 8 rows, rows_prep + the PRO_COPY GEMM above. No kernel code of its own.
 // Every entry returns a PTTS_* status; the message is in sh_last_error(). dtype: 0 = fp32 engine, 1 = bf16 engine.
 #include "ptts_common.h"
@@ -60,7 +60,7 @@ SH_API int sh_score(int dtype, const ShArgs* g, void* stream) {
   return dtype ? score_launch<bf16_t>(s, (hipStream_t)stream) : score_launch<float>(s, (hipStream_t)stream);
 }
 
-// out[m][n] = heads[n] . LayerNorm(x[m]) over M consecutive rows of x, as gemm_with_prologue<WT, PRO_LN, EPI_STORE> computes the engine's logits
+// out[m][n] = heads[n] . LayerNorm(x[m]) over M consecutive rows of x, as ln_gemm<WT, EPI_STORE> (ptts_lm.hip) computes the engine's logits
 template <typename WT>
 static int sh_project_t(const ShArgs* a, hipStream_t st) {
   GemmArgs g = {};

@@ -14,6 +14,7 @@
 #include "ptts_common.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemm_launch.h"
+#include "ptts_step_plan.h"
 
 #define SH_API extern "C" __attribute__((visibility("default")))
 
@@ -117,6 +118,25 @@ SH_API int sh_instances(int kind, int* out, int cap) {
   return n;
 }
 
+// ---- the product's plan of a strip-path forward (ptts_step_plan.h), host only: nothing is launched and no device is touched -------------------------------
+// 0: StepSwitches, 1: StepConfig, 2: StripPlan
+SH_API int sh_plan_size(int which) { return which == 0 ? (int)sizeof(StepSwitches) : which == 1 ? (int)sizeof(StepConfig) : which == 2 ? (int)sizeof(StripPlan) : -1; }
+SH_API int sh_lns_fits(int M, int K, int bf16) { return pro_lns_fits(M, K, bf16 ? 2 : 4) ? 1 : 0; }
+// strip_plan of a prefill over Q positions per utterance, or of a decode step (Q = 1), of B utterances; counts[0] = kernel launches of one layer,
+// counts[1] = of the head projection. PTTS_E_INVALID for a config ptts_engine_create refuses, or a call that does not run the strip path
+SH_API int sh_strip_plan(const ptts_config* c, const StepSwitches* sw, int prefill, int B, int Q, int prefill_attn_mode, StripPlan* out, int* counts) {
+  if (!c || !sw || !out || !counts || c->hidden_size <= 0 || c->num_heads <= 0 || c->hidden_size != 64 * c->num_heads || (c->dtype != PTTS_F32 && c->dtype != PTTS_BF16) ||
+      c->ffn_dim <= 0 || c->max_batch < 1 || c->max_ctx < 2 || c->max_enc < 1 || c->max_prompt < 1 || c->num_kv_heads < 0 || c->num_cross_kv_heads < 0 ||
+      (c->kv_fp8 && (c->dtype != PTTS_BF16 || c->max_batch <= GV_MAX_ROWS)))
+    return ptts_fail(PTTS_E_INVALID, "sh_strip_plan: null or invalid config");
+  const StepConfig sc = step_config(*c);
+  if (B < 1 || B > c->max_batch || Q < 1 || (prefill ? Q > c->max_prompt : Q != 1) || step_on_gemv(sc, prefill != 0, B))
+    return ptts_fail(PTTS_E_INVALID, "sh_strip_plan: prefill=%d B=%d Q=%d is no strip-path forward of this engine", prefill, B, Q);
+  *out = strip_plan(sc, *c, *sw, prefill != 0, B, Q, prefill_attn_mode);
+  counts[0] = out->launches(); counts[1] = out->head_launches();
+  return PTTS_OK;
+}
+
 // row-major fp32 W[N][K] -> A-fragment order of the engine dtype (bf16 = 1: bf16, else fp32), as the engines pack their weights
 SH_API int sh_pack(int bf16, const float* src, void* dst, int N, int K, void* stream) {
   const int KT = bf16 ? Elem<bf16_t>::KT : Elem<float>::KT;
@@ -159,7 +179,7 @@ typedef SH_WT WT;
 constexpr int PRO = SH_PRO, EPI = SH_EPI;
 
 // launch_gemm<WT, PRO, EPI> on up to 256 rows (the strip kernels; above, launch_gemm leaves them: tests/native/gemm_harness.hip), with the row limits
-// of ptts_lm.hip::gemm_with_prologue: fused prologues up to 8 rows, PRO_LNS at 9..32 rows where all rows fit in LDS
+// of the product's own choice (ptts_step_plan.h: pro_gemm): fused prologues up to 8 rows, PRO_LNS at 9..32 rows where all rows fit in LDS
 SH_API int SH_NAME(sh_gemm)(const ShGemm* g, void* stream) {
   const bool wt_out = EPI == EPI_GELU_WT;
   if (!g->W || !g->out || g->M <= 0 || g->M > 256 || g->N <= 0 || g->N % 16 || g->K <= 0 || g->K % KTw || g->out_ld < g->N || g->out_ld % 4)
@@ -177,10 +197,11 @@ SH_API int SH_NAME(sh_gemm)(const ShGemm* g, void* stream) {
     if (g->x_fo ? (g->x_row_mul != 1 || g->x_row_off != 0) : (g->x_ld < g->K || g->x_ld % (16 / (int)sizeof(WT))))
       return ptts_fail(PTTS_E_INVALID, "sh_gemm: PRO_COPY x_fo=%d x_ld=%d rows %d * m + %d", g->x_fo, g->x_ld, g->x_row_mul, g->x_row_off);
   } else {
-    if (g->x_fo || g->M > (PRO == PRO_LNS ? 32 : 8)) return ptts_fail(PTTS_E_INVALID, "sh_gemm: prologue %d on %d rows (x_fo=%d)", PRO, g->M, g->x_fo);
+    const int how = pro_gemm(g->M, g->K, sizeof(WT), PRO == PRO_LNS && g->lnstat);
+    if (g->x_fo || (PRO != PRO_LNS && how != PG_FUSED) || (PRO == PRO_LNS && g->M > 32)) return ptts_fail(PTTS_E_INVALID, "sh_gemm: prologue %d on %d rows (x_fo=%d)", PRO, g->M, g->x_fo);
     if (PRO != PRO_ATTN && (g->x_ld < g->K || g->x_ld % 4)) return ptts_fail(PTTS_E_INVALID, "sh_gemm: x_ld=%d K=%d", g->x_ld, g->K);
     if ((PRO == PRO_LN || PRO == PRO_LNS) && (!g->gamma || !g->beta)) return ptts_fail(PTTS_E_INVALID, "sh_gemm: LayerNorm without gamma / beta");
-    if (PRO == PRO_LNS && (!g->lnstat || g->M <= 8 || (g->K != 1024 && g->K != 1536) || (size_t)g->M * ((size_t)g->K * sizeof(WT) + 16) + 16 * 1024 > 159 * 1024))
+    if (PRO == PRO_LNS && how != PG_LNS)
       return ptts_fail(PTTS_E_INVALID, "sh_gemm: PRO_LNS on M=%d K=%d lnstat=%p", g->M, g->K, (void*)g->lnstat);
   }
   return launch_gemm<WT, PRO, EPI>(sh_gemm_args(*g), reinterpret_cast<hipStream_t>(stream));
@@ -208,9 +229,9 @@ SH_API int SH_NAME(sh_rows_prep)(int pro, const ShGemm* g, void* stream) {
 
 #elif defined(SH_LNPROJ)
 
-// launch_lnproj<WT, EPI_STORE | EPI_GELU_WT> with g utterances per workgroup, under strip_path's conditions for the node (lnproj_ok)
+// launch_lnproj<WT, EPI_STORE | EPI_GELU_WT> with g utterances per workgroup, under the plan's width rule for the node (lnproj_width_ok)
 SH_API int SH_NAME(sh_lnproj)(int epi, int gsz, const ShLnProj* g, void* stream) {
-  if (!g->W || !g->x || !g->gamma || !g->beta || !g->out || g->M <= 0 || g->N <= 0 || g->N % 64 || (g->K != 1024 && g->K != 1536) || ((g->K / KTw) / 2) % 8 ||
+  if (!g->W || !g->x || !g->gamma || !g->beta || !g->out || g->M <= 0 || g->N <= 0 || !lnproj_width_ok(g->K, KTw, g->N) ||
       g->x_ld < g->K || g->x_ld % 4 || g->out_ld < g->N || g->out_ld % 4 || (gsz != 4 && gsz != 8 && gsz != 16) || (epi != EPI_STORE && epi != EPI_GELU_WT))
     return ptts_fail(PTTS_E_INVALID, "sh_lnproj: M=%d N=%d K=%d x_ld=%d out_ld=%d g=%d epi=%d", g->M, g->N, g->K, g->x_ld, g->out_ld, gsz, epi);
   if (g->out_fo && (epi != EPI_GELU_WT || g->out_ld != g->N || g->N % KTw)) return ptts_fail(PTTS_E_INVALID, "sh_lnproj: out_fo on epilogue %d, out_ld=%d N=%d", epi, g->out_ld, g->N);
@@ -229,16 +250,16 @@ SH_API int SH_NAME(sh_lnproj)(int epi, int gsz, const ShLnProj* g, void* stream)
 
 #elif defined(SH_XATTN)
 
-// launch_xattn_fused<WT> with gsz utterances per workgroup, under strip_path's conditions for the node (the lengths behind dims / cur_len are the
+// launch_xattn_fused<WT> with gsz utterances per workgroup, under the plan's width and group rules for the node (the lengths behind dims / cur_len are the
 // test's to keep inside cap, mask_ld and the RoPE tables)
 SH_API int SH_NAME(sh_xattn)(int gsz, const ShXAttn* g, void* stream) {
   if (!g->W || !g->x || !g->gamma || !g->beta || !g->kcache || !g->vcache || !g->dims || !g->out || g->B <= 0 || g->B > 256 ||
-      (g->K != 512 && g->K != 1024 && g->K != 1536) || (g->K / KTw) % 16 || g->x_ld < g->K || g->x_ld % 4 || g->x_row_mul < 1 || g->x_row_off < 0 ||
+      !xattn_width_ok(g->K, KTw) || g->x_ld < g->K || g->x_ld % 4 || g->x_row_mul < 1 || g->x_row_off < 0 ||
       g->nheads * 64 != g->K || g->kv_heads <= 0 || g->n_rep <= 0 || g->kv_heads * g->n_rep != g->nheads || g->cap <= 0 || (g->mask && g->mask_ld <= 0) ||
       (!g->cos) != (!g->sin) || (g->cos && !g->cur_len))
     return ptts_fail(PTTS_E_INVALID, "sh_xattn: B=%d K=%d x_ld=%d heads=%d x %d / %d cap=%d mask_ld=%d", g->B, g->K, g->x_ld, g->kv_heads, g->n_rep, g->nheads, g->cap, g->mask_ld);
   // hidden 512 has the 8-utterance instance only (launch_xattn_fused would size the grid for gsz and run G = 8)
-  if ((gsz != 8 && gsz != 4 && gsz != 2) || (g->K == 512 && gsz != 8) || (g->B <= 8 && gsz != 8))
+  if (!xattn_group_ok(g->K, gsz, g->B))
     return ptts_fail(PTTS_E_INVALID, "sh_xattn: %d utterances per workgroup at K=%d B=%d", gsz, g->K, g->B);
   XAttnArgs x = {};
   x.W = g->W; x.x = g->x; x.x_ld = g->x_ld; x.x_row_mul = g->x_row_mul; x.x_row_off = g->x_row_off; x.gamma = g->gamma; x.beta = g->beta; x.K = g->K;

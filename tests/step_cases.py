@@ -37,7 +37,7 @@ W8_FALLBACK = {(SH.PRO_COPY, SH.EPI_GELU_WT, 1): (16, 1), (SH.PRO_COPY, SH.EPI_G
 
 
 def lns_fits(M, K, bf16):
-    """gemm_with_prologue's condition for PRO_LNS (ptts_lm.hip): 9..32 rows that all fit in LDS beside the reduction buffer, hidden 1024 / 1536.
+    """The product's condition for PRO_LNS (ptts_step_plan.h: pro_lns_fits; held equal to it by tests/test_step_harness_cpu.py): 9..32 rows that all fit in LDS beside the reduction buffer, hidden 1024 / 1536.
     The fp32 engine at hidden 1536 fits 23 rows: its 32-row case stays on rows_prep + PRO_COPY."""
     return 8 < M <= 32 and K in (1024, 1536) and M * (K * (2 if bf16 else 4) + 16) + 16 * 1024 <= 159 * 1024
 

@@ -1,11 +1,14 @@
 """Build and load tests/native/step_harness.hip: the product's batched decode-step kernels (the strip GEMMs with every prologue / epilogue pair
 of strip_path, rows_prep_kernel, lnproj_fused_kernel, xattn_fused_kernel, the e4m3 strips of ptts_lm_w8.hip) behind thin C entry points that take
-device pointers (see the .hip file)."""
+device pointers (see the .hip file), and the product's plan of a strip-path forward (ptts_step_plan.h) behind host-only ones. The plan asks the
+product's GEMV translation units which widths they serve (ptts_gemv_k_ok), so their objects are linked in as tests/gemv_harness.py links them: the ones
+build() left beside the sources where they are fresh, else compiled here as further parts."""
 import ctypes as C
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
+import step_plan as SP
 from gemm_harness import CSRC, HIPCC_FLAGS, ROOT
 
 SRC = os.path.join(ROOT, "tests", "native", "step_harness.hip")
@@ -16,7 +19,7 @@ PRO_PLAIN, PRO_LN, PRO_ATTN, PRO_COPY, PRO_LNS, PRO_RMS = 0, 1, 2, 3, 4, 5
 EPI_STORE, EPI_GELU, EPI_RESID, EPI_GELU_WT = 0, 1, 2, 4
 PRO_NAMES = {PRO_PLAIN: "PLAIN", PRO_LN: "LN", PRO_ATTN: "ATTN", PRO_COPY: "COPY", PRO_LNS: "LNS"}
 EPI_NAMES = {EPI_STORE: "STORE", EPI_GELU: "GELU", EPI_RESID: "RESID", EPI_GELU_WT: "GELU_WT"}
-# the (prologue, epilogue) pairs that strip_path and gemm_with_prologue instantiate (ptts_lm.hip)
+# the (prologue, epilogue) pairs that strip_path and its ln_gemm / prep_copy_gemm instantiate (ptts_lm.hip)
 GEMM_PAIRS = ((PRO_COPY, EPI_STORE), (PRO_COPY, EPI_RESID), (PRO_COPY, EPI_GELU_WT), (PRO_LNS, EPI_STORE), (PRO_LNS, EPI_GELU_WT),
               (PRO_LN, EPI_STORE), (PRO_LN, EPI_GELU), (PRO_LN, EPI_GELU_WT), (PRO_ATTN, EPI_RESID), (PRO_PLAIN, EPI_RESID))
 KINDS = ("lnproj_fused_kernel", "xattn_fused_kernel", "rows_prep_kernel", "gemm_strip_kernel_w8")  # sh_instances kinds
@@ -24,7 +27,7 @@ KIND_WIDTH = (5, 4, 2, 3)
 
 
 def entry_points():
-    names = {"sh_last_error", "sh_args_size", "sh_instances", "sh_pack", "sh_pack_w8"}
+    names = {"sh_last_error", "sh_args_size", "sh_instances", "sh_pack", "sh_pack_w8", "sh_plan_size", "sh_lns_fits", "sh_strip_plan"}
     for d in "tf":
         names |= {f"sh_gemm_{d}{p}{e}" for p, e in GEMM_PAIRS} | {f"sh_rows_prep_{d}", f"sh_lnproj_{d}", f"sh_xattn_{d}"}
     return names
@@ -58,10 +61,27 @@ def build(out_dir):
             raise RuntimeError("hipcc failed: " + " ".join(cmd) + "\n" + r.stderr[-4000:])
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(16, len(parts()), os.cpu_count() or 1)) as ex:
-        objs = list(ex.map(compile_part, parts()))
+    from gemv_harness import UNITS, product_object
+
+    def compile_unit(u):  # the product's own object, or the unit compiled with build()'s flags
+        obj = product_object(u)
+        if obj is None:
+            obj = os.path.join(out_dir, u + ".o")
+            cmd = ["hipcc"] + HIPCC_FLAGS + ["-I", CSRC, "-c", os.path.join(CSRC, u + ".hip"), "-o", obj]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("hipcc failed: " + " ".join(cmd) + "\n" + r.stderr[-4000:])
+        return obj
+
+    with ThreadPoolExecutor(max_workers=min(16, len(parts()) + len(UNITS), os.cpu_count() or 1)) as ex:
+        units = [ex.submit(compile_unit, u) for u in UNITS]
+        objs = list(ex.map(compile_part, parts())) + [u.result() for u in units]
+    # the product's units are compiled with default visibility: the version script keeps their symbols local (as tests/gemv_harness.py does)
+    vs = os.path.join(out_dir, "step_harness.map")
+    with open(vs, "w") as f:
+        f.write("{ global: " + " ".join(n + ";" for n in sorted(entry_points())) + " local: *; };\n")
     lib = os.path.join(out_dir, "libstep_harness.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib] + objs + ["-L" + torch_lib, "-l:libamdhip64.so", "-Wl,-rpath," + torch_lib])
+    subprocess.check_call(["g++", "-shared", "-o", lib] + objs + ["-Wl,--version-script=" + vs, "-L" + torch_lib, "-l:libamdhip64.so", "-Wl,-rpath," + torch_lib])
     return lib
 
 
@@ -103,6 +123,9 @@ class Harness:
         L.sh_instances.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int]
         L.sh_pack.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.sh_pack_w8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        for which, st in enumerate((SP.StepSwitches, SP.StepConfig, SP.StripPlan)):
+            assert L.sh_plan_size(which) == C.sizeof(st), f"{st.__name__} layout differs between ptts_step_plan.h and tests/step_plan.py"
+        L.sh_strip_plan.argtypes = [C.c_void_p, C.POINTER(SP.StepSwitches), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SP.StripPlan), C.POINTER(C.c_int)]
         for d in "tf":
             for p, e in GEMM_PAIRS:
                 getattr(L, f"sh_gemm_{d}{p}{e}").argtypes = [C.POINTER(ShGemm), C.c_void_p]
@@ -142,3 +165,15 @@ class Harness:
 
     def xattn(self, bf16, gsz, a, stream):
         return getattr(self.lib, f"sh_xattn_{'t' if bf16 else 'f'}")(gsz, C.byref(a), stream)
+
+    # ---- the product's plan (ptts_step_plan.h), host only ----
+    def lns_fits(self, M, K, bf16):
+        return bool(self.lib.sh_lns_fits(M, K, int(bf16)))
+
+    def strip_plan(self, cfg, sw, prefill, B, Q=1, prefill_attn_mode=3):
+        """(StripPlan, kernel launches of one layer, of the head projection) of a prefill over Q positions per utterance or of a decode step, or None
+        where the call is no strip-path forward of an engine of this config."""
+        plan, counts = SP.StripPlan(), (C.c_int * 2)()
+        if self.lib.sh_strip_plan(C.addressof(cfg), C.byref(sw), int(prefill), B, Q, prefill_attn_mode, C.byref(plan), counts) != PTTS_OK:
+            return None
+        return plan, counts[0], counts[1]

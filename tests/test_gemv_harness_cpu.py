@@ -1,9 +1,12 @@
 """CPU: the GEMV decode-step harness (tests/native/gemv_harness.hip) cross-compiles for gfx950 without a GPU, exports exactly its entry points, agrees
 with the Python side on its struct layouts, holds the same gemv_kernel / qkv_attn_kernel / xfold_attn_kernel / xq_attn_kernel instances as the
 product library, and tests/gemv_cases.py's restatement of the instance selection names only instances that exist and reaches, with a test case,
-every instance that a node of its node table reaches. That table is built from gemv_cases.WIDTHS, not from the product: what ties it to the
-product is the scan of ptts_qkvattn_ok / ptts_xqattn_ok / ptts_xfoldattn_ok / ptts_gemv_k_ok and GV_MAX_ROWS (a fused width, a chunk count or a
-larger batch added there fails here) and the lookup of every named instance among the library's symbols. Symbol names only; no instruction is read. Unsafe launches are declined on the host before anything touches a device."""
+every instance that a node of its node table reaches. That table is tied to the product by the product's own plan of the step
+(ptts_step_plan.h: gemv_plan, through the harness's host-only entry points): swept over the table's widths, batch sizes, contexts and every switch,
+the launches the plan lists are exactly gemv_cases.nodes() minus gemv_cases.UNREACHED_NODES - a node gemv_step starts or stops issuing fails here.
+The scan of ptts_qkvattn_ok / ptts_xqattn_ok / ptts_xfoldattn_ok / ptts_gemv_k_ok and GV_MAX_ROWS ties the widths themselves (a fused width, a chunk
+count or a larger batch added there fails here), and every named instance is looked up among the library's symbols. Symbol names only; no
+instruction is read. Unsafe launches are declined on the host before anything touches a device."""
 import ctypes as C
 import os
 import re
@@ -14,6 +17,7 @@ import pytest
 
 import gemv_cases as GC
 import gemv_harness as GH
+import step_plan as SP
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 KERNELS = ("gemv_kernel", "qkv_attn_kernel", "xfold_attn_kernel", "xq_attn_kernel")
@@ -84,6 +88,55 @@ def test_struct_layouts_and_constants_match_the_python_side(harness):
         e = GC.epl(mode)
         built = {K // (64 * e) for K in range(64, 64 * e * 32 + 1, 64) if harness.gemv_k_ok(K, mode)}
         assert built == set(GC.NCH_BUILT), (mode, built)
+
+
+# every switch the GEMV step reads, on both sides, one at a time beside the defaults
+GEMV_SWITCHES = ({}, dict(fuse_qa=0), dict(fuse_qa_max=1), dict(fuse_qa_max=8), dict(fuse_x=0), dict(fuse_x=1), dict(fuse_x_nur=4), dict(fuse_xq=0))
+
+
+def test_the_product_s_plan_issues_the_node_table(harness):
+    """gemv_plan over WIDTHS x {all K/V heads, half} x the three modes x M = 1..8 (fp32: 1) x max_batch in {M, 8} x max_ctx in {64, 300, 1100, 2048}
+    (S_self takes every value it can) x every 64-position bucket edge up to max_ctx x folded or not x each switch on both sides: what it lists is a
+    subset of gemv_cases.nodes(), and what is left over is exactly UNREACHED_NODES."""
+    listed, splits = set(), set()
+    for Hd, nh, F in GC.WIDTHS:
+        for nkv in (nh, nh // 2):
+            for mode in GH.MODES:
+                for M in range(1, (1 if mode == GH.GV_F32 else GC.GV_MAX_ROWS) + 1):
+                    for max_batch in sorted({M, GC.GV_MAX_ROWS}):
+                        for max_ctx in (64, 300, 1100, 2048):
+                            cfg = SP.config(Hd, nh, F, bf16=mode != GH.GV_F32, max_batch=max_batch, max_ctx=max_ctx, kv_heads=0 if nkv == nh else nkv,
+                                            weights_fp8=mode == GH.GV_BF16_W8)
+                            sc = harness.step_config(cfg)
+                            assert sc.use_gemv and (sc.nkv, sc.gemv_rows) == (nkv, 1 if mode == GH.GV_F32 else GC.GV_MAX_ROWS), (Hd, nkv, mode)
+                            splits.add(sc.S_self)
+                            for kv_bound in sorted({min(max_ctx, 64 * k) for k in range(1, max_ctx // 64 + 2)}):
+                                for xfold_valid in (False, True):
+                                    for kw in GEMV_SWITCHES:
+                                        plan = harness.gemv_plan(cfg, SP.StepSwitches(**kw), M, kv_bound, xfold_valid)
+                                        assert plan is not None, (Hd, nkv, mode, M, max_batch, max_ctx, kv_bound, harness.error())
+                                        assert all(n[3] == M for n in plan[0]) and plan[5] <= (8 if M == 1 else 4 if M <= 4 else 2)
+                                        listed |= set(plan[0])
+    assert splits == {1, 2, 4, 8}
+    assert listed <= GC.nodes(), sorted(listed - GC.nodes())[:4]
+    assert GC.nodes() - listed == GC.UNREACHED_NODES, sorted((GC.nodes() - listed) ^ GC.UNREACHED_NODES)[:4]
+    # a call the engine would not run as a GEMV step is declined: more utterances than the engine holds, or than the fp32 step serves
+    cfg = SP.config(1024, 16, 4096, max_batch=4)
+    assert harness.gemv_plan(cfg, SP.StepSwitches(), 5, 64, False) is None
+    assert harness.gemv_plan(SP.config(1024, 16, 4096, bf16=False, max_batch=4), SP.StepSwitches(), 2, 64, False) is None
+    assert harness.gemv_plan(SP.config(1024, 16, 4096, max_batch=9), SP.StepSwitches(), 1, 64, False) is None
+
+
+def test_plan_launch_counts_of_the_default_step(harness):
+    """Default switches, hidden 1024, 2 layers: 5 / 6 / 6 / 7 launches per layer at 1 / 2 / 3 / 4 utterances plus one for the head projection - the
+    numbers tests/test_lm_gpu.py reads off the captured step graphs (there with the sampler tail as one more node)."""
+    for M, per_layer in ((1, 5), (2, 6), (3, 6), (4, 7)):
+        cfg = SP.config(1024, 16, 4096, layers=2, max_batch=M, max_ctx=64, max_enc=16, max_prompt=5)
+        launches, layer, head, cross, fuse_qa, S_f = harness.gemv_plan(cfg, SP.StepSwitches(), M, 64, M == 1)
+        assert (layer, head) == (per_layer, 1), (M, layer, head)
+        assert cross == (SP.XFOLD_ONE_NODE if M == 1 else SP.XQ_FUSED) and fuse_qa == int(M <= 3) and S_f == 1
+        # the gemv_kernel launches among them: all but the two attention nodes of a layer (qkv_attn or attention, xfold_attn or xq_attn)
+        assert len(launches) == 2 * (per_layer - 2) + 1
 
 
 def test_harness_holds_the_product_s_instances(instances):

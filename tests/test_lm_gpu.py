@@ -396,6 +396,50 @@ def test_fused_qkv_attention_default_bound_is_three_utterances():
         eng.close()
 
 
+@pytest.fixture(scope="module")
+def plan_harnesses(tmp_path_factory):
+    """The two test harnesses, for their host-only entry points: the product's plan of a decode step (ptts_step_plan.h)."""
+    import gemv_harness as GH
+    import step_harness as SH
+
+    return GH.Harness(GH.build(str(tmp_path_factory.mktemp("gemv_harness")))), SH.Harness(SH.build(str(tmp_path_factory.mktemp("step_harness"))))
+
+
+@pytest.mark.parametrize("dtype,bsz,env", [
+    (torch.bfloat16, 1, {}), (torch.bfloat16, 2, {}), (torch.bfloat16, 4, {}), (torch.bfloat16, 9, {}), (torch.bfloat16, 33, {}),
+    (torch.bfloat16, 9, {"PTTS_LNPROJ": "0"}), (torch.bfloat16, 33, {"PTTS_LNPROJ": "0"}),   # PRO_LNS; rows_prep + PRO_COPY
+    (torch.bfloat16, 9, {"PTTS_NO_XATTN_GROUPS": "1"}), (torch.float32, 1, {})])
+def test_step_graph_holds_the_nodes_the_plan_lists(dtype, bsz, env, plan_harnesses, monkeypatch):
+    """The walkers of ptts_lm.hip issue what the plan lists: the captured step graph has layers x plan.launches() + the head projection's launches + the
+    sampler tail as kernel nodes, the plan read through the harnesses for the engine's own config and switches. The smallest shapes at which each
+    branch of the plan begins: the GEMV step folded (1), fused (2) and on two self-attention nodes (4), the fp32 step; the strip step on the
+    LayerNorm + projection nodes of 8 (9) and 16 (33) utterances, on producer statistics and on rows_prep + PRO_COPY, and on the two-node cross block."""
+    import step_plan as SP
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    gvh, sh = plan_harnesses
+    spec = DO.DecoderSpec(num_hidden_layers=2, max_position_embeddings=256)
+    sd = DO.make_decoder_weights(spec, seed=5)
+    g = torch.Generator().manual_seed(2)
+    enc, prompt = torch.randn(bsz, 9, spec.hidden_size, generator=g), torch.randn(bsz, 4, spec.hidden_size, generator=g)
+    eng = make_engine(spec, sd, dtype, max_batch=bsz, max_ctx=64, max_enc=16, max_prompt=5)
+    eng.set_gen_params(max_length=12, min_new_tokens=11)
+    eng.prefill(enc, None, prompt, None, sample=True)
+    eng.decode_steps(2)
+    nodes = eng.graph_nodes()
+    eng.close()
+    cfg = SP.config(spec.hidden_size, spec.num_attention_heads, spec.ffn_dim, bf16=dtype == torch.bfloat16, layers=spec.num_hidden_layers, max_batch=bsz,
+                    max_ctx=64, max_enc=16, max_prompt=5, codebooks=spec.num_codebooks, vocab=spec.vocab_size)
+    sw = SP.StepSwitches(lnproj=int(env.get("PTTS_LNPROJ", 3)), xattn_groups=int(not int(env.get("PTTS_NO_XATTN_GROUPS", 0))))
+    if bsz <= 8:
+        _, layer, head, *_ = gvh.gemv_plan(cfg, sw, bsz, 64, bsz == 1)  # one utterance: the folded cross block
+    else:
+        _, layer, head = sh.strip_plan(cfg, sw, False, bsz)
+    print(f"[step plan] {dtype} bsz={bsz} {env}: {layer} launches per layer + {head} (heads) + 1 (tail), graph nodes {nodes}")
+    assert nodes == spec.num_hidden_layers * layer + head + 1, (bsz, env, nodes, layer, head)
+
+
 @pytest.mark.parametrize("rope", [False, True])
 @pytest.mark.parametrize("P", [70, 32])
 def test_prefill_attention_tiled_kernel_vs_one_workgroup_per_row(rope, P, monkeypatch):

@@ -411,7 +411,7 @@ def test_strip_statistics_and_lns(H, K, bf16):
         assert r <= 1.0
         # consumer: PRO_LNS on the producer's own rows and statistics, both still on the device
         _, gamma, beta = SC.ln_inputs(1, K, 730 + M)
-        if not SC.lns_fits(M, K, bf16):  # gemm_with_prologue keeps rows_prep + PRO_COPY where the M rows do not fit in LDS: the harness declines too
+        if not SC.lns_fits(M, K, bf16):  # the plan (pro_gemm) keeps rows_prep + PRO_COPY where the M rows do not fit in LDS: the harness declines too
             gb, bb = gamma.to(DEV), beta.to(DEV)
             out = Guarded(M * 72, torch.float32)
             a = SH.ShGemm()

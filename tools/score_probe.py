@@ -2,7 +2,7 @@
   (a) ptts_score without logits, (b) with logits: the C call alone on preallocated buffers (no torch allocation or Python validation inside);
   (c) the heads + loss stage alone (score_launch through tests/native/score_harness.hip), no-store and store;
   (d) the baseline the parent commit offers: the existing PRO_LN / EPI_STORE projection over the same rows (rows_prep + GEMM, as
-      gemm_with_prologue runs it) into an fp32 [rows, K * V] buffer + torch.nn.functional.cross_entropy on it.
+      ptts_lm.hip's ln_gemm runs it) into an fp32 [rows, K * V] buffer + torch.nn.functional.cross_entropy on it.
 (c) and (d) alternate in one process; every figure is the median (min .. max) of REPS runs after WARM warm-ups. Also states the bytes the no-store
 path never allocates. Prints and records through tests/helpers.py::log_parity (the record is committed as profiles/score_forward.txt)."""
 import argparse
