@@ -11,6 +11,10 @@ from oracle import dac_oracle as DA
 # from itself (bf16 rounding flips amplified by ~30 layers, profiles/r04_dac_bf16_sensitivity.txt). The tight pin of the bf16 kernels is per stage,
 # on identical inputs: tests/test_dac_stage_parity_gpu.py (4e-4 on each stage's own contribution).
 DAC_BF16_TOL = 2e-2
+# The dh_snake probe (snake_f<true>: v_sin_f32 on alpha x / 2 pi) against the float64 Snake, relative to |v| + 1 / alpha, over |alpha v| <= pi:
+# 4 x the maximum measured on MI355X (1.527e-7, profiles/dac_kernels_parity.txt). tests/test_dac_kernels_gpu.py takes the probe as the reference of
+# every fast-path activation and requires this bar to stay below 2^-9, so that an error in the formula cannot hide behind it.
+DAC_SNAKE_S32_TOL = 4 * 1.527e-7
 
 
 def log_parity(msg, name="r04_parity_dac_bf16.txt"):
