@@ -143,6 +143,12 @@ SESSION_VOICE_SYMBOLS = {
     "ptts_debug_slot_voice": (C.c_int, [_VP, C.POINTER(_I32), _VP]),
 }
 
+# include/ptts_session_voice_rows.h, additive likewise: a group of such requests in one prefill pass
+SESSION_VOICE_ROWS_SYMBOLS = {
+    "ptts_admit_rows_voice": (C.c_int, [_VP, _I32, C.POINTER(_I32), _VP, _VP, _VP, _VP, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), _I32,
+                                        C.POINTER(C.POINTER(PttsGenParams)), _VP]),
+}
+
 # include/ptts_dac_stream_voice.h, additive likewise: streaming a request that continues a voice prompt out of a continuous session
 DAC_STREAM_VOICE_SYMBOLS = {
     "ptts_dac_stream_open_voice": (C.c_int, [_VP, _I32, _I32, _I32, _VP]),
@@ -189,7 +195,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 missing
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
     for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
-                              + list(SESSION_VOICE_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())
+                              + list(SESSION_VOICE_SYMBOLS.items()) + list(SESSION_VOICE_ROWS_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())
                               + list(WARP_SYMBOLS.items()) + list(SCORE_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)

@@ -95,7 +95,7 @@ class ContinuousBatcher:
     ``max_prompt_tokens + 1 + max_voice_frames`` positions. A limit given as ``max_new_tokens`` counts NEW tokens, as in ``generate()``: the
     session's ``max_length`` grows by ``max_voice_frames`` and a request with T frames gets ``max_new_tokens + 1 + T`` columns; a limit
     given as ``max_length`` stays the total. A request with a voice prompt is admitted alone (``ptts_admit_row_voice``), also with
-    ``admit_batch > 1``, and in streaming mode only with ``stream_voice_prompts`` (without it ``submit`` raises ``NotImplementedError``).
+    ``admit_batch > 1`` (but see ``admit_voice_groups``), and in streaming mode only with ``stream_voice_prompts`` (without it ``submit`` raises ``NotImplementedError``).
 
     ``stream_voice_prompts`` (default ``None``; needs ``stream_chunk_frames`` and ``max_voice_frames > 0``): a streaming session takes voice
     prompts. ``"emit"``: a request's chunks concatenate to the waveform of the non-streaming mode, the prompt's frames included. ``"skip"``:
@@ -103,15 +103,23 @@ class ContinuousBatcher:
     audio already. The codec's stream table then keeps each slot's prompt (``ptts_dac_stream_open_voice`` / ``_reset_voice``) and no pass
     emits more than ``max_emit = window_frames - 2 * halo`` frames per slot (``ptts_dac_stream_decode_capped``): a long prompt leaves in
     several chunks, starting at the poll that admits it, and a finished slot is drained by repeated final passes before it is reused. A
-    request without a prompt never has that much ready: its chunks are the ones of a session without the option."""
+    request without a prompt never has that much ready: its chunks are the ones of a session without the option.
+
+    ``admit_voice_groups`` (default ``False``; needs ``max_voice_frames > 0`` and ``admit_batch > 1``, ``ValueError`` otherwise): requests with
+    voice prompts are admitted in groups too. The FIFO queue is cut into runs of the same kind - with a prompt, without - and each run into
+    groups of at most ``spare``; a group of requests with prompts is ONE prefill pass over ``max_prompt_tokens + 1 + (the group's longest
+    prompt)`` positions per request (``ptts_admit_rows_voice``), the shorter ones padded. The order of admission stays FIFO, and
+    ``admission_groups`` counts these groups too. Like any group admission: within the engine's tolerance of the same request admitted alone."""
 
     def __init__(self, model, slots: int, max_description_tokens: int, max_prompt_tokens: int, poll_steps: int = 16,
                  stream_chunk_frames: Optional[int] = None, stream_first_chunk_frames: Optional[int] = None, admit_batch: int = 1, max_voice_frames: int = 0,
-                 stream_voice_prompts: Optional[str] = None, **generation_kwargs):
+                 stream_voice_prompts: Optional[str] = None, admit_voice_groups: bool = False, **generation_kwargs):
         if int(admit_batch) < 1:
             raise ValueError("`admit_batch` must be >= 1")
         if int(max_voice_frames) < 0:
             raise ValueError("`max_voice_frames` must be >= 0")
+        if admit_voice_groups and (int(max_voice_frames) < 1 or int(admit_batch) < 2):
+            raise ValueError("`admit_voice_groups` needs `max_voice_frames` > 0 and `admit_batch` > 1")
         if stream_voice_prompts not in (None, "emit", "skip"):
             raise ValueError(f"`stream_voice_prompts` must be None, 'emit' or 'skip', got {stream_voice_prompts!r}")
         if stream_voice_prompts is not None and (stream_chunk_frames is None or int(max_voice_frames) < 1):
@@ -152,6 +160,7 @@ class ContinuousBatcher:
             raise NotImplementedError("num_return_sequences > 1: submit the request several times")
         self.model, self.slots, self.N, self.P, self.poll_steps = model, int(slots), int(max_description_tokens), int(max_prompt_tokens), int(poll_steps)
         self.max_voice_frames = int(max_voice_frames)
+        self.voice_groups = bool(admit_voice_groups)
         # new tokens of a request that names no limit of its own (None: the session's limit is a total, `max_length`)
         self._max_new = int(gc.max_new_tokens) if gc.max_new_tokens is not None else None
         self.max_length = self._max_new + 1 + self.max_voice_frames if self._max_new is not None else int(gc.max_length)
@@ -382,13 +391,14 @@ class ContinuousBatcher:
 
     def _admit(self):
         """The one admission path of both modes. Idle slots in ascending order meet the queue in FIFO order; the pairs are cut into groups of
-        at most ``max(spare, 1)``, a request with a voice prompt going alone (``admit_rows`` takes none). A group of one is one ``admit_row``, a
-        larger one ONE prefill pass (``admit_rows``); behind each group its slots' stream tables are reset (streaming mode). A request
+        at most ``max(spare, 1)``, a request with a voice prompt going alone - or, with ``admit_voice_groups``, a group holding requests of one
+        kind only, with a prompt or without. A group of one is one ``admit_row``, a larger one ONE prefill pass (``admit_rows``, with ``voices=``
+        for a group with prompts); behind each group its slots' stream tables are reset (streaming mode). A request
         leaves the queue immediately before the engine call that admits it: if that call raises, the requests behind it are still queued."""
         groups = []
         for s, r in zip((s for s in range(self.slots) if self._slot[s] is None), self._queue):
             full = not groups or len(groups[-1]) == max(self.spare, 1)
-            if full or r.voice is not None or groups[-1][0][1].voice is not None:
+            if full or self._ends_group(groups[-1][0][1], r):
                 groups.append([])
             groups[-1].append((s, r))
         for group in groups:
@@ -409,7 +419,8 @@ class ContinuousBatcher:
                 stack = lambda ts: None if ts[0] is None else torch.stack(ts)
                 gens = None if all(r.gen is None for r in reqs) else [None if r.gen is None else dict(r.gen) for r in reqs]
                 self.eng.admit_rows([s for s, _ in group], stack([r.enc for r in reqs]), stack([r.enc_mask for r in reqs]), stack([r.prompt for r in reqs]),
-                                    stack([r.prompt_mask for r in reqs]), max_lengths=[r.max_length for r in reqs], sample=True, gens=gens)
+                                    stack([r.prompt_mask for r in reqs]), max_lengths=[r.max_length for r in reqs], sample=True, gens=gens,
+                                    **({} if reqs[0].voice is None else {"voices": [r.voice for r in reqs]}))  # no keyword for a plain group
                 self.admission_groups.append(len(group))
             self.admissions += len(group)
             for s, r in group:
@@ -417,6 +428,12 @@ class ContinuousBatcher:
                 if self.chunk is not None:  # a prompt comes only with stream_voice_prompts: submit refuses it otherwise
                     voice = {} if r.voice is None else {"voice": r.voice, "emit_prompt": self.stream_voice == "emit"}
                     self.model.audio_encoder.stream_reset(s, **voice)
+
+    def _ends_group(self, first: _Request, r: _Request) -> bool:
+        """Whether `r` may not join the group that `first` opened: a voice prompt on either side - or, with ``admit_voice_groups``, on one side only."""
+        if self.voice_groups:
+            return (first.voice is None) != (r.voice is None)
+        return first.voice is not None or r.voice is not None
 
     def _retire(self, s: int):
         self.eng.retire_row(s)

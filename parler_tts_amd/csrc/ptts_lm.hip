@@ -11,6 +11,7 @@
 #include "ptts_common.h"
 #include "../../include/ptts_session_kv8.h"
 #include "../../include/ptts_session_voice.h"
+#include "../../include/ptts_session_voice_rows.h"
 #include "../../include/ptts_penalty.h"
 #include "../../include/ptts_warp.h"
 #include "../../include/ptts_score.h"
@@ -113,7 +114,8 @@ struct ptts_engine {
   int* row_maxlen = nullptr;             // [max_batch] device: max_length of the request in each slot
   SlotGen* slot_gen = nullptr;           // [max_batch] device: sampler record of the request in each slot (ptts_admit_row_gen); own = 0: the session's
   int* slot_T = nullptr;                 // [max_batch] device: voice-prompt frames of the request in each slot (ptts_admit_row_voice); 0: none
-  DevDims* dims_adm = nullptr;           // [max_batch] device: per slot, the DevDims a voice admission's prefill embedding reads (the request's max_length, T, prefix rows)
+  DevDims* dims_adm = nullptr;           // [max_batch] device: per slot, the DevDims a voice admission's prefill embedding reads (the request's max_length, T, prefix rows);
+                                         // entries B .. B + n - 1 (the spare rows): those of the n requests of a group (ptts_admit_rows_voice, FwdView::row_dims)
   float* h_adm = nullptr;                // [max_prompt][H] residual rows of a row prefill: the step input h[B][H] of the other slots is live between steps
   KvLayer* kv_layers_rows = nullptr;     // [max_batch][layers] operands of the batched cross K/V projection with each slot's arena rows as base
   float* h_adm_rows = nullptr;           // [(max_batch - 1) * max_prompt][H] residual rows of a group prefill (ptts_admit_rows), allocated at its first use
@@ -163,6 +165,8 @@ struct FwdView {
   int *cur_len, *unfinished, *has_eos, *first_unf, *enc_mask, *prompt_mask;
   const KvLayer* kv_layers;      // [layers] operands of the batched cross K/V projection
   const DevDims* embed_dims;     // what the embedding reads its delay pattern from: the engine's, or a voice admission's own (ptts_admit_row_voice)
+  const DevDims* row_dims;       // [B] or null. A group of voice admissions (ptts_admit_rows_voice): every row of the prefill pass under its own request -
+                                 // its delay pattern, its T <= v.T columns (the rest of the row is padding), and the position its logits come from
   size_t self_off, cross_off;    // bytes from a layer's self / cross K/V arena to utterance 0 of this view
   size_t scale_off;              // kv_fp8 engines: floats from a layer's K / V scale array (LayerW::ks_self, vs_self) to utterance 0 of this view
 };
@@ -287,7 +291,9 @@ void launch_embed(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStrea
   ea.ids = v.ids; ea.ids_ld = e->ids_ld; ea.cur_len = v.cur_len; ea.dims = v.embed_dims; ea.h = v.h;
   ea.H = c.hidden_size; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.bos = c.bos_token_id; ea.pad = c.pad_token_id;
   ea.prefill = prefill ? 1 : 0;
-  if (v.session && !prefill)  // every slot under its own request's delay pattern
+  if (prefill && v.row_dims)  // every row of the pass under its own request's delay pattern and prefix length
+    hipLaunchKernelGGL((embed_rows_kernel<WT>), dim3(Q, v.B), dim3(256), 0, st, ea, v.row_dims);
+  else if (v.session && !prefill)  // every slot under its own request's delay pattern
     hipLaunchKernelGGL((embed_kernel<WT, true>), dim3(1, v.B), dim3(256), 0, st, EmbedSessionArgs{ea, e->row_maxlen, e->slot_T});
   else
     hipLaunchKernelGGL((embed_kernel<WT, false>), dim3(Q, v.B), dim3(256), 0, st, ea);
@@ -525,6 +531,7 @@ int strip_path(const ptts_engine* e, FwdView v, const StripPlan& p, hipStream_t 
     }
   }
   if (heads) {  // final LayerNorm + all K LM heads as one [K*V, H] projection, last position of each utterance only
+    if (prefill && v.row_dims) hipLaunchKernelGGL(gather_last_rows_kernel, dim3(B), dim3(256), 0, st, v.h, H, Q, v.row_dims);  // ... of a ragged group: the last GIVEN one
     GemmArgs g = {}; g.decode = p.dec;
     g.W = e->heads; g.W8 = e->heads_p8; g.wscale = e->heads_sc; g.x = v.h; g.x_ld = H; g.x_row_mul = Q; g.x_row_off = Q - 1; g.gamma = e->lnf_g; g.beta = e->lnf_b;
     g.out = v.logits; g.out_ld = c.num_codebooks * c.vocab_size; g.M = B; g.N = c.num_codebooks * c.vocab_size; g.K = H;
@@ -1426,6 +1433,25 @@ extern "C" int ptts_debug_slot_voice(ptts_engine* e, int32_t* frames_host, void*
   return PTTS_OK;
 }
 
+// first group admission of this engine: the residual rows of a group prefill and the operand tables of the move kernels
+static int ensure_group_rows(ptts_engine* e) {
+  const ptts_config& c = e->cfg;
+  if (!e->h_adm_rows) {
+    std::vector<AdmitMoveLayer> ml(c.num_layers);
+    for (int l = 0; l < c.num_layers; ++l) ml[l] = AdmitMoveLayer{e->L[l].k_self, e->L[l].v_self, e->L[l].k_cross, e->L[l].v_cross};
+    PTTS_TRY(e->alloc(&e->move_layers, (size_t)c.num_layers));
+    PTTS_HIP(hipMemcpy(e->move_layers, ml.data(), ml.size() * sizeof(AdmitMoveLayer), hipMemcpyHostToDevice));
+    if (c.kv_fp8) {
+      std::vector<AdmitScaleLayer> sl(c.num_layers);
+      for (int l = 0; l < c.num_layers; ++l) sl[l] = AdmitScaleLayer{e->L[l].ks_self, e->L[l].vs_self};
+      PTTS_TRY(e->alloc(&e->move_scales, (size_t)c.num_layers));
+      PTTS_HIP(hipMemcpy(e->move_scales, sl.data(), sl.size() * sizeof(AdmitScaleLayer), hipMemcpyHostToDevice));
+    }
+    PTTS_TRY(e->alloc(&e->h_adm_rows, (size_t)(c.max_batch - 1) * e->max_prompt * c.hidden_size));
+  }
+  return PTTS_OK;
+}
+
 // A group of n requests in one prefill pass: the static prefill forward of a batch of n on the spare arena rows B .. B + n - 1 (every array of the
 // engine is batch-outermost and sized for max_batch, so rows_view(e, B, n) is an n-utterance engine), then ONE launch that moves each spare row to its
 // slot (admit_move_rows_kernel), then per slot what ptts_admit_row_gen does: reset, record, tail. The tail runs on the slot itself: the draw hash of a
@@ -1438,7 +1464,7 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
   PTTS_CHECK(n >= 1, PTTS_E_INVALID, "ptts_admit_rows: n = %d requests (at least 1)", n);
   PTTS_CHECK(enc_dev && rows && max_lengths, PTTS_E_INVALID, "null argument");
   const ptts_config& c = e->cfg;
-  const int B = e->B, P = e->P, N = e->N, H = c.hidden_size, K = c.num_codebooks;
+  const int B = e->B, P = e->P, N = e->N, K = c.num_codebooks;
   std::vector<int> Ls(n);
   for (int j = 0; j < n; ++j) {
     PTTS_TRY(check_admission(e, rows[j], prompt_dev, max_lengths[j], gps ? gps[j] : nullptr, &Ls[j]));
@@ -1448,19 +1474,7 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
              c.max_batch - B, B, c.max_batch);
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
-  if (!e->h_adm_rows) {
-    std::vector<AdmitMoveLayer> ml(c.num_layers);
-    for (int l = 0; l < c.num_layers; ++l) ml[l] = AdmitMoveLayer{e->L[l].k_self, e->L[l].v_self, e->L[l].k_cross, e->L[l].v_cross};
-    PTTS_TRY(e->alloc(&e->move_layers, (size_t)c.num_layers));
-    PTTS_HIP(hipMemcpy(e->move_layers, ml.data(), ml.size() * sizeof(AdmitMoveLayer), hipMemcpyHostToDevice));
-    if (c.kv_fp8) {
-      std::vector<AdmitScaleLayer> sl(c.num_layers);
-      for (int l = 0; l < c.num_layers; ++l) sl[l] = AdmitScaleLayer{e->L[l].ks_self, e->L[l].vs_self};
-      PTTS_TRY(e->alloc(&e->move_scales, (size_t)c.num_layers));
-      PTTS_HIP(hipMemcpy(e->move_scales, sl.data(), sl.size() * sizeof(AdmitScaleLayer), hipMemcpyHostToDevice));
-    }
-    PTTS_TRY(e->alloc(&e->h_adm_rows, (size_t)(c.max_batch - 1) * e->max_prompt * H));
-  }
+  PTTS_TRY(ensure_group_rows(e));
   // the spare rows as ptts_prefill prepares a batch of n: sampler state (the prefill's embedding reads the BOS column and the clock), masks, staging
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((n * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
@@ -1492,6 +1506,92 @@ extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, c
                        e->row_maxlen, rows[j], 1, K, c.bos_token_id, 1, Ls[j]);
     PTTS_TRY(finish_admission(e, rows[j], Ls[j], gps ? gps[j] : nullptr, sample != 0, st));
   }
+  return PTTS_OK;
+}
+
+// A group of n requests that continue voice prompts of Ts[j] frames, in one prefill pass: ptts_admit_rows' pass on the spare rows over
+// P + 1 + Tmax positions per row, every row under its own request (FwdView::row_dims: delay pattern, prefix length, logits position), a shorter
+// request right-padded with PAD columns that causal attention keeps from its own positions. In front of the pass one launch does for the n slots
+// what ptts_admit_row_voice does for one (admit_voice_slots_kernel); behind it the ragged move carries P + 1 + Ts[j] self rows of request j to its
+// slot and nothing of the padding. n == 1 and "no request brings a prompt" are the calls that exist for them.
+extern "C" int ptts_admit_rows_voice(ptts_engine* e, int32_t n, const int32_t* rows, const float* enc_dev, const int32_t* enc_mask_dev,
+                                     const float* prompt_dev, const int32_t* prompt_mask_dev, const int64_t* const* codes_dev, const int32_t* Ts,
+                                     const int32_t* max_lengths, int32_t sample, const ptts_gen_params* const* gps, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_rows_voice: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(n >= 1, PTTS_E_INVALID, "ptts_admit_rows_voice: n = %d requests (at least 1)", n);
+  PTTS_CHECK(enc_dev && rows && max_lengths && Ts, PTTS_E_INVALID, "null argument");
+  int Tmax = 0;
+  for (int j = 0; j < n; ++j) {
+    PTTS_CHECK(Ts[j] >= 0 && (Ts[j] == 0 || (codes_dev && codes_dev[j])), PTTS_E_INVALID, "request %d: bad voice prompt (T = %d frames, codes %s)", j, Ts[j],
+               codes_dev && codes_dev[j] ? "given" : "null");
+    Tmax = std::max(Tmax, (int)Ts[j]);
+  }
+  if (Tmax == 0) return ptts_admit_rows(e, n, rows, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_lengths, sample, gps, stream);
+  if (n == 1)
+    return ptts_admit_row_voice(e, rows[0], enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, codes_dev[0], Ts[0], max_lengths[0], sample,
+                                gps ? gps[0] : nullptr, stream);
+  const ptts_config& c = e->cfg;
+  const int B = e->B, P = e->P, N = e->N, K = c.num_codebooks;
+  std::vector<int> Ls(n);
+  for (int j = 0; j < n; ++j) {
+    PTTS_TRY(check_admission(e, rows[j], prompt_dev, max_lengths[j], gps ? gps[j] : nullptr, &Ls[j]));
+    for (int i = 0; i < j; ++i) PTTS_CHECK(rows[i] != rows[j], PTTS_E_INVALID, "slot %d listed twice", rows[j]);
+    PTTS_CHECK(Ts[j] + 2 <= Ls[j], PTTS_E_INVALID, "request %d: voice prompt of %d frames leaves no room below max_length %d", j, Ts[j], Ls[j]);
+  }
+  PTTS_CHECK(n <= c.max_batch - B, PTTS_E_CAPACITY, "%d requests exceed the %d spare rows behind the session's %d slots (engine max_batch %d)", n,
+             c.max_batch - B, B, c.max_batch);
+  PTTS_CHECK(P + 1 + Tmax <= e->max_prompt, PTTS_E_CAPACITY, "P + 1 + T = %d positions exceed the engine's prefill capacity %d (max_prompt)", P + 1 + Tmax,
+             e->max_prompt);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = pick_stream(e, stream);
+  PTTS_TRY(ensure_group_rows(e));
+  // the spare rows as ptts_prefill prepares a batch of n, and every slot as ptts_admit_row_voice prepares it: reset, codes to its prefix rows
+  hipLaunchKernelGGL(session_reset_rows_kernel, dim3((n * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
+                     e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
+  for (int j = 0; j < n; ++j) {
+    hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
+                       e->row_maxlen, rows[j], 1, K, c.bos_token_id, 1, Ls[j]);
+    if (Ts[j] > 0)
+      PTTS_HIP(hipMemcpy2DAsync(e->prefix + (size_t)rows[j] * K * c.max_ctx, (size_t)c.max_ctx * 8, codes_dev[j], (size_t)Ts[j] * 8, (size_t)Ts[j] * 8,
+                                (size_t)K, hipMemcpyDeviceToDevice, st));
+  }
+  for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {  // id columns, slot_T, clock and the spare row's DevDims (dims_adm[B + j]: a spare row is nobody's slot)
+    const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
+    AdmitVoiceSlotsArgs a = {};
+    a.ids = e->ids; a.prefix = e->prefix; a.slot_T = e->slot_T; a.cur_len = e->cur_len; a.row_dims = e->dims_adm + B + j0;
+    a.ids_ld = e->ids_ld; a.prefix_ld = c.max_ctx; a.K = K; a.bos = c.bos_token_id; a.pad = c.pad_token_id; a.P = P; a.N = N;
+    for (int j = 0; j < nj; ++j) { a.rows[j] = rows[j0 + j]; a.Ts[j] = Ts[j0 + j]; a.Ls[j] = Ls[j0 + j]; }
+    hipLaunchKernelGGL(admit_voice_slots_kernel, dim3((K * Tmax + 255) / 256, nj), dim3(256), 0, st, a);
+  }
+  PTTS_TRY(stage_inputs(e, B, n, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
+  FwdView v = rows_view(e, B, n, e->h_adm_rows);  // n * (P + 1 + Tmax) <= (max_batch - 1) * max_prompt residual rows
+  v.T = Tmax; v.row_dims = e->dims_adm + B;
+  PTTS_TRY(forward_dispatch(e, v, true, st));
+  const int ru = (int)(64 * e->esize / 16), sru = c.kv_fp8 ? 4 : ru;  // 16-byte units of an arena row: engine dtype; self rows (e4m3: 64 bytes)
+  for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
+    const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
+    AdmitMoveRaggedArgs ra = {};
+    AdmitMoveArgs& a = ra.m;
+    a.layers = e->move_layers; a.logits = e->logits; a.enc_mask = e->enc_mask; a.prompt_mask = e->prompt_mask;
+    a.src0 = B + j0; a.nlayers = c.num_layers; a.nkv = e->sc.nkv; a.nkc = e->sc.nkc;
+    a.self_u = 0; a.self_cap_u = c.max_ctx * sru; a.cross_u = N * ru; a.cross_cap_u = c.max_enc * ru;
+    a.logit_u = K * c.vocab_size / 4;
+    a.enc_n = enc_mask_dev ? N : c.max_enc; a.enc_ld = c.max_enc;
+    a.prompt_n = (prompt_mask_dev && P > 0) ? P : e->max_prompt; a.prompt_ld = e->max_prompt;
+    ra.row_u = sru;
+    for (int j = 0; j < nj; ++j) { a.rows[j] = rows[j0 + j]; ra.self_rows[j] = P + 1 + Ts[j0 + j]; }
+    const int units = 2 * (e->sc.nkv * (P + 1 + Tmax) * sru + e->sc.nkc * a.cross_u);  // of the longest request
+    hipLaunchKernelGGL(admit_move_rows_ragged_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, ra);
+    if (c.kv_fp8) {  // the rows' scales travel with them
+      AdmitScaleRaggedArgs sa = {};
+      sa.s.layers = e->move_scales; sa.s.src0 = B + j0; sa.s.nkv = e->sc.nkv; sa.s.n = 0; sa.s.cap = c.max_ctx;
+      for (int j = 0; j < nj; ++j) { sa.s.rows[j] = rows[j0 + j]; sa.ns[j] = P + 1 + Ts[j0 + j]; }
+      hipLaunchKernelGGL(admit_move_scales_ragged_kernel, dim3(1, c.num_layers, nj), dim3(256), 0, st, sa);
+    }
+  }
+  PTTS_TRY(launch_status("admit_move_rows_ragged"));
+  for (int j = 0; j < n; ++j) PTTS_TRY(finish_admission(e, rows[j], Ls[j], gps ? gps[j] : nullptr, sample != 0, st, Ts[j]));
   return PTTS_OK;
 }
 

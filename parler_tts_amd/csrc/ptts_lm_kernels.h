@@ -2480,6 +2480,17 @@ __device__ __forceinline__ long long delayed_token(const long long* ids, int ld,
   return ids[(size_t)rowk * ld + j];
 }
 
+// value of column j (1 <= j <= T) of a request that continues a voice prompt: what build_delay_pattern_mask holds there for (BOS + prefix, the
+// request's own max_length): BOS for j <= k, PAD for j - k >= max_length - K + 1, prefix[j - k - 1] otherwise; the prefix un-shifted below
+// 2K - 1, where there is no pattern. prefix: the request's first row. What push_prefix_slot_kernel writes and what delayed_token then reads back
+__device__ __forceinline__ long long voice_column_token(const long long* prefix, int prefix_ld, int k, int j, int K, int bos, int pad,
+                                                        int max_length) {
+  if (max_length < 2 * K - 1) return prefix[(size_t)k * prefix_ld + (j - 1)];
+  if (j <= k) return bos;
+  if (j - k >= max_length - K + 1) return pad;
+  return prefix[(size_t)k * prefix_ld + (j - k - 1)];
+}
+
 struct EmbedArgs {
   const void* tables;      // [K][V+1][H] engine dtype
   const float* pos_table;  // [max_pos][H] or null (RoPE)
@@ -2537,6 +2548,49 @@ __global__ void embed_kernel(typename EmbedK<SESSION>::T p) {
     if (a.pos_table) acc += a.pos_table[(size_t)pos * a.H + d];
     out[d] = acc;
   }
+}
+
+// Prefill embedding of a group of voice admissions (ptts_admit_rows_voice): every row of the pass under its OWN request - row_dims[b] holds its
+// max_length, its T_prefix and its prefix rows (where the request's codes live: the destination slot's rows of the engine's prefix buffer, which
+// the decode steps read too). grid (Q, n) with Q = P + 1 + Tmax. The token of a given column comes from the prefix alone (voice_column_token;
+// column 0: BOS), never from the id columns of the row the pass runs on, which nobody wrote. A column behind the row's own T_prefix (a shorter
+// request, right-padded to Tmax) embeds PAD, an in-range row of every table: causal attention keeps it from the positions in front of it, and
+// what is computed there is thrown away.
+template <typename WT>
+__global__ void embed_rows_kernel(EmbedArgs a, const DevDims* __restrict__ row_dims) {
+  const int b = blockIdx.y, qi = blockIdx.x, Q = (int)gridDim.x;
+  const DevDims dd = row_dims[b];
+  const int P = dd.P, j = max(qi - P, 0);
+  float* out = a.h + ((size_t)b * Q + qi) * a.H;
+  const WT* tab = reinterpret_cast<const WT*>(a.tables);
+  if (qi < P) {
+    const float* pr = a.prompt + ((size_t)b * P + qi) * a.H;
+    for (int d = threadIdx.x; d < a.H; d += blockDim.x) out[d] = pr[d] + (a.pos_table ? a.pos_table[(size_t)qi * a.H + d] : 0.f);
+    return;
+  }
+  __shared__ int s_tok[32];
+  if (threadIdx.x < a.K) {
+    const int k = threadIdx.x;
+    s_tok[k] = j == 0 ? a.bos : j > dd.T_prefix ? a.pad : (int)voice_column_token(dd.prefix, dd.prefix_ld, k, j, a.K, a.bos, a.pad, dd.max_length);
+  }
+  __syncthreads();
+  for (int d = threadIdx.x; d < a.H; d += blockDim.x) {
+    float acc = 0.f;
+    for (int k = 0; k < a.K; ++k) acc += Elem<WT>::ld(tab + ((size_t)k * a.V1 + s_tok[k]) * a.H + d);  // sum([...]) order :1433
+    if (a.pos_table) acc += a.pos_table[(size_t)qi * a.H + d];
+    out[d] = acc;
+  }
+}
+
+// In front of the final LayerNorm + LM heads of such a pass: the heads read the LAST of every row's Q residual rows, and the logits of a request
+// with T_prefix < Tmax come from position P + T_prefix. Its residual row moves over the row's last one (a padded position: thrown away anyway),
+// so the heads projection is the launch of the static prefill. grid (n). A row with T_prefix == Tmax is left alone.
+static __global__ void __launch_bounds__(256) gather_last_rows_kernel(float* h, int H, int Q, const DevDims* __restrict__ row_dims) {
+  const int b = blockIdx.x, src = row_dims[b].P + row_dims[b].T_prefix;
+  if (src >= Q - 1) return;
+  const float* from = h + ((size_t)b * Q + src) * H;
+  float* to = h + ((size_t)b * Q + Q - 1) * H;
+  for (int d = threadIdx.x; d < H; d += 256) to[d] = from[d];
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2933,12 +2987,7 @@ static __global__ void push_prefix_slot_kernel(long long* ids, int ids_ld, const
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= K * T) return;
   const int k = i / T, j = 1 + i % T;
-  long long v;
-  if (max_length < 2 * K - 1) v = prefix[(size_t)k * prefix_ld + (j - 1)];
-  else if (j <= k) v = bos;
-  else if (j - k >= max_length - K + 1) v = pad;
-  else v = prefix[(size_t)k * prefix_ld + (j - k - 1)];
-  ids[(size_t)k * ids_ld + j] = v;
+  ids[(size_t)k * ids_ld + j] = voice_column_token(prefix, prefix_ld, k, j, K, bos, pad, max_length);
 }
 // the DevDims the prefill embedding of such an admission reads (the request's max_length, T and prefix rows; by value, as set_params_kernel's)
 static __global__ void set_dims_kernel(DevDims* dd, DevDims d) { *dd = d; }
@@ -2985,7 +3034,8 @@ struct AdmitMoveArgs {
   int enc_n, enc_ld, prompt_n, prompt_ld;  // mask positions to move and the row strides
   int rows[ADMIT_ROWS_MAX];
 };
-static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveArgs a) {
+// (self_u: the units of THIS request's self rows - a.self_u, or the ragged kernel's own count)
+__device__ __forceinline__ void admit_move_body(const AdmitMoveArgs& a, int self_u) {
   const size_t src = (size_t)(a.src0 + (int)blockIdx.z), dst = (size_t)a.rows[blockIdx.z];
   const int tid = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256, l = blockIdx.y;
   if (l == a.nlayers) {
@@ -2996,7 +3046,7 @@ static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveAr
     return;
   }
   const AdmitMoveLayer L = a.layers[l];
-  const int su = a.nkv * a.self_u, cu = a.nkc * a.cross_u;
+  const int su = a.nkv * self_u, cu = a.nkc * a.cross_u;
   for (int u = tid; u < 2 * (su + cu); u += stride) {
     uint4* base;
     size_t heads, cap;
@@ -3004,7 +3054,7 @@ static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveAr
     if (u < 2 * su) {
       const int v = u >= su, r = u - v * su;
       base = reinterpret_cast<uint4*>(v ? L.v_self : L.k_self);
-      head = r / a.self_u; off = r - head * a.self_u; heads = a.nkv; cap = a.self_cap_u;
+      head = r / self_u; off = r - head * self_u; heads = a.nkv; cap = a.self_cap_u;
     } else {
       const int r0 = u - 2 * su, v = r0 >= cu, r = r0 - v * cu;
       base = reinterpret_cast<uint4*>(v ? L.v_cross : L.k_cross);
@@ -3013,6 +3063,18 @@ static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveAr
     base[(dst * heads + head) * cap + off] = base[(src * heads + head) * cap + off];
   }
 }
+static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveArgs a) { admit_move_body(a, a.self_u); }
+
+// ptts_admit_rows_voice: the ragged form. Request j of the launch wrote self_rows[j] = P + 1 + T_j positions of its own; the pass ran
+// P + 1 + Tmax on every spare row, and what lies behind a shorter request's own positions is padding that must not reach its slot: the
+// slot's arena rows at and beyond self_rows[j] stay what they were. The lengths travel by value beside the slot list. Cross rows, logits
+// and masks move as in admit_move_rows_kernel (m.self_u is not read). Same grid.
+struct AdmitMoveRaggedArgs {
+  AdmitMoveArgs m;
+  int row_u;                       // 16-byte units of one self row (e4m3: 4)
+  int self_rows[ADMIT_ROWS_MAX];   // self K/V positions to move per request
+};
+static __global__ void __launch_bounds__(256) admit_move_rows_ragged_kernel(AdmitMoveRaggedArgs a) { admit_move_body(a.m, a.self_rows[blockIdx.z] * a.row_u); }
 
 // kv_fp8 engines, beside admit_move_rows_kernel (which moves the 64-byte e4m3 self rows as 4 units each): the P + 1 K scales and V scales per
 // (layer, K/V head) from spare row src0 + j to slot rows[j]. P + 1 floats are in general no multiple of 16 bytes: one float per thread.
@@ -3023,14 +3085,52 @@ struct AdmitScaleArgs {
   int src0, nkv, n, cap;  // first spare row; K/V heads; scales to move per head (P + 1); scales per head (max_ctx)
   int rows[ADMIT_ROWS_MAX];
 };
-static __global__ void __launch_bounds__(256) admit_move_scales_kernel(AdmitScaleArgs a) {
+__device__ __forceinline__ void admit_move_scales_body(const AdmitScaleArgs& a, int n) {  // n: a.n, or the ragged kernel's own count
   const size_t src = (size_t)(a.src0 + (int)blockIdx.z), dst = (size_t)a.rows[blockIdx.z];
   const AdmitScaleLayer L = a.layers[blockIdx.y];
-  const int per = a.nkv * a.n;
+  const int per = a.nkv * n;
   for (int u = threadIdx.x; u < 2 * per; u += 256) {
-    const int v = u >= per, r = u - v * per, head = r / a.n, off = r - head * a.n;
+    const int v = u >= per, r = u - v * per, head = r / n, off = r - head * n;
     float* base = v ? L.vs_self : L.ks_self;
     base[(dst * a.nkv + head) * a.cap + off] = base[(src * a.nkv + head) * a.cap + off];
+  }
+}
+static __global__ void __launch_bounds__(256) admit_move_scales_kernel(AdmitScaleArgs a) { admit_move_scales_body(a, a.n); }
+// the ragged form (ptts_admit_rows_voice): ns[j] = P + 1 + T_j scales per head of request j, by value (s.n is not read). Same grid.
+struct AdmitScaleRaggedArgs {
+  AdmitScaleArgs s;
+  int ns[ADMIT_ROWS_MAX];
+};
+static __global__ void __launch_bounds__(256) admit_move_scales_ragged_kernel(AdmitScaleRaggedArgs a) { admit_move_scales_body(a.s, a.ns[blockIdx.z]); }
+
+// ptts_admit_rows_voice, in front of the pass: for request j of the launch, what ptts_admit_row_voice does for one slot with
+// push_prefix_slot_kernel + fill_int_kernel(slot_T) + set_dims_kernel, in one launch for all. Id columns 1..Ts[j] of slot rows[j] (the delay
+// pattern of the request's own max_length Ls[j] over its codes, which already lie in the slot's prefix rows), slot_T[rows[j]], the slot's clock at
+// Ts[j] + 1 (the slot was reset in front of this launch; the pass itself reads no clock), and the DevDims the pass's embedding reads for the
+// spare row the request runs on (row_dims[j]; its prefix pointer: the SLOT's prefix rows). Everything by value. grid (cells of Tmax, n);
+// a request with Ts[j] == 0 gets slot_T 0, clock 1 and no column.
+struct AdmitVoiceSlotsArgs {
+  long long* ids;            // the engine's id buffer (slot 0)
+  const long long* prefix;   // the engine's prefix buffer (slot 0), [slots * K][prefix_ld]
+  int* slot_T;
+  int* cur_len;
+  DevDims* row_dims;         // [n] of this launch
+  int ids_ld, prefix_ld, K, bos, pad, P, N;
+  int rows[ADMIT_ROWS_MAX], Ts[ADMIT_ROWS_MAX], Ls[ADMIT_ROWS_MAX];
+};
+static __global__ void __launch_bounds__(256) admit_voice_slots_kernel(AdmitVoiceSlotsArgs a) {
+  const int jr = blockIdx.y, row = a.rows[jr], T = a.Ts[jr], L = a.Ls[jr];
+  const long long* pre = a.prefix + (size_t)row * a.K * a.prefix_ld;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < a.K * T) {
+    const int k = i / T, j = 1 + i % T;
+    a.ids[((size_t)row * a.K + k) * a.ids_ld + j] = voice_column_token(pre, a.prefix_ld, k, j, a.K, a.bos, a.pad, L);
+  }
+  if (i == 0) {
+    a.slot_T[row] = T;
+    a.cur_len[row] = T + 1;
+    DevDims d; d.P = a.P; d.N = a.N; d.max_length = L; d.T_prefix = T; d.prefix = pre; d.prefix_ld = a.prefix_ld;
+    a.row_dims[jr] = d;
   }
 }
 

@@ -453,14 +453,26 @@ class DecoderEngine:
         self._keep_rows[int(row)] = keep  # consumed asynchronously by the enqueued kernels
 
     def admit_rows(self, rows, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
-                   prompt_mask: Optional[torch.Tensor], max_lengths=None, sample: bool = True, gens=None):
+                   prompt_mask: Optional[torch.Tensor], max_lengths=None, sample: bool = True, gens=None, voices=None):
         """Prefills ``n = len(rows)`` requests into ``n`` distinct idle slots with ONE prefill pass (``ptts_admit_rows``): request ``j``
         (``enc[j]`` [N, H], ``prompt[j]`` [P, H], ``max_lengths[j]``, ``gens[j]``) goes into slot ``rows[j]``, which afterwards is what
         ``admit_row`` makes of it. The engine needs ``n`` spare rows behind the session's slots (``max_batch >= slots + n``).
         ``max_lengths``: one per request (``None``: the session's for all); ``gens``: ``None``, or one entry per request, each ``None`` or
-        ``admit_row``'s ``gen``."""
+        ``admit_row``'s ``gen``.
+        ``voices``: ``None``, or one entry per request, each ``None`` or ``admit_row``'s ``voice`` (int64 [K, T_j], ragged): the group runs
+        ONE pass over ``P + 1 + max T_j`` positions per request (``ptts_admit_rows_voice``), a shorter request right-padded; slot ``rows[j]``
+        afterwards is what ``admit_row(voice=voices[j])`` makes of it. Without the keyword, or with every entry ``None``: the call made without it."""
         rows = [int(r) for r in rows]
         n = len(rows)
+        if voices is not None:
+            if len(voices) != n:
+                raise ValueError(f"{n} slots, {len(voices)} voices")
+            for v in voices:
+                if v is not None and (v.dim() != 2 or v.shape[0] != self.K):
+                    raise ValueError(f"voice prompt codes {tuple(v.shape)}: expected [{self.K}, frames]")
+            voices = [None if v is None or v.shape[1] == 0 else v.to(self.device, torch.int64).contiguous() for v in voices]
+            if all(v is None for v in voices):
+                voices = None
         max_lengths = [0] * n if max_lengths is None else [int(x) for x in max_lengths]
         if len(max_lengths) != n or (gens is not None and len(gens) != n):
             raise ValueError(f"{n} slots, {len(max_lengths)} max_lengths, {None if gens is None else len(gens)} gens")
@@ -498,8 +510,16 @@ class DecoderEngine:
                 raise ValueError(f"prompt_attention_mask {tuple(pm.shape)} does not match [{n}, {self.P}]")
             keep.append(pm)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
-        N.check(self.lib.ptts_admit_rows(self._h, n, (C.c_int32 * max(n, 1))(*rows), ptr(enc), ptr(em), ptr(pr), ptr(pm), (C.c_int32 * max(n, 1))(*max_lengths),
-                                         int(sample), gp_arr, _stream_ptr(device=self.device)), "ptts_admit_rows")
+        if voices is not None:
+            keep.extend(v for v in voices if v is not None)
+            codes = (C.c_void_p * max(n, 1))(*[None if v is None else v.data_ptr() for v in voices])
+            Ts = (C.c_int32 * max(n, 1))(*[0 if v is None else int(v.shape[1]) for v in voices])
+            N.check(self.lib.ptts_admit_rows_voice(self._h, n, (C.c_int32 * max(n, 1))(*rows), ptr(enc), ptr(em), ptr(pr), ptr(pm), codes, Ts,
+                                                   (C.c_int32 * max(n, 1))(*max_lengths), int(sample), gp_arr, _stream_ptr(device=self.device)),
+                    "ptts_admit_rows_voice")
+        else:
+            N.check(self.lib.ptts_admit_rows(self._h, n, (C.c_int32 * max(n, 1))(*rows), ptr(enc), ptr(em), ptr(pr), ptr(pm),
+                                             (C.c_int32 * max(n, 1))(*max_lengths), int(sample), gp_arr, _stream_ptr(device=self.device)), "ptts_admit_rows")
         if not hasattr(self, "_keep_rows"):
             self._keep_rows = {}
         for r in rows:
