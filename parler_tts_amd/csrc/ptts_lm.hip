@@ -114,8 +114,8 @@ struct ptts_engine {
   int* row_maxlen = nullptr;             // [max_batch] device: max_length of the request in each slot
   SlotGen* slot_gen = nullptr;           // [max_batch] device: sampler record of the request in each slot (ptts_admit_row_gen); own = 0: the session's
   int* slot_T = nullptr;                 // [max_batch] device: voice-prompt frames of the request in each slot (ptts_admit_row_voice); 0: none
-  DevDims* dims_adm = nullptr;           // [max_batch] device: per slot, the DevDims a voice admission's prefill embedding reads (the request's max_length, T, prefix rows);
-                                         // entries B .. B + n - 1 (the spare rows): those of the n requests of a group (ptts_admit_rows_voice, FwdView::row_dims)
+  DevDims* dims_adm = nullptr;           // [max_batch] device: per arena row, the DevDims a voice admission's prefill embedding reads for the request that runs on it
+                                         // (its max_length, T, prefix rows; FwdView::row_dims): the slot itself in place, entries B .. B + n - 1 for a group on the spare rows
   float* h_adm = nullptr;                // [max_prompt][H] residual rows of a row prefill: the step input h[B][H] of the other slots is live between steps
   KvLayer* kv_layers_rows = nullptr;     // [max_batch][layers] operands of the batched cross K/V projection with each slot's arena rows as base
   float* h_adm_rows = nullptr;           // [(max_batch - 1) * max_prompt][H] residual rows of a group prefill (ptts_admit_rows), allocated at its first use
@@ -164,8 +164,7 @@ struct FwdView {
   long long* ids;
   int *cur_len, *unfinished, *has_eos, *first_unf, *enc_mask, *prompt_mask;
   const KvLayer* kv_layers;      // [layers] operands of the batched cross K/V projection
-  const DevDims* embed_dims;     // what the embedding reads its delay pattern from: the engine's, or a voice admission's own (ptts_admit_row_voice)
-  const DevDims* row_dims;       // [B] or null. A group of voice admissions (ptts_admit_rows_voice): every row of the prefill pass under its own request -
+  const DevDims* row_dims;       // [B] or null. A voice admission (one request or a group): every row of the prefill pass under its own request -
                                  // its delay pattern, its T <= v.T columns (the rest of the row is padding), and the position its logits come from
   size_t self_off, cross_off;    // bytes from a layer's self / cross K/V arena to utterance 0 of this view
   size_t scale_off;              // kv_fp8 engines: floats from a layer's K / V scale array (LayerW::ks_self, vs_self) to utterance 0 of this view
@@ -177,7 +176,6 @@ FwdView whole_view(const ptts_engine* e) {
   v.B = e->B; v.N = e->N; v.P = e->P; v.kv_bound = e->kv_bound; v.session = e->session; v.xfold_valid = e->xfold_valid;
   v.h = e->h; v.logits = e->logits; v.ids = e->ids; v.cur_len = e->cur_len; v.unfinished = e->unfinished; v.has_eos = e->has_eos;
   v.first_unf = e->first_unf; v.enc_mask = e->enc_mask; v.prompt_mask = e->prompt_mask; v.kv_layers = e->kv_layers;
-  v.embed_dims = e->dims;
   return v;
 }
 
@@ -288,7 +286,7 @@ void launch_embed(const ptts_engine* e, FwdView v, bool prefill, int Q, hipStrea
   const ptts_config& c = e->cfg;
   EmbedArgs ea = {};
   ea.tables = e->embed; ea.pos_table = c.rope ? nullptr : e->pos_table; ea.prompt = prefill ? e->ffn : nullptr;
-  ea.ids = v.ids; ea.ids_ld = e->ids_ld; ea.cur_len = v.cur_len; ea.dims = v.embed_dims; ea.h = v.h;
+  ea.ids = v.ids; ea.ids_ld = e->ids_ld; ea.cur_len = v.cur_len; ea.dims = e->dims; ea.h = v.h;
   ea.H = c.hidden_size; ea.K = c.num_codebooks; ea.V1 = c.vocab_size + 1; ea.bos = c.bos_token_id; ea.pad = c.pad_token_id;
   ea.prefill = prefill ? 1 : 0;
   if (prefill && v.row_dims)  // every row of the pass under its own request's delay pattern and prefix length
@@ -1336,7 +1334,7 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
 extern "C" int ptts_session_begin(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream) { return session_begin(e, B, N, P, stream, false); }
 extern "C" int ptts_session_begin_kv8(ptts_engine* e, int32_t B, int32_t N, int32_t P, void* stream) { return session_begin(e, B, N, P, stream, true); }
 
-// the checks of one admission (ptts_admit_row_gen, and every entry of ptts_admit_rows); *L_out = the request's max_length
+// the checks of one request of an admission; *L_out = the request's max_length
 static int check_admission(const ptts_engine* e, int row, const float* prompt_dev, int max_length, const ptts_gen_params* gp, int* L_out) {
   PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
   PTTS_CHECK(!e->slot_busy[row], PTTS_E_INVALID, "slot %d still holds a request (ptts_retire_row first)", row);
@@ -1362,64 +1360,6 @@ static int finish_admission(ptts_engine* e, int row, int L, const ptts_gen_param
   if (sample) return launch_tail(e, whole_view(e), st, true, row);  // first token of the request + the embedding of its next column into h[row]
   e->h_ready = false;                                               // manual path: the next forward embeds every slot's last column
   return PTTS_OK;
-}
-
-extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
-                                  const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, const ptts_gen_params* gp, void* stream) {
-  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
-  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_row: no continuous session (ptts_session_begin)");
-  int L = 0;
-  PTTS_TRY(check_admission(e, row, prompt_dev, max_length, gp, &L));
-  const ptts_config& c = e->cfg;
-  PTTS_DEVICE(c.device);
-  hipStream_t st = pick_stream(e, stream);
-  hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
-                     e->row_maxlen, row, 1, c.num_codebooks, c.bos_token_id, 1, L);  // before the forward: its embedding reads the BOS column and the clock
-  PTTS_TRY(stage_inputs(e, row, 1, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
-  PTTS_TRY(forward_dispatch(e, rows_view(e, row, 1, e->h_adm), true, st));
-  return finish_admission(e, row, L, gp, sample != 0, st);
-}
-
-extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
-                              const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream) {
-  return ptts_admit_row_gen(e, row, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_length, sample, nullptr, stream);
-}
-
-// A request that continues a voice prompt of T frames: the slot is admitted with 1 + T given columns. What ptts_set_audio_prefix + ptts_prefill do
-// for a static batch, for ONE slot: the codes go to the slot's rows of e->prefix, the delay pattern of (BOS + prefix, the request's max_length) to
-// its id columns 1..T, and P + 1 + T positions run in one pass through rows_view with T set - the ordinary prefill kernels, chosen by row count.
-// The prefill embedding reads the request's own DevDims (dims_adm: its max_length, T and prefix rows), so it feeds the model what the static
-// prefill of the same request feeds it; the decode steps read the slot's T from slot_T, which stays set until ptts_retire_row.
-extern "C" int ptts_admit_row_voice(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
-                                    const int32_t* prompt_mask_dev, const int64_t* codes_dev, int32_t T, int32_t max_length, int32_t sample,
-                                    const ptts_gen_params* gp, void* stream) {
-  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
-  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_row_voice: no continuous session (ptts_session_begin)");
-  PTTS_CHECK(T >= 0 && (T == 0 || codes_dev), PTTS_E_INVALID, "bad voice prompt (T = %d frames, codes %s)", T, codes_dev ? "given" : "null");
-  if (T == 0) return ptts_admit_row_gen(e, row, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_length, sample, gp, stream);
-  int L = 0;
-  PTTS_TRY(check_admission(e, row, prompt_dev, max_length, gp, &L));
-  const ptts_config& c = e->cfg;
-  const int P = e->P, K = c.num_codebooks;
-  PTTS_CHECK(P + 1 + T <= e->max_prompt, PTTS_E_CAPACITY, "P + 1 + T = %d positions exceed the engine's prefill capacity %d (max_prompt)", P + 1 + T, e->max_prompt);
-  PTTS_CHECK(T + 2 <= L, PTTS_E_INVALID, "voice prompt of %d frames leaves no room below max_length %d", T, L);
-  PTTS_DEVICE(c.device);
-  hipStream_t st = pick_stream(e, stream);
-  long long* pre = e->prefix + (size_t)row * K * c.max_ctx;
-  FwdView v = rows_view(e, row, 1, e->h_adm);
-  v.T = T; v.embed_dims = e->dims_adm + row;
-  hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
-                     e->row_maxlen, row, 1, K, c.bos_token_id, 1, L);
-  PTTS_HIP(hipMemcpy2DAsync(pre, (size_t)c.max_ctx * 8, codes_dev, (size_t)T * 8, (size_t)T * 8, (size_t)K, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(push_prefix_slot_kernel, dim3((K * T + 255) / 256), dim3(256), 0, st, v.ids, e->ids_ld, pre, c.max_ctx, T, K, c.bos_token_id,
-                     c.pad_token_id, L);
-  hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, st, e->slot_T + row, T, (size_t)1);  // before the prefill; read by every step from here on
-  DevDims hd; hd.P = P; hd.N = e->N; hd.max_length = L; hd.T_prefix = T; hd.prefix = pre; hd.prefix_ld = c.max_ctx;
-  hipLaunchKernelGGL(set_dims_kernel, dim3(1), dim3(1), 0, st, e->dims_adm + row, hd);
-  PTTS_TRY(stage_inputs(e, row, 1, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
-  PTTS_TRY(forward_dispatch(e, v, true, st));
-  hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(64), 0, st, v.cur_len, 1, T + 1);  // the slot's clock: BOS + T given columns
-  return finish_admission(e, row, L, gp, sample != 0, st, T);
 }
 
 extern "C" int ptts_debug_slot_voice(ptts_engine* e, int32_t* frames_host, void* stream) {
@@ -1452,147 +1392,170 @@ static int ensure_group_rows(ptts_engine* e) {
   return PTTS_OK;
 }
 
-// A group of n requests in one prefill pass: the static prefill forward of a batch of n on the spare arena rows B .. B + n - 1 (every array of the
-// engine is batch-outermost and sized for max_batch, so rows_view(e, B, n) is an n-utterance engine), then ONE launch that moves each spare row to its
-// slot (admit_move_rows_kernel), then per slot what ptts_admit_row_gen does: reset, record, tail. The tail runs on the slot itself: the draw hash of a
-// slot without a record of its own uses the slot index.
-extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
-                               const int32_t* prompt_mask_dev, const int32_t* max_lengths, int32_t sample, const ptts_gen_params* const* gps,
-                               void* stream) {
+// An admission is a list of n requests - slot, max_length, sampler record or none, voice codes and frames or none - and one choice: where its
+// prefill pass runs. Everything else is data, and the five entry points below only build the list.
+//
+// Where. In place: the pass of ONE request runs on the slot's own arena rows (rows_view(e, row, 1)); it needs no spare row. Or on the spare arena
+// rows B .. B + n - 1: every array of the engine is batch-outermost and sized for max_batch, so rows_view(e, B, n) is an n-utterance engine and the
+// pass is the static prefill forward of a batch of n - the ordinary prefill kernels, chosen by row count - and ONE launch then moves each spare row
+// to its slot (admit_move_rows_kernel). The tail runs on the slot itself either way: the draw hash of a slot without a record of its own uses the
+// slot index.
+//
+// Voice prompts. A request that continues a voice prompt of T_j frames is admitted with 1 + T_j given columns: what ptts_set_audio_prefix +
+// ptts_prefill do for a static batch. The codes go to the slot's rows of e->prefix, one launch in front of the pass (admit_voice_slots_kernel)
+// writes the delay pattern of (BOS + prefix, the request's max_length) to the slot's id columns 1..T_j, its slot_T (which stays set until
+// ptts_retire_row; the decode steps read it) and clock, and the DevDims of the row the request runs on; the pass covers P + 1 + Tmax positions per
+// row, every row under its own request (FwdView::row_dims: delay pattern, prefix length, logits position), so it feeds the model what the static
+// prefill of the same request feeds it. A shorter request is right-padded with PAD columns that causal attention keeps from its own positions, and
+// the move carries P + 1 + T_j self rows of request j to its slot and nothing of the padding.
+struct Admission {
+  const char* call;                    // the entry point, for its refusals
+  int n;
+  const int32_t* rows;                 // [n] destination slots
+  const int32_t* Ls;                   // [n] max_length as given (0: the session's)
+  const ptts_gen_params* const* gps;   // null, or [n]: each null or the request's own sampler record
+  bool takes_voices;                   // the entry point has voice prompts in its signature: Ts is required
+  const int64_t* const* codes;         // null, or [n] device pointers, each null or [K][T_j]
+  const int32_t* Ts;                   // null (no request brings a voice prompt), or [n] frames
+  bool in_place;                       // n == 1 and the pass runs in the slot itself
+  const float* enc; const int32_t* enc_mask; const float* prompt; const int32_t* prompt_mask;  // [n] requests at the session's widths, device
+};
+
+static int admit(ptts_engine* e, const Admission& a, bool sample, void* stream) {
+  // 1. every check of every request, before anything is launched
   PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
-  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_rows: no continuous session (ptts_session_begin)");
-  PTTS_CHECK(n >= 1, PTTS_E_INVALID, "ptts_admit_rows: n = %d requests (at least 1)", n);
-  PTTS_CHECK(enc_dev && rows && max_lengths, PTTS_E_INVALID, "null argument");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "%s: no continuous session (ptts_session_begin)", a.call);
+  PTTS_CHECK(a.n >= 1, PTTS_E_INVALID, "%s: n = %d requests (at least 1)", a.call, a.n);
+  PTTS_CHECK(a.enc && a.rows && a.Ls && (a.Ts || !a.takes_voices), PTTS_E_INVALID, "null argument");
   const ptts_config& c = e->cfg;
-  const int B = e->B, P = e->P, N = e->N, K = c.num_codebooks;
-  std::vector<int> Ls(n);
-  for (int j = 0; j < n; ++j) {
-    PTTS_TRY(check_admission(e, rows[j], prompt_dev, max_lengths[j], gps ? gps[j] : nullptr, &Ls[j]));
-    for (int i = 0; i < j; ++i) PTTS_CHECK(rows[i] != rows[j], PTTS_E_INVALID, "slot %d listed twice", rows[j]);
+  const int n = a.n, B = e->B, P = e->P, N = e->N, K = c.num_codebooks;
+  std::vector<int> Ls(n), Ts(n, 0);
+  int Tmax = 0;
+  for (int j = 0; j < n && a.Ts; ++j) {
+    const bool given = a.codes && a.codes[j];
+    PTTS_CHECK(a.Ts[j] >= 0 && (a.Ts[j] == 0 || given), PTTS_E_INVALID, "request %d: bad voice prompt (T = %d frames, codes %s)", j, a.Ts[j],
+               given ? "given" : "null");
+    Ts[j] = a.Ts[j];
+    Tmax = std::max(Tmax, Ts[j]);
   }
-  PTTS_CHECK(n <= c.max_batch - B, PTTS_E_CAPACITY, "%d requests exceed the %d spare rows behind the session's %d slots (engine max_batch %d)", n,
-             c.max_batch - B, B, c.max_batch);
+  for (int j = 0; j < n; ++j) {
+    PTTS_TRY(check_admission(e, a.rows[j], a.prompt, a.Ls[j], a.gps ? a.gps[j] : nullptr, &Ls[j]));
+    for (int i = 0; i < j; ++i) PTTS_CHECK(a.rows[i] != a.rows[j], PTTS_E_INVALID, "slot %d listed twice", a.rows[j]);
+    PTTS_CHECK(Ts[j] + 2 <= Ls[j], PTTS_E_INVALID, "request %d: voice prompt of %d frames leaves no room below max_length %d", j, Ts[j], Ls[j]);
+  }
+  if (!a.in_place)
+    PTTS_CHECK(n <= c.max_batch - B, PTTS_E_CAPACITY, "%d requests exceed the %d spare rows behind the session's %d slots (engine max_batch %d)", n,
+               c.max_batch - B, B, c.max_batch);
+  if (Tmax > 0)
+    PTTS_CHECK(P + 1 + Tmax <= e->max_prompt, PTTS_E_CAPACITY, "P + 1 + T = %d positions exceed the engine's prefill capacity %d (max_prompt)", P + 1 + Tmax,
+               e->max_prompt);
   PTTS_DEVICE(c.device);
   hipStream_t st = pick_stream(e, stream);
-  PTTS_TRY(ensure_group_rows(e));
-  // the spare rows as ptts_prefill prepares a batch of n: sampler state (the prefill's embedding reads the BOS column and the clock), masks, staging
-  hipLaunchKernelGGL(session_reset_rows_kernel, dim3((n * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
-                     e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
-  PTTS_TRY(stage_inputs(e, B, n, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
-  PTTS_TRY(forward_dispatch(e, rows_view(e, B, n, e->h_adm_rows), true, st));  // n * (P + 1) residual rows; the step graphs do not reference them
-  const int ru = (int)(64 * e->esize / 16), sru = c.kv_fp8 ? 4 : ru;  // 16-byte units of an arena row: engine dtype; self rows (e4m3: 64 bytes)
-  for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
-    const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
-    AdmitMoveArgs a = {};
-    a.layers = e->move_layers; a.logits = e->logits; a.enc_mask = e->enc_mask; a.prompt_mask = e->prompt_mask;
-    a.src0 = B + j0; a.nlayers = c.num_layers; a.nkv = e->sc.nkv; a.nkc = e->sc.nkc;
-    a.self_u = (P + 1) * sru; a.self_cap_u = c.max_ctx * sru; a.cross_u = N * ru; a.cross_cap_u = c.max_enc * ru;
-    a.logit_u = K * c.vocab_size / 4;
-    a.enc_n = enc_mask_dev ? N : c.max_enc; a.enc_ld = c.max_enc;  // what ptts_admit_row writes of each mask row
-    a.prompt_n = (prompt_mask_dev && P > 0) ? P : e->max_prompt; a.prompt_ld = e->max_prompt;
-    for (int j = 0; j < nj; ++j) a.rows[j] = rows[j0 + j];
-    const int units = 2 * (e->sc.nkv * a.self_u + e->sc.nkc * a.cross_u);
-    hipLaunchKernelGGL(admit_move_rows_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, a);
-    if (c.kv_fp8) {  // the rows' scales travel with them
-      AdmitScaleArgs sa = {};
-      sa.layers = e->move_scales; sa.src0 = B + j0; sa.nkv = e->sc.nkv; sa.n = P + 1; sa.cap = c.max_ctx;
-      for (int j = 0; j < nj; ++j) sa.rows[j] = rows[j0 + j];
-      hipLaunchKernelGGL(admit_move_scales_kernel, dim3(1, c.num_layers, nj), dim3(256), 0, st, sa);
+  const int row0 = a.in_place ? a.rows[0] : B;  // first arena row of the pass
+  // 2. sampler state (the prefill's embedding reads the BOS column): the spare rows as ptts_prefill prepares a batch of n, every slot under its own
+  // max_length. The move touches no sampler state, so the slots could always be reset here; but only a pass in place and the voice preparation read
+  // what the reset writes, and n launches in front of the pass are n launch latencies on an idle GPU (a session start in groups of 4 or 8 measured
+  // 87 us longer with them there, 37 us without: profiles/admission_one_body.txt), so a plain group resets its slots behind the move, where the
+  // pass hides them.
+  auto reset_slots = [&] {
+    for (int j = 0; j < n; ++j)
+      hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
+                         e->row_maxlen, a.rows[j], 1, K, c.bos_token_id, 1, Ls[j]);
+  };
+  const bool reset_first = a.in_place || Tmax > 0;
+  if (!a.in_place) {
+    PTTS_TRY(ensure_group_rows(e));
+    hipLaunchKernelGGL(session_reset_rows_kernel, dim3((n * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
+                       e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
+  }
+  if (reset_first) reset_slots();
+  // 3. voice prompts: codes to the slots' prefix rows; id columns, slot_T, clock and the DevDims of the row each request runs on (dims_adm[row0 + j])
+  if (Tmax > 0) {
+    for (int j = 0; j < n; ++j)
+      if (Ts[j] > 0)
+        PTTS_HIP(hipMemcpy2DAsync(e->prefix + (size_t)a.rows[j] * K * c.max_ctx, (size_t)c.max_ctx * 8, a.codes[j], (size_t)Ts[j] * 8, (size_t)Ts[j] * 8,
+                                  (size_t)K, hipMemcpyDeviceToDevice, st));
+    for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
+      const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
+      AdmitVoiceSlotsArgs va = {};
+      va.ids = e->ids; va.prefix = e->prefix; va.slot_T = e->slot_T; va.cur_len = e->cur_len; va.row_dims = e->dims_adm + row0 + j0;
+      va.ids_ld = e->ids_ld; va.prefix_ld = c.max_ctx; va.K = K; va.bos = c.bos_token_id; va.pad = c.pad_token_id; va.P = P; va.N = N;
+      for (int j = 0; j < nj; ++j) { va.rows[j] = a.rows[j0 + j]; va.Ts[j] = Ts[j0 + j]; va.Ls[j] = Ls[j0 + j]; }
+      hipLaunchKernelGGL(admit_voice_slots_kernel, dim3((K * Tmax + 255) / 256, nj), dim3(256), 0, st, va);
     }
   }
-  PTTS_TRY(launch_status("admit_move_rows"));
-  for (int j = 0; j < n; ++j) {
-    hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
-                       e->row_maxlen, rows[j], 1, K, c.bos_token_id, 1, Ls[j]);
-    PTTS_TRY(finish_admission(e, rows[j], Ls[j], gps ? gps[j] : nullptr, sample != 0, st));
+  // 4. the pass: n * (P + 1 + Tmax) residual rows (in place: h_adm; a group: h_adm_rows, at most (max_batch - 1) * max_prompt); the step graphs
+  // reference neither
+  PTTS_TRY(stage_inputs(e, row0, n, a.enc, a.enc_mask, a.prompt, a.prompt_mask, st));
+  FwdView v = rows_view(e, row0, n, a.in_place ? e->h_adm : e->h_adm_rows);
+  v.T = Tmax;
+  if (Tmax > 0) v.row_dims = e->dims_adm + row0;
+  PTTS_TRY(forward_dispatch(e, v, true, st));
+  // 5. spare rows to their slots
+  if (!a.in_place) {
+    const int ru = (int)(64 * e->esize / 16), sru = c.kv_fp8 ? 4 : ru;  // 16-byte units of an arena row: engine dtype; self rows (e4m3: 64 bytes)
+    for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
+      const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
+      AdmitMoveArgs m = {};
+      m.layers = e->move_layers; m.logits = e->logits; m.enc_mask = e->enc_mask; m.prompt_mask = e->prompt_mask;
+      m.src0 = B + j0; m.nlayers = c.num_layers; m.nkv = e->sc.nkv; m.nkc = e->sc.nkc;
+      m.row_u = sru; m.self_cap_u = c.max_ctx * sru; m.cross_u = N * ru; m.cross_cap_u = c.max_enc * ru;
+      m.logit_u = K * c.vocab_size / 4;
+      m.enc_n = a.enc_mask ? N : c.max_enc; m.enc_ld = c.max_enc;  // what stage_inputs wrote of each mask row
+      m.prompt_n = (a.prompt_mask && P > 0) ? P : e->max_prompt; m.prompt_ld = e->max_prompt;
+      for (int j = 0; j < nj; ++j) { m.rows[j] = a.rows[j0 + j]; m.self_rows[j] = P + 1 + Ts[j0 + j]; }
+      const int units = 2 * (e->sc.nkv * (P + 1 + Tmax) * sru + e->sc.nkc * m.cross_u);  // of the longest request
+      hipLaunchKernelGGL(admit_move_rows_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, m);
+      if (c.kv_fp8) {  // the rows' scales travel with them
+        AdmitScaleArgs sa = {};
+        sa.layers = e->move_scales; sa.src0 = B + j0; sa.nkv = e->sc.nkv; sa.cap = c.max_ctx;
+        for (int j = 0; j < nj; ++j) { sa.rows[j] = a.rows[j0 + j]; sa.ns[j] = P + 1 + Ts[j0 + j]; }
+        hipLaunchKernelGGL(admit_move_scales_kernel, dim3(1, c.num_layers, nj), dim3(256), 0, st, sa);
+      }
+    }
+    PTTS_TRY(launch_status("admit_move_rows"));
   }
+  if (!reset_first) reset_slots();
+  // 6. per slot: bookkeeping, record, tail
+  for (int j = 0; j < n; ++j) PTTS_TRY(finish_admission(e, a.rows[j], Ls[j], a.gps ? a.gps[j] : nullptr, sample, st, Ts[j]));
   return PTTS_OK;
 }
 
-// A group of n requests that continue voice prompts of Ts[j] frames, in one prefill pass: ptts_admit_rows' pass on the spare rows over
-// P + 1 + Tmax positions per row, every row under its own request (FwdView::row_dims: delay pattern, prefix length, logits position), a shorter
-// request right-padded with PAD columns that causal attention keeps from its own positions. In front of the pass one launch does for the n slots
-// what ptts_admit_row_voice does for one (admit_voice_slots_kernel); behind it the ragged move carries P + 1 + Ts[j] self rows of request j to its
-// slot and nothing of the padding. n == 1 and "no request brings a prompt" are the calls that exist for them.
+extern "C" int ptts_admit_row_gen(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                                  const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, const ptts_gen_params* gp, void* stream) {
+  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
+  return admit(e, Admission{"ptts_admit_row", 1, &row, &max_length, gp ? &gp : nullptr, false, nullptr, nullptr, true, enc_dev, enc_mask_dev, prompt_dev,
+                            prompt_mask_dev}, sample != 0, stream);
+}
+
+extern "C" int ptts_admit_row(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                              const int32_t* prompt_mask_dev, int32_t max_length, int32_t sample, void* stream) {
+  return ptts_admit_row_gen(e, row, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_length, sample, nullptr, stream);
+}
+
+extern "C" int ptts_admit_row_voice(ptts_engine* e, int32_t row, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                                    const int32_t* prompt_mask_dev, const int64_t* codes_dev, int32_t T, int32_t max_length, int32_t sample,
+                                    const ptts_gen_params* gp, void* stream) {
+  PTTS_CHECK(e && enc_dev, PTTS_E_INVALID, "null argument");
+  return admit(e, Admission{"ptts_admit_row_voice", 1, &row, &max_length, gp ? &gp : nullptr, true, &codes_dev, &T, true, enc_dev, enc_mask_dev,
+                            prompt_dev, prompt_mask_dev}, sample != 0, stream);
+}
+
+// (also n = 1 runs on a spare row: an engine without one keeps refusing the call)
+extern "C" int ptts_admit_rows(ptts_engine* e, int32_t n, const int32_t* rows, const float* enc_dev, const int32_t* enc_mask_dev, const float* prompt_dev,
+                               const int32_t* prompt_mask_dev, const int32_t* max_lengths, int32_t sample, const ptts_gen_params* const* gps,
+                               void* stream) {
+  return admit(e, Admission{"ptts_admit_rows", n, rows, max_lengths, gps, false, nullptr, nullptr, false, enc_dev, enc_mask_dev, prompt_dev,
+                            prompt_mask_dev}, sample != 0, stream);
+}
+
+// (one request that brings a voice prompt runs in place, as ptts_admit_row_voice; a list in which none does is ptts_admit_rows' call)
 extern "C" int ptts_admit_rows_voice(ptts_engine* e, int32_t n, const int32_t* rows, const float* enc_dev, const int32_t* enc_mask_dev,
                                      const float* prompt_dev, const int32_t* prompt_mask_dev, const int64_t* const* codes_dev, const int32_t* Ts,
                                      const int32_t* max_lengths, int32_t sample, const ptts_gen_params* const* gps, void* stream) {
-  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
-  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_admit_rows_voice: no continuous session (ptts_session_begin)");
-  PTTS_CHECK(n >= 1, PTTS_E_INVALID, "ptts_admit_rows_voice: n = %d requests (at least 1)", n);
-  PTTS_CHECK(enc_dev && rows && max_lengths && Ts, PTTS_E_INVALID, "null argument");
-  int Tmax = 0;
-  for (int j = 0; j < n; ++j) {
-    PTTS_CHECK(Ts[j] >= 0 && (Ts[j] == 0 || (codes_dev && codes_dev[j])), PTTS_E_INVALID, "request %d: bad voice prompt (T = %d frames, codes %s)", j, Ts[j],
-               codes_dev && codes_dev[j] ? "given" : "null");
-    Tmax = std::max(Tmax, (int)Ts[j]);
-  }
-  if (Tmax == 0) return ptts_admit_rows(e, n, rows, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, max_lengths, sample, gps, stream);
-  if (n == 1)
-    return ptts_admit_row_voice(e, rows[0], enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, codes_dev[0], Ts[0], max_lengths[0], sample,
-                                gps ? gps[0] : nullptr, stream);
-  const ptts_config& c = e->cfg;
-  const int B = e->B, P = e->P, N = e->N, K = c.num_codebooks;
-  std::vector<int> Ls(n);
-  for (int j = 0; j < n; ++j) {
-    PTTS_TRY(check_admission(e, rows[j], prompt_dev, max_lengths[j], gps ? gps[j] : nullptr, &Ls[j]));
-    for (int i = 0; i < j; ++i) PTTS_CHECK(rows[i] != rows[j], PTTS_E_INVALID, "slot %d listed twice", rows[j]);
-    PTTS_CHECK(Ts[j] + 2 <= Ls[j], PTTS_E_INVALID, "request %d: voice prompt of %d frames leaves no room below max_length %d", j, Ts[j], Ls[j]);
-  }
-  PTTS_CHECK(n <= c.max_batch - B, PTTS_E_CAPACITY, "%d requests exceed the %d spare rows behind the session's %d slots (engine max_batch %d)", n,
-             c.max_batch - B, B, c.max_batch);
-  PTTS_CHECK(P + 1 + Tmax <= e->max_prompt, PTTS_E_CAPACITY, "P + 1 + T = %d positions exceed the engine's prefill capacity %d (max_prompt)", P + 1 + Tmax,
-             e->max_prompt);
-  PTTS_DEVICE(c.device);
-  hipStream_t st = pick_stream(e, stream);
-  PTTS_TRY(ensure_group_rows(e));
-  // the spare rows as ptts_prefill prepares a batch of n, and every slot as ptts_admit_row_voice prepares it: reset, codes to its prefix rows
-  hipLaunchKernelGGL(session_reset_rows_kernel, dim3((n * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
-                     e->first_unf, e->row_maxlen, B, n, K, c.bos_token_id, 1, e->session_max_length);
-  for (int j = 0; j < n; ++j) {
-    hipLaunchKernelGGL(session_reset_rows_kernel, dim3(1), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos, e->first_unf,
-                       e->row_maxlen, rows[j], 1, K, c.bos_token_id, 1, Ls[j]);
-    if (Ts[j] > 0)
-      PTTS_HIP(hipMemcpy2DAsync(e->prefix + (size_t)rows[j] * K * c.max_ctx, (size_t)c.max_ctx * 8, codes_dev[j], (size_t)Ts[j] * 8, (size_t)Ts[j] * 8,
-                                (size_t)K, hipMemcpyDeviceToDevice, st));
-  }
-  for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {  // id columns, slot_T, clock and the spare row's DevDims (dims_adm[B + j]: a spare row is nobody's slot)
-    const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
-    AdmitVoiceSlotsArgs a = {};
-    a.ids = e->ids; a.prefix = e->prefix; a.slot_T = e->slot_T; a.cur_len = e->cur_len; a.row_dims = e->dims_adm + B + j0;
-    a.ids_ld = e->ids_ld; a.prefix_ld = c.max_ctx; a.K = K; a.bos = c.bos_token_id; a.pad = c.pad_token_id; a.P = P; a.N = N;
-    for (int j = 0; j < nj; ++j) { a.rows[j] = rows[j0 + j]; a.Ts[j] = Ts[j0 + j]; a.Ls[j] = Ls[j0 + j]; }
-    hipLaunchKernelGGL(admit_voice_slots_kernel, dim3((K * Tmax + 255) / 256, nj), dim3(256), 0, st, a);
-  }
-  PTTS_TRY(stage_inputs(e, B, n, enc_dev, enc_mask_dev, prompt_dev, prompt_mask_dev, st));
-  FwdView v = rows_view(e, B, n, e->h_adm_rows);  // n * (P + 1 + Tmax) <= (max_batch - 1) * max_prompt residual rows
-  v.T = Tmax; v.row_dims = e->dims_adm + B;
-  PTTS_TRY(forward_dispatch(e, v, true, st));
-  const int ru = (int)(64 * e->esize / 16), sru = c.kv_fp8 ? 4 : ru;  // 16-byte units of an arena row: engine dtype; self rows (e4m3: 64 bytes)
-  for (int j0 = 0; j0 < n; j0 += ADMIT_ROWS_MAX) {
-    const int nj = std::min(n - j0, ADMIT_ROWS_MAX);
-    AdmitMoveRaggedArgs ra = {};
-    AdmitMoveArgs& a = ra.m;
-    a.layers = e->move_layers; a.logits = e->logits; a.enc_mask = e->enc_mask; a.prompt_mask = e->prompt_mask;
-    a.src0 = B + j0; a.nlayers = c.num_layers; a.nkv = e->sc.nkv; a.nkc = e->sc.nkc;
-    a.self_u = 0; a.self_cap_u = c.max_ctx * sru; a.cross_u = N * ru; a.cross_cap_u = c.max_enc * ru;
-    a.logit_u = K * c.vocab_size / 4;
-    a.enc_n = enc_mask_dev ? N : c.max_enc; a.enc_ld = c.max_enc;
-    a.prompt_n = (prompt_mask_dev && P > 0) ? P : e->max_prompt; a.prompt_ld = e->max_prompt;
-    ra.row_u = sru;
-    for (int j = 0; j < nj; ++j) { a.rows[j] = rows[j0 + j]; ra.self_rows[j] = P + 1 + Ts[j0 + j]; }
-    const int units = 2 * (e->sc.nkv * (P + 1 + Tmax) * sru + e->sc.nkc * a.cross_u);  // of the longest request
-    hipLaunchKernelGGL(admit_move_rows_ragged_kernel, dim3(std::max(1, std::min(64, (units + 1023) / 1024)), c.num_layers + 1, nj), dim3(256), 0, st, ra);
-    if (c.kv_fp8) {  // the rows' scales travel with them
-      AdmitScaleRaggedArgs sa = {};
-      sa.s.layers = e->move_scales; sa.s.src0 = B + j0; sa.s.nkv = e->sc.nkv; sa.s.n = 0; sa.s.cap = c.max_ctx;
-      for (int j = 0; j < nj; ++j) { sa.s.rows[j] = rows[j0 + j]; sa.ns[j] = P + 1 + Ts[j0 + j]; }
-      hipLaunchKernelGGL(admit_move_scales_ragged_kernel, dim3(1, c.num_layers, nj), dim3(256), 0, st, sa);
-    }
-  }
-  PTTS_TRY(launch_status("admit_move_rows_ragged"));
-  for (int j = 0; j < n; ++j) PTTS_TRY(finish_admission(e, rows[j], Ls[j], gps ? gps[j] : nullptr, sample != 0, st, Ts[j]));
-  return PTTS_OK;
+  const bool in_place = n == 1 && Ts && Ts[0] > 0;
+  return admit(e, Admission{"ptts_admit_rows_voice", n, rows, max_lengths, gps, true, codes_dev, Ts, in_place, enc_dev, enc_mask_dev, prompt_dev,
+                            prompt_mask_dev}, sample != 0, stream);
 }
 
 extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {

@@ -2482,7 +2482,7 @@ __device__ __forceinline__ long long delayed_token(const long long* ids, int ld,
 
 // value of column j (1 <= j <= T) of a request that continues a voice prompt: what build_delay_pattern_mask holds there for (BOS + prefix, the
 // request's own max_length): BOS for j <= k, PAD for j - k >= max_length - K + 1, prefix[j - k - 1] otherwise; the prefix un-shifted below
-// 2K - 1, where there is no pattern. prefix: the request's first row. What push_prefix_slot_kernel writes and what delayed_token then reads back
+// 2K - 1, where there is no pattern. prefix: the request's first row. What admit_voice_slots_kernel writes and what delayed_token then reads back
 __device__ __forceinline__ long long voice_column_token(const long long* prefix, int prefix_ld, int k, int j, int K, int bos, int pad,
                                                         int max_length) {
   if (max_length < 2 * K - 1) return prefix[(size_t)k * prefix_ld + (j - 1)];
@@ -2550,8 +2550,8 @@ __global__ void embed_kernel(typename EmbedK<SESSION>::T p) {
   }
 }
 
-// Prefill embedding of a group of voice admissions (ptts_admit_rows_voice): every row of the pass under its OWN request - row_dims[b] holds its
-// max_length, its T_prefix and its prefix rows (where the request's codes live: the destination slot's rows of the engine's prefix buffer, which
+// Prefill embedding of a voice admission (one request in place in its slot, or a group on the spare rows): every row of the pass under its OWN
+// request - row_dims[b] holds its max_length, its T_prefix and its prefix rows (where the request's codes live: the destination slot's rows of the engine's prefix buffer, which
 // the decode steps read too). grid (Q, n) with Q = P + 1 + Tmax. The token of a given column comes from the prefix alone (voice_column_token;
 // column 0: BOS), never from the id columns of the row the pass runs on, which nobody wrote. A column behind the row's own T_prefix (a shorter
 // request, right-padded to Tmax) embeds PAD, an in-range row of every table: causal attention keeps it from the positions in front of it, and
@@ -2979,18 +2979,6 @@ static __global__ void push_prefix_all_kernel(long long* ids, int ids_ld, const 
   const DevDims dd = *dims;
   ids[(size_t)row * ids_ld + j] = j <= k ? (long long)bos : dd.prefix[(size_t)row * dd.prefix_ld + (j - k - 1)];
 }
-// ptts_admit_row_voice: columns 1..T of ONE slot's raw ids = what build_delay_pattern_mask holds there for (BOS + prefix, the request's own
-// max_length): BOS for j <= k, PAD for j - k >= max_length - K + 1, prefix[j - k - 1] otherwise; the prefix un-shifted below 2K - 1, where there
-// is no pattern. ids / prefix: the slot's first row. One thread per cell; T >= 1
-static __global__ void push_prefix_slot_kernel(long long* ids, int ids_ld, const long long* prefix, int prefix_ld, int T, int K, int bos, int pad,
-                                               int max_length) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= K * T) return;
-  const int k = i / T, j = 1 + i % T;
-  ids[(size_t)k * ids_ld + j] = voice_column_token(prefix, prefix_ld, k, j, K, bos, pad, max_length);
-}
-// the DevDims the prefill embedding of such an admission reads (the request's max_length, T and prefix rows; by value, as set_params_kernel's)
-static __global__ void set_dims_kernel(DevDims* dd, DevDims d) { *dd = d; }
 static __global__ void set_len_kernel(int* cur_len, int B, int v) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) cur_len[b] = v;
@@ -3015,11 +3003,14 @@ static __global__ void fill_int_kernel(int* p, int v, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// ptts_admit_rows: a group of n requests is prefilled as a static batch of n on the spare arena rows behind the session's slots (rows
+// Group admission: n requests are prefilled as a static batch of n on the spare arena rows behind the session's slots (rows
 // src0 .. src0 + n - 1 of every batch-outermost array); this kernel then moves request j from spare row src0 + j to its slot rows[j], in one
-// launch: per layer and K/V head the self K/V rows [0, P + 1) and the cross K/V rows [0, N), and (blockIdx.y == nlayers) the K * V step-0
-// logits and both mask rows. Arena rows are 128 or 256 bytes and a slot's logits a multiple of 64, so everything but the masks moves in
-// 16-byte units. The slot list travels by value as a kernel argument (no staging buffer, no copy to wait on). grid (pieces, layers + 1, n).
+// launch: per layer and K/V head the self K/V rows [0, self_rows[j]) and the cross K/V rows [0, N), and (blockIdx.y == nlayers) the K * V step-0
+// logits and both mask rows. Request j wrote self_rows[j] = P + 1 + T_j positions of its own (T_j: its voice-prompt frames, 0 without one); the
+// pass ran P + 1 + Tmax on every spare row, and what lies behind a shorter request's own positions is padding that must not reach its slot: the
+// slot's arena rows at and beyond self_rows[j] stay what they were. Arena rows are 64 (e4m3), 128 or 256 bytes and a slot's logits a multiple
+// of 64, so everything but the masks moves in 16-byte units. The slot list and the lengths travel by value as kernel arguments (no staging
+// buffer, no copy to wait on). grid (pieces, layers + 1, n).
 constexpr int ADMIT_ROWS_MAX = 64;  // slots per launch; a longer list takes several
 struct AdmitMoveLayer { void *k_self, *v_self, *k_cross, *v_cross; };  // one layer's arenas (slot 0)
 struct AdmitMoveArgs {
@@ -3028,14 +3019,14 @@ struct AdmitMoveArgs {
   int *enc_mask, *prompt_mask;
   int src0;                    // first spare row of this launch
   int nlayers, nkv, nkc;       // self / cross K/V heads
-  int self_u, self_cap_u;      // 16-byte units per (slot, head): the P + 1 rows to move, the head's capacity (max_ctx rows)
+  int row_u, self_cap_u;       // 16-byte units of one self row (e4m3: 4), of a head's capacity (max_ctx rows)
   int cross_u, cross_cap_u;    // the N rows to move, max_enc rows
   int logit_u;                 // K * V * 4 / 16
   int enc_n, enc_ld, prompt_n, prompt_ld;  // mask positions to move and the row strides
   int rows[ADMIT_ROWS_MAX];
+  int self_rows[ADMIT_ROWS_MAX];  // self K/V positions to move per request
 };
-// (self_u: the units of THIS request's self rows - a.self_u, or the ragged kernel's own count)
-__device__ __forceinline__ void admit_move_body(const AdmitMoveArgs& a, int self_u) {
+static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveArgs a) {
   const size_t src = (size_t)(a.src0 + (int)blockIdx.z), dst = (size_t)a.rows[blockIdx.z];
   const int tid = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256, l = blockIdx.y;
   if (l == a.nlayers) {
@@ -3046,6 +3037,7 @@ __device__ __forceinline__ void admit_move_body(const AdmitMoveArgs& a, int self
     return;
   }
   const AdmitMoveLayer L = a.layers[l];
+  const int self_u = a.self_rows[blockIdx.z] * a.row_u;  // the units of THIS request's self rows
   const int su = a.nkv * self_u, cu = a.nkc * a.cross_u;
   for (int u = tid; u < 2 * (su + cu); u += stride) {
     uint4* base;
@@ -3063,52 +3055,33 @@ __device__ __forceinline__ void admit_move_body(const AdmitMoveArgs& a, int self
     base[(dst * heads + head) * cap + off] = base[(src * heads + head) * cap + off];
   }
 }
-static __global__ void __launch_bounds__(256) admit_move_rows_kernel(AdmitMoveArgs a) { admit_move_body(a, a.self_u); }
 
-// ptts_admit_rows_voice: the ragged form. Request j of the launch wrote self_rows[j] = P + 1 + T_j positions of its own; the pass ran
-// P + 1 + Tmax on every spare row, and what lies behind a shorter request's own positions is padding that must not reach its slot: the
-// slot's arena rows at and beyond self_rows[j] stay what they were. The lengths travel by value beside the slot list. Cross rows, logits
-// and masks move as in admit_move_rows_kernel (m.self_u is not read). Same grid.
-struct AdmitMoveRaggedArgs {
-  AdmitMoveArgs m;
-  int row_u;                       // 16-byte units of one self row (e4m3: 4)
-  int self_rows[ADMIT_ROWS_MAX];   // self K/V positions to move per request
-};
-static __global__ void __launch_bounds__(256) admit_move_rows_ragged_kernel(AdmitMoveRaggedArgs a) { admit_move_body(a.m, a.self_rows[blockIdx.z] * a.row_u); }
-
-// kv_fp8 engines, beside admit_move_rows_kernel (which moves the 64-byte e4m3 self rows as 4 units each): the P + 1 K scales and V scales per
-// (layer, K/V head) from spare row src0 + j to slot rows[j]. P + 1 floats are in general no multiple of 16 bytes: one float per thread.
-// grid (1, layers, n). AdmitScaleArgs::layers: [nlayers] device memory, written once.
+// kv_fp8 engines, beside admit_move_rows_kernel (which moves the 64-byte e4m3 self rows as 4 units each): the ns[j] = P + 1 + T_j K scales and
+// V scales per (layer, K/V head) of request j from spare row src0 + j to slot rows[j]. That many floats are in general no multiple of 16 bytes:
+// one float per thread. grid (1, layers, n). AdmitScaleArgs::layers: [nlayers] device memory, written once.
 struct AdmitScaleLayer { float *ks_self, *vs_self; };  // one layer's scale arrays (slot 0)
 struct AdmitScaleArgs {
   const AdmitScaleLayer* layers;
-  int src0, nkv, n, cap;  // first spare row; K/V heads; scales to move per head (P + 1); scales per head (max_ctx)
+  int src0, nkv, cap;  // first spare row; K/V heads; scales per head (max_ctx)
   int rows[ADMIT_ROWS_MAX];
+  int ns[ADMIT_ROWS_MAX];  // scales to move per head and request
 };
-__device__ __forceinline__ void admit_move_scales_body(const AdmitScaleArgs& a, int n) {  // n: a.n, or the ragged kernel's own count
+static __global__ void __launch_bounds__(256) admit_move_scales_kernel(AdmitScaleArgs a) {
   const size_t src = (size_t)(a.src0 + (int)blockIdx.z), dst = (size_t)a.rows[blockIdx.z];
   const AdmitScaleLayer L = a.layers[blockIdx.y];
-  const int per = a.nkv * n;
+  const int n = a.ns[blockIdx.z], per = a.nkv * n;
   for (int u = threadIdx.x; u < 2 * per; u += 256) {
     const int v = u >= per, r = u - v * per, head = r / n, off = r - head * n;
     float* base = v ? L.vs_self : L.ks_self;
     base[(dst * a.nkv + head) * a.cap + off] = base[(src * a.nkv + head) * a.cap + off];
   }
 }
-static __global__ void __launch_bounds__(256) admit_move_scales_kernel(AdmitScaleArgs a) { admit_move_scales_body(a, a.n); }
-// the ragged form (ptts_admit_rows_voice): ns[j] = P + 1 + T_j scales per head of request j, by value (s.n is not read). Same grid.
-struct AdmitScaleRaggedArgs {
-  AdmitScaleArgs s;
-  int ns[ADMIT_ROWS_MAX];
-};
-static __global__ void __launch_bounds__(256) admit_move_scales_ragged_kernel(AdmitScaleRaggedArgs a) { admit_move_scales_body(a.s, a.ns[blockIdx.z]); }
 
-// ptts_admit_rows_voice, in front of the pass: for request j of the launch, what ptts_admit_row_voice does for one slot with
-// push_prefix_slot_kernel + fill_int_kernel(slot_T) + set_dims_kernel, in one launch for all. Id columns 1..Ts[j] of slot rows[j] (the delay
-// pattern of the request's own max_length Ls[j] over its codes, which already lie in the slot's prefix rows), slot_T[rows[j]], the slot's clock at
-// Ts[j] + 1 (the slot was reset in front of this launch; the pass itself reads no clock), and the DevDims the pass's embedding reads for the
-// spare row the request runs on (row_dims[j]; its prefix pointer: the SLOT's prefix rows). Everything by value. grid (cells of Tmax, n);
-// a request with Ts[j] == 0 gets slot_T 0, clock 1 and no column.
+// A voice admission, in front of its prefill pass: for request j of the launch, id columns 1..Ts[j] of slot rows[j] (the delay pattern of the
+// request's own max_length Ls[j] over its codes, which already lie in the slot's prefix rows), slot_T[rows[j]] (read by every decode step from
+// here on), the slot's clock at Ts[j] + 1 (the slot was reset in front of this launch; the pass itself reads no clock), and the DevDims the
+// pass's embedding reads for the row the request runs on (row_dims[j]: a spare row, or the slot itself when the pass runs in place; its prefix
+// pointer: the SLOT's prefix rows). Everything by value. grid (cells of Tmax, n); a request with Ts[j] == 0 gets slot_T 0, clock 1 and no column.
 struct AdmitVoiceSlotsArgs {
   long long* ids;            // the engine's id buffer (slot 0)
   const long long* prefix;   // the engine's prefix buffer (slot 0), [slots * K][prefix_ld]

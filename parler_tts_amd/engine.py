@@ -404,41 +404,11 @@ class DecoderEngine:
         ``voice``: un-delayed audio codes int64 [K, T] the request continues (``ptts_admit_row_voice``): the slot starts with 1 + T given
         columns and ``max_length`` counts them, as ``set_audio_prefix`` + ``prefill`` do for a static batch. ``None`` or T == 0: the call made
         without it."""
+        voice = None if voice is None else self._voice_codes([voice])[0]
+        gp = None if gen is None else self._gen_params(gen)
+        enc, em, pr, pm = self._session_inputs(None, enc, enc_mask, prompt, prompt_mask)
+        ptr = self._ptr
         if voice is not None:
-            if voice.dim() != 2 or voice.shape[0] != self.K:
-                raise ValueError(f"voice prompt codes {tuple(voice.shape)}: expected [{self.K}, frames]")
-            voice = voice.to(self.device, torch.int64).contiguous() if voice.shape[1] > 0 else None
-        gp = None
-        if gen is not None:
-            unknown = set(gen) - {"min_new_tokens", "do_sample", "temperature", "top_k", "top_p", "use_eos_gate", "seed"}
-            if unknown:
-                raise ValueError(f"unknown per-request generation parameters {sorted(unknown)}")
-            gp = N.PttsGenParams(0, int(gen.get("min_new_tokens", 0)), int(bool(gen.get("do_sample", False))), float(gen.get("temperature", 1.0)),
-                                 int(gen.get("top_k", 0) or 0), float(gen.get("top_p", 1.0)), int(bool(gen.get("use_eos_gate", True))),
-                                 int(gen.get("seed", 0)) & (2 ** 64 - 1))  # max_length 0: the `max_length` argument rules the slot's end
-        enc = enc.to(self.device, torch.float32).contiguous()
-        if enc.dim() != 2 or tuple(enc.shape) != (self.session_N, self.H):
-            raise ValueError(f"encoder states {tuple(enc.shape)} do not match the session's [{self.session_N}, {self.H}]")
-        keep = [enc]
-        pr = em = pm = None
-        if self.P > 0:
-            if prompt is None or tuple(prompt.shape) != (self.P, self.H):
-                raise ValueError(f"prompt embeddings {None if prompt is None else tuple(prompt.shape)} do not match the session's [{self.P}, {self.H}]")
-            pr = prompt.to(self.device, torch.float32).contiguous()
-            keep.append(pr)
-        if enc_mask is not None:
-            em = enc_mask.to(self.device, torch.int32).reshape(-1).contiguous()
-            if em.numel() != self.session_N:
-                raise ValueError(f"attention_mask of {em.numel()} positions does not match the session's {self.session_N}")
-            keep.append(em)
-        if prompt_mask is not None and self.P > 0:
-            pm = prompt_mask.to(self.device, torch.int32).reshape(-1).contiguous()
-            if pm.numel() != self.P:
-                raise ValueError(f"prompt_attention_mask of {pm.numel()} positions does not match the session's {self.P}")
-            keep.append(pm)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
-        if voice is not None:
-            keep.append(voice)
             N.check(self.lib.ptts_admit_row_voice(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), ptr(voice), int(voice.shape[1]), int(max_length),
                                                   int(sample), C.byref(gp) if gp is not None else None, _stream_ptr(device=self.device)),
                     "ptts_admit_row_voice")
@@ -448,9 +418,64 @@ class DecoderEngine:
         else:
             N.check(self.lib.ptts_admit_row_gen(self._h, int(row), ptr(enc), ptr(em), ptr(pr), ptr(pm), int(max_length), int(sample), C.byref(gp),
                                                 _stream_ptr(device=self.device)), "ptts_admit_row_gen")
+        self._keep_admitted([int(row)], [enc, em, pr, pm, voice])
+
+    @staticmethod
+    def _ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+
+    @staticmethod
+    def _gen_params(gen: dict):
+        """``admit_row``'s ``gen`` as a ``PttsGenParams``; its max_length 0: the admission's ``max_length`` argument rules the slot's end."""
+        unknown = set(gen) - {"min_new_tokens", "do_sample", "temperature", "top_k", "top_p", "use_eos_gate", "seed"}
+        if unknown:
+            raise ValueError(f"unknown per-request generation parameters {sorted(unknown)}")
+        return N.PttsGenParams(0, int(gen.get("min_new_tokens", 0)), int(bool(gen.get("do_sample", False))), float(gen.get("temperature", 1.0)),
+                               int(gen.get("top_k", 0) or 0), float(gen.get("top_p", 1.0)), int(bool(gen.get("use_eos_gate", True))),
+                               int(gen.get("seed", 0)) & (2 ** 64 - 1))
+
+    def _voice_codes(self, voices):
+        """Per request ``None`` or int64 [K, T] codes -> the same list on the device; a prompt of no frames is ``None``."""
+        for v in voices:
+            if v is not None and (v.dim() != 2 or v.shape[0] != self.K):
+                raise ValueError(f"voice prompt codes {tuple(v.shape)}: expected [{self.K}, frames]")
+        return [None if v is None or v.shape[1] == 0 else v.to(self.device, torch.int64).contiguous() for v in voices]
+
+    def _session_inputs(self, n, enc, enc_mask, prompt, prompt_mask):
+        """The inputs of ``n`` requests, [n, ...] at the session's widths (``n`` None: of one request, without the leading dimension), checked
+        and on the device: ``(enc, enc_mask, prompt, prompt_mask)``, ``None`` where the admission passes a null pointer."""
+        one = n is None
+        shape = (lambda *w: w) if one else (lambda *w: (n,) + w)
+        enc = enc.to(self.device, torch.float32).contiguous()
+        if tuple(enc.shape) != shape(self.session_N, self.H):
+            raise ValueError(f"encoder states {tuple(enc.shape)} do not match " + (f"the session's [{self.session_N}, {self.H}]" if one else
+                             f"[{n}, {self.session_N}, {self.H}] ({n} slots at the session's widths)"))
+        pr = em = pm = None
+        if self.P > 0:
+            if prompt is None or tuple(prompt.shape) != shape(self.P, self.H):
+                raise ValueError(f"prompt embeddings {None if prompt is None else tuple(prompt.shape)} do not match " +
+                                 (f"the session's [{self.P}, {self.H}]" if one else f"[{n}, {self.P}, {self.H}]"))
+            pr = prompt.to(self.device, torch.float32).contiguous()
+        if enc_mask is not None:
+            em = enc_mask.to(self.device, torch.int32).contiguous()
+            em = em.reshape(-1) if one else em
+            if tuple(em.shape) != shape(self.session_N):
+                raise ValueError(f"attention_mask of {em.numel()} positions does not match the session's {self.session_N}" if one else
+                                 f"attention_mask {tuple(em.shape)} does not match [{n}, {self.session_N}]")
+        if prompt_mask is not None and self.P > 0:
+            pm = prompt_mask.to(self.device, torch.int32).contiguous()
+            pm = pm.reshape(-1) if one else pm
+            if tuple(pm.shape) != shape(self.P):
+                raise ValueError(f"prompt_attention_mask of {pm.numel()} positions does not match the session's {self.P}" if one else
+                                 f"prompt_attention_mask {tuple(pm.shape)} does not match [{n}, {self.P}]")
+        return enc, em, pr, pm
+
+    def _keep_admitted(self, rows, tensors):
         if not hasattr(self, "_keep_rows"):
             self._keep_rows = {}
-        self._keep_rows[int(row)] = keep  # consumed asynchronously by the enqueued kernels
+        keep = [t for t in tensors if t is not None]
+        for r in rows:
+            self._keep_rows[r] = keep  # consumed asynchronously by the enqueued kernels
 
     def admit_rows(self, rows, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
                    prompt_mask: Optional[torch.Tensor], max_lengths=None, sample: bool = True, gens=None, voices=None):
@@ -467,63 +492,28 @@ class DecoderEngine:
         if voices is not None:
             if len(voices) != n:
                 raise ValueError(f"{n} slots, {len(voices)} voices")
-            for v in voices:
-                if v is not None and (v.dim() != 2 or v.shape[0] != self.K):
-                    raise ValueError(f"voice prompt codes {tuple(v.shape)}: expected [{self.K}, frames]")
-            voices = [None if v is None or v.shape[1] == 0 else v.to(self.device, torch.int64).contiguous() for v in voices]
+            voices = self._voice_codes(voices)
             if all(v is None for v in voices):
                 voices = None
         max_lengths = [0] * n if max_lengths is None else [int(x) for x in max_lengths]
         if len(max_lengths) != n or (gens is not None and len(gens) != n):
             raise ValueError(f"{n} slots, {len(max_lengths)} max_lengths, {None if gens is None else len(gens)} gens")
-        gp_arr, gps = None, []
+        gp_arr = None
         if gens is not None:
-            gp_arr = (C.POINTER(N.PttsGenParams) * max(n, 1))()
-            for j, gen in enumerate(gens):
-                if gen is None:
-                    continue
-                unknown = set(gen) - {"min_new_tokens", "do_sample", "temperature", "top_k", "top_p", "use_eos_gate", "seed"}
-                if unknown:
-                    raise ValueError(f"unknown per-request generation parameters {sorted(unknown)}")
-                gps.append(N.PttsGenParams(0, int(gen.get("min_new_tokens", 0)), int(bool(gen.get("do_sample", False))), float(gen.get("temperature", 1.0)),
-                                           int(gen.get("top_k", 0) or 0), float(gen.get("top_p", 1.0)), int(bool(gen.get("use_eos_gate", True))),
-                                           int(gen.get("seed", 0)) & (2 ** 64 - 1)))
-                gp_arr[j] = C.pointer(gps[-1])
-        enc = enc.to(self.device, torch.float32).contiguous()
-        if enc.dim() != 3 or tuple(enc.shape) != (n, self.session_N, self.H):
-            raise ValueError(f"encoder states {tuple(enc.shape)} do not match [{n}, {self.session_N}, {self.H}] ({n} slots at the session's widths)")
-        keep = [enc]
-        pr = em = pm = None
-        if self.P > 0:
-            if prompt is None or tuple(prompt.shape) != (n, self.P, self.H):
-                raise ValueError(f"prompt embeddings {None if prompt is None else tuple(prompt.shape)} do not match [{n}, {self.P}, {self.H}]")
-            pr = prompt.to(self.device, torch.float32).contiguous()
-            keep.append(pr)
-        if enc_mask is not None:
-            em = enc_mask.to(self.device, torch.int32).contiguous()
-            if tuple(em.shape) != (n, self.session_N):
-                raise ValueError(f"attention_mask {tuple(em.shape)} does not match [{n}, {self.session_N}]")
-            keep.append(em)
-        if prompt_mask is not None and self.P > 0:
-            pm = prompt_mask.to(self.device, torch.int32).contiguous()
-            if tuple(pm.shape) != (n, self.P):
-                raise ValueError(f"prompt_attention_mask {tuple(pm.shape)} does not match [{n}, {self.P}]")
-            keep.append(pm)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+            gps = [None if gen is None else self._gen_params(gen) for gen in gens]  # alive until the call returns: it copies the records
+            gp_arr = (C.POINTER(N.PttsGenParams) * max(n, 1))(*[None if g is None else C.pointer(g) for g in gps])
+        enc, em, pr, pm = self._session_inputs(n, enc, enc_mask, prompt, prompt_mask)
+        ptr = self._ptr
+        ints = lambda xs: (C.c_int32 * max(n, 1))(*xs)
         if voices is not None:
-            keep.extend(v for v in voices if v is not None)
             codes = (C.c_void_p * max(n, 1))(*[None if v is None else v.data_ptr() for v in voices])
-            Ts = (C.c_int32 * max(n, 1))(*[0 if v is None else int(v.shape[1]) for v in voices])
-            N.check(self.lib.ptts_admit_rows_voice(self._h, n, (C.c_int32 * max(n, 1))(*rows), ptr(enc), ptr(em), ptr(pr), ptr(pm), codes, Ts,
-                                                   (C.c_int32 * max(n, 1))(*max_lengths), int(sample), gp_arr, _stream_ptr(device=self.device)),
-                    "ptts_admit_rows_voice")
+            N.check(self.lib.ptts_admit_rows_voice(self._h, n, ints(rows), ptr(enc), ptr(em), ptr(pr), ptr(pm), codes,
+                                                   ints(0 if v is None else int(v.shape[1]) for v in voices), ints(max_lengths), int(sample), gp_arr,
+                                                   _stream_ptr(device=self.device)), "ptts_admit_rows_voice")
         else:
-            N.check(self.lib.ptts_admit_rows(self._h, n, (C.c_int32 * max(n, 1))(*rows), ptr(enc), ptr(em), ptr(pr), ptr(pm),
-                                             (C.c_int32 * max(n, 1))(*max_lengths), int(sample), gp_arr, _stream_ptr(device=self.device)), "ptts_admit_rows")
-        if not hasattr(self, "_keep_rows"):
-            self._keep_rows = {}
-        for r in rows:
-            self._keep_rows[r] = keep  # consumed asynchronously by the enqueued kernels
+            N.check(self.lib.ptts_admit_rows(self._h, n, ints(rows), ptr(enc), ptr(em), ptr(pr), ptr(pm), ints(max_lengths), int(sample), gp_arr,
+                                             _stream_ptr(device=self.device)), "ptts_admit_rows")
+        self._keep_admitted(rows, [enc, em, pr, pm] + (voices or []))
 
     def row_state(self) -> Tuple[list, list]:
         """(cur_len, live) per slot: columns written so far incl. BOS, and whether the slot is still generating. Synchronises."""

@@ -1,7 +1,7 @@
 // Test-only harness of the per-slot voice-prompt length of a continuous session (tests/test_session_voice_tail_gpu.py). Next to
 // slot_gen_harness.hip, which keeps launching tail_launch with its six arguments: this one passes the seventh (the per-slot prefix lengths)
-// and launches the product's kernels that a voice admission runs on the sampler state (push_prefix_slot_kernel, fill_int_kernel,
-// set_len_kernel). No kernel code of its own. Built by the tests with build()'s hipcc flags as one translation unit. Every entry returns a
+// and launches the product's kernels that a voice admission runs on the sampler state (admit_voice_slots_kernel with a list of
+// one; fill_int_kernel). No kernel code of its own. Built by the tests with build()'s hipcc flags as one translation unit. Every entry returns a
 // PTTS_* status; the message is in sv_last_error().
 #include "ptts_common.h"
 #include "ptts_lm_kernels.h"
@@ -81,17 +81,23 @@ SV_API int sv_embed(const ThArgs* g, const int* slot_tprefix, void* stream) {
   return sv_launched("embed_kernel");
 }
 
-// What ptts_admit_row_voice runs on the sampler state of slot `row` behind its session_reset_rows_kernel: the id columns 1..T from the slot's
+// What a voice admission runs on the sampler state of slot `row` behind its session_reset_rows_kernel: the id columns 1..T from the slot's
 // prefix rows (`prefix` [B*K][prefix_ld], already holding the codes), the slot's prefix length, and its clock at T + 1. T == 0 only writes the length
 // (what ptts_retire_row and session begin do).
 SV_API int sv_set_prefix(const ThArgs* g, const long long* prefix, int prefix_ld, int* slot_tprefix, int row, int T, int max_length, void* stream) {
   if (!g->ids || !g->cur_len || !slot_tprefix || row < 0 || row >= g->B || T < 0 || (T > 0 && (!prefix || T > prefix_ld || T + 1 >= g->ids_ld)))
     return ptts_fail(PTTS_E_INVALID, "sv_set_prefix: row=%d T=%d B=%d prefix_ld=%d ids_ld=%d", row, T, g->B, prefix_ld, g->ids_ld);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (T > 0)
-    hipLaunchKernelGGL(push_prefix_slot_kernel, dim3((g->K * T + 255) / 256), dim3(256), 0, st, g->ids + (size_t)row * g->K * g->ids_ld, g->ids_ld,
-                       prefix + (size_t)row * g->K * prefix_ld, prefix_ld, T, g->K, g->bos, g->pad, max_length);
-  hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, st, slot_tprefix + row, T, (size_t)1);
-  if (T > 0) hipLaunchKernelGGL(set_len_kernel, dim3(1), dim3(64), 0, st, g->cur_len + row, 1, T + 1);
-  return sv_launched("push_prefix_slot_kernel");
+  if (T == 0) {
+    hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, st, slot_tprefix + row, 0, (size_t)1);
+    return sv_launched("fill_int_kernel");
+  }
+  static DevDims* row_dims = nullptr;  // the kernel also writes the DevDims of the admission's prefill pass: nobody reads them here
+  if (!row_dims && hipMalloc(reinterpret_cast<void**>(&row_dims), sizeof(DevDims)) != hipSuccess) return ptts_fail(PTTS_E_HIP, "sv_set_prefix: hipMalloc failed");
+  AdmitVoiceSlotsArgs a = {};
+  a.ids = g->ids; a.prefix = prefix; a.slot_T = slot_tprefix; a.cur_len = g->cur_len; a.row_dims = row_dims;
+  a.ids_ld = g->ids_ld; a.prefix_ld = prefix_ld; a.K = g->K; a.bos = g->bos; a.pad = g->pad;
+  a.rows[0] = row; a.Ts[0] = T; a.Ls[0] = max_length;
+  hipLaunchKernelGGL(admit_voice_slots_kernel, dim3((g->K * T + 255) / 256, 1), dim3(256), 0, st, a);
+  return sv_launched("admit_voice_slots_kernel");
 }

@@ -1,5 +1,5 @@
 """Restatements (numpy, no GPU) of what a voice admission into a continuous session writes and of what the session tail does behind it: the id
-columns 1..T of the slot (``push_prefix_slot_kernel``), and ``tail_kernel<NV, true>`` over slots that each carry their own ``max_length`` and
+columns 1..T of the slot (``admit_voice_slots_kernel``), and ``tail_kernel<NV, true>`` over slots that each carry their own ``max_length`` and
 voice-prompt length (``sampler_model.TailModel`` with a prefix length per slot). tests/test_session_voice_cpu.py checks both against
 ``build_delay_pattern_mask`` and ``sample_loop(decoder_input_ids=)``; tests/test_session_voice_gpu.py checks the kernels against them."""
 import numpy as np

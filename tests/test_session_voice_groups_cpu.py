@@ -94,7 +94,7 @@ def test_a_torch_free_c_client_compiles_against_the_header(tmp_path):
 
 # ---- the ragged move: a host model of the kernels' index arithmetic against a plain restatement -------------------------------------------------
 def _move_model(arena, scales, src0, rows, self_rows, row_u, nkv, cap, threads):
-    """admit_move_body / admit_move_scales_body for the self arena of one layer, in units: arena [slots, nkv, cap * row_u] (K or V; both move
+    """admit_move_rows_kernel / admit_move_scales_kernel for the self arena of one layer, in units: arena [slots, nkv, cap * row_u] (K or V; both move
     alike), scales [slots, nkv, cap] or None. Request z of the launch moves self_rows[z] * row_u units per head from slot src0 + z to slot
     rows[z]; the kernels walk a flat unit index `u` with a grid stride, restated here thread for thread."""
     out, out_s = arena.copy(), None if scales is None else scales.copy()
@@ -139,12 +139,15 @@ def test_the_ragged_move_carries_each_requests_own_rows_and_nothing_of_the_paddi
         assert not np.array_equal(got[dst, :, : self_rows[z] * row_u], arena[dst, :, : self_rows[z] * row_u])
     untouched = [s for s in range(slots) if s not in rows]
     assert np.array_equal(got[untouched], arena[untouched])
-    # the kernels this restates exist, take the lengths by value next to the slot list, and share their bodies with the equal-length kernels
+    # the kernels this restates exist and take the lengths by value next to the slot list; an equal-length group runs them too: there is exactly
+    # one move kernel and one scale-move kernel, and no ragged twin
     src = open(os.path.join(ROOT, "parler_tts_amd", "csrc", "ptts_lm_kernels.h")).read()
-    for name in ("admit_move_rows_ragged_kernel", "admit_move_scales_ragged_kernel", "admit_voice_slots_kernel", "embed_rows_kernel", "gather_last_rows_kernel"):
+    for name in ("admit_move_rows_kernel", "admit_move_scales_kernel", "admit_voice_slots_kernel", "embed_rows_kernel", "gather_last_rows_kernel"):
         assert re.search(r"__global__ void (__launch_bounds__\(256\) )?" + name + r"\(", src), name
     assert re.search(r"int self_rows\[ADMIT_ROWS_MAX\]", src) and re.search(r"int ns\[ADMIT_ROWS_MAX\]", src)
-    assert src.count("admit_move_body(") == 3 and src.count("admit_move_scales_body(") == 3
+    assert len(re.findall(r"__global__ void (?:__launch_bounds__\(\d+\) )?admit_move_rows\w*\(", src)) == 1
+    assert len(re.findall(r"__global__ void (?:__launch_bounds__\(\d+\) )?admit_move_scales\w*\(", src)) == 1
+    assert "_ragged_kernel" not in src
 
 
 # ---- the batcher's grouping on an oracle-backed stand-in --------------------------------------------------------------------------------------

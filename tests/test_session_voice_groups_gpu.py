@@ -540,3 +540,30 @@ def test_continuous_batcher_with_voice_groups_equals_generate_on_each_request_al
             worst = float((got - whole[i][skip:]).abs().max()) if got.shape[0] else 0.0
             assert worst <= 1e-5, (mode, i, worst)  # the streaming bar of tests/test_continuous_streaming_voice_gpu.py
         cs.close()
+
+
+# ---- 11: an engine without spare rows ----------------------------------------------------------------------------------------------------------
+def test_one_voice_request_runs_in_its_slot_and_needs_no_spare_row():
+    """2 slots on an engine of max_batch 2, T = 3: admit_row(voice=) and admit_rows([r], voices=[v]) both run their pass in the slot itself, and
+    each slot's step-0 logits are those of ptts_set_audio_prefix + ptts_prefill of the request alone on the same engine, bit for bit. The same
+    list without a voice prompt runs on a spare row and is refused for want of one."""
+    slots, L = 2, 24
+    reqs = [VC.request(751, 3), VC.request(752, 3)]
+    eng = _engine("fp32", slots, 0)
+    eng.set_gen_params(max_length=L, min_new_tokens=0)
+    static = []
+    for r in reqs:
+        eng.set_audio_prefix(r[4][None])
+        eng.prefill(r[0][None], r[1][None], r[2][None], r[3][None], sample=False)
+        static.append(eng.logits().cpu().view(K, V).clone())
+    _begin(eng, "fp32", slots)
+    with pytest.raises(ValueError, match="spare rows"):
+        eng.admit_rows([1], *[t[None] for t in reqs[1][:4]], max_lengths=[L], sample=False)
+    assert eng.row_state() == ([1, 1], [False, False]) and eng.slot_voice() == [0, 0]
+    _admit_one(eng, 0, reqs[0], L, sample=False)
+    _admit_group(eng, [1], [reqs[1]], [L], sample=False)
+    got = eng.logits().cpu().view(slots, K, V)
+    for s in range(slots):
+        assert torch.equal(got[s].view(torch.int32), static[s].view(torch.int32)), s
+    assert eng.row_state() == ([4, 4], [True, True]) and eng.slot_voice() == [3, 3]
+    eng.close()

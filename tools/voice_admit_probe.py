@@ -2,7 +2,7 @@
 P + 1 + T positions each) against ONE ``admit_rows(voices=)`` (``ptts_admit_rows_voice``: one pass of n x (P + 1 + Tmax) positions).
 
 Shapes: Mini-v1 decoder, bf16, P = 32 prompt and N = 64 description positions, 16 slots of which 8 stay live and decode between the
-admissions, n = 2 / 4 / 8 requests with T = 430 frames each (5 s) and with ragged T from 86 to 430, on the bf16 self-attention cache and
+admissions, n = 1 / 2 / 4 / 8 requests with T = 430 frames each (5 s) and with ragged T from 86 to 430 (n = 1: 86), on the bf16 self-attention cache and
 with ``enable_fp8_kv_cache()``. Both sides are timed in the same process on the same engine, alternating, with device events around the
 calls (the stream runs nothing else); the first round of every shape is a warm-up and is dropped. The figure is the GPU time from the first
 launch of the admission to the first token of its last request.
@@ -100,7 +100,7 @@ def main():
         if kv8:
             model.enable_fp8_kv_cache()
         for ragged in (False, True):
-            for n in (2, 4, 8):
+            for n in (1, 2, 4, 8):  # n = 1: both sides run in place in the slot
                 runs, on_kv8 = measure(model, ev, n, ragged, args.repeats)
                 assert on_kv8 == kv8
                 one, grp = [a for a, _ in runs], [b for _, b in runs]
