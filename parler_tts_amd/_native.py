@@ -46,6 +46,14 @@ class PttsSampleWarp(C.Structure):
     _fields_ = [("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
 
 
+class PttsLogitEdits(C.Structure):
+    """ptts_logit_edits (include/ptts_logit_edit.h): host arrays of the five options, read during the call."""
+    _fields_ = [("bias_tokens", C.POINTER(C.c_int32)), ("bias_values", C.POINTER(C.c_float)), ("bad_tokens", C.POINTER(C.c_int32)),
+                ("suppress_tokens", C.POINTER(C.c_int32)), ("begin_suppress_tokens", C.POINTER(C.c_int32)),
+                ("n_bias", C.c_int32), ("n_bad", C.c_int32), ("n_suppress", C.c_int32), ("n_begin_suppress", C.c_int32),
+                ("decay_on", C.c_int32), ("decay_start", C.c_int32), ("decay_factor", C.c_double)]
+
+
 class PttsScoreIO(C.Structure):
     """ptts_score_io (include/ptts_score.h): device pointers of one teacher-forced scoring call."""
     _fields_ = [("input_ids", C.c_void_p), ("labels", C.c_void_p), ("nll", C.c_void_p), ("counted", C.c_void_p), ("logits", C.c_void_p)]
@@ -168,6 +176,13 @@ WARP_SYMBOLS = {
     "ptts_set_slot_sample_warp": (C.c_int, [_VP, _I32, C.POINTER(PttsSampleWarp), _VP]),
 }
 
+# include/ptts_logit_edit.h, additive likewise: sequence_bias / bad_words_ids (single tokens), exponential_decay_length_penalty, suppress_tokens and
+# begin_suppress_tokens as a device node between the penalty node and the sampler tail
+LOGIT_EDIT_SYMBOLS = {
+    "ptts_set_logit_edits": (C.c_int, [_VP, C.POINTER(PttsLogitEdits), _VP]),
+    "ptts_set_slot_logit_edits": (C.c_int, [_VP, _I32, C.POINTER(PttsLogitEdits), _VP]),
+}
+
 # include/ptts_score.h, additive likewise: one teacher-forced forward ending in the fused LM-heads + cross-entropy kernel
 SCORE_SYMBOLS = {
     "ptts_score": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(PttsScoreIO), _VP]),
@@ -196,7 +211,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
     for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
                               + list(SESSION_VOICE_SYMBOLS.items()) + list(SESSION_VOICE_ROWS_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())
-                              + list(WARP_SYMBOLS.items()) + list(SCORE_SYMBOLS.items())):
+                              + list(WARP_SYMBOLS.items()) + list(SCORE_SYMBOLS.items()) + list(LOGIT_EDIT_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

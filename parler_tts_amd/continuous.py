@@ -23,7 +23,7 @@ from typing import Deque, Dict, Iterable, Iterator, List, Optional, Tuple
 import torch
 
 from .engine import DecoderEngine
-from .generation_extras import active_extras, check_generation_mode
+from .generation_extras import LOGIT_EDIT_OPTIONS, active_extras, check_generation_mode, logit_edit_rule_broken, logit_edits_of
 from .modeling_parler_tts import apply_delay_pattern_mask, build_delay_pattern_mask
 
 _HOST_LOOP_ARGUMENTS = ("logits_processor", "stopping_criteria", "output_scores", "output_logits")
@@ -33,10 +33,11 @@ _DEVICE_WARPERS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
 
 
 class _Request:
-    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept", "pen", "warp",
+    __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept", "pen", "warp", "edits",
                  "cols", "absorbed", "kept", "emitted", "first_out")
 
-    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None, pen=None, warp=None):
+    def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None, pen=None, warp=None, edits=None):
+        self.edits = edits  # the request's own generation_extras.LogitEdits (set_slot_logit_edits), or None: the session's
         self.warp = warp  # the request's own (min_p, typical_p, epsilon_cutoff, eta_cutoff) (set_slot_sample_warp), or None: the session's
         self.pen = pen  # the request's own (repetition_penalty, no_repeat_ngram_size) (set_slot_history_penalty), or None: the session's
         self.ticket, self.enc, self.enc_mask, self.prompt, self.prompt_mask, self.max_length = ticket, enc, enc_mask, prompt, prompt_mask, max_length
@@ -154,6 +155,10 @@ class ContinuousBatcher:
         self.device_warpers = bool(getattr(model, "device_warpers", False))
         if self.device_warpers:
             extras = [x for x in extras if x not in _DEVICE_WARPERS]
+        # model.enable_device_logit_edits(): the five position / token edits as a device node of the session's step (ptts_logit_edit.h)
+        self.device_logit_edits = bool(getattr(model, "device_logit_edits", False))
+        if self.device_logit_edits:
+            extras = [x for x in extras if x not in LOGIT_EDIT_OPTIONS]
         if extras:
             raise NotImplementedError(f"generation options {extras} run on generate()'s host loop (generation_extras): not available in a continuous batch")
         if int(getattr(gc, "num_return_sequences", 1) or 1) != 1:
@@ -184,6 +189,11 @@ class ContinuousBatcher:
         self._pen = self._penalty(gc.repetition_penalty, gc.no_repeat_ngram_size, (1.0, 0)) if self.device_penalties else None
         self._warp = (self._warpers(gc.min_p, gc.typical_p, gc.epsilon_cutoff, gc.eta_cutoff, (0.0, 1.0, 0.0, 0.0))
                       if self.device_warpers else None)
+        # ... and its logit edits: the options as given (what a request's own start from) and their record, under the two rules of the node's place
+        self.V, self.eos = d.vocab_size, d.eos_token_id
+        self._edit_opts = {n: getattr(gc, n, None) for n in LOGIT_EDIT_OPTIONS} if self.device_logit_edits else None
+        self._edits = self._logit_edits(self._edit_opts, self.max_length, gc.repetition_penalty, gc.no_repeat_ngram_size, min_new) if self.device_logit_edits else None
+        self._min_new = min_new
         self.eng = model._get_engine(self.slots + self.spare, self.N, self.P, self.max_length, *voice_room)
         self.eng.set_gen_params(max_length=self.max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                                 top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0), use_eos_gate=True, seed=seed)
@@ -198,6 +208,11 @@ class ContinuousBatcher:
             self.eng.set_sample_warp(*self._warp)
         elif getattr(self.eng, "sample_warp", None) is not None:
             self.eng.set_sample_warp(enabled=False)
+        # The logit-edit node likewise: part of the session's step from its begin
+        if self.device_logit_edits:
+            self.eng.set_logit_edits(self._edits)
+        elif getattr(self.eng, "logit_edits", None) is not None:
+            self.eng.set_logit_edits(enabled=False)
         # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
         self.eng.begin_session(self.slots, self.N, self.P, **({"kv_fp8": True} if getattr(self.eng, "kv_fp8", False) else {}))
         # what a request's own record starts from (submit): the session's values as the caller gave them (top_k is not zeroed for a greedy session)
@@ -294,12 +309,22 @@ class ContinuousBatcher:
         DecoderEngine._sample_warp(*vals)  # the engine wrapper's own checks, here so that a bad value never reaches the queue
         return tuple(float(v) for v in vals)
 
+    def _logit_edits(self, options: dict, max_length: int, repetition_penalty, no_repeat_ngram_size, min_new_tokens):
+        """The five options as the node's record; ``ValueError`` on what the node does not compute (a multi-token key, a bad value) and on the
+        two combinations in which its place in the chain is not transformers' order, beside the penalties and ``min_new_tokens`` in effect."""
+        edits = logit_edits_of(self.V, self.eos, max_length, **options)
+        broken = logit_edit_rule_broken(edits, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
+        if broken:
+            raise ValueError(broken + ": not available in a continuous batch")
+        return edits
+
     @torch.no_grad()
     def submit(self, input_ids, attention_mask=None, prompt_input_ids=None, prompt_attention_mask=None, max_new_tokens: Optional[int] = None,
                do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                min_new_tokens: Optional[int] = None, seed: Optional[int] = None, input_values=None, decoder_input_ids=None,
                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_p: Optional[float] = None,
-               typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None) -> int:
+               typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, sequence_bias=None,
+               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, exponential_decay_length_penalty=None) -> int:
         """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path).
         ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_new_tokens``: the request's own sampler settings; an option left ``None``
         takes the session's value. A request that sets any of them (or ``seed``) draws from its own stream ``(seed, column, codebook)``: with a
@@ -313,7 +338,17 @@ class ContinuousBatcher:
         columns - BOS, the voice prompt's, what it generated - as ``generate()`` computes them for the same request alone.
         ``min_p`` / ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` (a model with ``enable_device_warpers()``; ``NotImplementedError``
         otherwise): the request's own warpers behind top-p, an option left ``None`` taking the session's value; without effect on a greedy
-        request."""
+        request.
+        ``sequence_bias`` / ``bad_words_ids`` (single-token keys) / ``suppress_tokens`` / ``begin_suppress_tokens`` /
+        ``exponential_decay_length_penalty`` (a model with ``enable_device_logit_edits()``; ``NotImplementedError`` otherwise): the request's
+        own logit edits, an option left ``None`` taking the session's value. The begin index and the decay's start count from the request's
+        own given columns (BOS and its voice prompt's). ``ValueError``: a multi-token key, a token outside the vocabulary, ``sequence_bias``
+        beside a history penalty, a decay with ``min_new_tokens > start + 1``."""
+        own_edits = dict(sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
+                         begin_suppress_tokens=begin_suppress_tokens, exponential_decay_length_penalty=exponential_decay_length_penalty)
+        if any(v is not None for v in own_edits.values()) and not self.device_logit_edits:
+            raise NotImplementedError(f"generation options {list(LOGIT_EDIT_OPTIONS)} run on generate()'s host loop "
+                                      "(generation_extras): not available in a continuous batch without model.enable_device_logit_edits()")
         warp = None
         if any(v is not None for v in (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
             if not self.device_warpers:
@@ -339,6 +374,13 @@ class ContinuousBatcher:
         if max_length - 1 - T > room:
             raise ValueError(f"max_new_tokens {max_length - 1 - T} exceeds the session's {room}")
         gen = self._request_gen(do_sample, temperature, top_k, top_p, min_new_tokens, seed)
+        edits = None
+        if self.device_logit_edits:  # the record in effect - the request's own over the session's - beside the penalties and min_new_tokens in effect
+            opts = {n: self._edit_opts[n] if v is None else v for n, v in own_edits.items()}
+            rp, ng = pen if pen is not None else (self._pen if self._pen is not None else (None, None))
+            in_effect = self._logit_edits(opts, max_length, rp, ng, self._min_new if gen is None else gen["min_new_tokens"])
+            if any(v is not None for v in own_edits.values()):
+                edits = in_effect
         dev = self.model.device
         ids, mask = self._pad_ids(input_ids, attention_mask, self.N, "description")
         enc = self.model._encode_description(ids[None].to(dev), mask[None].to(dev))[0].float()
@@ -358,7 +400,7 @@ class ContinuousBatcher:
         if voice is not None and self.stream_voice == "skip":  # what the filter keeps of the prompt, known here: the codec's pairs do not say
             prompt_kept = [0] + self._valid_frames(voice).long().cumsum(0).tolist()
         self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept, *(() if pen is None else (pen,)),
-                                    **({} if warp is None else {"warp": warp})))
+                                    **({} if warp is None else {"warp": warp}), **({} if edits is None else {"edits": edits})))
         return ticket
 
     def _voice(self, input_values, decoder_input_ids) -> Optional[torch.Tensor]:
@@ -407,6 +449,8 @@ class ContinuousBatcher:
                     self.eng.set_slot_history_penalty(s, *r.pen)
                 if r.warp is not None:
                     self.eng.set_slot_sample_warp(s, *r.warp)
+                if r.edits is not None:
+                    self.eng.set_slot_logit_edits(s, r.edits)
             reqs = [self._queue.popleft() for _ in group]
             if len(reqs) == 1:
                 (s, r), = group

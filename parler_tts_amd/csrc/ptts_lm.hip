@@ -14,6 +14,7 @@
 #include "../../include/ptts_session_voice_rows.h"
 #include "../../include/ptts_penalty.h"
 #include "../../include/ptts_warp.h"
+#include "../../include/ptts_logit_edit.h"
 #include "../../include/ptts_score.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
@@ -22,6 +23,7 @@
 #include "ptts_gemm_launch.h"
 #include "ptts_tail_launch.h"
 #include "ptts_penalty_launch.h"
+#include "ptts_logit_edit_launch.h"
 #include "ptts_score_launch.h"
 
 thread_local std::string g_ptts_err;
@@ -131,6 +133,14 @@ struct ptts_engine {
   DevWarp* warp = nullptr;               // [max_batch] device: the record of each utterance / slot; allocated at the first switch-on, the step graphs hold the pointer
   bool warp_on = false;                  // the tail of every launch (and of the step graph: its own key bit) is tail_warp_kernel<NV, SESSION>
   DevWarp warp_default = {0.f, 1.f, 0.f, 0.f};  // the values of ptts_set_sample_warp
+  // logit edits (ptts_logit_edit.h): one node between the penalty node and every sampler tail while le_on
+  LogitEditRecs le = {};                 // device: max_batch + 1 records - each utterance's / slot's, then (index max_batch) the values of ptts_set_logit_edits;
+                                         // allocated at the first switch-on, the step graphs hold the pointers
+  bool le_on = false;                    // the node is part of every tail (and of the step graph: its own key bit)
+  bool le_ready = false;                 // every array of `le` is allocated and zeroed (ensure_logit_edit_records)
+  unsigned char* le_stage = nullptr;     // pinned host: one staging area per record, what its last upload copies from
+  size_t le_stage_stride = 0;
+  std::vector<hipEvent_t> le_ev;         // per record: the end of that upload (waited for before the area is written again)
 #ifdef PTTS_TIMING
   long long* dbg_stamps = nullptr;  // measurement build: [layers + 1][5 or 7 nodes][3 workgroups][16] wall-clock stamps of the decode step (ptts_debug_stamps)
 #endif
@@ -572,6 +582,16 @@ int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next
     p.ids_ld = e->ids_ld; p.K = e->cfg.num_codebooks; p.V = e->cfg.vocab_size;
     if (!penalty_launch(p, row < 0 ? 0 : row, row < 0 ? v.B : 1, st)) return ptts_fail(PTTS_E_UNSUPPORTED, "history penalty: no kernel for vocab_size %d", p.V);
   }
+  if (e->le_on) {  // position and token edits, behind the penalties as in transformers' chain; records and voice-prompt lengths indexed like cur_len
+    const size_t off = (size_t)(v.cur_len - e->cur_len);
+    LogitEditArgs a = {};
+    a.logits = v.logits; a.cur_len = v.cur_len; a.recs = e->le;
+    a.recs.hdr += off; a.recs.bias += off * e->le.ld_v; a.recs.decay += off * e->le.ld_t; a.recs.flags += off * e->le.ld_v;
+    // given columns = 1 + T: a slot's own frames in a session, the call's (DevDims::T_prefix, what the tail reads) otherwise
+    a.t_prefix = v.session ? e->slot_T + off : &e->dims->T_prefix; a.t_prefix_stride = v.session ? 1 : 0;
+    a.K = e->cfg.num_codebooks; a.V = e->cfg.vocab_size; a.eos = e->cfg.eos_token_id;
+    if (!logit_edit_launch(a, row < 0 ? 0 : row, row < 0 ? v.B : 1, st)) return ptts_fail(PTTS_E_UNSUPPORTED, "logit edits: no kernel for vocab_size %d", a.V);
+  }
   // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
   // warpers on: the WARP instances, with the records indexed like cur_len (null picks the instances of an engine without the feature)
   const DevWarp* warp = e->warp_on ? e->warp + (v.cur_len - e->cur_len) : nullptr;
@@ -867,6 +887,8 @@ extern "C" void ptts_engine_destroy(ptts_engine* e) {
   for (auto& kv : e->graphs) hipGraphExecDestroy(kv.second);
   for (void* p : e->allocs) hipFree(p);
   if (e->host_pinned) hipHostFree(e->host_pinned);
+  if (e->le_stage) hipHostFree(e->le_stage);
+  for (hipEvent_t ev : e->le_ev) if (ev) hipEventDestroy(ev);
   if (e->own_stream) hipStreamDestroy(e->own_stream);
   if (e->ev_first) hipEventDestroy(e->ev_first);
   if (e->ev_tail0) hipEventDestroy(e->ev_tail0);
@@ -1145,11 +1167,12 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
 static int get_graph(ptts_engine* e, int kv_bound, hipGraphExec_t* out) {
   // The node set of the step is its plan (ptts_step_plan.h), and gemv_plan / strip_plan take no engine: beside the engine's fixed cfg, sc and sw they
   // see the batch size, the folded-cross-block flag and the 64-position bucket `kv_bound` (also a kernel argument: the attention fetch bound) -
-  // all three in the key. The tail adds session, pen_on and warp_on: the key's upper bits. (Several steps of one bucket per
+  // all three in the key. The tail adds session, pen_on, warp_on and le_on: the key's upper bits. (Several steps of one bucket per
   // graph launch - round 4's PTTS_GRAPH_STEPS - measured 0.3-0.7 %, profiles/r04_experiments.txt call 19: removed in round 6.)
   const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (kv_bound / 64) + (e->session ? 1LL << 40 : 0)  // session steps end in their own tail
                         + (e->pen_on ? 1LL << 41 : 0)                                                                            // the history-penalty node is present
-                        + (e->warp_on ? 1LL << 42 : 0);                                                                          // the tail is the WARP instance
+                        + (e->warp_on ? 1LL << 42 : 0)                                                                           // the tail is the WARP instance
+                        + (e->le_on ? 1LL << 43 : 0);                                                                            // the logit-edit node is present
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) { if (out) *out = it->second; return PTTS_OK; }
   hipGraph_t g = nullptr;
@@ -1305,6 +1328,7 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
   hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, e->slot_T, 0, (size_t)c.max_batch);  // ... nor a voice prompt
   if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->pen, 0, c.max_batch, e->pen_default);  // ... nor penalties of its own
   if (e->warp_on) hipLaunchKernelGGL(set_warp_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->warp, 0, c.max_batch, e->warp_default);  // ... nor warpers
+  if (e->le_on) hipLaunchKernelGGL(copy_logit_edit_kernel, dim3(4, c.max_batch), dim3(256), 0, st, e->le, c.max_batch, 0);  // ... nor logit edits
   // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);
@@ -1569,6 +1593,7 @@ extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
   hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->slot_T + row, 0, (size_t)1);  // ... and continues no voice prompt
   if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->pen, row, 1, e->pen_default);  // ... under the session's penalties
   if (e->warp_on) hipLaunchKernelGGL(set_warp_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->warp, row, 1, e->warp_default);  // ... and warpers
+  if (e->le_on) hipLaunchKernelGGL(copy_logit_edit_kernel, dim3(4, 1), dim3(256), 0, pick_stream(e, stream), e->le, e->cfg.max_batch, row);  // ... and logit edits
   e->slot_busy[row] = 0; e->slot_ub[row] = e->P + 1;
   return PTTS_OK;
 }
@@ -1649,6 +1674,135 @@ extern "C" int ptts_set_slot_sample_warp(ptts_engine* e, int32_t row, const ptts
   const DevWarp rec = w ? DevWarp{w->min_p, w->typical_p, w->epsilon_cutoff, w->eta_cutoff} : e->warp_default;
   hipLaunchKernelGGL(set_warp_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->warp, row, 1, rec);
   return launch_status("set_warp");
+}
+
+// ---- logit edits (ptts_logit_edit.h) ------------------------------------------------------------------------------------------------------
+// one record on the host, as its staging area holds it: header, bias row, decay table, class flags
+struct HostLogitEdit {
+  LogitEditHeader hdr = {};
+  std::vector<float> bias, decay;
+  std::vector<unsigned char> flags;
+};
+
+// every check of a record, then its arrays; nothing of the engine changes here
+static int build_logit_edit(const ptts_engine* e, const ptts_logit_edits* le, HostLogitEdit* out) {
+  const int V = e->cfg.vocab_size, eos = e->cfg.eos_token_id, ld_t = e->ids_ld;
+  PTTS_CHECK(le->n_bias >= 0 && le->n_bad >= 0 && le->n_suppress >= 0 && le->n_begin_suppress >= 0, PTTS_E_INVALID, "logit edits: a negative count");
+  PTTS_CHECK((le->n_bias == 0 || (le->bias_tokens && le->bias_values)) && (le->n_bad == 0 || le->bad_tokens) && (le->n_suppress == 0 || le->suppress_tokens) &&
+                 (le->n_begin_suppress == 0 || le->begin_suppress_tokens), PTTS_E_INVALID, "logit edits: a null array with a positive count");
+  for (int i = 0; i < le->n_bias; ++i) {
+    PTTS_CHECK(le->bias_tokens[i] >= 0 && le->bias_tokens[i] < V, PTTS_E_INVALID, "sequence_bias token %d outside the vocabulary [0, %d)", le->bias_tokens[i], V);
+    PTTS_CHECK(std::isfinite(le->bias_values[i]), PTTS_E_INVALID, "sequence_bias of token %d must be finite, got %g", le->bias_tokens[i], (double)le->bias_values[i]);
+  }
+  for (int i = 0; i < le->n_bad; ++i)
+    PTTS_CHECK(le->bad_tokens[i] >= 0 && le->bad_tokens[i] < V, PTTS_E_INVALID, "bad_words_ids token %d outside the vocabulary [0, %d)", le->bad_tokens[i], V);
+  if (le->decay_on) {
+    PTTS_CHECK(le->decay_start >= 0, PTTS_E_INVALID, "exponential_decay_length_penalty start must be >= 0, got %d", le->decay_start);
+    PTTS_CHECK(std::isfinite(le->decay_factor) && le->decay_factor > 0.0, PTTS_E_INVALID, "exponential_decay_length_penalty factor must be finite and > 0, got %g",
+               le->decay_factor);
+  }
+  HostLogitEdit& r = *out;
+  r.bias.assign((size_t)V, 0.0f); r.flags.assign((size_t)V, 0); r.decay.clear();
+  int mask = 0;
+  for (int i = 0; i < le->n_bias; ++i) { r.bias[le->bias_tokens[i]] = le->bias_values[i]; mask |= PTTS_LE_BIAS; }
+  for (int i = 0; i < le->n_bad; ++i) {  // NoBadWordsLogitsProcessor drops [eos] and still adds its bias row, all zeros if nothing is left
+    mask |= PTTS_LE_BAD;
+    if (le->bad_tokens[i] != eos) r.flags[le->bad_tokens[i]] |= PTTS_LEF_BAD;
+  }
+  for (int i = 0; i < le->n_suppress; ++i) {  // torch.isin over arange(V): a token outside it matches nothing, the stage itself stays
+    mask |= PTTS_LE_SUPPRESS;
+    if (le->suppress_tokens[i] >= 0 && le->suppress_tokens[i] < V) r.flags[le->suppress_tokens[i]] |= PTTS_LEF_SUPPRESS;
+  }
+  for (int i = 0; i < le->n_begin_suppress; ++i) {
+    mask |= PTTS_LE_BEGIN;
+    if (le->begin_suppress_tokens[i] >= 0 && le->begin_suppress_tokens[i] < V) r.flags[le->begin_suppress_tokens[i]] |= PTTS_LEF_BEGIN;
+  }
+  if (le->decay_on) {  // m[idx] for every idx a clock of this engine can reach (idx < t < ids_ld), with the C library's pow as Python's float pow is
+    mask |= PTTS_LE_DECAY;
+    r.decay.resize((size_t)ld_t);
+    for (int i = 0; i < ld_t; ++i) r.decay[i] = (float)(pow(le->decay_factor, (double)i) - 1.0);
+  }
+  r.hdr = LogitEditHeader{mask, le->decay_on ? le->decay_start : 0, le->decay_on ? ld_t : 0, 0};
+  return PTTS_OK;
+}
+
+// First switch-on: the records, their staging areas and events. Every piece is kept in the engine as soon as it exists, so a call that fails half
+// way (out of memory) leaves nothing behind that the next call allocates again; the records count as ready (le_ready) only once all of them are
+// there and zeroed. The zeroing is ordered on the setter's stream, in front of its first upload.
+static int ensure_logit_edit_records(ptts_engine* e, hipStream_t st) {
+  if (e->le_ready) return PTTS_OK;
+  const ptts_config& c = e->cfg;
+  const size_t n = (size_t)c.max_batch + 1, ld_v = (size_t)((c.vocab_size + 3) & ~3), ld_t = (size_t)e->ids_ld;
+  const size_t stride = (sizeof(LogitEditHeader) + 4 * ld_v + 4 * ld_t + ld_v + 15) & ~(size_t)15;
+  if (!e->le_stage && hipHostMalloc((void**)&e->le_stage, n * stride) != hipSuccess) return ptts_fail(PTTS_E_HIP, "hipHostMalloc failed");
+  e->le_stage_stride = stride;
+  if (e->le_ev.size() != n) e->le_ev.assign(n, nullptr);
+  e->le.ld_v = (int)ld_v; e->le.ld_t = (int)ld_t;
+  if (!e->le.bias) PTTS_TRY(e->alloc(&e->le.bias, n * ld_v));
+  if (!e->le.decay) PTTS_TRY(e->alloc(&e->le.decay, n * ld_t));
+  if (!e->le.flags) PTTS_TRY(e->alloc(&e->le.flags, n * ld_v));
+  if (!e->le.hdr) PTTS_TRY(e->alloc(&e->le.hdr, n));
+  PTTS_HIP(hipMemsetAsync(e->le.bias, 0, n * ld_v * 4, st));
+  PTTS_HIP(hipMemsetAsync(e->le.decay, 0, n * ld_t * 4, st));
+  PTTS_HIP(hipMemsetAsync(e->le.flags, 0, n * ld_v, st));
+  PTTS_HIP(hipMemsetAsync(e->le.hdr, 0, n * sizeof(LogitEditHeader), st));
+  e->le_ready = true;
+  return PTTS_OK;
+}
+
+// record `rec` of the device arrays = r, ordered on st: through the record's own pinned staging area, so that the caller's arrays are free at return
+static int upload_logit_edit(ptts_engine* e, int rec, const HostLogitEdit& r, hipStream_t st) {
+  const size_t ld_v = (size_t)e->le.ld_v, ld_t = (size_t)e->le.ld_t, V = (size_t)e->cfg.vocab_size;
+  if (e->le_ev[rec]) PTTS_HIP(hipEventSynchronize(e->le_ev[rec]));  // the area's last upload has left it
+  else PTTS_HIP(hipEventCreateWithFlags(&e->le_ev[rec], hipEventDisableTiming));
+  unsigned char* s = e->le_stage + (size_t)rec * e->le_stage_stride;
+  unsigned char *s_bias = s + sizeof(LogitEditHeader), *s_decay = s_bias + 4 * ld_v, *s_flags = s_decay + 4 * ld_t;
+  memcpy(s, &r.hdr, sizeof(LogitEditHeader));
+  memcpy(s_bias, r.bias.data(), 4 * V);
+  memcpy(s_flags, r.flags.data(), V);
+  if (!r.decay.empty()) memcpy(s_decay, r.decay.data(), 4 * std::min(r.decay.size(), ld_t));
+  // Only the arrays of the stages in the mask travel: the slot's other arrays keep what an earlier request left there, and logit_edit_kernel
+  // reads an array only under its stage's mask bit. (Nothing reads the record between these copies, so their order does not matter.)
+  if (r.hdr.mask & PTTS_LE_BIAS) PTTS_HIP(hipMemcpyAsync(e->le.bias + rec * ld_v, s_bias, 4 * V, hipMemcpyHostToDevice, st));
+  if (r.hdr.mask & (PTTS_LE_BAD | PTTS_LE_SUPPRESS | PTTS_LE_BEGIN)) PTTS_HIP(hipMemcpyAsync(e->le.flags + rec * ld_v, s_flags, V, hipMemcpyHostToDevice, st));
+  if (r.hdr.mask & PTTS_LE_DECAY) PTTS_HIP(hipMemcpyAsync(e->le.decay + rec * ld_t, s_decay, 4 * ld_t, hipMemcpyHostToDevice, st));
+  PTTS_HIP(hipMemcpyAsync(e->le.hdr + rec, s, sizeof(LogitEditHeader), hipMemcpyHostToDevice, st));
+  PTTS_HIP(hipEventRecord(e->le_ev[rec], st));
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_logit_edits(ptts_engine* e, const ptts_logit_edits* le, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  if (e->session)  // a session that holds a request is running: its node set was fixed at its begin
+    for (char busy : e->slot_busy) PTTS_CHECK(!busy, PTTS_E_INVALID, "ptts_set_logit_edits inside a running session (call it before ptts_session_begin)");
+  if (!le) { e->le_on = false; return PTTS_OK; }
+  const ptts_config& c = e->cfg;
+  HostLogitEdit r;
+  PTTS_TRY(build_logit_edit(e, le, &r));
+  PTTS_CHECK(c.vocab_size <= PTTS_LOGIT_EDIT_MAX_V, PTTS_E_UNSUPPORTED, "logit edits serve vocabularies up to %d, this engine's is %d", PTTS_LOGIT_EDIT_MAX_V, c.vocab_size);
+  PTTS_DEVICE(c.device);
+  hipStream_t st = pick_stream(e, stream);
+  PTTS_TRY(ensure_logit_edit_records(e, st));
+  PTTS_TRY(upload_logit_edit(e, c.max_batch, r, st));
+  hipLaunchKernelGGL(copy_logit_edit_kernel, dim3(4, c.max_batch), dim3(256), 0, st, e->le, c.max_batch, 0);
+  PTTS_TRY(launch_status("copy_logit_edit"));
+  e->le_on = true;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_slot_logit_edits(ptts_engine* e, int32_t row, const ptts_logit_edits* le, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_set_slot_logit_edits: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(e->le_on, PTTS_E_INVALID, "ptts_set_slot_logit_edits: the session was begun without logit edits (ptts_set_logit_edits first)");
+  PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
+  PTTS_CHECK(!e->slot_busy[row], PTTS_E_INVALID, "slot %d still holds a request (ptts_retire_row first)", row);
+  HostLogitEdit r;
+  if (le) PTTS_TRY(build_logit_edit(e, le, &r));
+  PTTS_DEVICE(e->cfg.device);
+  hipStream_t st = pick_stream(e, stream);
+  if (le) return upload_logit_edit(e, row, r, st);
+  hipLaunchKernelGGL(copy_logit_edit_kernel, dim3(4, 1), dim3(256), 0, st, e->le, e->cfg.max_batch, row);
+  return launch_status("copy_logit_edit");
 }
 
 extern "C" int ptts_row_state(ptts_engine* e, int32_t* cur_len_host, int32_t* live_host, void* stream) {

@@ -65,6 +65,7 @@ class DecoderEngine:
         self.B = 0
         self.history_penalty = None  # (repetition_penalty, no_repeat_ngram_size) while the device node is on (set_history_penalty)
         self.sample_warp = None  # (min_p, typical_p, epsilon_cutoff, eta_cutoff) while the tail's WARP instances are on (set_sample_warp)
+        self.logit_edits = None  # the engine-wide generation_extras.LogitEdits while the logit-edit node is on (set_logit_edits)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -211,6 +212,55 @@ class DecoderEngine:
         w = None if default else self._sample_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
         N.check(self.lib.ptts_set_slot_sample_warp(self._h, int(slot), None if w is None else C.byref(w), _stream_ptr(device=self.device)),
                 "ptts_set_slot_sample_warp")
+
+    @staticmethod
+    def _logit_edits(edits):
+        """A ``generation_extras.LogitEdits`` (``None``: the neutral record) as a ``ptts_logit_edits`` and the arrays it points to, which the
+        caller keeps alive over the call."""
+        from .generation_extras import LogitEdits
+
+        ed = LogitEdits() if edits is None else edits
+        I32 = C.c_int32
+        arrays = [(I32 * len(ed.bias))(*[t for t, _ in ed.bias]), (C.c_float * len(ed.bias))(*[b for _, b in ed.bias]), (I32 * len(ed.bad))(*ed.bad),
+                  (I32 * max(len(ed.suppress), 1))(*ed.suppress), (I32 * max(len(ed.begin_suppress), 1))(*ed.begin_suppress)]
+        # a suppress list none of whose tokens lies in the vocabulary is still a stage: one token outside it, which the library ignores
+        n_sup = len(ed.suppress) or (1 if ed.suppress_on else 0)
+        n_beg = len(ed.begin_suppress) or (1 if ed.begin_suppress_on else 0)
+        if not ed.suppress:
+            arrays[3][0] = -1
+        if not ed.begin_suppress:
+            arrays[4][0] = -1
+        start, factor = ed.decay if ed.decay is not None else (0, 1.0)
+        rec = N.PttsLogitEdits(C.cast(arrays[0], C.POINTER(I32)), C.cast(arrays[1], C.POINTER(C.c_float)), C.cast(arrays[2], C.POINTER(I32)),
+                               C.cast(arrays[3], C.POINTER(I32)), C.cast(arrays[4], C.POINTER(I32)), len(ed.bias), len(ed.bad), n_sup, n_beg,
+                               int(ed.decay is not None), int(start), float(factor))
+        return rec, arrays
+
+    def set_logit_edits(self, edits=None, enabled: bool = True):
+        """transformers' ``sequence_bias`` / ``bad_words_ids`` (single-token keys), ``exponential_decay_length_penalty``, ``suppress_tokens`` and
+        ``begin_suppress_tokens`` on the device (``ptts_set_logit_edits``): one kernel node between the history-penalty node and every sampler
+        tail from the next ``prefill`` / ``begin_session`` on, with ``edits`` (a ``generation_extras.LogitEdits``) for every utterance (a
+        session: for every request that brings none of its own). ``None`` is the neutral record: the node is there and changes no logit, how a
+        session is opened when only some requests will bring edits. ``enabled=False`` switches the node off (the state of a new engine).
+        ``ValueError`` inside a session that holds a request."""
+        if not enabled:
+            N.check(self.lib.ptts_set_logit_edits(self._h, None, _stream_ptr(device=self.device)), "ptts_set_logit_edits")
+            self.logit_edits = None
+            return
+        rec, keep = self._logit_edits(edits)
+        N.check(self.lib.ptts_set_logit_edits(self._h, C.byref(rec), _stream_ptr(device=self.device)), "ptts_set_logit_edits")
+        del keep
+        from .generation_extras import LogitEdits
+
+        self.logit_edits = LogitEdits() if edits is None else edits
+
+    def set_slot_logit_edits(self, slot: int, edits=None, default: bool = False):
+        """The record the next admission into the idle slot ``slot`` runs under (``ptts_set_slot_logit_edits``), its first token included;
+        ``default=True`` restores the session's record, as ``retire_row`` does. Only in a session begun with the node on."""
+        rec, keep = (None, None) if default else self._logit_edits(edits)
+        N.check(self.lib.ptts_set_slot_logit_edits(self._h, int(slot), None if rec is None else C.byref(rec), _stream_ptr(device=self.device)),
+                "ptts_set_slot_logit_edits")
+        del keep
 
     def prefill(self, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
                 prompt_mask: Optional[torch.Tensor], sample: bool = True):

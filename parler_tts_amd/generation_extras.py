@@ -12,7 +12,7 @@ here: transformers' OWN classes, instantiated with the arguments and in the orde
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -88,6 +88,105 @@ def active_extras(gc) -> List[str]:
             if v is not None and 0.0 < v < 1.0:
                 on.append(name)
     return on
+
+
+# The options the logit-edit node computes on the device (include/ptts_logit_edit.h, model.enable_device_logit_edits()): pure functions of the
+# step's logits, the utterance's clock and fixed token lists.
+LOGIT_EDIT_OPTIONS = ("sequence_bias", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "exponential_decay_length_penalty")
+
+
+class LogitEdits(NamedTuple):
+    """The five options in the form the engine takes (``DecoderEngine.set_logit_edits``); every field empty / ``None``: the neutral record."""
+    bias: Tuple[Tuple[int, float], ...] = ()    # sequence_bias: (token, bias), single-token keys
+    bad: Tuple[int, ...] = ()                   # bad_words_ids: single-token entries ([eos] among them still is: the library drops it, the stage stays)
+    suppress: Tuple[int, ...] = ()              # suppress_tokens inside [0, V)
+    begin_suppress: Tuple[int, ...] = ()        # begin_suppress_tokens inside [0, V)
+    decay: Optional[Tuple[int, float]] = None   # exponential_decay_length_penalty = (start, factor)
+    suppress_on: bool = False                   # the option was given (a list of nothing but tokens outside the vocabulary still is a stage)
+    begin_suppress_on: bool = False
+
+    @property
+    def neutral(self) -> bool:
+        return not (self.bias or self.bad or self.suppress_on or self.begin_suppress_on or self.decay is not None)
+
+
+def _token_list(name: str, tokens, vocab_size: int) -> Tuple[int, ...]:
+    try:
+        vals = list(tokens)
+    except TypeError:
+        raise ValueError(f"`{name}` must be a list of token ids, got {tokens!r}") from None
+    out = []
+    for t in vals:
+        try:
+            whole = not isinstance(t, bool) and int(t) == t
+        except (TypeError, ValueError):
+            whole = False
+        if not whole:
+            raise ValueError(f"`{name}` must be a list of integer token ids, got {tokens!r}")
+        if 0 <= int(t) < vocab_size:  # torch.isin over arange(vocab_size): a token outside it matches nothing
+            out.append(int(t))
+    return tuple(out)
+
+
+def logit_edits_of(vocab_size: int, eos_token_id: int, max_length: Optional[int] = None, sequence_bias=None, bad_words_ids=None, suppress_tokens=None,
+                   begin_suppress_tokens=None, exponential_decay_length_penalty=None) -> LogitEdits:
+    """The five options as the record of the device node, or ``ValueError`` naming what the node does not compute (a multi-token key, a token
+    outside the vocabulary, a non-finite bias, a bad decay pair). ``sequence_bias`` and ``bad_words_ids`` pass transformers' own validation
+    first (the constructors of its two processors), so nothing is accepted here that the host loop would refuse."""
+    import math
+
+    from transformers.generation import logits_process as LP
+
+    bias, bad, sup, beg, decay = (), (), (), (), None
+    if sequence_bias is not None:
+        keys = LP.SequenceBiasLogitsProcessor(sequence_bias=sequence_bias).sequence_bias
+        if any(len(k) != 1 for k in keys):
+            raise ValueError(f"`sequence_bias` on the device takes single-token keys only, got {sorted(k for k in keys if len(k) != 1)}")
+        for (tok,), b in keys.items():
+            if not 0 <= int(tok) < vocab_size:
+                raise ValueError(f"`sequence_bias` token {tok} lies outside the vocabulary [0, {vocab_size})")
+            if not math.isfinite(float(b)):
+                raise ValueError(f"`sequence_bias` on the device takes finite biases only, got {b} for token {tok}")
+        bias = tuple((int(k[0]), float(b)) for k, b in keys.items())
+    if bad_words_ids is not None:
+        LP.NoBadWordsLogitsProcessor(bad_words_ids, torch.tensor([eos_token_id]))  # its validation. It drops [eos] and still adds its (zero) bias row
+        if any(len(w) != 1 for w in bad_words_ids):
+            raise ValueError(f"`bad_words_ids` on the device takes single-token entries only, got {[list(w) for w in bad_words_ids if len(w) != 1]}")
+        for (tok,) in bad_words_ids:
+            if not 0 <= int(tok) < vocab_size:
+                raise ValueError(f"`bad_words_ids` token {tok} lies outside the vocabulary [0, {vocab_size})")
+        bad = tuple(int(w[0]) for w in bad_words_ids)
+    if suppress_tokens is not None:
+        sup = _token_list("suppress_tokens", suppress_tokens, vocab_size)
+    if begin_suppress_tokens is not None:
+        beg = _token_list("begin_suppress_tokens", begin_suppress_tokens, vocab_size)
+    if exponential_decay_length_penalty is not None:
+        try:
+            start, factor = exponential_decay_length_penalty
+            ok = not isinstance(start, bool) and int(start) == start and int(start) >= 0 and math.isfinite(float(factor)) and float(factor) > 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"`exponential_decay_length_penalty` must be (start >= 0, factor > 0 and finite), got {exponential_decay_length_penalty!r}")
+        try:  # Python's float pow raises where the C library returns inf: such a pair stays with the host loop's own error
+            pow(float(factor), int(max_length or 0))
+        except OverflowError:
+            raise ValueError(f"`exponential_decay_length_penalty` factor {factor} overflows within max_length {max_length}") from None
+        decay = (int(start), float(factor))
+    return LogitEdits(bias, bad, sup, beg, decay, suppress_tokens is not None, begin_suppress_tokens is not None)
+
+
+def logit_edit_rule_broken(edits: LogitEdits, repetition_penalty, no_repeat_ngram_size, min_new_tokens) -> Optional[str]:
+    """The two cases in which the node's place in the chain (behind the history penalties, in front of the tail) is not transformers' order;
+    the message names the rule, ``None``: the record may run on the device beside these values."""
+    pen = (repetition_penalty is not None and repetition_penalty != 1.0) or bool(no_repeat_ngram_size)
+    if edits.bias and pen:
+        return ("`sequence_bias` with a history penalty (repetition_penalty / no_repeat_ngram_size): transformers adds the bias in front of the "
+                "penalty and the device node runs behind it")
+    if edits.decay is not None and int(min_new_tokens or 0) > edits.decay[0] + 1:
+        return (f"`exponential_decay_length_penalty` inside the min_new_tokens block (min_new_tokens {int(min_new_tokens)} > start {edits.decay[0]} + 1): "
+                "transformers turns the blocked EOS logit into NaN there")
+    return None
 
 
 def build_processors(gc, input_ids_seq_length: int, encoder_input_ids: Optional[torch.Tensor], custom, device, eos_token_id: int):

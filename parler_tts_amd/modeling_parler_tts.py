@@ -23,7 +23,8 @@ from torch import nn
 from .configuration_parler_tts import DACConfig, ParlerTTSConfig, ParlerTTSDecoderConfig
 from .dac_wrapper import DACModel
 from .engine import DecoderEngine, T5Engine
-from .generation_extras import active_extras, build_processors, build_stopping_criteria, check_generation_mode, check_model_kwargs
+from .generation_extras import (LOGIT_EDIT_OPTIONS, active_extras, build_processors, build_stopping_criteria, check_generation_mode, check_model_kwargs,
+                                logit_edit_rule_broken, logit_edits_of)
 from .logits_processors import ParlerTTSLogitsProcessor
 
 # the generation options that have a device implementation behind a switch of the model (enable_device_penalties / enable_device_warpers)
@@ -728,6 +729,18 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         self._engine = None
         return self
 
+    def enable_device_logit_edits(self, enabled: bool = True):
+        """Opt-in: ``sequence_bias`` and ``bad_words_ids`` with single-token keys, ``exponential_decay_length_penalty``, ``suppress_tokens`` and
+        ``begin_suppress_tokens`` run on the device, as one kernel node between the history-penalty node and the sampler tail
+        (``ptts_logit_edit.h``), bit for bit what transformers' five processors compute. ``generate()`` then stays on the captured step graph
+        when every option beyond the device sampler's has a device implementation under the switches that are on, the request is eligible -
+        single-token keys only, no ``sequence_bias`` beside a history penalty, ``min_new_tokens <= start + 1`` beside a decay - and the caller
+        brings no processors, stopping criteria or score outputs (anything else runs the host loop as before), and ``ContinuousBatcher``
+        takes the five options for a session and per request. Off (the default): every call is routed exactly as without this switch."""
+        self.device_logit_edits = bool(enabled)
+        self._engine = None
+        return self
+
     def _get_engine(self, B: int, N: int, P: int, max_length: int, T: int = 0) -> DecoderEngine:
         """T = voice-prompt frames: the prefill runs the P prompt positions, the BOS column and the T given columns in one pass."""
         dev, dt = self.device, self.dtype
@@ -1000,9 +1013,21 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         # model.enable_device_penalties(): the two history penalties alone, with nothing that needs the host's view of a step, stay on the device
         # model.enable_device_warpers(): likewise min_p / typical_p / epsilon_cutoff / eta_cutoff, which the sampler tail applies behind top-p
         # (active only in a sampling call). With both switches a call may bring both kinds
-        on_device = (_DEVICE_PENALTIES if getattr(self, "device_penalties", False) else ()) + (_DEVICE_WARPERS if getattr(self, "device_warpers", False) else ())
+        # model.enable_device_logit_edits(): likewise the five position / token edits, when the request is one the node computes in transformers'
+        # order (single-token keys, and the two rules of ptts_logit_edit.h); a request that is not runs the host loop, which also owns its errors
+        on_device = ((_DEVICE_PENALTIES if getattr(self, "device_penalties", False) else ()) + (_DEVICE_WARPERS if getattr(self, "device_warpers", False) else ())
+                     + (LOGIT_EDIT_OPTIONS if getattr(self, "device_logit_edits", False) else ()))
         stays = (bool(extras) and set(extras) <= set(on_device)
                  and not manual and not (bool(getattr(gc, "return_dict_in_generate", False)) and (getattr(gc, "output_scores", False) or getattr(gc, "output_logits", False))))
+        edits = None
+        if stays and any(x in LOGIT_EDIT_OPTIONS for x in extras):
+            try:
+                edits = logit_edits_of(d.vocab_size, d.eos_token_id, max_length, **{n: getattr(gc, n, None) for n in LOGIT_EDIT_OPTIONS})
+            except ValueError:
+                stays = False
+            if stays and logit_edit_rule_broken(edits, getattr(gc, "repetition_penalty", None), getattr(gc, "no_repeat_ngram_size", None), min_new):
+                stays = False
+        dev_edit = stays and edits is not None
         dev_pen = stays and any(x in _DEVICE_PENALTIES for x in extras)
         dev_warp = stays and any(x in _DEVICE_WARPERS for x in extras)
         if stays:
@@ -1033,6 +1058,10 @@ class ParlerTTSForConditionalGeneration(nn.Module):
             eng.set_sample_warp(min_p=gc.min_p, typical_p=gc.typical_p, epsilon_cutoff=gc.epsilon_cutoff, eta_cutoff=gc.eta_cutoff)
         elif getattr(eng, "sample_warp", None) is not None:  # the instances of an earlier call: off, this call's graphs are the plain ones
             eng.set_sample_warp(enabled=False)
+        if dev_edit:
+            eng.set_logit_edits(edits)
+        elif getattr(eng, "logit_edits", None) is not None:  # the node of an earlier call: off, this call's graphs are the plain ones
+            eng.set_logit_edits(enabled=False)
         pad, eos = gc.pad_token_id if gc.pad_token_id is not None else d.pad_token_id, d.eos_token_id
         bos_col = torch.full((B * K, 1), bos, dtype=torch.long, device=dev)
         dec_ids = bos_col if prefix is None else torch.cat([bos_col, prefix], dim=-1)  # :3011-3018
