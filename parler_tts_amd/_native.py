@@ -54,6 +54,11 @@ class PttsLogitEdits(C.Structure):
                 ("decay_on", C.c_int32), ("decay_start", C.c_int32), ("decay_factor", C.c_double)]
 
 
+class PttsStepRecords(C.Structure):
+    """ptts_step_records (include/ptts_step_record.h): the caller's device arenas of one call's / one slot's step records."""
+    _fields_ = [("scores_dev", C.c_void_p), ("logits_dev", C.c_void_p), ("cap_steps", C.c_int32)]
+
+
 class PttsScoreIO(C.Structure):
     """ptts_score_io (include/ptts_score.h): device pointers of one teacher-forced scoring call."""
     _fields_ = [("input_ids", C.c_void_p), ("labels", C.c_void_p), ("nll", C.c_void_p), ("counted", C.c_void_p), ("logits", C.c_void_p)]
@@ -183,6 +188,12 @@ LOGIT_EDIT_SYMBOLS = {
     "ptts_set_slot_logit_edits": (C.c_int, [_VP, _I32, C.POINTER(PttsLogitEdits), _VP]),
 }
 
+# include/ptts_step_record.h, additive likewise: output_scores / output_logits written on the device, step by step, into the caller's arenas
+STEP_RECORD_SYMBOLS = {
+    "ptts_set_step_records": (C.c_int, [_VP, C.POINTER(PttsStepRecords), _VP]),
+    "ptts_set_slot_step_records": (C.c_int, [_VP, _I32, C.POINTER(PttsStepRecords), _VP]),
+}
+
 # include/ptts_score.h, additive likewise: one teacher-forced forward ending in the fused LM-heads + cross-entropy kernel
 SCORE_SYMBOLS = {
     "ptts_score": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(PttsScoreIO), _VP]),
@@ -211,7 +222,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         raise NativeLibraryError(f"failed to load {p}: {e}") from e
     for name, (res, args) in (list(SYMBOLS.items()) + list(SESSION_SYMBOLS.items()) + list(SESSION_KV8_SYMBOLS.items())
                               + list(SESSION_VOICE_SYMBOLS.items()) + list(SESSION_VOICE_ROWS_SYMBOLS.items()) + list(DAC_STREAM_VOICE_SYMBOLS.items()) + list(PENALTY_SYMBOLS.items())
-                              + list(WARP_SYMBOLS.items()) + list(SCORE_SYMBOLS.items()) + list(LOGIT_EDIT_SYMBOLS.items())):
+                              + list(WARP_SYMBOLS.items()) + list(SCORE_SYMBOLS.items()) + list(LOGIT_EDIT_SYMBOLS.items()) + list(STEP_RECORD_SYMBOLS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -34,7 +34,7 @@ _DEVICE_WARPERS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
 
 class _Request:
     __slots__ = ("ticket", "enc", "enc_mask", "prompt", "prompt_mask", "max_length", "gen", "voice", "prompt_kept", "pen", "warp", "edits",
-                 "cols", "absorbed", "kept", "emitted", "first_out")
+                 "cols", "absorbed", "kept", "emitted", "first_out", "want_records", "records")
 
     def __init__(self, ticket, enc, enc_mask, prompt, prompt_mask, max_length, gen=None, voice=None, prompt_kept=None, pen=None, warp=None, edits=None):
         self.edits = edits  # the request's own generation_extras.LogitEdits (set_slot_logit_edits), or None: the session's
@@ -50,6 +50,9 @@ class _Request:
         self.cols = 0
         # Streaming: raw frames the stream table has absorbed, frames it kept of them and frames emitted; the first chunk is still outstanding
         self.absorbed, self.kept, self.emitted, self.first_out = 0, 0, 0, True
+        # step records (submit's output_scores / output_logits): the kinds asked for, and the slot's buffers {kind: [max_new_tokens, K, V]} from
+        # the admission on
+        self.want_records, self.records = (False, False), None
 
     @property
     def T(self) -> int:
@@ -105,6 +108,10 @@ class ContinuousBatcher:
     emits more than ``max_emit = window_frames - 2 * halo`` frames per slot (``ptts_dac_stream_decode_capped``): a long prompt leaves in
     several chunks, starting at the poll that admits it, and a finished slot is drained by repeated final passes before it is reused. A
     request without a prompt never has that much ready: its chunks are the ones of a session without the option.
+
+    A model with ``enable_device_step_records()`` opens the session with step records on (``ptts_step_record.h``): ``submit(output_scores=True)`` /
+    ``submit(output_logits=True)`` then records that request's per-step scores / raw logits on the device, and ``step_records(ticket)`` hands them
+    out once the request has finished. Requests that ask for none run beside them untouched.
 
     ``admit_voice_groups`` (default ``False``; needs ``max_voice_frames > 0`` and ``admit_batch > 1``, ``ValueError`` otherwise): requests with
     voice prompts are admitted in groups too. The FIFO queue is cut into runs of the same kind - with a prompt, without - and each run into
@@ -213,6 +220,13 @@ class ContinuousBatcher:
             self.eng.set_logit_edits(self._edits)
         elif getattr(self.eng, "logit_edits", None) is not None:
             self.eng.set_logit_edits(enabled=False)
+        # Step records likewise: "on, no slot records yet" before the session begins; a request's buffers are set at its admission
+        self.device_step_records = bool(getattr(model, "device_step_records", False))
+        self._records: Dict[int, Dict[str, torch.Tensor]] = {}  # ticket -> the finished request's records, until step_records() reads them
+        if self.device_step_records:
+            self.eng.set_step_records(None, None, 0)
+        elif getattr(self.eng, "step_records", None) is not None:
+            self.eng.set_step_records(enabled=False)
         # model.enable_fp8_kv_cache() and more than 8 rows: the session runs on the e4m3 self-attention cache
         self.eng.begin_session(self.slots, self.N, self.P, **({"kv_fp8": True} if getattr(self.eng, "kv_fp8", False) else {}))
         # what a request's own record starts from (submit): the session's values as the caller gave them (top_k is not zeroed for a greedy session)
@@ -324,7 +338,8 @@ class ContinuousBatcher:
                min_new_tokens: Optional[int] = None, seed: Optional[int] = None, input_values=None, decoder_input_ids=None,
                repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_p: Optional[float] = None,
                typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None, sequence_bias=None,
-               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, exponential_decay_length_penalty=None) -> int:
+               bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, exponential_decay_length_penalty=None,
+               output_scores: bool = False, output_logits: bool = False) -> int:
         """Queues one request and returns its ticket. The description is encoded here (the model's own T5 path).
         ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``min_new_tokens``: the request's own sampler settings; an option left ``None``
         takes the session's value. A request that sets any of them (or ``seed``) draws from its own stream ``(seed, column, codebook)``: with a
@@ -343,7 +358,13 @@ class ContinuousBatcher:
         ``exponential_decay_length_penalty`` (a model with ``enable_device_logit_edits()``; ``NotImplementedError`` otherwise): the request's
         own logit edits, an option left ``None`` taking the session's value. The begin index and the decay's start count from the request's
         own given columns (BOS and its voice prompt's). ``ValueError``: a multi-token key, a token outside the vocabulary, ``sequence_bias``
-        beside a history penalty, a decay with ``min_new_tokens > start + 1``."""
+        beside a history penalty, a decay with ``min_new_tokens > start + 1``.
+        ``output_scores`` / ``output_logits`` (a model with ``enable_device_step_records()``; ``ValueError`` otherwise): the request's per-step
+        processed scores / raw logits are recorded on the device into buffers ``[max_new_tokens, K, V]`` (fp32, allocated at its admission);
+        ``step_records(ticket)`` returns them once the request has finished."""
+        if (output_scores or output_logits) and not self.device_step_records:
+            raise ValueError("`output_scores` / `output_logits` need the session's step records: call model.enable_device_step_records() before "
+                             "constructing the batcher")
         own_edits = dict(sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
                          begin_suppress_tokens=begin_suppress_tokens, exponential_decay_length_penalty=exponential_decay_length_penalty)
         if any(v is not None for v in own_edits.values()) and not self.device_logit_edits:
@@ -399,9 +420,20 @@ class ContinuousBatcher:
         prompt_kept = None
         if voice is not None and self.stream_voice == "skip":  # what the filter keeps of the prompt, known here: the codec's pairs do not say
             prompt_kept = [0] + self._valid_frames(voice).long().cumsum(0).tolist()
-        self._queue.append(_Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept, *(() if pen is None else (pen,)),
-                                    **({} if warp is None else {"warp": warp}), **({} if edits is None else {"edits": edits})))
+        req = _Request(ticket, enc, mask, prompt, pmask, max_length, gen, voice, prompt_kept, *(() if pen is None else (pen,)),
+                       **({} if warp is None else {"warp": warp}), **({} if edits is None else {"edits": edits}))
+        req.want_records = (bool(output_scores), bool(output_logits))
+        self._queue.append(req)
         return ticket
+
+    def step_records(self, ticket: int) -> Dict[str, torch.Tensor]:
+        """The step records of a finished request that asked for them: ``{"scores": [steps, K, V], "logits": [steps, K, V]}`` with the kinds it
+        asked for, ``steps`` = the tokens it generated (step i: what ``generate()`` returns as ``scores[i]`` / ``logits[i]`` for the same request
+        alone). Available once the request's waveform (its last chunk) has been yielded; handed out once - the batcher keeps no reference.
+        Until then the batcher holds the tensors (``max_new_tokens x K x V x 4`` bytes per kind and request as allocated): a caller that asks for
+        records reads them - ``run()`` does not - or drops them with ``close()``.
+        ``KeyError``: an unknown, unfinished or cancelled ticket, one that asked for no record, or one read before."""
+        return self._records.pop(ticket)
 
     def _voice(self, input_values, decoder_input_ids) -> Optional[torch.Tensor]:
         """The voice prompt of one request as un-delayed codes [K, T >= 1], or None: generate()'s own preparation (``input_values`` through
@@ -451,6 +483,11 @@ class ContinuousBatcher:
                     self.eng.set_slot_sample_warp(s, *r.warp)
                 if r.edits is not None:
                     self.eng.set_slot_logit_edits(s, r.edits)
+                if any(r.want_records):  # the slot's own buffers, set before the admission: its first-token tail is step 0
+                    cap = r.max_length - 1 - r.T
+                    r.records = {kind: torch.empty([cap, self.K, self.V], dtype=torch.float32, device=self.model.device)
+                                 for kind, on in zip(("scores", "logits"), r.want_records) if on}
+                    self.eng.set_slot_step_records(s, r.records.get("scores"), r.records.get("logits"), cap)
             reqs = [self._queue.popleft() for _ in group]
             if len(reqs) == 1:
                 (s, r), = group
@@ -511,8 +548,12 @@ class ContinuousBatcher:
             while rows:  # more than once only under stream_voice_prompts: a finished slot that had more than max_emit frames ready is drained here
                 rows = self._codec_pass(rows)
         group = [(r, self.eng.row_ids(s, cur[s])) for s, r in whole]
-        for s, _ in busy:
+        for s, r in busy:
             if not live[s]:
+                if r.records is not None:  # steps made = the slot's final clock - its given columns
+                    steps = max(0, min(int(cur[s]), r.max_length) - 1 - r.T)
+                    self._records[r.ticket] = {kind: buf[:steps] for kind, buf in r.records.items()}
+                    r.records = None
                 self._retire(s)
         if group:
             self._decode_group(group)
@@ -629,6 +670,7 @@ class ContinuousBatcher:
             self._queue.remove(r)
         running = [s for s, r in enumerate(self._slot) if r is not None and r.ticket == ticket]
         for s in running:
+            self._slot[s].records = None  # the slot's buffers go with it (retire_row clears the engine's record)
             self._retire(s)
         if queued or running:
             out = self._done if self.chunk is None else self._out  # in place: a generator of _drain holds on to it
@@ -690,3 +732,4 @@ class ContinuousBatcher:
         for s in range(self.slots):
             if self._slot[s] is not None:
                 self._retire(s)
+        self._records.clear()  # step records nobody read

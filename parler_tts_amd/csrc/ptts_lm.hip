@@ -16,6 +16,7 @@
 #include "../../include/ptts_warp.h"
 #include "../../include/ptts_logit_edit.h"
 #include "../../include/ptts_score.h"
+#include "../../include/ptts_step_record.h"
 #include "ptts_lm_kernels.h"
 #include "ptts_gemv.h"
 #include "ptts_step_plan.h"
@@ -24,6 +25,7 @@
 #include "ptts_tail_launch.h"
 #include "ptts_penalty_launch.h"
 #include "ptts_logit_edit_launch.h"
+#include "ptts_step_record_launch.h"
 #include "ptts_score_launch.h"
 
 thread_local std::string g_ptts_err;
@@ -141,6 +143,11 @@ struct ptts_engine {
   unsigned char* le_stage = nullptr;     // pinned host: one staging area per record, what its last upload copies from
   size_t le_stage_stride = 0;
   std::vector<hipEvent_t> le_ev;         // per record: the end of that upload (waited for before the area is written again)
+  // step records (ptts_step_record.h): the raw-logits node in front of the penalty node while rec_node, the RECORD tail instances while rec_tail
+  StepRecord* rec = nullptr;             // [max_batch] device: the record of each utterance / slot; allocated at the first switch-on, the step graphs hold the pointer
+  bool rec_on = false;                   // ptts_set_step_records(non-null) holds
+  bool rec_node = false, rec_tail = false;  // what every tail launch (and the step graph: a key bit each) carries: both in a session, by the arenas given in a static call
+  ptts_step_records rec_call = {};       // the arenas of ptts_set_step_records: laid out over the batch at the next ptts_prefill
 #ifdef PTTS_TIMING
   long long* dbg_stamps = nullptr;  // measurement build: [layers + 1][5 or 7 nodes][3 workgroups][16] wall-clock stamps of the decode step (ptts_debug_stamps)
 #endif
@@ -576,6 +583,14 @@ int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next
   t.logits = v.logits; t.ids = v.ids; t.ids_ld = e->ids_ld; t.cur_len = v.cur_len; t.unfinished = v.unfinished;
   t.has_eos = v.has_eos; t.first_unf = v.first_unf; t.gen = e->gen; t.sort_buf = e->sort_buf;
   t.B = v.B; t.K = e->cfg.num_codebooks; t.V = e->cfg.vocab_size; t.eos = e->cfg.eos_token_id; t.pad = e->cfg.pad_token_id;
+  const StepRecord* rec = e->rec_on ? e->rec + (v.cur_len - e->cur_len) : nullptr;  // indexed like cur_len
+  if (rec && e->rec_node) {  // the logits as the heads wrote them: in front of the nodes that rewrite them in place
+    LogitsRecordArgs r = {};
+    r.logits = v.logits; r.cur_len = v.cur_len; r.unfinished = v.unfinished; r.rec = rec;
+    r.t_prefix = v.session ? e->slot_T + (v.cur_len - e->cur_len) : &e->dims->T_prefix; r.t_prefix_stride = v.session ? 1 : 0;  // as the logit-edit node
+    r.B = v.B; r.K = e->cfg.num_codebooks; r.V = e->cfg.vocab_size; r.session = v.session ? 1 : 0;
+    if (!step_logits_record_launch(r, row < 0 ? 0 : row, row < 0 ? v.B : 1, st)) return ptts_fail(PTTS_E_INVALID, "step records: bad launch arguments");
+  }
   if (e->pen_on) {  // history penalties rewrite the logits the tail is about to read; the records are indexed like cur_len
     PenaltyArgs p = {};
     p.logits = v.logits; p.ids = v.ids; p.cur_len = v.cur_len; p.pen = e->pen + (v.cur_len - e->cur_len);
@@ -595,8 +610,10 @@ int launch_tail(const ptts_engine* e, FwdView v, hipStream_t st, bool embed_next
   // the instance (NV by vocabulary, static or per-slot clocks) and the wave count are chosen in tail_launch, shared with the test harness
   // warpers on: the WARP instances, with the records indexed like cur_len (null picks the instances of an engine without the feature)
   const DevWarp* warp = e->warp_on ? e->warp + (v.cur_len - e->cur_len) : nullptr;
-  if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen, e->slot_T, warp);
-  else tail_launch(t, nullptr, 0, dim3(v.B), st, nullptr, nullptr, warp);
+  // step records on: the RECORD instances, likewise
+  const StepRecord* trec = e->rec_tail ? rec : nullptr;
+  if (v.session) tail_launch(t, e->row_maxlen, row < 0 ? 0 : row, dim3(row < 0 ? v.B : 1), st, e->slot_gen, e->slot_T, warp, trec);
+  else tail_launch(t, nullptr, 0, dim3(v.B), st, nullptr, nullptr, warp, trec);
   return launch_status("tail");
 }
 
@@ -1117,6 +1134,12 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
   const int K = c.num_codebooks;
   e->B = B; e->N = N; e->P = P;
   e->session = false;  // a static batch ends a continuous session
+  if (e->rec_on) {  // step records: the arenas of ptts_set_step_records laid out over this call's B utterances ([cap_steps][B][K][V])
+    const long long kv = (long long)K * c.vocab_size;
+    e->rec_node = e->rec_call.logits_dev != nullptr; e->rec_tail = e->rec_call.scores_dev != nullptr;
+    hipLaunchKernelGGL(set_step_record_kernel, dim3((B + 255) / 256), dim3(256), 0, st, e->rec, 0, B,
+                       StepRecord{e->rec_call.scores_dev, e->rec_call.logits_dev, e->rec_call.cap_steps, 0, (long long)B * kv}, kv);
+  }
   if (sample) PTTS_HIP(hipEventRecord(e->ev_pre0, st));
   launch_set_params(e, e->pending_T, st);
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished,
@@ -1167,12 +1190,14 @@ extern "C" int ptts_prefill(ptts_engine* e, const float* enc_dev, const int32_t*
 static int get_graph(ptts_engine* e, int kv_bound, hipGraphExec_t* out) {
   // The node set of the step is its plan (ptts_step_plan.h), and gemv_plan / strip_plan take no engine: beside the engine's fixed cfg, sc and sw they
   // see the batch size, the folded-cross-block flag and the 64-position bucket `kv_bound` (also a kernel argument: the attention fetch bound) -
-  // all three in the key. The tail adds session, pen_on, warp_on and le_on: the key's upper bits. (Several steps of one bucket per
+  // all three in the key. The tail adds session, pen_on, warp_on, le_on and the two step-record bits: the key's upper bits. (Several steps of one bucket per
   // graph launch - round 4's PTTS_GRAPH_STEPS - measured 0.3-0.7 %, profiles/r04_experiments.txt call 19: removed in round 6.)
   const long long key = e->B * 2 + (e->xfold_valid ? 1 : 0) + 4096LL * (kv_bound / 64) + (e->session ? 1LL << 40 : 0)  // session steps end in their own tail
                         + (e->pen_on ? 1LL << 41 : 0)                                                                            // the history-penalty node is present
                         + (e->warp_on ? 1LL << 42 : 0)                                                                           // the tail is the WARP instance
-                        + (e->le_on ? 1LL << 43 : 0);                                                                            // the logit-edit node is present
+                        + (e->le_on ? 1LL << 43 : 0)                                                                             // the logit-edit node is present
+                        + (e->rec_on && e->rec_node ? 1LL << 44 : 0)                                                             // the raw-logits record node is present
+                        + (e->rec_on && e->rec_tail ? 1LL << 45 : 0);                                                            // the tail is the RECORD instance
   auto it = e->graphs.find(key);
   if (it != e->graphs.end()) { if (out) *out = it->second; return PTTS_OK; }
   hipGraph_t g = nullptr;
@@ -1329,6 +1354,10 @@ static int session_begin(ptts_engine* e, int B, int N, int P, void* stream, bool
   if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->pen, 0, c.max_batch, e->pen_default);  // ... nor penalties of its own
   if (e->warp_on) hipLaunchKernelGGL(set_warp_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->warp, 0, c.max_batch, e->warp_default);  // ... nor warpers
   if (e->le_on) hipLaunchKernelGGL(copy_logit_edit_kernel, dim3(4, c.max_batch), dim3(256), 0, st, e->le, c.max_batch, 0);  // ... nor logit edits
+  if (e->rec_on) {  // ... nor a step record; the session carries both the logits node and the RECORD tail: a slot may ask for either kind
+    e->rec_node = e->rec_tail = true;
+    hipLaunchKernelGGL(set_step_record_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, st, e->rec, 0, c.max_batch, StepRecord{}, 0LL);
+  }
   // every slot idle; masks all-ones and step inputs zero so that an idle slot's (discarded) step computes on defined values
   hipLaunchKernelGGL(session_reset_rows_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, e->ids, e->ids_ld, e->cur_len, e->unfinished, e->has_eos,
                      e->first_unf, e->row_maxlen, 0, B, K, c.bos_token_id, 0, e->gp.max_length);
@@ -1594,6 +1623,7 @@ extern "C" int ptts_retire_row(ptts_engine* e, int32_t row, void* stream) {
   if (e->pen_on) hipLaunchKernelGGL(set_penalty_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->pen, row, 1, e->pen_default);  // ... under the session's penalties
   if (e->warp_on) hipLaunchKernelGGL(set_warp_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->warp, row, 1, e->warp_default);  // ... and warpers
   if (e->le_on) hipLaunchKernelGGL(copy_logit_edit_kernel, dim3(4, 1), dim3(256), 0, pick_stream(e, stream), e->le, e->cfg.max_batch, row);  // ... and logit edits
+  if (e->rec_on) hipLaunchKernelGGL(set_step_record_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->rec, row, 1, StepRecord{}, 0LL);  // ... and records nothing
   e->slot_busy[row] = 0; e->slot_ub[row] = e->P + 1;
   return PTTS_OK;
 }
@@ -1674,6 +1704,47 @@ extern "C" int ptts_set_slot_sample_warp(ptts_engine* e, int32_t row, const ptts
   const DevWarp rec = w ? DevWarp{w->min_p, w->typical_p, w->epsilon_cutoff, w->eta_cutoff} : e->warp_default;
   hipLaunchKernelGGL(set_warp_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->warp, row, 1, rec);
   return launch_status("set_warp");
+}
+
+// ---- step records (ptts_step_record.h) ----------------------------------------------------------------------------------------------------
+static int check_step_records(const ptts_step_records* r) {
+  PTTS_CHECK(r->cap_steps >= 0, PTTS_E_INVALID, "step records: cap_steps must be >= 0, got %d", r->cap_steps);
+  PTTS_CHECK(r->cap_steps > 0 || (!r->scores_dev && !r->logits_dev), PTTS_E_INVALID, "step records: an arena with cap_steps == 0");
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_step_records(ptts_engine* e, const ptts_step_records* r, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  if (e->session)  // a session that holds a request is running: its node set and its tail instance were fixed at its begin
+    for (char busy : e->slot_busy) PTTS_CHECK(!busy, PTTS_E_INVALID, "ptts_set_step_records inside a running session (call it before ptts_session_begin)");
+  if (!r) { e->rec_on = e->rec_node = e->rec_tail = false; e->rec_call = ptts_step_records{}; return PTTS_OK; }
+  PTTS_TRY(check_step_records(r));
+  const ptts_config& c = e->cfg;
+  PTTS_CHECK(c.vocab_size <= PTTS_SORT_N, PTTS_E_UNSUPPORTED, "step records serve vocabularies up to %d, this engine's is %d", PTTS_SORT_N, c.vocab_size);
+  PTTS_DEVICE(c.device);
+  if (!e->rec) PTTS_TRY(e->alloc(&e->rec, (size_t)c.max_batch));
+  hipLaunchKernelGGL(set_step_record_kernel, dim3((c.max_batch + 255) / 256), dim3(256), 0, pick_stream(e, stream), e->rec, 0, c.max_batch, StepRecord{}, 0LL);
+  PTTS_TRY(launch_status("set_step_record"));
+  e->rec_call = *r;
+  e->rec_on = true;
+  // until the next ptts_prefill / ptts_session_begin decides: what a call of this shape will carry (both kinds when no arena is given: a session)
+  e->rec_node = r->logits_dev != nullptr || !r->scores_dev;
+  e->rec_tail = r->scores_dev != nullptr || !r->logits_dev;
+  return PTTS_OK;
+}
+
+extern "C" int ptts_set_slot_step_records(ptts_engine* e, int32_t row, const ptts_step_records* r, void* stream) {
+  PTTS_CHECK(e, PTTS_E_INVALID, "null engine");
+  PTTS_CHECK(e->session, PTTS_E_INVALID, "ptts_set_slot_step_records: no continuous session (ptts_session_begin)");
+  PTTS_CHECK(e->rec_on, PTTS_E_INVALID, "ptts_set_slot_step_records: the session was begun without step records (ptts_set_step_records first)");
+  PTTS_CHECK(row >= 0 && row < e->B, PTTS_E_INVALID, "slot %d outside the session's %d slots", row, e->B);
+  PTTS_CHECK(!e->slot_busy[row], PTTS_E_INVALID, "slot %d still holds a request (ptts_retire_row first)", row);
+  if (r) PTTS_TRY(check_step_records(r));
+  PTTS_DEVICE(e->cfg.device);
+  const long long kv = (long long)e->cfg.num_codebooks * e->cfg.vocab_size;
+  const StepRecord rec = r ? StepRecord{r->scores_dev, r->logits_dev, r->cap_steps, 0, kv} : StepRecord{};
+  hipLaunchKernelGGL(set_step_record_kernel, dim3(1), dim3(64), 0, pick_stream(e, stream), e->rec, row, 1, rec, 0LL);
+  return launch_status("set_step_record");
 }
 
 // ---- logit edits (ptts_logit_edit.h) ------------------------------------------------------------------------------------------------------

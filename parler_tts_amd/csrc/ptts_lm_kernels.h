@@ -9,6 +9,7 @@
 //   sampler state   ids int64 [B*K][ld], cur_len[B], unfinished[B*K], has_eos[B*K], first_unf[B]
 #pragma once
 #include "ptts_common.h"
+#include "ptts_step_record_kernels.h"
 
 // ------------------------------------------------------------------------------------------------------
 // device-resident per-call dims and generation parameters (so one captured hipGraph serves every call)
@@ -2622,6 +2623,7 @@ struct TailArgs {
 struct DevWarp {
   float min_p, typical_p, epsilon_cutoff, eta_cutoff;
 };
+// (the record of one utterance for the RECORD instances, StepRecord: ptts_step_record_kernels.h, shared with the raw-logits node)
 
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -2655,10 +2657,16 @@ __device__ __forceinline__ unsigned f32_key(float x) {
 //                   ln tot cancels, and x_i is recomputed from lg[i], so no new per-lane array is live
 //   epsilon_cutoff: drop p_i < v where x_i is below the maximum of the survivors
 //   eta_cutoff:     the same with eta = min(v, sqrt(v) exp(-H)), i.e. e_i < min(v tot, sqrt(v) exp(-A))
-template <int NV, bool WARP = false>
+// RECORD (the step-record instances, ptts_step_record.h): the processed scores of the row - what transformers' _sample appends to `scores` - go to
+// rec[0 .. V) unless rec is null: lg / temperature (the division of the first loop, so the bits are the sampler's own), -inf at the blocked EOS and
+// at every entry a stage REMOVED. Which entries those are is kept in one bit per entry of the lane (`drop`, NV <= 32), set where a stage's own
+// threshold test removes the entry - never read back from e[i] > 0: with top_p == 1 an entry whose numerator underflows to 0 is still kept by
+// transformers and has a finite score. Every addition sits behind `if constexpr (RECORD)`; nothing the draw reads is touched.
+template <int NV, bool WARP = false, bool RECORD = false>
 __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int lane, const DevGen& g, bool eos_blocked, int eos, float u01,
-                                               const DevWarp& wp = DevWarp{0.f, 1.f, 0.f, 0.f}) {
+                                               const DevWarp& wp = DevWarp{0.f, 1.f, 0.f, 0.f}, float* rec = nullptr) {
   const int nv = (V + 63) >> 6;
+  unsigned drop = 0u;  // RECORD: bit i = entry lane + 64 i was removed by a stage
   float x[NV];
   unsigned key[NV];
 #pragma unroll
@@ -2684,7 +2692,10 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-      if (i < nv && key[i] < T) x[i] = -INFINITY;
+      if (i < nv && key[i] < T) {
+        x[i] = -INFINITY;
+        if constexpr (RECORD) drop |= 1u << i;
+      }
   }
   float mx = -INFINITY;
 #pragma unroll
@@ -2713,7 +2724,10 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
     ls = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      if (i < nv && key[i] < L) e[i] = 0.f;
+      if (i < nv && key[i] < L) {
+        e[i] = 0.f;
+        if constexpr (RECORD) drop |= 1u << i;
+      }
       ls += e[i];
     }
     tot = wave_sum(ls);
@@ -2746,7 +2760,10 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
     if (wp.min_p > 0.f) {
 #pragma unroll
       for (int i = 0; i < NV; ++i)
-        if (e[i] < wp.min_p) e[i] = 0.f;
+        if (e[i] < wp.min_p) {
+          e[i] = 0.f;
+          if constexpr (RECORD) drop |= 1u << i;
+        }
       retotal();
     }
     if (wp.typical_p < 1.0f) {
@@ -2765,7 +2782,10 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
       }
 #pragma unroll
       for (int i = 0; i < NV; ++i)
-        if (key[i] > L) e[i] = 0.f;
+        if (key[i] > L) {
+          e[i] = 0.f;
+          if constexpr (RECORD) drop |= 1u << i;
+        }
       retotal();
     }
     if (wp.epsilon_cutoff > 0.f) {
@@ -2773,6 +2793,11 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
 #pragma unroll
       for (int i = 0; i < NV; ++i)
         if (i < nv && e[i] > 0.f && e[i] < thr && score(i) < smx) e[i] = 0.f;
+      if constexpr (RECORD) {  // p_i < threshold holds for a numerator that underflowed to 0 as well: e[i] stays 0, the entry is removed
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+          if (i < nv && e[i] == 0.f) drop |= 1u << i;
+      }
       retotal();
     }
     if (wp.eta_cutoff > 0.f) {
@@ -2780,6 +2805,11 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
 #pragma unroll
       for (int i = 0; i < NV; ++i)
         if (i < nv && e[i] > 0.f && e[i] < thr && score(i) < smx) e[i] = 0.f;
+      if constexpr (RECORD) {  // p_i < threshold holds for a numerator that underflowed to 0 as well: e[i] stays 0, the entry is removed
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+          if (i < nv && e[i] == 0.f) drop |= 1u << i;
+      }
       retotal();
     }
   }
@@ -2805,6 +2835,15 @@ __device__ __forceinline__ int wave_sample_row(const float (&lg)[NV], int V, int
     }
   }
   if (pick < 0) pick = last;
+  if constexpr (RECORD) {
+    if (rec) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int v = lane + 64 * i;
+        if (i < nv && v < V) rec[v] = ((drop >> i) & 1u) || (eos_blocked && v == eos) ? -INFINITY : lg[i] / g.temperature;
+      }
+    }
+  }
   return __shfl(pick, sel);
 }
 
@@ -2888,6 +2927,23 @@ template <bool SESSION, bool WARP = false> struct TailK { using T = TailArgs; };
 template <> struct TailK<true, false> { using T = TailSessionArgs; };
 template <> struct TailK<false, true> { using T = TailWarpArgs; };
 template <> struct TailK<true, true> { using T = TailSessionWarpArgs; };
+// the RECORD instances: the same arguments and, behind them, the per-utterance step records (ptts_step_record_kernels.h)
+struct TailRecordArgs : TailArgs {
+  const StepRecord* rec;  // [B]
+};
+struct TailSessionRecordArgs : TailSessionArgs {
+  const StepRecord* rec;  // [B], one per slot
+};
+struct TailWarpRecordArgs : TailWarpArgs {
+  const StepRecord* rec;
+};
+struct TailSessionWarpRecordArgs : TailSessionWarpArgs {
+  const StepRecord* rec;
+};
+template <bool SESSION, bool WARP> struct TailRK { using T = TailRecordArgs; };
+template <> struct TailRK<true, false> { using T = TailSessionRecordArgs; };
+template <> struct TailRK<false, true> { using T = TailWarpRecordArgs; };
+template <> struct TailRK<true, true> { using T = TailSessionWarpRecordArgs; };
 
 // NV = logits per lane: 8 (vocab <= 512), 18 (<= 1152: Mini / Large v1, vocab 1088) or 32 (<= 2048)
 // SESSION = the per-slot instance (TailSessionArgs); the body is written once, here, not in a shared device function: the static
@@ -2896,14 +2952,27 @@ template <> struct TailK<true, true> { using T = TailSessionWarpArgs; };
 // tail_warp_kernel<NV, SESSION>. The body is still written once - ptts_tail_body.inc, included into both kernels with WARP a constant of
 // each - and not in a shared device function, for the reason above: the instances without WARP keep their names AND their instructions
 // (profiles/device_warpers_isa_compare.txt; through a forced-inline device function they did not)
+// RECORD = the step-record instances (ptts_step_record.h): tail_record_kernel / tail_warp_record_kernel<NV, SESSION> store the processed scores
+// of every codebook row of the step into the utterance's own record (StepRecord, [B] indexed like cur_len, behind the existing arguments). Their
+// argument types come from a trait of their own (TailRK): a third parameter on TailK would be spelled in the names of the twelve instances above.
 template <int NV, bool SESSION>
 __global__ void __launch_bounds__(1024) tail_kernel(typename TailK<SESSION>::T p) {
-  constexpr bool WARP = false;
+  constexpr bool WARP = false, RECORD = false;
 #include "ptts_tail_body.inc"
 }
 template <int NV, bool SESSION>
 __global__ void __launch_bounds__(1024) tail_warp_kernel(typename TailK<SESSION, true>::T p) {
-  constexpr bool WARP = true;
+  constexpr bool WARP = true, RECORD = false;
+#include "ptts_tail_body.inc"
+}
+template <int NV, bool SESSION>
+__global__ void __launch_bounds__(1024) tail_record_kernel(typename TailRK<SESSION, false>::T p) {
+  constexpr bool WARP = false, RECORD = true;
+#include "ptts_tail_body.inc"
+}
+template <int NV, bool SESSION>
+__global__ void __launch_bounds__(1024) tail_warp_record_kernel(typename TailRK<SESSION, true>::T p) {
+  constexpr bool WARP = true, RECORD = true;
 #include "ptts_tail_body.inc"
 }
 

@@ -1,5 +1,9 @@
-// The body of the sampler tail, included into tail_kernel<NV, SESSION> and tail_warp_kernel<NV, SESSION> (ptts_lm_kernels.h), which define
-// NV, SESSION, the constant WARP and the argument struct `p` (TailK<SESSION, WARP>::T). Not a header: no include guard, no declarations.
+// The body of the sampler tail, included into tail_kernel<NV, SESSION>, tail_warp_kernel<NV, SESSION> and their step-record twins
+// tail_record_kernel / tail_warp_record_kernel<NV, SESSION> (ptts_lm_kernels.h), which define NV, SESSION, the constants WARP and RECORD and the
+// argument struct `p` (TailK<SESSION, WARP>::T; RECORD: TailRK<SESSION, WARP>::T). Not a header: no include guard, no declarations.
+// RECORD: the processed scores of every codebook row of this step go to the utterance's record (p.rec[b], ptts_step_record_kernels.h) at step
+// cur_len - given. Everything it adds sits behind `if constexpr (RECORD)`: the other instances keep their instructions
+// (profiles/device_step_records_isa_compare.txt).
   const TailArgs& a = p;
   __shared__ int s_tok[32];
   int b = blockIdx.x;
@@ -25,6 +29,13 @@
   const int fu0 = a.first_unf[b];
   DevWarp wp = {0.f, 1.f, 0.f, 0.f};
   if constexpr (WARP) wp = p.warp[b];  // one more load of this batch: its address needs the kernel arguments and b alone
+  [[maybe_unused]] float* rs = nullptr;  // RECORD: where this step's K rows of scores go, or null (no record, or a step at or beyond cap_steps)
+  [[maybe_unused]] int rcap = 0;
+  [[maybe_unused]] long long rstride = 0;
+  if constexpr (RECORD) {  // likewise one load of this batch
+    const StepRecord sr = p.rec[b];
+    rs = sr.scores; rcap = sr.cap_steps; rstride = sr.step_stride;
+  }
   DevDims dd = *a.dims;  // the embedding of the next column needs P / max_length / the voice-prompt prefix: fetched now, not after the argmax
   if constexpr (SESSION) {
     dd.max_length = p.row_maxlen[b];  // the pad triangle (and whether there is a pattern at all) follows the request's own length
@@ -70,6 +81,10 @@
   if (__shfl(he, fu0) > 0 && fu0 < a.K - 1) fu += 1;  // logits_processors.py:48 (advance <= 1 per step)
   if (tid == 0) a.first_unf[b] = fu;
   const bool block_eos_all = (t - 1 - t_prefix) < g.min_new_tokens;  // new tokens = columns after the (1 + T_prefix) given ones
+  if constexpr (RECORD) {  // step index = cur_len - given; the engine never writes at or beyond cap_steps records
+    const int ridx = t - 1 - t_prefix;
+    rs = (rs && ridx >= 0 && ridx < rcap) ? rs + (size_t)ridx * (size_t)rstride : nullptr;
+  }
 
   // one wave per codebook row, no workgroup barrier until every row has its token. greedy: torch.argmax semantics (first
   // index on ties); do_sample: the warpers + multinomial on the same wave (wave_sample_row)
@@ -90,6 +105,9 @@
         const int v = lane + 64 * i;
         float x = lg[i];
         if (eos_blocked && v == a.eos) x = -INFINITY;
+        if constexpr (RECORD) {  // greedy: the logits as read, -inf at the blocked EOS, every other entry with its bits
+          if (rs && v < a.V) rs[(size_t)k * a.V + v] = x;
+        }
         if (v < a.V && (x > best || (x == best && v < bi))) { best = x; bi = v; }
       }
       const float wbest = wave_max(best);
@@ -99,7 +117,8 @@
       const int hrow = SESSION ? hrow0 + k : row;  // a slot with its own record: the codebook index inside the slot
       const unsigned long long hsh = splitmix64(g.seed ^ splitmix64(((unsigned long long)t << 32) ^ (unsigned long long)hrow));
       const float u = (float)((hsh >> 40) + 0.5) * (1.0f / 16777216.0f);  // [2^-25, 1], DESIGN.md 4.6
-      if constexpr (WARP) widx = wave_sample_row<NV, true>(lg, a.V, lane, g, eos_blocked, a.eos, u, wp);
+      if constexpr (RECORD) widx = wave_sample_row<NV, WARP, true>(lg, a.V, lane, g, eos_blocked, a.eos, u, wp, rs ? rs + (size_t)k * a.V : nullptr);
+      else if constexpr (WARP) widx = wave_sample_row<NV, true>(lg, a.V, lane, g, eos_blocked, a.eos, u, wp);
       else widx = wave_sample_row<NV>(lg, a.V, lane, g, eos_blocked, a.eos, u);
     }
     if (lane == 0) {

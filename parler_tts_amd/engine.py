@@ -66,6 +66,8 @@ class DecoderEngine:
         self.history_penalty = None  # (repetition_penalty, no_repeat_ngram_size) while the device node is on (set_history_penalty)
         self.sample_warp = None  # (min_p, typical_p, epsilon_cutoff, eta_cutoff) while the tail's WARP instances are on (set_sample_warp)
         self.logit_edits = None  # the engine-wide generation_extras.LogitEdits while the logit-edit node is on (set_logit_edits)
+        self.step_records = None  # (scores, logits, cap_steps) while step records are on (set_step_records): the arenas of the next static call
+        self._slot_records = {}  # slot -> (scores, logits) of set_slot_step_records: the engine writes into them until the slot is retired
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -262,6 +264,48 @@ class DecoderEngine:
                 "ptts_set_slot_logit_edits")
         del keep
 
+    def _step_records(self, scores, logits, cap_steps, lead):
+        """The two arenas as a ``ptts_step_records``; each fp32, contiguous, on the engine's device, with room for ``cap_steps`` records of
+        ``lead`` (a number of [K, V] blocks per step; ``None``: not checked, the batch is not known yet)."""
+        for name, t in (("scores", scores), ("logits", logits)):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"step records: `{name}` must be a contiguous float32 tensor on {self.device}")
+            if lead is not None and t.numel() < int(cap_steps) * lead * self.K * self.V:
+                raise ValueError(f"step records: `{name}` holds {t.numel()} values, {cap_steps} steps of {lead} x {self.K} x {self.V} need more")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+        return N.PttsStepRecords(ptr(scores), ptr(logits), int(cap_steps))
+
+    def set_step_records(self, scores: Optional[torch.Tensor] = None, logits: Optional[torch.Tensor] = None, cap_steps: int = 0, enabled: bool = True):
+        """transformers' ``output_scores`` / ``output_logits`` on the device (``ptts_set_step_records``): from the next ``prefill`` on, step i of
+        the call writes its processed scores into ``scores[i]`` and the raw logits of the heads into ``logits[i]`` - fp32 arenas
+        ``[cap_steps, B*K, V]`` the caller allocates for that call's batch; ``None`` leaves a kind out. Both ``None`` with ``cap_steps=0`` is how a
+        session is opened whose requests may bring records (``set_slot_step_records``). ``enabled=False`` switches the feature off (the state of
+        a new engine). The engine holds a reference to the tensors until the next call of this function. ``ValueError`` inside a session that
+        holds a request."""
+        if not enabled:
+            N.check(self.lib.ptts_set_step_records(self._h, None, _stream_ptr(device=self.device)), "ptts_set_step_records")
+            self.step_records = None
+            self._slot_records = {}
+            return
+        rec = self._step_records(scores, logits, cap_steps, None)
+        N.check(self.lib.ptts_set_step_records(self._h, C.byref(rec), _stream_ptr(device=self.device)), "ptts_set_step_records")
+        self.step_records = (scores, logits, int(cap_steps))
+
+    def set_slot_step_records(self, slot: int, scores: Optional[torch.Tensor] = None, logits: Optional[torch.Tensor] = None, cap_steps: int = 0,
+                              default: bool = False):
+        """The record of the next admission into the idle slot ``slot`` (``ptts_set_slot_step_records``): fp32 ``[cap_steps, K, V]`` each, the
+        admission's own first token is step 0. ``default=True`` clears it, as ``retire_row`` does. Only in a session begun with step records on.
+        The engine holds a reference to the tensors until the slot's record is set again or the slot is retired."""
+        rec = None if default else self._step_records(scores, logits, cap_steps, 1)
+        N.check(self.lib.ptts_set_slot_step_records(self._h, int(slot), None if rec is None else C.byref(rec), _stream_ptr(device=self.device)),
+                "ptts_set_slot_step_records")
+        if default:
+            self._slot_records.pop(int(slot), None)
+        else:
+            self._slot_records[int(slot)] = (scores, logits)
+
     def prefill(self, enc: torch.Tensor, enc_mask: Optional[torch.Tensor], prompt: Optional[torch.Tensor],
                 prompt_mask: Optional[torch.Tensor], sample: bool = True):
         enc = enc.to(self.device, torch.float32).contiguous()
@@ -282,6 +326,9 @@ class DecoderEngine:
             pm = prompt_mask.to(self.device, torch.int32).contiguous()
             keep.append(pm)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+        if getattr(self, "step_records", None) is not None:  # the batch is known now: the arenas of set_step_records must hold cap_steps x B x K x V
+            scores, logits, cap = self.step_records
+            self._step_records(scores, logits, cap, B)
         N.check(self.lib.ptts_prefill(self._h, ptr(enc), ptr(em), ptr(pr), ptr(pm), B, Nn, P, int(sample), _stream_ptr(device=self.device)), "ptts_prefill")
         self.B, self.P = B, P
         self._keep = keep  # inputs are consumed asynchronously by the enqueued kernels
@@ -573,6 +620,7 @@ class DecoderEngine:
 
     def retire_row(self, row: int):
         N.check(self.lib.ptts_retire_row(self._h, int(row), _stream_ptr(device=self.device)), "ptts_retire_row")
+        self._slot_records.pop(int(row), None)  # the slot's step record is cleared with it
 
     def slot_voice(self) -> list:
         """Voice-prompt frames per slot as the device holds them (``ptts_debug_slot_voice``; for tests). Synchronises."""

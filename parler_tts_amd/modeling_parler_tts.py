@@ -741,6 +741,19 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         self._engine = None
         return self
 
+    def enable_device_step_records(self, enabled: bool = True):
+        """Opt-in: ``return_dict_in_generate=True`` with ``output_scores`` and / or ``output_logits`` is served on the device
+        (``ptts_step_record.h``): the raw logits of every step by one small kernel node in front of the penalty node, the processed scores by the
+        sampler tail's RECORD instances, both straight into arenas ``[max_new_tokens, B*K, V]`` (fp32) that ``generate()`` allocates - ``max_new_tokens
+        x B x K x V x 4`` bytes per kind. The call then stays on the captured step graph (streamer and ``overlap_codec`` paths included) whenever
+        nothing else needs the host loop: a user ``logits_processor`` / ``stopping_criteria``, an option whose own switch is off, or one of the two
+        excluded logit-edit combinations still run it. The tuples have the host loop's length and shapes; in a sampling call the scores carry
+        the device sampler's ties and bands. ``ContinuousBatcher.submit`` takes ``output_scores`` / ``output_logits`` per
+        request. Off (the default): every call is routed exactly as without this switch."""
+        self.device_step_records = bool(enabled)
+        self._engine = None
+        return self
+
     def _get_engine(self, B: int, N: int, P: int, max_length: int, T: int = 0) -> DecoderEngine:
         """T = voice-prompt frames: the prefill runs the P prompt positions, the BOS column and the T given columns in one pass."""
         dev, dt = self.device, self.dtype
@@ -1017,8 +1030,11 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         # order (single-token keys, and the two rules of ptts_logit_edit.h); a request that is not runs the host loop, which also owns its errors
         on_device = ((_DEVICE_PENALTIES if getattr(self, "device_penalties", False) else ()) + (_DEVICE_WARPERS if getattr(self, "device_warpers", False) else ())
                      + (LOGIT_EDIT_OPTIONS if getattr(self, "device_logit_edits", False) else ()))
+        # model.enable_device_step_records(): score outputs no longer force the host loop (the engine writes them, ptts_step_record.h)
+        dev_records_on = bool(getattr(self, "device_step_records", False))
+        wants_records = bool(getattr(gc, "return_dict_in_generate", False)) and bool(getattr(gc, "output_scores", False) or getattr(gc, "output_logits", False))
         stays = (bool(extras) and set(extras) <= set(on_device)
-                 and not manual and not (bool(getattr(gc, "return_dict_in_generate", False)) and (getattr(gc, "output_scores", False) or getattr(gc, "output_logits", False))))
+                 and not manual and not (wants_records and not dev_records_on))
         edits = None
         if stays and any(x in LOGIT_EDIT_OPTIONS for x in extras):
             try:
@@ -1034,14 +1050,16 @@ class ParlerTTSForConditionalGeneration(nn.Module):
             extras = []
         manual = manual or bool(extras)
         # return_dict_in_generate + output_scores / output_logits: the reference returns `_sample`'s per-step tuples next to the waveform
-        # (:3648-3651 keeps the ModelOutput); they exist on the host loop only
+        # (:3648-3651 keeps the ModelOutput); they come from the host loop, or - model.enable_device_step_records() and nothing else that
+        # needs the host loop - from the engine's step records
         as_dict = bool(getattr(gc, "return_dict_in_generate", False))
         keep_scores = as_dict and bool(getattr(gc, "output_scores", False))
         keep_logits = as_dict and bool(getattr(gc, "output_logits", False))
         if as_dict and (getattr(gc, "output_attentions", False) or getattr(gc, "output_hidden_states", False)):
             raise NotImplementedError("output_attentions / output_hidden_states: the HIP decoder does not materialise attention maps or per-layer states")
-        manual = manual or keep_scores or keep_logits
-        self._step_records = ([] if keep_scores else None, [] if keep_logits else None)
+        dev_rec = dev_records_on and (keep_scores or keep_logits) and not manual
+        manual = manual or ((keep_scores or keep_logits) and not dev_rec)
+        self._step_records = ([] if keep_scores and not dev_rec else None, [] if keep_logits and not dev_rec else None)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if do_sample else 0  # follows torch.manual_seed()
         gen_kw = dict(max_length=max_length, min_new_tokens=min_new, do_sample=do_sample, temperature=float(gc.temperature or 1.0),
                       top_k=int(gc.top_k or 0) if do_sample else 0, top_p=float(gc.top_p if gc.top_p is not None else 1.0),
@@ -1062,6 +1080,14 @@ class ParlerTTSForConditionalGeneration(nn.Module):
             eng.set_logit_edits(edits)
         elif getattr(eng, "logit_edits", None) is not None:  # the node of an earlier call: off, this call's graphs are the plain ones
             eng.set_logit_edits(enabled=False)
+        rec_scores = rec_logits = None
+        if dev_rec:  # one arena per requested kind, step-major: step i is the [B*K, V] matrix transformers' _sample appends
+            cap = max_length - 1 - T0
+            rec_scores = torch.empty([cap, B * K, d.vocab_size], dtype=torch.float32, device=dev) if keep_scores else None
+            rec_logits = torch.empty([cap, B * K, d.vocab_size], dtype=torch.float32, device=dev) if keep_logits else None
+            eng.set_step_records(rec_scores, rec_logits, cap)
+        elif getattr(eng, "step_records", None) is not None:  # the records of an earlier call: off, this call's graphs are the plain ones
+            eng.set_step_records(enabled=False)
         pad, eos = gc.pad_token_id if gc.pad_token_id is not None else d.pad_token_id, d.eos_token_id
         bos_col = torch.full((B * K, 1), bos, dtype=torch.long, device=dev)
         dec_ids = bos_col if prefix is None else torch.cat([bos_col, prefix], dim=-1)  # :3011-3018
@@ -1091,9 +1117,16 @@ class ParlerTTSForConditionalGeneration(nn.Module):
         wav, lengths = self._undelay_and_decode(output_ids, pattern, bos_col, bos, pad, wav_pre)
         if as_dict:
             out = GenerateOutput(sequences=wav, audios_length=lengths)
-            if keep_scores:
+            if dev_rec:  # steps made = the final clock - the given columns: the host loop's tuple length
+                steps_made = int(output_ids.shape[1]) - int(delayed.shape[1])
+                if keep_scores:
+                    out["scores"] = tuple(rec_scores[i] for i in range(steps_made))
+                if keep_logits:
+                    out["logits"] = tuple(rec_logits[i] for i in range(steps_made))
+                eng.set_step_records(enabled=False)  # the engine lets go of the arenas; the views keep them alive
+            if keep_scores and not dev_rec:
                 out["scores"] = tuple(self._step_records[0])
-            if keep_logits:
+            if keep_logits and not dev_rec:
                 out["logits"] = tuple(self._step_records[1])
             self._step_records = (None, None)
             return out
